@@ -6,17 +6,23 @@ bootstrap SMC with 1e6 particles, systematic resampling every step.
 One "step" of this harness = one whole sweep (N * T particle-steps), issued as
 one hipGraph replay with every input already resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: one rank per GPU — either launched by torch.distributed.run, or bare: without WORLD_SIZE in the
    environment this process only spawns the N ranks (spawn_ranks; it never touches a GPU itself) and relays
    rank 0's JSON line)
+
+A plain run does only what the headline needs: set up, W warm-up sweeps, K timed sweeps, the JSON line.
+`--full` adds everything else this file measures, after the timed region: `roofline`, `cpu_baseline`,
+`other_configs` (and, on the sharded path, the other scaling's record and the sharded configs 3 / 4).
+`--dump-outputs DIR` writes what the last timed sweep computed, as DIR/<name>.npy (float32 / float64; see
+dump_outputs): the inputs are fixed by the arguments, so two builds can be compared output for output.
 
 N > 1 is STRONG scaling by default — BASELINE's metric: the same 1e6-particle sweep split over the N ranks
 (contiguous blocks of global particle indices; the total is rounded up to a multiple of N x 1024 because a shard
 starts on a tile of the integer CDF; the JSON names the exact count).  `--weak` keeps ~1e6 particles PER GPU instead.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel — the hiprtc-specialised site program of the
-SMC step (gmx_jit_kernel; the interpreter k_vm only when GENMI_JIT=0): algorithmic bytes per launch / its average
+Prints ONE JSON line (rank 0).  With --full: `roofline` is for the dominant kernel — the hiprtc-specialised site
+program of the SMC step (gmx_jit_kernel; the interpreter k_vm only when GENMI_JIT=0): algorithmic bytes per launch / its average
 duration, measured here with HIP events on the launch stream, plus its VALU-issue fraction (the limiter that binds:
 `roofline.valu`).  `cpu_baseline` times the oracle's C statement of the same sweep on the host cores.  The other
 BASELINE configs (3: nonlinear SSM + MH, 4: 64-d mixture importance, 5: mixture Gibbs sweep) ride along in
@@ -808,6 +814,47 @@ def pick_sharded_sweep(args, dist, world, rank, on_gpu, be, make):
     return best[0], results
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, sw, single, dist, world, log_ml):
+    """--dump-outputs: what the last timed sweep handed back, as float32 / float64 .npy files in `out_dir`.
+      single GPU (BootstrapSweep.state()):  particles.npy (x_T before the last resampling, f32), log_weights.npy (f32),
+                                            ancestors.npy (the last resampling's indices, f64)
+      sharded (ShardedBootstrapSweep.state(), every rank's slots in global order):  resampled_particles.npy (f32)
+      both:                                 log_ml.npy (f64, one element)
+    COLLECTIVE on the sharded path (state() and the gather).  Past DUMP_MAX_BYTES in all, every per-particle array is
+    cut to the same fixed, seeded sample of particle indices, written as sample_index.npy (f64)."""
+    import numpy as np
+    import torch
+    if single:
+        x, lw, anc = sw.state()
+        anc = anc.cpu().numpy()
+        if getattr(sw, "fuse", False):
+            anc = anc & 0xffffff            # the one-launch step leaves TAGGED ancestor words: the index is the low 24 bits
+        arrays = {"particles": x.cpu().numpy().astype(np.float32), "log_weights": lw.cpu().numpy().astype(np.float32),
+                  "ancestors": anc.astype(np.float64)}
+    else:
+        mine = sw.state().contiguous()
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine)
+        arrays = {"resampled_particles": torch.cat(parts).cpu().numpy().astype(np.float32)}
+    if dist is not None and dist.get_rank() != 0:
+        return
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        keep = int(n * (DUMP_MAX_BYTES - (1 << 20)) // (total + 8 * n))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays["log_ml"] = np.array([log_ml], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(world: int) -> int:
     """`python bench.py --gpus N` with no launcher: THIS process becomes the launcher.  It never imports torch, never
     loads the HIP library and never touches a GPU; it starts N children of the same command line — one rank per GPU,
@@ -862,12 +909,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--particles", type=int, default=N_PARTICLES)
     ap.add_argument("--T", type=int, default=T_STEPS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure roofline, cpu_baseline and the other configs (sharded path: "
+                         "the other scaling and the sharded configs 3 / 4); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed sweep computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs 3 / 4 / 5 block after the headline")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip the configs 3 / 4 / 5 block after the headline")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="only the timed sweeps (rocprofv3's kernel-trace pass: its per-kernel averages are then IN-SWEEP "
-                         "durations, not mixed with the isolated timing loops of the roofline block)")
+                    help="with --full: no roofline measurements (rocprofv3's kernel-trace pass: its per-kernel averages "
+                         "are then IN-SWEEP durations, not mixed with the isolated timing loops of the roofline block)")
     ap.add_argument("--sharded", action="store_true", help="use the multi-GPU code path even at world size 1")
     ap.add_argument("--rccl-graph", action="store_true",
                     help="N > 1: capture the RCCL collectives into the sweep's hipGraph too (default: eager across GPUs)")
@@ -1003,7 +1056,10 @@ def main():
         out["config"]["capacity_per_peer"] = sw.capacity
         out["config"]["full_capacity_reruns"] = sw.reruns
 
-    if not single and world > 1 and dist is not None and not args.no_other_configs:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sw, single, dist, world, log_ml)       # COLLECTIVE on the sharded path
+
+    if args.full and not single and world > 1 and dist is not None and not args.no_other_configs:
         # the OTHER scaling beside the headline's: a strong-scaling line also carries the weak
         # record (--particles PER GPU), a --weak line the strong one — same communicator, three sweeps, MAX over ranks
         from genjax_amd.inference.sharded import ShardedBootstrapSweep
@@ -1036,11 +1092,12 @@ def main():
         out["weak" if want_weak else "strong"] = rec
     if not single:
         out["config"]["one_launch_per_step"] = bool(getattr(sw, "fuse_sh", False))
-    if not single and on_gpu and not args.no_other_configs and dist is not None and n * world >= N_PARTICLES and T == T_STEPS:
+    if (args.full and not single and on_gpu and not args.no_other_configs and dist is not None
+            and n * world >= N_PARTICLES and T == T_STEPS):
         oc = other_configs_sharded(dist, world, rank, sw.cx, be)       # COLLECTIVE: every rank
         if rank == 0:
             out["other_configs"] = oc
-    if rank == 0 and on_gpu:
+    if args.full and rank == 0 and on_gpu:
         out["roofline"] = ({"code_identity": code_identity(sw), "note": "--no-roofline"} if args.no_roofline
                            else measure_roofline(be, sw, n, T, world, single, value))
         if single and not args.no_other_configs and n == N_PARTICLES and T == T_STEPS:

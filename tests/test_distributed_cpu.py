@@ -273,8 +273,8 @@ def test_bench_contract_control_flow(world, weak, bare):
     if bare:
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
             env.pop(k, None)
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--particles", "3000", "--T", "4", "--no-cpu-baseline",
-            "--no-graph"] + (["--weak"] if weak else [])
+    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--particles", "3000", "--T", "4", "--full",
+            "--no-cpu-baseline", "--no-graph"] + (["--weak"] if weak else [])
     if world == 1 or bare:
         cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_on_cpu.py")] + args
     else:
@@ -306,3 +306,48 @@ def test_bench_contract_control_flow(world, weak, bare):
         assert other["particles_per_gpu"] == (2048 if weak else 3072) and other["particles_total"] == other["particles_per_gpu"] * world
         assert abs(other["log_ml"] - out["log_ml_kalman"]) < 0.5
     assert out["value"] > 0 and abs(out["log_ml"] - out["log_ml_kalman"]) < 0.5
+
+
+def _bench_on_cpu(args, tmp_path):
+    # the CPU mirror of the C-ABI with gloo, also where a GPU is present (bench.py picks nccl when torch sees one)
+    env = dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_on_cpu.py")] + args, env=env,
+                       capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline only — nothing of what --full adds — and
+    `--dump-outputs DIR` writes the last timed sweep's outputs as float32 / float64 .npy files: the same files for the
+    same arguments run after run, and the 2-rank population (gathered in global slot order) is the single-process
+    one resampled by its ancestors."""
+    base = ["--steps", "3", "--warmup", "1", "--particles", "4096", "--T", "4", "--no-graph"]
+    outs = {}
+    for name, gpus in (("a", 1), ("b", 1), ("two", 2)):
+        d = tmp_path / name
+        out = _bench_on_cpu(["--gpus", str(gpus)] + base + ["--dump-outputs", str(d)], tmp_path)
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out
+        for k in ("roofline", "cpu_baseline", "other_configs", "weak", "strong"):
+            assert k not in out, k
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith(".npy") for f in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["log_ml"].tolist() == [out["log_ml"]]
+        outs[name] = arrays
+    a, b, two = outs["a"], outs["b"], outs["two"]
+    assert sorted(a) == ["ancestors", "log_ml", "log_weights", "particles"]
+    assert a["particles"].shape == a["log_weights"].shape == a["ancestors"].shape == (4096,)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert sorted(two) == ["log_ml", "resampled_particles"]
+    assert np.array_equal(two["resampled_particles"], a["particles"][a["ancestors"].astype(np.int64)])
+    assert two["log_ml"][0] == a["log_ml"][0]
