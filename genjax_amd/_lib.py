@@ -245,6 +245,10 @@ class Backend:
         c.gmx_mh_accept.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
         c.gmx_select.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                  POINTER(c_int32), c_int32, c_int64, c_void_p]
+        c.gmx_history_record.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_uint32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]
+        c.gmx_lineage.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]
         c.gmx_capture_begin.argtypes = [c_void_p]
         c.gmx_capture_end.argtypes = [c_void_p, POINTER(c_void_p)]
         c.gmx_graph_launch.argtypes = [c_void_p, c_void_p]

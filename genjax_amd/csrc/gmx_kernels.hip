@@ -3512,6 +3512,56 @@ extern "C" int gmx_mh_accept(const uint32_t* keys_d, const float* log_alpha_d, i
 }
 
 // ---------------------------------------------------------------------------
+// sweep history: the per-step record and the lineage walk (gmx_history.h)
+// ---------------------------------------------------------------------------
+#include "gmx_history.h"
+
+extern "C" int gmx_history_record(const float* x_d, int32_t D, const float* lw_d, const uint32_t* anc_d, int64_t n,
+                                  uint32_t expect_tag, float* x_out_d, float* lw_out_d, int32_t* anc_out_d,
+                                  int64_t* status_d, gmx_stream stream) {
+  if (!x_d || !lw_d || !anc_d || !x_out_d || !lw_out_d || !anc_out_d) return gmx_fail("gmx_history_record: null argument%s");
+  if (D <= 0 || D > 65533) return gmx_fail("gmx_history_record: D = %s%lld is outside [1, 65533]", "", (long long)D);
+  if (n <= 0 || n > 0x7fffffffLL) return gmx_fail("gmx_history_record: n = %s%lld is outside [1, 2^31)", "", (long long)n);
+  if (expect_tag > 255u) return gmx_fail("gmx_history_record: expect_tag = %s%lld is outside [0, 255]", "", (long long)expect_tag);
+  if (expect_tag != 0u && !status_d) return gmx_fail("gmx_history_record: a tag check needs status_d%s");
+  if (expect_tag != 0u && n > (1LL << GMX_HIST_TAG_SHIFT))
+    return gmx_fail("gmx_history_record: tagged ancestors hold 24-bit indices (n = %s%lld)", "", (long long)n);
+  const int64_t blocks = (n / 4 + GMX_HIST_BLOCK) / GMX_HIST_BLOCK;       // >= 1: thread 0 moves the row's head and tail
+  hipLaunchKernelGGL(k_history_record, dim3((unsigned)blocks, (unsigned)(D + 2)), dim3(GMX_HIST_BLOCK), 0, (hipStream_t)stream,
+                     (const uint32_t*)x_d, D, (const uint32_t*)lw_d, anc_d, n, expect_tag, (uint32_t*)x_out_d,
+                     (uint32_t*)lw_out_d, (uint32_t*)anc_out_d, (unsigned long long*)status_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmx_lineage(const int32_t* anc_d, const float* xs_d, int32_t T, int32_t D, int64_t n, const int32_t* start_d,
+                           int64_t m, int32_t* paths_d, float* traj_d, int64_t* status_d, gmx_stream stream) {
+  if (!start_d || !status_d) return gmx_fail("gmx_lineage: null argument%s");
+  if (!paths_d && !traj_d) return gmx_fail("gmx_lineage: null argument (paths_d and traj_d)%s");
+  if (traj_d && !xs_d) return gmx_fail("gmx_lineage: null argument (xs_d with traj_d)%s");
+  if (T <= 0 || D <= 0 || n <= 0 || m <= 0) return gmx_fail("gmx_lineage: T, D, n and m must be positive%s");
+  if (T > 1 && !anc_d) return gmx_fail("gmx_lineage: null argument (anc_d)%s");
+  if (n > 0x7fffffffLL) return gmx_fail("gmx_lineage: n = %s%lld does not fit the int32 indices", "", (long long)n);
+  constexpr int C = GMX_LINEAGE_CHAINS;
+  const int64_t per_block = (int64_t)GMX_HIST_BLOCK * C;
+  const int64_t blocks = (m + per_block - 1) / per_block;
+  if (blocks > 0x7fffffffLL) return gmx_fail("gmx_lineage: m = %s%lld is too large for one launch", "", (long long)m);
+  if (!anc_d) anc_d = start_d;          // T == 1: never read
+  auto* st = (unsigned long long*)status_d;
+  const dim3 g((unsigned)blocks), b(GMX_HIST_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  switch (traj_d ? D : 1) {
+    case 1: hipLaunchKernelGGL((k_lineage<1, C>), g, b, 0, s, anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, st); break;
+    case 2: hipLaunchKernelGGL((k_lineage<2, C>), g, b, 0, s, anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, st); break;
+    case 3: hipLaunchKernelGGL((k_lineage<3, C>), g, b, 0, s, anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, st); break;
+    case 4: hipLaunchKernelGGL((k_lineage<4, C>), g, b, 0, s, anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, st); break;
+    default: hipLaunchKernelGGL((k_lineage<0, C>), g, b, 0, s, anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, st); break;
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------
 struct gmx_graph { hipGraph_t graph; hipGraphExec_t exec; };

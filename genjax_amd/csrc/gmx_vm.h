@@ -310,3 +310,9 @@ GMX_HD bool gmx_op_needs_full(uint32_t op) {
   return op == OP_POW || op == OP_SIN || op == OP_COS || op == OP_TANH || op == OP_SOFTPLUS ||
          op == OP_LGAMMA || op == OP_S_BETA || op == OP_S_CATSTEP || op == OP_L_BETA || op == OP_S_LOGGAMMA;
 }
+
+// A plain host compiler building the C-ABI from these headers (the CPU mirror the host-logic tests load) also gets the
+// sweep-history entry points as sequential loops (gmx_history.h); hipcc and hiprtc see nothing here.
+#if defined(__cplusplus) && !defined(__HIPCC__) && !defined(__HIPCC_RTC__)
+#include "gmx_history.h"
+#endif

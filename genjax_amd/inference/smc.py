@@ -909,6 +909,73 @@ class _NoiseAhead:
             A.wait_stream(Bs)
 
 
+class SweepHistory:
+    """What BootstrapSweep(history=True) recorded: every step's particles, log-weights and ancestors.
+
+      x            [T, n] (scalar state), [T, n, D] (vector state) or a tuple of [T, n] (tuple state)
+      log_weights  [T, n]
+      ancestors    [T, n] int32: row t is the resampling AFTER step t (row T-1 = state()[2])
+
+    The reference's SMC carries whole Scan traces through every resampling; here a step is recorded once and a
+    trajectory is ONE backward walk through the ancestor rows (gmx_lineage: one launch, one lane per trajectory)."""
+
+    def __init__(self, xs, lws, ancs, event=(), tuple_state=None):
+        self._xs, self.log_weights, self.ancestors = xs, lws, ancs
+        self._event, self._tuple = tuple(event), tuple_state
+        self.T, self.D, self.n = (int(v) for v in xs.shape)
+
+    def _state_view(self, a, lead):
+        """[T, D, k] -> the state's shape with the step axis at `lead` = 0 ([T, k, ...]) or 1 ([k, T, ...])"""
+        if self._tuple is not None:
+            return self._tuple((a[:, d] if lead == 0 else a[:, d].t()) for d in range(self.D))
+        if not self._event:
+            return a[:, 0] if lead == 0 else a[:, 0].t()
+        return a.transpose(1, 2) if lead == 0 else a.permute(2, 0, 1)
+
+    @property
+    def x(self):
+        return self._state_view(self._xs, 0)
+
+    def _walk(self, start, want_paths, want_traj):
+        be = _lib.get()
+        dev = self._xs.device
+        if start is None:
+            start = self.ancestors[self.T - 1]
+        start = torch.as_tensor(start, device=dev).to(torch.int32).contiguous().reshape(-1)
+        m = int(start.numel())
+        paths = torch.empty((self.T, m), dtype=torch.int32, device=dev) if want_paths else None
+        traj = torch.empty((self.T, self.D, m), dtype=torch.float32, device=dev) if want_traj else None
+        if m == 0:
+            return paths, traj
+        status = torch.zeros((1,), dtype=torch.int64, device=dev)
+        be.check(be.c.gmx_lineage(be.ptr(self.ancestors), be.ptr(self._xs), self.T, self.D, self.n, be.ptr(start), m,
+                                  be.ptr(paths), be.ptr(traj), be.ptr(status), be.stream()), "gmx_lineage")
+        bad = int(status.item())
+        if bad:
+            raise IndexError(f"SweepHistory: {bad} index(es) outside [0, {self.n}) on the walk (start, or a recorded "
+                             "ancestor): they were clamped, nothing outside the history was read")
+        return paths, traj
+
+    def lineage(self, start=None):
+        """int32 [T, m]: row t = the step-t particle on the lineage of each of `start`'s step-(T-1) particles (default:
+        ancestors[T-1], the sweep's own last resampling — n equally weighted draws from the final weights)"""
+        return self._walk(start, True, False)[0]
+
+    def trajectories(self, start=None):
+        """the states along those lineages: [m, T] / [m, T, D] / a tuple of [m, T] (views of the kernel's [T, D, m])"""
+        return self._state_view(self._walk(start, False, True)[1], 1)
+
+    def filter_mean(self):
+        """E[x_t | y_1..t] per step: sum_i softmax(lw_t)_i x_t[i], float64 [T] (scalar state) or [T, D]"""
+        # the softmax written out (torch.softmax on float64 was measured at float32-level error on the device: weights
+        # off by 4e-9, against the 1e-16 of exp / sum / divide in float64)
+        lw = self.log_weights.double()
+        e = torch.exp(lw - lw.max(dim=1, keepdim=True).values)
+        w = e / e.sum(dim=1, keepdim=True)
+        mean = (w[:, None, :] * self._xs.double()).sum(dim=2)
+        return mean[:, 0] if (self._tuple is None and not self._event) else mean
+
+
 class BootstrapSweep(_NoiseAhead):
     """A whole bootstrap particle filter (T steps, resampling every step) as a
     fixed sequence of launches on one stream, capturable into a hipGraph — two launches per step:
@@ -949,15 +1016,22 @@ class BootstrapSweep(_NoiseAhead):
 
     def __init__(self, init, step, n_particles: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, specialize=True, rejuvenate=None, state_addr="x", noise_ahead=None, chain_mh=True,
-                 noise_roots=None, fuse_resample=None):
+                 noise_roots=None, fuse_resample=None, history=False):
         """chain_mh=False keeps the MH move and the extension as two launches (the form a chained program too large
         for the tile statistics falls back to); noise_roots: which keys' draws of the chained program the background
         stream takes ("LDKEY" = the move's proposal + accept draws, the default; "KSPLITU" = the extension's; "all").
         rejuvenate: an edit request (e.g. StaticRequest({"x": Rejuvenate(...)})) applied as one fused
         MH move per particle after every resampling, before the next extension (BASELINE config 3; the
         graph-captured form of smc.resample -> smc.rejuvenate -> smc.extend, same keys, same results).
-        Supported for models whose trace is {state_addr: the return value, obs_addr: the observation}."""
+        Supported for models whose trace is {state_addr: the return value, obs_addr: the observation}.
+        history=True keeps EVERY step's particles, log-weights and ancestors (one gmx_history_record launch per step on
+        the chain's stream, inside a captured graph too) — `history()` gives the per-step filtering distribution and the
+        ancestral lineage of the survivors (SweepHistory).  Off: nothing is allocated, nothing is launched."""
         self.init, self.step, self.n, self.T = init, step, int(n_particles), int(T)
+        self.keep_history = bool(history)
+        if self.keep_history and rejuvenate is not None:
+            raise NotImplementedError("BootstrapSweep(history=True, rejuvenate=...): the trajectory's state would be the "
+                                      "moved state, which is not recorded yet (drop rejuvenate= or history=)")
         self.obs_addr, self.state_addr, self.rejuvenate = obs_addr, state_addr, rejuvenate
         self.kind = _KINDS[resample] if isinstance(resample, str) else int(resample)
         self.step_extra = step_extra or (lambda t: ())
@@ -1165,7 +1239,28 @@ class BootstrapSweep(_NoiseAhead):
             ks = split(fold_in(key, t), 3)
             self.step_keys.append((ks[0], ks[1], ks[2]))
         self._slot_uniforms_setup()
+        self.hist_xs = self.hist_lws = self.hist_ancs = self.hist_status = None
+        if self.keep_history:
+            # row t of each slab: step t's particles [D, n] / log-weights / ancestors (the resampling AFTER step t)
+            self.hist_xs = torch.zeros((T, D, n), dtype=torch.float32, device=dev)
+            self.hist_lws = torch.zeros((T, n), dtype=torch.float32, device=dev)
+            self.hist_ancs = torch.zeros((T, n), dtype=torch.int32, device=dev)
+            self.hist_status = torch.zeros((1,), dtype=torch.int64, device=dev)
         return self
+
+    def _record(self, t, tagged=False):
+        """Step t into the history slabs (gmx_history_record), enqueued at the one point where its state x_store[t % 2],
+        its log-weights and its ancestors are all in place: right after step t's resampler — which, in the one-launch
+        form, is the prologue of step t + 1's launch (tagged=True: `anc` then holds that launch's tagged words, tag
+        1 + t % 255 as in _resample_in(t + 1); the record stores the indices and counts any word with another tag) —
+        and before the launch of step t + 2 overwrites the first two."""
+        be = _lib.get()
+        w = t % 2 if self.fuse else 0
+        tag = 1 + t % _lib.ANC_TAG_MAX if tagged else 0
+        be.check(be.c.gmx_history_record(be.ptr(self.x_store[t % 2]), self.x_store[0].shape[0], be.ptr(self.lw_pp[w]),
+                                         be.ptr(self.anc), self.n, tag, be.ptr(self.hist_xs[t]), be.ptr(self.hist_lws[t]),
+                                         be.ptr(self.hist_ancs[t]), be.ptr(self.hist_status), be.stream()),
+                 "gmx_history_record")
 
     def _gathered(self, which):
         """the resampled state x[which][anc] as the step model's first argument (lazy: the gather is fused)"""
@@ -1384,6 +1479,8 @@ class BootstrapSweep(_NoiseAhead):
                 self._launch_mhvm(t)
             else:
                 self._launch_vm(t)
+            if self.keep_history and self.fuse and t >= 1:
+                self._record(t - 1, tagged=True)      # (this launch's prologue resampled step t - 1)
         if self.fuse and t < self.T - 1:
             return                         # step t's weights are resampled by step t + 1's launch itself
         if self.fused:
@@ -1391,6 +1488,8 @@ class BootstrapSweep(_NoiseAhead):
         else:
             self._launch_cdf(t)
             self._launch_anc(t)
+        if self.keep_history:
+            self._record(t)
 
     def enqueue(self, skip_vm=False):
         """Issue every launch of the sweep on the current stream (no syncs, no allocations).
@@ -1408,6 +1507,8 @@ class BootstrapSweep(_NoiseAhead):
                     self._launch_mh(t)
                 if not skip_vm:
                     self._launch_vm(t)
+            if self.keep_history and self.fuse and t >= 1 and not skip_vm:
+                self._record(t - 1, tagged=True)      # (this launch's prologue resampled step t - 1)
             if self.fuse and t < self.T - 1:
                 continue                   # step t's weights are resampled by step t + 1's launch itself
             if self.fused:
@@ -1415,6 +1516,8 @@ class BootstrapSweep(_NoiseAhead):
             else:
                 self._launch_cdf(t)
                 self._launch_anc(t)
+            if self.keep_history:
+                self._record(t)
 
     def kernel_timers(self):
         """Representative single launches (a mid-sweep step) for per-kernel timing in bench.py."""
@@ -1473,6 +1576,19 @@ class BootstrapSweep(_NoiseAhead):
         """clear the sticky timeout word (after the cause — e.g. another process holding compute units — is gone)"""
         if getattr(self, "rs_status", None) is not None:
             self.rs_status.zero_()
+        if getattr(self, "hist_status", None) is not None:
+            self.hist_status.zero_()
+
+    def history(self) -> "SweepHistory":
+        """Every step of the last launch (BootstrapSweep(history=True); synchronises): views of the history slabs — the
+        next launch() overwrites them."""
+        if not self.keep_history:
+            raise RuntimeError("BootstrapSweep.history(): the sweep was built without history=True")
+        self._check_valid()
+        if int(self.hist_status.item()) != 0:
+            raise RuntimeError("BootstrapSweep.history(): a recorded ancestor word carried another step's tag (a stale "
+                               "word of the fused resampling prologue): the history is not valid")
+        return SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state)
 
     def log_ml(self) -> float:
         """sum_t [ ref(M_t) + log(total_t * 2^-shift) - log N ] in float64 (synchronises)."""

@@ -582,6 +582,37 @@ int gmx_select(const uint8_t* mask_d, const void* const* a_d, const void* const*
                gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Sweep history: every step's particles, log-weights and ancestors, and the ancestral lineage of the survivors.
+ * Reference call site: the reference's SMC extends a Scan trace, so every resampling gathers the WHOLE history
+ * (src/genjax/_src/inference/smc.py: ParticleCollection.get_particle / __getitem__ — jtu.tree_map(lambda v: v[idx], ...)
+ * over whole traces, O(T) per step) and its final particles are whole trajectories.  Here a sweep keeps one step in memory; these two entry points give the same information back at O(1)
+ * per step plus one backward walk when it is asked for.
+ *   gmx_history_record   one launch on the sweep's stream (capturable: no host round trip) copies one step — D state
+ *                        rows [D, n], the log-weights [n], the ancestors [n] — into its rows of the history slabs.  The
+ *                        destination rows may start at any 4-byte-aligned address (row t of a [T, D, n] slab with n
+ *                        odd); 16-byte stores where the destination allows, scalar head and tail.
+ *                        expect_tag = 0: anc_d holds plain int32 indices, copied as they are.  expect_tag in [1, 255]:
+ *                        anc_d holds the fused resampling prologue's tagged words {tag: bits 24..31 | index: bits 0..23}
+ *                        (gmx_run_args.rs); the index is stored, and every word whose tag differs from expect_tag adds 1
+ *                        to *status_d (a vector atomic add; status_d may be null when expect_tag = 0).
+ *                        Limits: 1 <= D <= 65533, 1 <= n < 2^31 (n <= 2^24 with a tag).
+ *   gmx_lineage          one launch walks m lineages back through T resampling levels and gathers the states on the way:
+ *                        anc_d[t][i] = the step-t particle that step-(t+1) particle i was extended from (rows 0 .. T-2
+ *                        are read);  p = start_d[j]; for t = T-1 .. 0: paths[t][j] = p; traj[t][d][j] = xs[t][d][p];
+ *                        if (t) p = anc_d[t-1][p].  paths_d or traj_d may be null (not both); xs_d may be null when
+ *                        traj_d is; anc_d may be null when T = 1.  An index outside [0, n) — in start_d or in anc_d —
+ *                        is clamped into range BEFORE any read and counted in *status_d (the caller zeroes it): no lane
+ *                        reads outside its rows.  Element offsets are 64-bit.  Limits: T, D, m >= 1, 1 <= n < 2^31.
+ * A null pointer or a non-positive size returns non-zero before anything is launched.
+ * ---------------------------------------------------------------------- */
+int gmx_history_record(const float* x_d /* [D, n] */, int32_t D, const float* lw_d /* [n] */, const uint32_t* anc_d /* [n] */,
+                       int64_t n, uint32_t expect_tag, float* x_out_d /* [D, n] */, float* lw_out_d /* [n] */,
+                       int32_t* anc_out_d /* [n] */, int64_t* status_d, gmx_stream stream);
+int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n] */, int32_t T, int32_t D, int64_t n,
+                const int32_t* start_d /* [m] */, int64_t m, int32_t* paths_d /* [T, m] */, float* traj_d /* [T, D, m] */,
+                int64_t* status_d /* [1] */, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
  * gmx_run_args.peer + gmx_shard_step_peer, no collective launch at all).  gmx_p2p_alloc / _open / _close / _free stay:
  * they are how the fused exchange's landing blocks are allocated and mapped.
