@@ -3562,6 +3562,38 @@ extern "C" int gmx_lineage(const int32_t* anc_d, const float* xs_d, int32_t T, i
 }
 
 // ---------------------------------------------------------------------------
+// row-wise exact-integer draws: one multinomial index per row of logits (gmx_backward.h)
+// ---------------------------------------------------------------------------
+#include "gmx_backward.h"
+static_assert(GMX_PICK_TILE == RS_TILE, "gmx_pick_rows draws from the resamplers' two-level CDF: the same definition tile");
+
+extern "C" size_t gmx_pick_rows_workspace(int64_t rows, int64_t n) { return gmx_pick_rows_bytes_(rows, n); }
+
+extern "C" int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
+                             int32_t* out_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !logits_d || !out_d || !status_d || !workspace_d) return gmx_fail("gmx_pick_rows: null argument%s");
+  if (rows < 1 || rows > 0x7fffffffLL) return gmx_fail("gmx_pick_rows: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
+  if (n < 1 || n > 0x7fffffffLL) return gmx_fail("gmx_pick_rows: n = %s%lld is outside [1, 2^31)", "", (long long)n);
+  if (ld < n) return gmx_fail("gmx_pick_rows: ld = %s%lld is smaller than n", "", (long long)ld);
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_pick_rows: workspace_d must be 8-byte aligned%s");
+  if (((uintptr_t)logits_d & 3) || ((uintptr_t)keys_d & 3)) return gmx_fail("gmx_pick_rows: keys_d and logits_d must be 4-byte aligned%s");
+  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
+  uint64_t* agg = (uint64_t*)workspace_d;
+  float* tmax = (float*)(agg + rows * tiles);
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
+    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
+    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, logits_d, n, ld,
+                       tiles, row0, scale, tmax, agg);
+  }
+  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
+                     (const float*)tmax, (const uint64_t*)agg, out_d, (unsigned long long*)status_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------
 struct gmx_graph { hipGraph_t graph; hipGraphExec_t exec; };

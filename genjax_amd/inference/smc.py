@@ -909,6 +909,64 @@ class _NoiseAhead:
             A.wait_stream(Bs)
 
 
+BACKWARD_ROWS_MAX = 16                 # rows of backward-simulation logits per density launch (and per gmx_pick_rows call)
+BACKWARD_CHUNK_BYTES = 256 << 20       # ... and at most this much of them in memory
+_BACKWARD_CACHE = engine.new_cache()
+
+
+def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
+    """out[k, i] = lw[i] + step.assess({sites[d]: x_next[d][k], obs_addr: y}, (x_prev[i], *extra))[0] in float32, for the
+    R = out.shape[0] rows in ONE launch: the model's `assess` traced R times, row k's constrained state read from the
+    launch-uniform short vectors x_next[d] (as inference/gibbs.py traces K categories), the R sums stored as the rows
+    of `out` ([R, n], rows contiguous).  The program is cached on the model, the leaves' kinds and R."""
+    from .. import tracer as Tr
+    from ..engine import Broadcast, Compiled, Flat, Sym, Tracing, leaf_spec, unflatten
+    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
+    R, n = int(out.shape[0]), int(lw.shape[0])
+    batch = (n,)
+    flat = Flat()
+    atree = flat.add((x_prev,) + tuple(extra))
+    jy = len(flat.leaves)
+    flat.add(y)
+    jx = len(flat.leaves)
+    for v in x_next:
+        flat.add(Broadcast(v))
+    jl = len(flat.leaves)
+    flat.add(lw)
+    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
+    ck = (_gfkey(step), atree, specs, tuple(sites), obs_addr, R)
+    ent = _BACKWARD_CACHE.get(ck)
+    if ent is None:
+        tr = Tracing(1)
+        ctx = _Ctx(tr)
+        ctx.store_sites = False
+        with Tr.tracing(tr.graph):
+            syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
+            sargs = unflatten(atree, lambda j: syms[j].value)
+            rows = np.empty((R,), dtype=object)
+            for k in range(R):
+                con = ChoiceMap.empty().set(obs_addr, syms[jy])
+                for d, a in enumerate(sites):
+                    con = con.set(a, Sym(syms[jx + d].value[k], None))
+                try:
+                    _, _, _, s = call_gen_fn(ctx, "assess", step, None, sargs, con, None, None, None, ())
+                except MissingAddress as e:
+                    addr = tuple(a for a in e.args if a != ())
+                    raise NotImplementedError(
+                        f"SweepHistory.backward_sample: the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
+                        f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
+                        "transition density would have to integrate it out") from None
+                rows[k] = syms[jl].value + Tr.as_float(s)
+                tr.prestore(rows[k])            # (stored now: the row's register dies here)
+            o = tr.emit_output(rows)
+        ent = (Compiled(tr), o)
+        _BACKWARD_CACHE[ck] = ent
+    comp, o = ent
+    bufs = [None] * len(comp.outputs)
+    bufs[o[1]] = out
+    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+
+
 class SweepHistory:
     """What BootstrapSweep(history=True) recorded: every step's particles, log-weights and ancestors.
 
@@ -919,10 +977,15 @@ class SweepHistory:
     The reference's SMC carries whole Scan traces through every resampling; here a step is recorded once and a
     trajectory is ONE backward walk through the ancestor rows (gmx_lineage: one launch, one lane per trajectory)."""
 
-    def __init__(self, xs, lws, ancs, event=(), tuple_state=None):
+    def __init__(self, xs, lws, ancs, event=(), tuple_state=None, *, step=None, ys=None, step_extra=None, obs_addr=None,
+                 state_addr=None):
+        """step / ys / step_extra / obs_addr / state_addr: the sweep's model, for backward_sample() (BootstrapSweep.history()
+        hands them over; every other method works without)"""
         self._xs, self.log_weights, self.ancestors = xs, lws, ancs
         self._event, self._tuple = tuple(event), tuple_state
         self.T, self.D, self.n = (int(v) for v in xs.shape)
+        self._step, self._ys, self._step_extra = step, ys, step_extra
+        self._obs_addr, self._state_addr = obs_addr, state_addr
 
     def _state_view(self, a, lead):
         """[T, D, k] -> the state's shape with the step axis at `lead` = 0 ([T, k, ...]) or 1 ([k, T, ...])"""
@@ -964,6 +1027,83 @@ class SweepHistory:
     def trajectories(self, start=None):
         """the states along those lineages: [m, T] / [m, T, D] / a tuple of [m, T] (views of the kernel's [T, D, m])"""
         return self._state_view(self._walk(start, False, True)[1], 1)
+
+    def backward_sample(self, key: Key, m: int, state_sites=None, return_paths=False):
+        """m trajectories by forward filtering, backward simulation (Godsill, Doucet & West 2004) over the recorded steps:
+        the last state is drawn from the final weights, and going back every particle of step t is re-weighted by the
+        transition density into the state already chosen at step t + 1 — where the lineages of `trajectories()` coalesce
+        to a handful of early ancestors, these draws do not.
+
+          k_t = fold_in(key, t)                                                    (key: ONE key)
+          paths[T-1, :] = ancestors_from_cdf(MULTINOMIAL, k_{T-1}, *weight_cdf(lw_{T-1})[:2], n_out=m)
+          t = T-2 .. 0, row keys split(k_t, m):
+            logits[k, i] = lw_t[i] + step.assess({site_d: x~_{t+1}[k][d], obs_addr: y_{t+1}}, (x_t[i], *step_extra(t+1)))[0]
+            paths[t, k]  = gmx_pick_rows: the exact-integer multinomial draw of row k under its key
+            x~_t[k]      = x_t[paths[t, k]]
+
+        (float32 sums; the observation's term is constant along a row and kept so that the bits are defined).  The
+        densities of up to BACKWARD_ROWS_MAX rows are ONE launch of one cached site program (the model's own `assess`
+        traced once per row with that row's chosen state as launch-uniform values); nothing passes through the host
+        between steps.  Every draw has the resolution of the multinomial resampler's 23-bit uniform, as everywhere else
+        in the project: a particle whose share of a row's mass is below 2^-23 may never be drawn.
+
+        state_sites: the address of each state component, in order (default (state_addr,) for a scalar state; required
+        for D > 1).  The model may have no latent site besides them and the observation.
+        Returns the trajectories in trajectories()'s layout ([m, T] / [m, T, D] / a tuple of [m, T]); with
+        return_paths=True, (paths int32 [T, m], trajectories).  A row without any mass (every candidate's density -inf)
+        raises FloatingPointError naming the step."""
+        if self._step is None or self._ys is None or self._obs_addr is None:
+            raise RuntimeError("SweepHistory.backward_sample: this SweepHistory was built without the model (step=, ys=, "
+                               "step_extra=, obs_addr=, state_addr=): take it from BootstrapSweep.history()")
+        if tuple(key.shape) != ():
+            raise ValueError("SweepHistory.backward_sample takes ONE key")
+        if state_sites is None:
+            if self.D > 1:
+                raise NotImplementedError("SweepHistory.backward_sample: a state of more than one component needs "
+                                          "state_sites= (the address of each component, in order)")
+            state_sites = (self._state_addr,)
+        sites = tuple(state_sites)
+        if len(sites) != self.D:
+            raise ValueError(f"SweepHistory.backward_sample: state_sites names {len(sites)} addresses for a state of "
+                             f"{self.D} components")
+        be = _lib.get()
+        dev = self._xs.device
+        T_, D, n, m = self.T, self.D, self.n, int(m)
+        paths = torch.empty((T_, m), dtype=torch.int32, device=dev)
+        traj = torch.empty((T_, D, m), dtype=torch.float32, device=dev)
+        if m > 0:
+            lw_last = self.log_weights[T_ - 1]
+            if lw_last.data_ptr() % 16:        # row T-1 of a [T, n] slab with n % 4 != 0: gmx_weight_cdf loads float4
+                lw_last = lw_last.clone()
+            cdf, total, _, _ = weight_cdf(lw_last)
+            paths[T_ - 1] = ancestors_from_cdf(MULTINOMIAL, fold_in(key, T_ - 1), cdf, total, n_out=m)
+            traj[T_ - 1] = self._xs[T_ - 1].index_select(1, paths[T_ - 1].long())
+            status = torch.zeros((T_,), dtype=torch.int64, device=dev)      # word t: the rows of step t without any mass
+            extra = self._step_extra or (lambda t: ())
+            R = max(1, min(BACKWARD_ROWS_MAX, m, BACKWARD_CHUNK_BYTES // (4 * n), 40 // D))
+            logits = torch.empty((R, n), dtype=torch.float32, device=dev)
+            ws = torch.empty(((be.c.gmx_pick_rows_workspace(R, n) + 7) // 8,), dtype=torch.int64, device=dev)
+            for t in range(T_ - 2, -1, -1):
+                keys = split(fold_in(key, t), m).data()
+                x_t = self._state_view(self._xs[t:t + 1], 0)
+                x_t = type(x_t)(v[0] for v in x_t) if self._tuple is not None else x_t[0]
+                for r0 in range(0, m, R):
+                    rc = min(R, m - r0)
+                    _backward_logits(self._step, sites, self._obs_addr, x_t, tuple(extra(t + 1)),
+                                     [traj[t + 1, d, r0:r0 + rc] for d in range(D)], self._ys[t + 1], self.log_weights[t],
+                                     logits[:rc])
+                    be.check(be.c.gmx_pick_rows(be.ptr(keys[r0:]), be.ptr(logits), rc, n, n, be.ptr(paths[t, r0:]),
+                                                be.ptr(status[t:]), be.ptr(ws), be.stream()), "gmx_pick_rows")
+                traj[t] = self._xs[t].index_select(1, paths[t].long())
+            if int(total.item()) == 0:
+                raise FloatingPointError(f"SweepHistory.backward_sample: step {T_ - 1}: the final weights carry no mass")
+            bad = torch.nonzero(status).reshape(-1).tolist()
+            if bad:
+                raise FloatingPointError(f"SweepHistory.backward_sample: step {bad[-1]}: {int(status[bad[-1]].item())} of the {m} "
+                                         "trajectories found no step-t particle with a positive transition density into "
+                                         "their next state (a row of -inf logits)")
+        out = self._state_view(traj, 1)
+        return (paths, out) if return_paths else out
 
     def filter_mean(self):
         """E[x_t | y_1..t] per step: sum_i softmax(lw_t)_i x_t[i], float64 [T] (scalar state) or [T, D]"""
@@ -1588,7 +1728,8 @@ class BootstrapSweep(_NoiseAhead):
         if int(self.hist_status.item()) != 0:
             raise RuntimeError("BootstrapSweep.history(): a recorded ancestor word carried another step's tag (a stale "
                                "word of the fused resampling prologue): the history is not valid")
-        return SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state)
+        return SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state, step=self.step,
+                            ys=self.ys, step_extra=self.step_extra, obs_addr=self.obs_addr, state_addr=self.state_addr)
 
     def log_ml(self) -> float:
         """sum_t [ ref(M_t) + log(total_t * 2^-shift) - log N ] in float64 (synchronises)."""

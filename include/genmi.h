@@ -613,6 +613,29 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
                 int64_t* status_d /* [1] */, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Row-wise exact-integer draws: one multinomial index per row of a matrix of logits (additive, ABI still v8).
+ * Reference call site: none of its own — backward simulation over a sweep's history (forward filtering, backward
+ * simulation: Godsill, Doucet & West 2004) draws, per trajectory and step, one particle with probability proportional to
+ * weight x transition density; in the reference that is jax.random.categorical over a [m, n] matrix.
+ *   gmx_pick_rows   out[r] = what the per-row path gives for row r (logits_d + r * ld, n columns) under keys_d[r]:
+ *                   gmx_weight_cdf of the row with shift = 62 - ceil(log2 n), then gmx_ancestors(
+ *                   GMX_RESAMPLE_MULTINOMIAL, keys[r], cdf, n, 0, total, 1, 0, 1, ...) — the two-level block-floating-point
+ *                   integer CDF over tiles of 1024 columns, then the first i with cdf_i * 2^23 >= total * (2^23 - u), u the
+ *                   23-bit uniform bits32(keys[r], 0) >> 9, compared in 128-bit integers.  Two launches (tile statistics
+ *                   per (row, tile); one workgroup per row) and no n-entry CDF array; everything after the per-element exp
+ *                   is integer arithmetic, so the result does not depend on the grid.  A row whose total is 0 (every
+ *                   logit -inf or NaN) returns n - 1 and adds 1 to *status_d (a vector atomic add; the caller zeroes it).
+ *                   Rows are ld >= n elements apart and may start at any 4-byte boundary; element offsets are 64-bit.
+ *                   Limits: 1 <= rows < 2^31, 1 <= n < 2^31; workspace_d: gmx_pick_rows_workspace(rows, n) bytes, 8-byte
+ *                   aligned, contents irrelevant on entry.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched.
+ * ---------------------------------------------------------------------- */
+size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
+int gmx_pick_rows(const uint32_t* keys_d /* [rows, 2] */, const float* logits_d, int64_t rows, int64_t n,
+                  int64_t ld /* elements between rows, >= n */, int32_t* out_d /* [rows] */, int64_t* status_d /* [1] */,
+                  void* workspace_d, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
  * gmx_run_args.peer + gmx_shard_step_peer, no collective launch at all).  gmx_p2p_alloc / _open / _close / _free stay:
  * they are how the fused exchange's landing blocks are allocated and mapped.
