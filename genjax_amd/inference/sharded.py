@@ -34,16 +34,15 @@ from __future__ import annotations
 
 import math
 import os
-from ctypes import c_uint32
 
 import numpy as np
 import torch
 
 from .. import _lib
 from ..core.choice_map import ChoiceMap
-from ..random import Key, fold_in, lazy_split, split
+from ..random import Key, lazy_split, split
 from ..engine import Gathered
-from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _NoiseAhead, cdf_reference, cdf_shift
+from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _NoiseAhead, _key_words, cdf_reference, cdf_shift
 
 
 def systematic_slot_bounds(offsets, total: int, n_total: int, u0: int):
@@ -165,11 +164,7 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.fuse_mh = False
         self._noise_progs = {}
         self.__dict__.pop("_noise_run_cache", None)
-        if getattr(self, "graph", None) is not None:     # prepared again: the graph captured for the previous run goes
-            if be.uses_streams:
-                torch.cuda.synchronize()
-            be.c.gmx_graph_destroy(self.graph)
-            self.graph = None
+        self._drop_graph()                               # prepared again: the graph captured for the previous run goes
 
         def MinimalGenerate(*a):
             return _MG(*a, hoist_noise=bool(want_na))
@@ -309,10 +304,7 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.lw_pp = [self.lw, torch.zeros_like(self.lw)] if self.fuse_sh else [self.lw, self.lw]
         if self.fuse_sh:
             self.sh_status = torch.zeros((1,), dtype=torch.int64, device=dev)
-        self.step_keys = []
-        for t in range(T):
-            ks = split(fold_in(key, t), 3)
-            self.step_keys.append((ks[0], ks[1], ks[2]))
+        self._set_step_keys(key)
         self.sorted_tab = self.sorted_keys = None
         if self.kind == MULTINOMIAL_SORTED:
             # every rank draws the SAME table of the N global slots from the step's resampling key (integers)
@@ -460,8 +452,7 @@ class ShardedBootstrapSweep(_NoiseAhead):
         else:
             vm = prog.comp.bind(leaves, (n,), lazy_split(k_prop, self.N), red_out=self.partials, out_buffers=bufs,
                                 index_offset=g * n)
-        kh = k_res.host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
+        kk = _key_words(k_res)
         m = self.maxs[t:t + 1]
         tot = self.totals[t:t + 1]
         P = be.ptr
@@ -636,26 +627,10 @@ class ShardedBootstrapSweep(_NoiseAhead):
         RCCL collectives, which comm.RcclComm issues on this same stream — into one hipGraph so
         the host leaves the loop.  Exercised at world size 1 only (no multi-GPU box in the build
         loop); the default multi-GPU path enqueues eagerly."""
-        be = _lib.get()
         if self.comm and not self.cx.graph_safe:
             raise RuntimeError("capture() needs the direct RCCL communicator (torch.distributed's watchdog "
                                "queries events recorded inside the capture)")
-        from ctypes import c_void_p
-        s = torch.cuda.Stream(device=be.device)
-        s.wait_stream(torch.cuda.current_stream(be.device))
-        with torch.cuda.stream(s):
-            self.enqueue()
-            s.synchronize()
-            be.check(be.c.gmx_capture_begin(be.stream()), "gmx_capture_begin")
-            try:
-                self.enqueue()
-            finally:
-                h = c_void_p()
-                rc = be.c.gmx_capture_end(be.stream(), h)
-            be.check(rc, "gmx_capture_end")
-        torch.cuda.current_stream(be.device).wait_stream(s)
-        self.graph = h
-        return self
+        return super().capture()
 
     def launch(self):
         if self.graph is not None:
@@ -681,15 +656,10 @@ class ShardedBootstrapSweep(_NoiseAhead):
         if flag != 0:
             self.reruns += 1
             self.capacity = self.n
-            if self.graph is not None:
-                # the captured sweep holds the old exchange buffers and the communicator's kernels: release it
-                # (after the stream has drained) before the buffers go away — a dropped-but-live graph is what
-                # made ncclCommDestroy hang at teardown; the re-run and later launches are eager
-                be = _lib.get()
-                if be.uses_streams:
-                    torch.cuda.synchronize()
-                be.c.gmx_graph_destroy(self.graph)
-                self.graph = None
+            # the captured sweep holds the old exchange buffers and the communicator's kernels: release it
+            # (after the stream has drained) before the buffers go away — a dropped-but-live graph is what
+            # made ncclCommDestroy hang at teardown; the re-run and later launches are eager
+            self._drop_graph()
             self._alloc_exchange()
             self.enqueue()
             assert int(self.plan[2].item()) == 0
@@ -701,9 +671,7 @@ class ShardedBootstrapSweep(_NoiseAhead):
         holds the communicator's kernels and ncclCommDestroy waits on it forever otherwise (measured: a hang at
         teardown).  COLLECTIVE when a communicator exists."""
         be = _lib.get()
-        if self.graph is not None:
-            be.c.gmx_graph_destroy(self.graph)
-            self.graph = None
+        self._drop_graph()
         if self.cx is not None and hasattr(self.cx, "destroy") and getattr(self, "_own_cx", True):
             if be.uses_streams:
                 torch.cuda.synchronize()
@@ -792,8 +760,7 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
     trs, lw = target.importance(lazy_split(sub, n, offset=g * n), ChoiceMap.empty())
     lw = lw.float().contiguous()
     shift = cdf_shift(K)
-    kh = key.host()                                                  # resampling key: the algorithm's leftover `key`
-    kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
+    kk = _key_words(key)                                             # resampling key: the algorithm's leftover `key`
     mx = torch.empty((1,), dtype=torch.float32, device=dev)
     calloc = (lambda shape, dt: comm.alloc(shape, dt)) if (comm is not None and hasattr(comm.inner, "alloc")) else \
         (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev))          # destinations of collectives

@@ -482,6 +482,12 @@ class LogMLOffset:
         return acc
 
 
+def _key_words(key: Key):
+    """ONE key as the `const uint32_t key[2]` argument of the C-ABI"""
+    kh = key.host()
+    return (c_uint32 * 2)(int(kh[0]), int(kh[1]))
+
+
 def weight_cdf(lw: torch.Tensor, n_total=None, max_partials=None):
     """gmx_weight_cdf: returns (cdf int64-bits [n], total [1], max [1], shift)."""
     be = _lib.get()
@@ -495,18 +501,17 @@ def weight_cdf(lw: torch.Tensor, n_total=None, max_partials=None):
     total = torch.empty((1,), dtype=torch.int64, device=lw.device)
     mx = torch.empty((1,), dtype=torch.float32, device=lw.device)
     ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64, device=lw.device)
+    partials, rows = None, 0
     if max_partials is None:
         # max via the deterministic LSE kernel's max output
         rows_ws = torch.empty(((be.c.gmx_logsumexp_workspace(1, n) + 3) // 4,), dtype=torch.int32, device=lw.device)
         dummy = torch.empty((1,), dtype=torch.float32, device=lw.device)
         be.check(be.c.gmx_logsumexp(be.ptr(lw), 1, n, be.ptr(dummy), be.ptr(mx), be.ptr(rows_ws), be.stream()),
                  "gmx_logsumexp")
-        be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, shift, None, 0, be.ptr(mx), be.ptr(cdf), be.ptr(total),
-                                     be.ptr(ws), be.stream()), "gmx_weight_cdf")
     else:
-        be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, shift, be.ptr(max_partials), max_partials.shape[-1],
-                                     be.ptr(mx), be.ptr(cdf), be.ptr(total), be.ptr(ws), be.stream()),
-                 "gmx_weight_cdf")
+        partials, rows = be.ptr(max_partials), max_partials.shape[-1]
+    be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, shift, partials, rows, be.ptr(mx), be.ptr(cdf), be.ptr(total), be.ptr(ws),
+                                 be.stream()), "gmx_weight_cdf")
     return cdf, total, mx, shift
 
 
@@ -515,10 +520,139 @@ FUSE_RESAMPLE_LOOP_MAX = 1 << 24 # ... or, LOOPED, 1024 workgroups walking up to
 FUSED_RESAMPLE_MAX = 2048 * 1024        # RS_MAX_TILES tiles of 1024 particles (csrc/gmx_kernels.hip)
 
 
+class _Resampler:
+    """THE place that launches a resampler: picks the form for (kind, n, n_out) once, owns that form's workspaces
+    (allocated here, never in `launch`), and issues the form's C calls.
+
+      "tiles"   n <= FUSED_RESAMPLE_MAX, no CDF array: the kind's tile-form entry point from the (tile maxima, tile sums)
+                statistics a site program or gmx_tile_stats left; systematic / stratified without statistics: gmx_resample
+      "prefix"  past FUSED_RESAMPLE_MAX (BASELINE config 4: k = 1e7), still no CDF array: gmx_tile_prefix (the tile
+                prefixes from one workgroup) + gmx_resample_tiles_p / gmx_resample_sorted_p; one-off calls only
+      "cdf"     gmx_weight_cdf into the CDF array + gmx_ancestors, or gmx_multinomial (the guide table) for the iid
+                multinomial from MULTINOMIAL_GUIDED_MIN particles on
+
+    sweep=True: a BootstrapSweep's launcher (persistent buffers; past FUSED_RESAMPLE_MAX it takes the CDF array).
+    with_stats=True: the caller brings statistics to every launch (no gmx_resample workspace)."""
+
+    @staticmethod
+    def fused_form(kind, n):
+        """which of the two forms without a CDF array resample_fused takes (their entry points refuse what they cannot)"""
+        return "prefix" if n > FUSED_RESAMPLE_MAX and kind != MULTINOMIAL_TILED else "tiles"
+
+    @staticmethod
+    def form_of(kind, n, n_out=None, sweep=False):
+        """the form for this kind and size: "tiles" / "prefix" where that form takes them, else the CDF array — which the
+        two ordered multinomials do not have: NotImplementedError"""
+        form = _Resampler.fused_form(kind, n)
+        if kind in _TILE_KINDS and n_out in (None, n) and \
+                (0 < n <= FUSED_RESAMPLE_MAX if form == "tiles" else (not sweep and n < 2 ** 31 - 8192)):
+            return form
+        if kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):
+            if sweep:
+                raise NotImplementedError("resample='multinomial_tiled' / 'multinomial_sorted': n <= 2^21 per GPU (use 'multinomial')")
+            raise NotImplementedError("resample(kind='multinomial_tiled'): n_out = n <= 2^21; 'multinomial_sorted': n_out = n "
+                                      "(use 'multinomial')")
+        return "cdf"
+
+    @staticmethod
+    def needs_stats(kind, form):
+        """forms that only run from tile statistics (the others can do without: gmx_resample, the CDF array)"""
+        return form == "prefix" or (form == "tiles" and kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED))
+
+    def __init__(self, kind, n, n_out=None, *, form=None, sweep=False, with_stats=False, cdf=None):
+        """cdf: a ready CDF array ("cdf" form: ancestors_from_cdf) instead of one of the launcher's own"""
+        be = _lib.get()
+        dev = be.device
+        self.kind, self.n, self.n_out = int(kind), int(n), int(n if n_out is None else n_out)
+        self.form = form or self.form_of(self.kind, self.n, n_out, sweep)
+        self.shift = cdf_shift(self.n)
+        fresh = torch.zeros if sweep else torch.empty      # (a one-off call's workspaces are written before they are read)
+
+        def words(nbytes, dtype, alloc=fresh):
+            size = torch.empty((), dtype=dtype).element_size()
+            return alloc(((int(nbytes) + size - 1) // size,), dtype=dtype, device=dev)
+        self.cdf = self.cdf_ws = self.ws = self.table = self.prefix = None
+        if self.form == "cdf":
+            self.cdf = torch.zeros((self.n,), dtype=torch.int64, device=dev) if cdf is None else cdf
+        if sweep or (self.form == "cdf" and cdf is None):
+            # (a sweep keeps gmx_weight_cdf's workspace in every form: its spin-bound word is part of what a sweep shows)
+            self.cdf_ws = words(be.c.gmx_weight_cdf_workspace(self.n), torch.int64, torch.zeros)
+        self.guided = self.form == "cdf" and self.kind == MULTINOMIAL and self.n >= MULTINOMIAL_GUIDED_MIN
+        if self.guided:
+            self.ws = words(be.c.gmx_multinomial_workspace(self.n), torch.int32)
+        elif self.form == "tiles" and self.kind == MULTINOMIAL_TILED:
+            self.ws = words(be.c.gmx_multinomial_tiled_workspace(self.n), torch.int32, torch.zeros)     # the count buffers
+        elif self.form == "tiles" and self.kind != MULTINOMIAL_SORTED and not with_stats:
+            self.ws = words(be.c.gmx_resample_workspace(self.n), torch.int64)
+        if self.kind == MULTINOMIAL_SORTED and self.form != "cdf":
+            self.table = words(4 * int(be.c.gmx_sorted_uniforms_words(self.n)), torch.int32)
+        if self.form == "prefix":
+            self.prefix = words(8 * int(be.c.gmx_tile_prefix_words(self.n)), torch.int64)
+
+    def launch(self, key, lw, max_out, total_out, anc, *, stats=None, uniforms=None, partials=None, rows=0, phase=-1,
+               cdf_ready=False):
+        """Resample `lw` under `key`: the global max, the integer total and the ancestors into max_out / total_out / anc.
+
+        stats     (tile maxima, tile sums) of lw, where they exist
+        uniforms  drawn ahead from the key alone (the noise-ahead sweep): the stratified / two-stage multinomial slot
+                  uniforms, or the sorted multinomial's ready order-statistics table
+        partials, rows   block maxima of lw for gmx_resample / gmx_weight_cdf (without: they take a pass of their own)
+        phase     gmx_multinomial_tiled: which count buffer is zero (-1: neither, the call clears both)
+        "cdf" form: anc=None stops after the CDF array; cdf_ready=True starts from it (total_out then holds its total)"""
+        be = _lib.get()
+        c, P, n, st = be.c, be.ptr, self.n, be.stream()
+        kk, shift = _key_words(key), self.shift
+        tile_max, tile_agg = (P(stats[0]), P(stats[1])) if stats is not None else (None, None)
+        if self.form == "cdf":
+            if not cdf_ready:
+                be.check(c.gmx_weight_cdf(P(lw), n, shift, P(partials), rows, P(max_out), P(self.cdf), P(total_out),
+                                          P(self.cdf_ws), st), "gmx_weight_cdf")
+            if anc is None:
+                pass
+            elif self.guided:
+                # unordered slots: through the guide table (two table reads + a search over ~3 entries per slot instead
+                # of a binary search over n) — the same ancestors
+                be.check(c.gmx_multinomial(kk, P(self.cdf), n, P(total_out), self.n_out, P(anc), P(self.ws), st),
+                         "gmx_multinomial")
+            else:
+                be.check(c.gmx_ancestors(self.kind, kk, P(self.cdf), n, 0, P(total_out), self.n_out, 0, self.n_out, P(anc),
+                                         st), "gmx_ancestors")
+        elif self.form == "prefix":
+            be.check(c.gmx_tile_prefix(tile_max, tile_agg, n, P(self.prefix), st), "gmx_tile_prefix")
+            if self.kind == MULTINOMIAL_SORTED:
+                be.check(c.gmx_resample_sorted_p(kk, P(lw), n, shift, tile_max, P(self.prefix), P(self.table), 0, P(max_out),
+                                                 P(total_out), P(anc), st), "gmx_resample_sorted_p")
+            else:
+                be.check(c.gmx_resample_tiles_p(self.kind, kk, P(lw), n, shift, tile_max, P(self.prefix), P(max_out),
+                                                P(total_out), P(anc), st), "gmx_resample_tiles_p")
+        elif self.kind == MULTINOMIAL_TILED:
+            be.check(c.gmx_multinomial_tiled(kk, P(lw), n, shift, tile_max, tile_agg, P(uniforms), P(max_out), P(total_out),
+                                             P(anc), P(self.ws), phase, st), "gmx_multinomial_tiled")
+        elif self.kind == MULTINOMIAL_SORTED:
+            table, ready = (self.table, 0) if uniforms is None else (uniforms, 1)
+            be.check(c.gmx_resample_sorted(kk, P(lw), n, shift, tile_max, tile_agg, P(table), ready, P(max_out),
+                                           P(total_out), P(anc), st), "gmx_resample_sorted")
+        elif uniforms is not None:
+            be.check(c.gmx_resample_tiles_u(self.kind, kk, P(lw), n, shift, tile_max, tile_agg, P(uniforms), P(max_out),
+                                            P(total_out), P(anc), st), "gmx_resample_tiles_u")
+        elif stats is not None:        # (in a sweep: tile maxima = the workgroup maxima the site program left)
+            be.check(c.gmx_resample_tiles(self.kind, kk, P(lw), n, shift, tile_max, tile_agg, P(max_out), P(total_out),
+                                          P(anc), st), "gmx_resample_tiles")
+        else:
+            be.check(c.gmx_resample(self.kind, kk, P(lw), n, shift, P(partials), rows, P(max_out), P(total_out), P(anc),
+                                    P(self.ws), st), "gmx_resample")
+
+
+def _tile_stats(lw, shift, tile_max, tile_agg):
+    """gmx_tile_stats: the CDF tile statistics of log-weights no site program left them for"""
+    be = _lib.get()
+    be.check(be.c.gmx_tile_stats(be.ptr(lw), lw.numel(), shift, be.ptr(tile_max), be.ptr(tile_agg), be.stream()),
+             "gmx_tile_stats")
+
+
 def resample_fused(kind, key: Key, lw: torch.Tensor):
     """gmx_resample: log-weights -> (ancestors int32 [n], total [1], max [1], shift) in two launches with no CDF
     array (tile statistics + k_offspring_tile); the same integers as weight_cdf + ancestors_from_cdf."""
-    be = _lib.get()
     stats = getattr(lw, "_gmx_tile_stats", None)       # left by the program that computed these weights (run_gfi)
     if stats is not None and (len(stats) < 5 or stats[4] != lw._version):
         stats = None                       # the weights were changed in place since: the statistics are stale
@@ -528,82 +662,31 @@ def resample_fused(kind, key: Key, lw: torch.Tensor):
         stats = None
     n = lw.numel()
     shift = cdf_shift(n)
+    if stats is not None and not (stats[2] == shift and stats[3] == n):
+        stats = None
     anc = torch.empty((n,), dtype=torch.int32, device=lw.device)
     total = torch.empty((1,), dtype=torch.int64, device=lw.device)
     mx = torch.empty((1,), dtype=torch.float32, device=lw.device)
-    if int(kind) in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):     # tile statistics, then the kind's own entry point
-        kh = key.host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-        if not (stats is not None and stats[2] == shift and stats[3] == n):
-            tiles = (n + 1023) // 1024
-            stats = (torch.empty((tiles,), dtype=torch.float32, device=lw.device),
-                     torch.empty((tiles,), dtype=torch.int64, device=lw.device))
-            be.check(be.c.gmx_tile_stats(be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(stats[1]), be.stream()), "gmx_tile_stats")
-        if int(kind) == MULTINOMIAL_SORTED and n > FUSED_RESAMPLE_MAX:
-            # past 2048 tiles (config 4's k = 1e7): the tile prefixes from one workgroup, the table kernels in chunks
-            table = torch.empty((int(be.c.gmx_sorted_uniforms_words(n)),), dtype=torch.int32, device=lw.device)
-            pref = torch.empty((int(be.c.gmx_tile_prefix_words(n)),), dtype=torch.int64, device=lw.device)
-            be.check(be.c.gmx_tile_prefix(be.ptr(stats[0]), be.ptr(stats[1]), n, be.ptr(pref), be.stream()), "gmx_tile_prefix")
-            be.check(be.c.gmx_resample_sorted_p(kk, be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(pref), be.ptr(table), 0,
-                                                be.ptr(mx), be.ptr(total), be.ptr(anc), be.stream()), "gmx_resample_sorted_p")
-            return anc, total, mx, shift
-        if int(kind) == MULTINOMIAL_SORTED:
-            table = torch.empty((int(be.c.gmx_sorted_uniforms_words(n)),), dtype=torch.int32, device=lw.device)
-            be.check(be.c.gmx_resample_sorted(kk, be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(stats[1]), be.ptr(table), 0,
-                                              be.ptr(mx), be.ptr(total), be.ptr(anc), be.stream()), "gmx_resample_sorted")
-            return anc, total, mx, shift
-        # count buffers zeroed HERE (a fill kernel; phase 0: "buffer 0 is zero") rather than by the call's own memset
-        # (phase -1): inside `smc.capture` the memset node of a one-off workspace did not hold across replays (replay 0
-        # right, every later one wrong: tools/experiments/capture_kinds_dbg.py) — a sweep's persistent workspace is fine
-        ws = torch.zeros(((be.c.gmx_multinomial_tiled_workspace(n) + 3) // 4,), dtype=torch.int32, device=lw.device)
-        be.check(be.c.gmx_multinomial_tiled(kk, be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(stats[1]), None, be.ptr(mx),
-                                            be.ptr(total), be.ptr(anc), be.ptr(ws), 0, be.stream()), "gmx_multinomial_tiled")
-        return anc, total, mx, shift
-    if n > FUSED_RESAMPLE_MAX:
-        # more than 2048 tiles (BASELINE config 4: k = 1e7): the same kernel reading tile PREFIXES that one workgroup
-        # computes (gmx_tile_prefix) instead of every workgroup reducing the whole statistics table — still no CDF array
-        kh = key.host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-        if not (stats is not None and stats[2] == shift and stats[3] == n):
-            tiles = (n + 1023) // 1024
-            stats = (torch.empty((tiles,), dtype=torch.float32, device=lw.device),
-                     torch.empty((tiles,), dtype=torch.int64, device=lw.device))
-            be.check(be.c.gmx_tile_stats(be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(stats[1]), be.stream()), "gmx_tile_stats")
-        pref = torch.empty((int(be.c.gmx_tile_prefix_words(n)),), dtype=torch.int64, device=lw.device)
-        be.check(be.c.gmx_tile_prefix(be.ptr(stats[0]), be.ptr(stats[1]), n, be.ptr(pref), be.stream()), "gmx_tile_prefix")
-        be.check(be.c.gmx_resample_tiles_p(int(kind), kk, be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(pref), be.ptr(mx),
-                                           be.ptr(total), be.ptr(anc), be.stream()), "gmx_resample_tiles_p")
-        return anc, total, mx, shift
-    if stats is not None and stats[2] == shift and stats[3] == n:
-        kh = key.host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-        be.check(be.c.gmx_resample_tiles(int(kind), kk, be.ptr(lw), n, shift, be.ptr(stats[0]), be.ptr(stats[1]),
-                                         be.ptr(mx), be.ptr(total), be.ptr(anc), be.stream()), "gmx_resample_tiles")
-        return anc, total, mx, shift
-    ws = torch.empty(((be.c.gmx_resample_workspace(n) + 7) // 8,), dtype=torch.int64, device=lw.device)
-    kh = key.host()
-    kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-    be.check(be.c.gmx_resample(int(kind), kk, be.ptr(lw), n, shift, None, 0, be.ptr(mx), be.ptr(total), be.ptr(anc),
-                               be.ptr(ws), be.stream()), "gmx_resample")
+    form = _Resampler.fused_form(int(kind), n)
+    if stats is None and _Resampler.needs_stats(int(kind), form):
+        tiles = (n + 1023) // 1024
+        stats = (torch.empty((tiles,), dtype=torch.float32, device=lw.device),
+                 torch.empty((tiles,), dtype=torch.int64, device=lw.device))
+        _tile_stats(lw, shift, *stats)
+    # the two-stage multinomial's count buffers are zeroed HERE (the fill kernel of the launcher's allocation; phase 0:
+    # "buffer 0 is zero") rather than by the call's own memset
+    # (phase -1): inside `smc.capture` the memset node of a one-off workspace did not hold across replays (replay 0
+    # right, every later one wrong: tools/experiments/capture_kinds_dbg.py) — a sweep's persistent workspace is fine
+    rs = _Resampler(kind, n, form=form, with_stats=stats is not None)
+    rs.launch(key, lw, mx, total, anc, stats=stats and stats[:2], phase=0)
     return anc, total, mx, shift
 
 
 def ancestors_from_cdf(kind, key: Key, cdf, total, n_out=None) -> torch.Tensor:
-    be = _lib.get()
     n_in = cdf.numel()
     n_out = n_in if n_out is None else int(n_out)
-    kh = key.host()
-    kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
     anc = torch.empty((n_out,), dtype=torch.int32, device=cdf.device)
-    if int(kind) == MULTINOMIAL and n_in >= MULTINOMIAL_GUIDED_MIN:
-        # unordered slots: through the guide table (two table reads + a search over ~3 entries per slot instead of a
-        # binary search over n_in) — the same ancestors
-        ws = torch.empty(((be.c.gmx_multinomial_workspace(n_in) + 3) // 4,), dtype=torch.int32, device=cdf.device)
-        be.check(be.c.gmx_multinomial(kk, be.ptr(cdf), n_in, be.ptr(total), n_out, be.ptr(anc), be.ptr(ws), be.stream()),
-                 "gmx_multinomial")
-        return anc
-    be.check(be.c.gmx_ancestors(int(kind), kk, be.ptr(cdf), n_in, 0, be.ptr(total), n_out, 0, n_out,
-                                be.ptr(anc), be.stream()), "gmx_ancestors")
+    _Resampler(kind, n_in, n_out, form="cdf", cdf=cdf).launch(key, None, None, total, anc, cdf_ready=True)
     return anc
 
 
@@ -616,12 +699,8 @@ def resample(key: Key, collection: ParticleCollection, kind="systematic", n_out=
         raise NotImplementedError("resample: batched collections")
     kind = _KINDS[kind] if isinstance(kind, str) else int(kind)
     n = lw.numel()
-    if (kind in _TILE_KINDS and n_out in (None, n) and 0 < n <= FUSED_RESAMPLE_MAX) or \
-            (kind in (SYSTEMATIC, STRATIFIED, MULTINOMIAL_SORTED) and n_out in (None, n) and FUSED_RESAMPLE_MAX < n < 2 ** 31 - 8192):
+    if _Resampler.form_of(kind, n, n_out) != "cdf":
         anc, total, mx, shift = resample_fused(kind, key, lw)        # no CDF in memory (gmx_resample[_tiles[_p]])
-    elif kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):
-        raise NotImplementedError("resample(kind='multinomial_tiled'): n_out = n <= 2^21; 'multinomial_sorted': n_out = n "
-                                  "(use 'multinomial')")
     else:
         cdf, total, mx, shift = weight_cdf(lw)
         anc = ancestors_from_cdf(kind, key, cdf, total, n_out)
@@ -741,15 +820,56 @@ def capture(loop_fn, *args, warmup: int = 1, noise_ahead=None) -> CapturedLoop:
 class _NoiseAhead:
     """The noise-ahead machinery shared by BootstrapSweep and sharded.ShardedBootstrapSweep: background
     programs that draw the chain programs' hoisted normal / uniform values on a second stream, a group of steps ahead.
-    The host class provides n, T, step_keys, specialize, fuse_mh, `_chain_prog(t)` (the site program of step t) and
-    `_chain_step(t, skip_vm)` (everything step t launches on the chain); `_noise_total` / `_noise_offset`: the keys of
-    this shard are children offset .. offset + n - 1 of split(k, total) (a single GPU: total = n, offset = 0)."""
+    The host class provides n, T, specialize, fuse_mh, `_chain_prog(t)` (the site program of step t),
+    `_chain_step(t, skip_vm)` (everything step t launches on the chain) and `enqueue()`; `_noise_total` /
+    `_noise_offset`: the keys of this shard are children offset .. offset + n - 1 of split(k, total) (a single GPU:
+    total = n, offset = 0).  Also what the two sweeps do alike besides: the per-step key schedule, capturing enqueue()
+    into a graph and dropping that graph."""
 
     NOISE_LDS_PAD = 56000      # bytes of unused LDS per noise workgroup: two of them per CU (160 KB)
     NOISE_GROUP = 10           # steps per group of noise launches (the noise runs one group ahead of the chain)
     NOISE_RING = 3             # groups of noise buffers (the background stream runs at most NOISE_RING - 1 groups ahead)
     _noise_offset = 0
     _noise_total = None
+    graph = None
+
+    def _set_step_keys(self, key):
+        """step key = fold_in(run key, t); (k_prop, k_res, k_mh) = split(step key, 3) — on the host"""
+        self.step_keys = []
+        for t in range(self.T):
+            ks = split(fold_in(key, t), 3)
+            self.step_keys.append((ks[0], ks[1], ks[2]))
+
+    def _drop_graph(self):
+        """release the captured graph (it holds the launch arguments and buffers of the run it was captured for), once
+        the stream has drained"""
+        if self.graph is None:
+            return
+        be = _lib.get()
+        if be.uses_streams:
+            torch.cuda.synchronize()
+        be.c.gmx_graph_destroy(self.graph)
+        self.graph = None
+
+    def capture(self):
+        """Capture enqueue() into a hipGraph (launch-bound: ~5 nodes per step)."""
+        be = _lib.get()
+        from ctypes import c_void_p
+        s = torch.cuda.Stream(device=be.device)
+        s.wait_stream(torch.cuda.current_stream(be.device))
+        with torch.cuda.stream(s):
+            self.enqueue()          # warm-up outside capture (program upload, lazy init)
+            s.synchronize()
+            be.check(be.c.gmx_capture_begin(be.stream()), "gmx_capture_begin")
+            try:
+                self.enqueue()
+            finally:
+                h = c_void_p()
+                rc = be.c.gmx_capture_end(be.stream(), h)
+            be.check(rc, "gmx_capture_end")
+        torch.cuda.current_stream(be.device).wait_stream(s)
+        self.graph = h
+        return self
 
     def _noise_split(self, k):
         total = self._noise_total or self.n
@@ -1176,7 +1296,6 @@ class BootstrapSweep(_NoiseAhead):
         self.kind = _KINDS[resample] if isinstance(resample, str) else int(resample)
         self.step_extra = step_extra or (lambda t: ())
         self.specialize = specialize
-        self.graph = None
         self.noise_ahead_req = noise_ahead
         self.chain_mh = bool(chain_mh)
         self.noise_roots = noise_roots or self.NOISE_ROOTS_MH
@@ -1193,11 +1312,7 @@ class BootstrapSweep(_NoiseAhead):
         # survives — the background launches' key rows in particular (found by the unbiasedness test on the GPU: a
         # second prepare() replayed the first run's noise launches)
         self.__dict__.pop("_noise_run_cache", None)
-        if self.graph is not None:           # a graph captured for the previous run holds its launch arguments
-            if be.uses_streams:
-                torch.cuda.synchronize()
-            be.c.gmx_graph_destroy(self.graph)
-            self.graph = None
+        self._drop_graph()                   # a graph captured for the previous run holds its launch arguments
         # noise ahead: asked for explicitly, or by default on a device with streams on the fast path (specialised
         # programs; with rejuvenate=, the MH move chained into the extension)
         fuse_mh_ok = self.chain_mh
@@ -1219,24 +1334,14 @@ class BootstrapSweep(_NoiseAhead):
         self.ys = ys.to(dev).float().contiguous()
         assert self.ys.numel() >= T
         self.lw = torch.zeros((n,), dtype=torch.float32, device=dev)
-        self.cdf = torch.zeros((n,), dtype=torch.int64, device=dev)
         self.anc = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.maxs = torch.zeros((T,), dtype=torch.float32, device=dev)
         self.totals = torch.zeros((T,), dtype=torch.int64, device=dev)
         self.shift = cdf_shift(n)
-        self.ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64, device=dev)
-        self.fused = self.kind in _TILE_KINDS and n <= (512 * 4096)
+        # fused: the resampler works from tile statistics, no CDF array (the launcher itself is built below, once it is
+        # known whether the site programs leave the statistics)
+        self.fused = _Resampler.form_of(self.kind, n, sweep=True) == "tiles"
         self.fuse = False
-        if self.kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED) and not self.fused:
-            raise NotImplementedError("resample='multinomial_tiled' / 'multinomial_sorted': n <= 2^21 per GPU (use 'multinomial')")
-        self.sorted_ws = torch.zeros((int(be.c.gmx_sorted_uniforms_words(n)),), dtype=torch.int32, device=dev) \
-            if self.kind == MULTINOMIAL_SORTED else None
-        self.mnt_ws = torch.zeros(((be.c.gmx_multinomial_tiled_workspace(n) + 3) // 4,), dtype=torch.int32, device=dev) \
-            if self.kind == MULTINOMIAL_TILED else None
-        self.mn_ws = torch.zeros(((be.c.gmx_multinomial_workspace(n) + 3) // 4,), dtype=torch.int32, device=dev) \
-            if self.kind == MULTINOMIAL else None
-        self.rs_ws = torch.zeros(((be.c.gmx_resample_workspace(n) + 7) // 8,), dtype=torch.int64, device=dev) \
-            if self.fused else None
         obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
         self.p_init = MinimalGenerate(self.init, (), obs0, (n,))
         # the state is the model's return value: a scalar, or ONE vector of D floats per particle, stored
@@ -1305,7 +1410,6 @@ class BootstrapSweep(_NoiseAhead):
             # the steady-state program draws nothing ahead although another one would: the plain programs throughout
             self.noise_ahead_req = False
             return self.prepare(key, ys)
-        self.fused = self.kind in _TILE_KINDS and n <= (512 * 4096)
         want_fuse = self.fuse_req
         if want_fuse is None:
             want_fuse = be.uses_streams
@@ -1350,6 +1454,8 @@ class BootstrapSweep(_NoiseAhead):
                                                                      and self.p_mhvm_step.comp.writes_tile_stats()):
             self.p_mhvm_init = self.p_mhvm_step = None      # the chained programs are too large for the tile form
         self.fuse_mh = self.p_mhvm_init is not None
+        self.resampler = _Resampler(self.kind, n, sweep=True, with_stats=self.tile_stats)
+        self.ws = self.resampler.cdf_ws
         if self.noise_ahead and self.rejuvenate is not None and not self.fuse_mh:
             # the noise-ahead form needs the chained program: start over with the plain ones
             if self.noise_ahead_req:
@@ -1373,11 +1479,7 @@ class BootstrapSweep(_NoiseAhead):
             self.rs_status = torch.zeros((1,), dtype=torch.int64, device=dev)
         else:
             self.lw_pp, self.partials_pp, self.tile_agg_pp = [self.lw] * 2, [self.partials] * 2, [self.tile_agg] * 2
-        # per-step keys on the host
-        self.step_keys = []
-        for t in range(T):
-            ks = split(fold_in(key, t), 3)
-            self.step_keys.append((ks[0], ks[1], ks[2]))
+        self._set_step_keys(key)
         self._slot_uniforms_setup()
         self.hist_xs = self.hist_lws = self.hist_ancs = self.hist_status = None
         if self.keep_history:
@@ -1496,31 +1598,7 @@ class BootstrapSweep(_NoiseAhead):
 
     def _rows(self, t) -> int:
         """partial rows the site program of step t wrote"""
-        prog = self.p_init if t == 0 else (self.p_step if not self.fuse_mh else
-                                           (self.p_mhvm_init if t == 1 else self.p_mhvm_step))
-        return int(_lib.get().c.gmx_program_grid(prog.comp.handle, self.n))
-
-    def _launch_cdf(self, t):
-        be = _lib.get()
-        w = t % 2 if self.fuse else 0          # (a one-launch sweep alternates two sets of log-weights / partials)
-        be.check(be.c.gmx_weight_cdf(be.ptr(self.lw_pp[w]), self.n, self.shift, be.ptr(self.partials_pp[w]),
-                                     self._rows(t), be.ptr(self.maxs[t:t + 1]), be.ptr(self.cdf),
-                                     be.ptr(self.totals[t:t + 1]), be.ptr(self.ws), be.stream()),
-                 "gmx_weight_cdf")
-
-    def _launch_anc(self, t):
-        be = _lib.get()
-        kh = self.step_keys[t][1].host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-        if self.kind == MULTINOMIAL and self.n >= MULTINOMIAL_GUIDED_MIN:
-            if getattr(self, "mn_ws", None) is None:
-                self.mn_ws = torch.zeros(((be.c.gmx_multinomial_workspace(self.n) + 3) // 4,), dtype=torch.int32,
-                                         device=be.device)
-            be.check(be.c.gmx_multinomial(kk, be.ptr(self.cdf), self.n, be.ptr(self.totals[t:t + 1]), self.n,
-                                          be.ptr(self.anc), be.ptr(self.mn_ws), be.stream()), "gmx_multinomial")
-            return
-        be.check(be.c.gmx_ancestors(self.kind, kk, be.ptr(self.cdf), self.n, 0, be.ptr(self.totals[t:t + 1]),
-                                    self.n, 0, self.n, be.ptr(self.anc), be.stream()), "gmx_ancestors")
+        return int(_lib.get().c.gmx_program_grid(self._chain_prog(t).comp.handle, self.n))
 
     def _slot_uniforms_setup(self):
         """Stratified resampling draws one uniform per SLOT, keyed by the step's resampling key and the slot number —
@@ -1528,14 +1606,14 @@ class BootstrapSweep(_NoiseAhead):
         normals (gmx_slot_uniforms, one 2-D launch per group of steps) and the resampler reads them
         (gmx_resample_tiles_u): the same ancestors, one Threefry block per slot-edge evaluation less on the chain
         (the one-stream form draws them inside the resampler)."""
-        self.ubuf = None
+        self._u_ring = None
         if not (self.noise_ahead and self.kind in (STRATIFIED, MULTINOMIAL_TILED, MULTINOMIAL_SORTED) and self.fused
                 and self.tile_stats):
             return
         dev = self.zbuf.device
         # (the sorted multinomial's row is its whole order-statistics table: gmx_sorted_uniforms_words(n) words)
         row_words = int(_lib.get().c.gmx_sorted_uniforms_words(self.n)) if self.kind == MULTINOMIAL_SORTED else self.n
-        self.ubuf = torch.zeros((self.noise_ring, self.noise_group, row_words), dtype=torch.int32, device=dev)
+        self._u_ring = torch.zeros((self.noise_ring, self.noise_group, row_words), dtype=torch.int32, device=dev)
         self._u_keys = []
         for t0, t1 in self.noise_groups:
             # stratified: the resampling key itself; the two-stage multinomial: its first child (stage 1's key)
@@ -1547,73 +1625,47 @@ class BootstrapSweep(_NoiseAhead):
             self._u_pad = self.SORTED_LDS_PAD
 
     def _launch_group_extras(self, g):
-        if getattr(self, "ubuf", None) is None:
+        if self._u_ring is None:
             return
         be = _lib.get()
         t0, t1 = self.noise_groups[g]
         half, row = self.noise_slot[t0]
         if self.kind == MULTINOMIAL_SORTED:
             be.check(be.c.gmx_sorted_uniforms(be.ptr(self._u_keys[g]), t1 - t0, self.n,
-                                              be.ptr(self.ubuf[half, row:row + (t1 - t0)]), self._u_pad, be.stream()),
+                                              be.ptr(self._u_ring[half, row:row + (t1 - t0)]), self._u_pad, be.stream()),
                      "gmx_sorted_uniforms")
             return
-        be.check(be.c.gmx_slot_uniforms(be.ptr(self._u_keys[g]), t1 - t0, self.n, be.ptr(self.ubuf[half, row:row + (t1 - t0)]),
+        be.check(be.c.gmx_slot_uniforms(be.ptr(self._u_keys[g]), t1 - t0, self.n, be.ptr(self._u_ring[half, row:row + (t1 - t0)]),
                                         self._u_pad, be.stream()), "gmx_slot_uniforms")
 
-    def _launch_resample(self, t):
-        be = _lib.get()
-        kh = self.step_keys[t][1].host()
-        kk = (c_uint32 * 2)(int(kh[0]), int(kh[1]))
-        if self.kind == MULTINOMIAL_TILED:
-            if not self.tile_stats:
-                be.check(be.c.gmx_tile_stats(be.ptr(self.lw), self.n, self.shift, be.ptr(self.partials),
-                                             be.ptr(self.tile_agg), be.stream()), "gmx_tile_stats")
-            u_d = None
-            if getattr(self, "ubuf", None) is not None:
-                half, row = self.noise_slot[t]
-                u_d = be.ptr(self.ubuf[half, row])
-            be.check(be.c.gmx_multinomial_tiled(kk, be.ptr(self.lw), self.n, self.shift, be.ptr(self.partials),
-                                                be.ptr(self.tile_agg), u_d, be.ptr(self.maxs[t:t + 1]),
-                                                be.ptr(self.totals[t:t + 1]), be.ptr(self.anc), be.ptr(self.mnt_ws),
-                                                -1 if t == 0 else (t & 1),      # count buffers alternate: one memset per sweep
-                                                be.stream()), "gmx_multinomial_tiled")
-            return
-        if self.kind == MULTINOMIAL_SORTED:
-            if not self.tile_stats:
-                be.check(be.c.gmx_tile_stats(be.ptr(self.lw), self.n, self.shift, be.ptr(self.partials),
-                                             be.ptr(self.tile_agg), be.stream()), "gmx_tile_stats")
-            table, ready = self.sorted_ws, 0
-            if getattr(self, "ubuf", None) is not None:        # drawn ahead on the background stream
-                half, row = self.noise_slot[t]
-                table, ready = self.ubuf[half, row], 1
-            be.check(be.c.gmx_resample_sorted(kk, be.ptr(self.lw), self.n, self.shift, be.ptr(self.partials),
-                                              be.ptr(self.tile_agg), be.ptr(table), ready, be.ptr(self.maxs[t:t + 1]),
-                                              be.ptr(self.totals[t:t + 1]), be.ptr(self.anc), be.stream()),
-                     "gmx_resample_sorted")
-            return
-        if getattr(self, "ubuf", None) is not None:
-            half, row = self.noise_slot[t]
-            be.check(be.c.gmx_resample_tiles_u(self.kind, kk, be.ptr(self.lw), self.n, self.shift,
-                                               be.ptr(self.partials), be.ptr(self.tile_agg),
-                                               be.ptr(self.ubuf[half, row]), be.ptr(self.maxs[t:t + 1]),
-                                               be.ptr(self.totals[t:t + 1]), be.ptr(self.anc), be.stream()),
-                     "gmx_resample_tiles_u")
-            return
+    def _resample(self, t, cdf_only=False, cdf_ready=False):
+        """step t's resampler: the launcher's call on the persistent buffers (ancestors into `anc`, the evidence terms
+        into maxs[t] / totals[t]); cdf_only / cdf_ready: one half of the CDF-array form (kernel_timers)"""
+        rs = self.resampler
+        w = t % 2 if self.fuse else 0          # (a one-launch sweep alternates two sets of log-weights / partials)
+        lw, partials, tile_agg = self.lw_pp[w], self.partials_pp[w], self.tile_agg_pp[w]
+        stats = None
         if self.tile_stats:        # tile maxima = the workgroup maxima the site program left in partials[0]
-            w = t % 2 if self.fuse else 0
-            be.check(be.c.gmx_resample_tiles(self.kind, kk, be.ptr(self.lw_pp[w]), self.n, self.shift,
-                                             be.ptr(self.partials_pp[w]), be.ptr(self.tile_agg_pp[w]),
-                                             be.ptr(self.maxs[t:t + 1]),
-                                             be.ptr(self.totals[t:t + 1]), be.ptr(self.anc), be.stream()),
-                     "gmx_resample_tiles")
-            return
-        be.check(be.c.gmx_resample(self.kind, kk, be.ptr(self.lw), self.n, self.shift, be.ptr(self.partials),
-                                   self._rows(t), be.ptr(self.maxs[t:t + 1]),
-                                   be.ptr(self.totals[t:t + 1]), be.ptr(self.anc), be.ptr(self.rs_ws),
-                                   be.stream()), "gmx_resample")
+            stats = (partials, tile_agg)
+        elif rs.needs_stats(rs.kind, rs.form):
+            stats = (partials, tile_agg)
+            _tile_stats(lw, self.shift, *stats)
+        uniforms = None
+        if self._u_ring is not None:           # drawn ahead on the background stream
+            half, row = self.noise_slot[t]
+            uniforms = self._u_ring[half, row]
+        rows = 0
+        if (rs.form == "cdf" and not cdf_ready) or (rs.form == "tiles" and stats is None):
+            rows = self._rows(t)               # gmx_weight_cdf / gmx_resample reduce the site program's block maxima
+        rs.launch(self.step_keys[t][1], lw, self.maxs[t:t + 1], self.totals[t:t + 1], None if cdf_only else self.anc,
+                  stats=stats, uniforms=uniforms, partials=partials, rows=rows,
+                  phase=-1 if t == 0 else (t & 1),       # count buffers alternate: one memset per sweep
+                  cdf_ready=cdf_ready)
 
     def _chain_step(self, t, skip_vm=False):
-        """everything step t launches on the chain (noise-ahead form): site program', then the resampler"""
+        """everything step t launches on the chain: [the MH move], site program', then the resampler"""
+        if t >= 1 and self.rejuvenate is not None and not self.fuse_mh:
+            self._launch_mh(t)                    # (a launch of its own — one-stream form only — and not part of skip_vm)
         if not skip_vm:
             if t >= 1 and self.fuse_mh:
                 self._launch_mhvm(t)
@@ -1623,11 +1675,7 @@ class BootstrapSweep(_NoiseAhead):
                 self._record(t - 1, tagged=True)      # (this launch's prologue resampled step t - 1)
         if self.fuse and t < self.T - 1:
             return                         # step t's weights are resampled by step t + 1's launch itself
-        if self.fused:
-            self._launch_resample(t)
-        else:
-            self._launch_cdf(t)
-            self._launch_anc(t)
+        self._resample(t)
         if self.keep_history:
             self._record(t)
 
@@ -1639,25 +1687,7 @@ class BootstrapSweep(_NoiseAhead):
         if self.noise_ahead:
             return self._enqueue_noise_ahead(skip_vm)
         for t in range(self.T):
-            if t >= 1 and self.fuse_mh:
-                if not skip_vm:
-                    self._launch_mhvm(t)
-            else:
-                if t >= 1 and self.rejuvenate is not None:
-                    self._launch_mh(t)
-                if not skip_vm:
-                    self._launch_vm(t)
-            if self.keep_history and self.fuse and t >= 1 and not skip_vm:
-                self._record(t - 1, tagged=True)      # (this launch's prologue resampled step t - 1)
-            if self.fuse and t < self.T - 1:
-                continue                   # step t's weights are resampled by step t + 1's launch itself
-            if self.fused:
-                self._launch_resample(t)
-            else:
-                self._launch_cdf(t)
-                self._launch_anc(t)
-            if self.keep_history:
-                self._record(t)
+            self._chain_step(t, skip_vm)
 
     def kernel_timers(self):
         """Representative single launches (a mid-sweep step) for per-kernel timing in bench.py."""
@@ -1668,33 +1698,13 @@ class BootstrapSweep(_NoiseAhead):
         if self.fuse:
             pass                           # (the resampler is the prologue of k_vm's launch)
         elif self.fused and self.tile_stats:
-            out["k_offspring_tile"] = lambda: self._launch_resample(t)
+            out["k_offspring_tile"] = lambda: self._resample(t)
         elif self.fused:
-            out["resample(k_tile_stats+k_offspring_tile)"] = lambda: self._launch_resample(t)
+            out["resample(k_tile_stats+k_offspring_tile)"] = lambda: self._resample(t)
         else:
-            out["k_weight_cdf"] = lambda: self._launch_cdf(t)
-            out["k_ancestors"] = lambda: self._launch_anc(t)
+            out["k_weight_cdf"] = lambda: self._resample(t, cdf_only=True)
+            out["k_ancestors"] = lambda: self._resample(t, cdf_ready=True)
         return out
-
-    def capture(self):
-        """Capture enqueue() into a hipGraph (launch-bound: ~5 nodes per step)."""
-        be = _lib.get()
-        from ctypes import c_void_p
-        s = torch.cuda.Stream(device=be.device)
-        s.wait_stream(torch.cuda.current_stream(be.device))
-        with torch.cuda.stream(s):
-            self.enqueue()          # warm-up outside capture (program upload, lazy init)
-            s.synchronize()
-            be.check(be.c.gmx_capture_begin(be.stream()), "gmx_capture_begin")
-            try:
-                self.enqueue()
-            finally:
-                h = c_void_p()
-                rc = be.c.gmx_capture_end(be.stream(), h)
-            be.check(rc, "gmx_capture_end")
-        torch.cuda.current_stream(be.device).wait_stream(s)
-        self.graph = h
-        return self
 
     def launch(self):
         be = _lib.get()

@@ -1,0 +1,350 @@
+"""Shared body of tests/test_launch_trace.py and tests/golden/make_launch_trace.py: WHICH C-ABI calls a sweep or a
+one-off resampling issues, in which order, with which integers and which buffers — recorded by a proxy put in place of
+`backend.c` (after Backend._proto() has set the prototypes) and compared with a record made at an earlier commit
+(tests/golden/launch_trace_{cpu,gpu}.json).  The bit-exact tests say that the results are right; this one says that a
+change to the Python that launches (inference/smc.py, inference/sharded.py) left the launches themselves alone.
+
+What is recorded for each `gmx_*` call: the name; every integer argument; a `c_uint32 * 2` key as its two words; a
+struct (gmx_run_args, gmx_peer) as its non-zero fields.  Pointers: inside a prepared sweep every buffer is persistent,
+so a pointer is recorded as the ordinal of its first appearance in that trace ("p0", "p1", ...: which calls share which
+buffers, independent of addresses and attribute names); in a one-off call the buffers are fresh allocations and a
+pointer is recorded as "ptr" or "null" only."""
+from __future__ import annotations
+
+import ctypes
+import gc
+import json
+import os
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = {"cpu": os.path.join(HERE, "golden", "launch_trace_cpu.json"),
+          "gpu": os.path.join(HERE, "golden", "launch_trace_gpu.json")}
+KINDS = ("systematic", "stratified", "multinomial", "multinomial_tiled", "multinomial_sorted")
+TILE_KINDS = ("systematic", "stratified", "multinomial_tiled", "multinomial_sorted")
+
+
+class Recorder:
+    """stands in for Backend.c: every attribute is the library's own; `gmx_*` functions are wrapped"""
+
+    def __init__(self, c):
+        self._c, self.calls, self.identity, self._ord = c, None, False, {}
+
+    def __getattr__(self, name):
+        f = getattr(self._c, name)
+        if not name.startswith("gmx_"):
+            return f
+
+        def call(*args):
+            if self.calls is not None:
+                self.calls.append([name] + [self._arg(a) for a in args])
+            return f(*args)
+        return call
+
+    def start(self, identity):
+        self.calls, self.identity, self._ord = [], identity, {}
+
+    def stop(self):
+        out, self.calls = self.calls, None
+        return out
+
+    def _ptr(self, v):
+        if not v:
+            return "null"
+        if not self.identity:
+            return "ptr"
+        return "p%d" % self._ord.setdefault(int(v), len(self._ord))
+
+    def _arg(self, a):
+        if a is None:
+            return "null"
+        if isinstance(a, (bool, int, np.integer)):
+            return int(a)
+        if isinstance(a, float):
+            return float(a).hex()
+        if isinstance(a, bytes):
+            return a.decode()
+        if isinstance(a, ctypes.c_void_p):
+            return self._ptr(a.value)
+        if isinstance(a, ctypes.Array):
+            if a._type_ is ctypes.c_void_p:
+                return self._trim([self._ptr(v) for v in a], "null")
+            if a._type_ is ctypes.c_uint32 and len(a) == 2:
+                return {"key": [int(a[0]), int(a[1])]}
+            return self._trim([int(v) for v in a], 0)
+        if isinstance(a, ctypes.Structure):
+            return self._struct(a)
+        if hasattr(a, "_obj"):                    # ctypes.byref(struct)
+            return self._arg(a._obj)
+        if hasattr(a, "value"):                   # c_int32(3), ...
+            return self._arg(a.value)
+        return "<%s>" % type(a).__name__
+
+    @staticmethod
+    def _trim(vals, empty):
+        while vals and vals[-1] == empty:
+            vals.pop()
+        return vals
+
+    def _struct(self, s):
+        out = {}
+        for field in s._fields_:
+            if field[0].startswith("reserved"):
+                continue
+            v = getattr(s, field[0])
+            v = self._ptr(v) if field[1] is ctypes.c_void_p else self._arg(v)
+            if v not in (0, "null", [], {}):
+                out[field[0]] = v
+        return out
+
+
+def install(be):
+    """put a Recorder in place of be.c (idempotent); returns it"""
+    if not isinstance(be.c, Recorder):
+        be.c = Recorder(be.c)
+    return be.c
+
+
+def uninstall(be):
+    if isinstance(be.c, Recorder):
+        be.c = be.c._c
+
+
+def _key(seed):
+    import genjax_amd as G
+    return G.key(seed)
+
+
+# --- sweeps ----------------------------------------------------------------------------------------------------------
+def _lgssm(n=3000, T=5, **kw):
+    def make():
+        import genjax_amd as G
+        from genjax_amd import workloads
+        from genjax_amd.inference.smc import BootstrapSweep
+        init, step = workloads.make_lgssm(G)
+        return BootstrapSweep(init, step, n, T, **kw).prepare(_key(2718), torch.from_numpy(workloads.lgssm_data(T)))
+    return make
+
+
+def _nlssm_mh(n=1500, T=5, **kw):
+    """the model and the move of tests/parity.check_nlssm_mh_sweep"""
+    def make():
+        import genjax_amd as G
+        from genjax_amd import workloads
+        from genjax_amd.inference.smc import BootstrapSweep
+        init, step = workloads.make_nlssm(G)
+        req = G.StaticRequest({"x": G.Rejuvenate(G.normal, lambda chm: (chm.get_value(), 0.5))})
+        return BootstrapSweep(init, step, n, T, step_extra=lambda t: (float(t),), rejuvenate=req,
+                              **kw).prepare(_key(7), torch.from_numpy(workloads.nlssm_data(T)))
+    return make
+
+
+def _without_program_stats(make):
+    """the sweep a device builds from programs that cannot leave the CDF tile statistics (interpreted ones; the mirror's
+    always can): the resampler then takes its own pass over the log-weights"""
+    def patched():
+        from genjax_amd import engine
+        old = engine.Compiled.writes_tile_stats
+        engine.Compiled.writes_tile_stats = lambda self: False
+        try:
+            sw = make()
+        finally:
+            engine.Compiled.writes_tile_stats = old
+        assert not sw.tile_stats
+        return sw
+    return patched
+
+
+def sweep_cases():
+    """name -> a function that builds and prepares the sweep; specialize / noise_ahead / fuse_resample always explicit"""
+    cases = {}
+    for kind in KINDS:
+        for na in (False, True):
+            cases[f"lgssm/{kind}/na{int(na)}"] = _lgssm(resample=kind, specialize=True, noise_ahead=na, fuse_resample=False)
+    for na in (False, True):
+        cases[f"lgssm/systematic/fuse/na{int(na)}"] = _lgssm(specialize=True, noise_ahead=na, fuse_resample=True)
+    cases["lgssm/systematic/fuse/na1/history"] = _lgssm(specialize=True, noise_ahead=True, fuse_resample=True, history=True)
+    cases["lgssm/systematic/na0/history"] = _lgssm(specialize=True, noise_ahead=False, fuse_resample=False, history=True)
+    for kind in KINDS:         # interpreted programs leave no tile statistics: gmx_resample, gmx_tile_stats + the kind's own
+        cases[f"lgssm/{kind}/interpreted"] = _lgssm(resample=kind, specialize=False, noise_ahead=False, fuse_resample=False)
+    for kind in TILE_KINDS:
+        cases[f"lgssm/{kind}/no_program_stats"] = _without_program_stats(
+            _lgssm(resample=kind, specialize=False, noise_ahead=False, fuse_resample=False))
+    cases["lgssm/systematic/n700"] = _lgssm(n=700, specialize=True, noise_ahead=False, fuse_resample=False)
+    cases["lgssm/systematic/n1024"] = _lgssm(n=1024, specialize=True, noise_ahead=False, fuse_resample=False)
+    # (n >= MULTINOMIAL_GUIDED_MIN: the iid multinomial through its guide table)
+    cases["lgssm/multinomial/n9000"] = _lgssm(n=9000, T=3, resample="multinomial", specialize=True, noise_ahead=False,
+                                              fuse_resample=False)
+    cases["nlssm_mh/chained"] = _nlssm_mh(specialize=True, noise_ahead=False, fuse_resample=False, chain_mh=True)
+    cases["nlssm_mh/two_launches"] = _nlssm_mh(specialize=True, noise_ahead=False, fuse_resample=False, chain_mh=False)
+    cases["nlssm_mh/chained/na1"] = _nlssm_mh(specialize=True, noise_ahead=True, fuse_resample=False, chain_mh=True)
+    return cases
+
+
+CAPTURED = ("systematic", "multinomial_tiled")          # (GPU half only: the mirror has no graph capture)
+
+
+def trace_sweep(be, make):
+    """{"enqueue": [...], "skip_vm": [...]} of one prepared sweep, after one untraced enqueue (program upload, first-launch
+    checks); `enqueue` is traced twice and must come out the same (a buffer made per launch would show here)"""
+    rec = install(be)
+    sw = make()
+    sw.enqueue()
+    out = {}
+    for name, kw in (("enqueue", {}), ("enqueue_again", {}), ("skip_vm", {"skip_vm": True})):
+        rec.start(identity=True)
+        sw.enqueue(**kw)
+        out[name] = rec.stop()
+    _sync(be)
+    assert out["enqueue"] == out.pop("enqueue_again"), "two enqueues of one prepared sweep issued different calls"
+    return out
+
+
+def trace_captured(be, kind):
+    """prepare().capture() (the warm-up and the captured enqueue), then two launch()es"""
+    rec = install(be)
+    sw = _lgssm(resample=kind, specialize=True, noise_ahead=True, fuse_resample=False)()
+    rec.start(identity=True)
+    sw.capture()
+    sw.launch()
+    sw.launch()
+    out = rec.stop()
+    _sync(be)
+    sw.log_ml()
+    return {"capture_launch_launch": out}
+
+
+def trace_sharded(be):
+    """ShardedBootstrapSweep at world size 1, collectives issued (the fused peer exchange, as tests/parity.check_sweep_verdict)"""
+    import genjax_amd as G
+    from genjax_amd import workloads
+    from genjax_amd.inference.sharded import ShardedBootstrapSweep
+
+    class _Solo:
+        @staticmethod
+        def get_rank(): return 0
+        @staticmethod
+        def get_world_size(): return 1
+    rec = install(be)
+    old = os.environ.get("GENMI_COMM")
+    os.environ["GENMI_COMM"] = "peer"
+    try:
+        n, T = 3072, 5
+        init, step = workloads.make_lgssm(G)
+        sw = ShardedBootstrapSweep(init, step, n, T, _Solo, always_communicate=True, specialize=True,
+                                   noise_ahead=be.uses_streams).prepare(_key(3), torch.from_numpy(workloads.lgssm_data(T)))
+        sw.launch()
+        sw.finish()
+        rec.start(identity=True)
+        sw.launch()
+        sw.finish()
+        out = rec.stop()
+        assert sw.reruns == 0
+        sw.close()
+    finally:
+        if old is None:
+            os.environ.pop("GENMI_COMM", None)
+        else:
+            os.environ["GENMI_COMM"] = old
+    return {"launch_finish": out}
+
+
+def _sync(be):
+    if be.uses_streams:
+        torch.cuda.synchronize()
+
+
+# --- one-off calls ---------------------------------------------------------------------------------------------------
+def _weights(be, n, seed=5):
+    lw = (np.random.default_rng(seed).normal(size=n) * 1.5).astype(np.float32)
+    return torch.from_numpy(lw).to(be.device)
+
+
+def _with_stats(be, lw):
+    """leave on `lw` what a site program leaves (static.run_gfi): (tile maxima, tile sums, shift, n, version)"""
+    from genjax_amd.inference import smc
+    n = lw.numel()
+    tiles, shift = (n + 1023) // 1024, smc.cdf_shift(n)
+    tmax = torch.empty((tiles,), dtype=torch.float32, device=lw.device)
+    tagg = torch.empty((tiles,), dtype=torch.int64, device=lw.device)
+    be.check(be.c.gmx_tile_stats(be.ptr(lw), n, shift, be.ptr(tmax), be.ptr(tagg), be.stream()), "gmx_tile_stats")
+    lw._gmx_tile_stats = (tmax, tagg, shift, n, lw._version)
+    return lw
+
+
+def _collection(lw):
+    from genjax_amd.inference.smc import ParticleCollection
+    from genjax_amd.static import DistributionTrace
+    return ParticleCollection(DistributionTrace(None, (), lw.clone(), lw.clone()), lw)
+
+
+def trace_one_offs(be, n=3000):
+    from genjax_amd.inference import smc
+    rec = install(be)
+    out = {}
+
+    def traced(name, fn):
+        rec.start(identity=False)
+        fn()
+        out[name] = rec.stop()
+        _sync(be)
+    for kind in TILE_KINDS:
+        kid = smc._KINDS[kind]
+        lw = _with_stats(be, _weights(be, n))
+        traced(f"resample_fused/{kind}/stats", lambda: smc.resample_fused(kid, _key(11), lw))
+        lw.add_(0.25)                                   # in place: the statistics on the tensor are stale now
+        traced(f"resample_fused/{kind}/stale", lambda: smc.resample_fused(kid, _key(11), lw))
+    for kind in KINDS:
+        coll = _collection(_weights(be, n))
+        traced(f"resample/{kind}", lambda: smc.resample(_key(12), coll, kind))
+    coll = _collection(_weights(be, n))
+    traced("resample/multinomial/n_out100", lambda: smc.resample(_key(12), coll, "multinomial", n_out=100))
+    coll = _collection(_weights(be, 9000))
+    traced("resample/multinomial/n9000", lambda: smc.resample(_key(12), coll, "multinomial"))
+    big = _weights(be, 2 ** 21 + 1)                     # the smallest size past RS_MAX_TILES tiles: the prefix form
+    for kind in ("systematic", "multinomial_sorted"):
+        traced(f"resample_fused/{kind}/prefix", lambda: smc.resample_fused(smc._KINDS[kind], _key(13), big))
+    return out
+
+
+# --- the whole record ------------------------------------------------------------------------------------------------
+def case_names(backend):
+    names = list(sweep_cases()) + ["sharded", "one_offs"]
+    if backend == "gpu":
+        names += [f"captured/{k}" for k in CAPTURED]
+    return names
+
+
+def trace_case(be, name):
+    gc.collect()                   # programs of earlier sweeps are destroyed (gmx_program_destroy) now, not whenever the
+    gc.disable()                   # collector happens to run inside a record
+    try:
+        if name == "sharded":
+            return trace_sharded(be)
+        if name == "one_offs":
+            return trace_one_offs(be)
+        if name.startswith("captured/"):
+            return trace_captured(be, name.split("/", 1)[1])
+        return trace_sweep(be, sweep_cases()[name])
+    finally:
+        gc.enable()
+        uninstall(be)
+
+
+def load_golden(backend):
+    with open(GOLDEN[backend]) as fh:
+        return json.load(fh)
+
+
+def check_case(be, backend, name):
+    """the case's record equals the committed one, call for call"""
+    want = load_golden(backend)["cases"][name]
+    got = json.loads(json.dumps(trace_case(be, name)))
+    assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    for part in want:
+        a, b = got[part], want[part]
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert x == y, f"{name} / {part}: call {i} is {x}, recorded at the parent: {y}"
+        assert len(a) == len(b), f"{name} / {part}: {len(a)} calls, recorded at the parent: {len(b)}"
