@@ -905,6 +905,14 @@ extern "C" int gmx_random_bits(const uint32_t* keys_d, int64_t n, int64_t m, uin
 #define LSE_ITEMS 16
 #define LSE_TILE (GMX_BLOCK * LSE_ITEMS)
 
+// Special values (include/genmi.h "Log-normaliser").  The maximum m ignores NaN (gmx_rmax), so it is never NaN.  A
+// finite m takes the sequence m + log(sum exp(x - m)): a NaN in the row reaches the sum through exp.  An infinite m
+// (+inf: the row holds +inf; -inf: nothing in it is finite or +inf) would give exp(inf - inf), so there the sum runs
+// over 0 for every number and x itself for every NaN, and the result is m + that sum: m, or NaN.  In the two-stage
+// form a tile's partial sum is NaN exactly when the tile holds a NaN, whichever branch made it.
+__device__ __forceinline__ bool lse_finite(float m) { return m > -gmx_inf() && m < gmx_inf(); }
+__device__ __forceinline__ float lse_nan_only(float x) { return x != x ? x : 0.0f; }
+
 // stage 1: one block per (row, tile) -> partial (max, sum exp(x - max))
 __global__ void __launch_bounds__(GMX_BLOCK)
 k_lse_tiles(const float* __restrict__ lw, int64_t cols, int64_t tiles_per_row,
@@ -923,9 +931,12 @@ k_lse_tiles(const float* __restrict__ lw, int64_t cols, int64_t tiles_per_row,
   }
   m = block_max(m, lds4);
   float s = 0.0f;
-  if (m > -gmx_inf()) {
+  if (lse_finite(m)) {
 #pragma unroll
     for (int k = 0; k < LSE_ITEMS; ++k) s += gmx_expf(v[k] - m);
+  } else {
+#pragma unroll
+    for (int k = 0; k < LSE_ITEMS; ++k) s += lse_nan_only(v[k]);
   }
   s = block_sum(s, lds4);
   if (threadIdx.x == 0) {
@@ -944,12 +955,14 @@ k_lse_final(const float* __restrict__ partials, int64_t n_part, float* __restric
   for (int64_t j = threadIdx.x; j < n_part; j += GMX_BLOCK) m = gmx_rmax(m, p[2 * j]);
   m = block_max(m, lds4);
   float s = 0.0f;
-  if (m > -gmx_inf())
+  if (lse_finite(m))
     for (int64_t j = threadIdx.x; j < n_part; j += GMX_BLOCK)
       s += p[2 * j + 1] * gmx_expf(p[2 * j] - m);
+  else
+    for (int64_t j = threadIdx.x; j < n_part; j += GMX_BLOCK) s += lse_nan_only(p[2 * j + 1]);
   s = block_sum(s, lds4);
   if (threadIdx.x == 0) {
-    out[row] = (m > -gmx_inf()) ? m + gmx_logf(s) : m;
+    out[row] = lse_finite(m) ? m + gmx_logf(s) : m + s;
     if (out_max) out_max[row] = m;
   }
 }
@@ -965,11 +978,13 @@ k_lse_rows(const float* __restrict__ lw, int64_t rows, int64_t cols, float* __re
   for (int64_t j = lane; j < cols; j += GMX_WAVE) m = gmx_rmax(m, x[j]);
   m = wave_max(m);
   float s = 0.0f;
-  if (m > -gmx_inf())
+  if (lse_finite(m))
     for (int64_t j = lane; j < cols; j += GMX_WAVE) s += gmx_expf(x[j] - m);
+  else
+    for (int64_t j = lane; j < cols; j += GMX_WAVE) s += lse_nan_only(x[j]);
   s = wave_sum(s);
   if (lane == 0) {
-    out[row] = (m > -gmx_inf()) ? m + gmx_logf(s) : m;
+    out[row] = lse_finite(m) ? m + gmx_logf(s) : m + s;
     if (out_max) out_max[row] = m;
   }
 }

@@ -279,6 +279,15 @@ int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_args* args_h,
  *   src/genjax/_src/inference/smc.py:96-97 (log-ML estimate), :107, :464.
  * out_d[r] = logsumexp(lw_d[r, 0:cols]); deterministic (fixed reduction tree).
  * workspace: gmx_logsumexp_workspace(rows, cols) bytes.
+ * Special values, as jax.scipy.special.logsumexp answers them:
+ *   a row that is all -inf      -> -inf   (no mass)
+ *   a row that holds +inf       -> +inf
+ *   a row that holds a NaN      -> NaN    (all NaN, one NaN among numbers, NaN beside +inf or -inf alike)
+ * out_max_d[r] = the largest NUMBER of the row (NaN is ignored there; -inf when the row holds no number): the
+ * reference point a caller subtracts, not a NaN detector.
+ * Dispatch: rows >= 32 with cols <= 4096 take one wave per row (any number of rows, 16 bytes of workspace); every
+ * other shape takes two stages over tiles of 4096 columns (two floats of workspace per (row, tile)) and is refused
+ * with rows > 65535.
  * ---------------------------------------------------------------------- */
 size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols);
 int gmx_logsumexp(const float* lw_d, int64_t rows, int64_t cols, float* out_d,

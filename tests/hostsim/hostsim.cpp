@@ -216,15 +216,27 @@ extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_ar
 }
 
 // ---- logsumexp (sequential; float tolerance vs the device tree) ----
-extern "C" size_t gmx_logsumexp_workspace(int64_t, int64_t) { return 16; }
+// (the size the device asks for: 16 bytes on its one-wave-per-row path, two floats per (row, tile of 4096) otherwise)
+extern "C" size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols) {
+  if (rows <= 0 || cols <= 0 || (rows >= 32 && cols <= 4096)) return 16;
+  return (size_t)(rows * ((cols + 4095) / 4096) * 2 * sizeof(float)) + 16;
+}
+// special values as the device's kernels (csrc/gmx_kernels.hip, include/genmi.h): an infinite maximum gives m, or NaN
+// when the row holds a NaN; the refusal of more than 65535 rows on the two-stage path is the device's too
 extern "C" int gmx_logsumexp(const float* lw, int64_t rows, int64_t cols, float* out, float* out_max, void*, gmx_stream) {
+  if (rows <= 0) return 0;
+  if (cols <= 0) return fail("gmx_logsumexp: cols must be positive");
+  if (!lw || !out) return fail("gmx_logsumexp: null argument");
+  if (!(rows >= 32 && cols <= 4096) && rows > 65535) return fail("gmx_logsumexp: too many long rows");
   for (int64_t r = 0; r < rows; ++r) {
     const float* x = lw + r * cols;
     float m = -gmx_inf();
     for (int64_t j = 0; j < cols; ++j) m = gmx_rmax(m, x[j]);
+    const bool finite = m > -gmx_inf() && m < gmx_inf();
     float s = 0.0f;
-    if (m > -gmx_inf()) for (int64_t j = 0; j < cols; ++j) s += gmx_expf(x[j] - m);
-    out[r] = (m > -gmx_inf()) ? m + gmx_logf(s) : m;
+    if (finite) for (int64_t j = 0; j < cols; ++j) s += gmx_expf(x[j] - m);
+    else for (int64_t j = 0; j < cols; ++j) s += x[j] != x[j] ? x[j] : 0.0f;
+    out[r] = finite ? m + gmx_logf(s) : m + s;
     if (out_max) out_max[r] = m;
   }
   return 0;
@@ -251,7 +263,8 @@ extern "C" size_t gmx_sum_rows_workspace(int64_t rows, int64_t cols) {
 }
 extern "C" int gmx_sum_rows(const float* x, int64_t rows, int64_t cols, float* out, void* ws, gmx_stream) {
   if (rows <= 0) return 0;
-  if (cols <= 0 || !x || !out || !ws) return fail("sum_rows: bad argument");
+  if (cols <= 0 || !x || !out || !ws) return fail("gmx_sum_rows: bad argument");
+  if (rows > 65535) return fail("gmx_sum_rows: too many rows");
   const int64_t tiles = (cols + 4095) / 4096;
   float* part = (float*)ws;
   for (int64_t r = 0; r < rows; ++r) {
