@@ -77,16 +77,195 @@ def _check_shard_alignment(n_per_rank: int, world: int):
                          f"use {((n_per_rank + CDF_TILE - 1) // CDF_TILE) * CDF_TILE}")
 
 
+class _ShardRouter:
+    """The exchange of ONE sharded resampling, for the sweep and for the one-off global resample alike — the sharded
+    counterpart of smc._Resampler.  form_of() picks the form once; the constructor allocates that form's workspaces and
+    no other's; bind() builds that form's argument tuples for one step; launch() issues the chain that follows the site
+    program: statistics or CDF, collective or local copy, totals, then per routed leaf the routing launch and its
+    all-to-all.  Every C entry point of the exchange has its one call site in launch().
+
+      "tiles"  all-gather of the ranks' CDF tile statistics; gmx_shard_step_fused (one leaf, fused=True), else
+               gmx_shard_totals + one gmx_shard_step_tiles per leaf
+      "peer"   the tiles form over comm.PeerComm: no collective launch — gmx_shard_step_peer routes every leaf, or
+               (deferred=True: the one-launch step) the next step's program does
+      "cdf"    all-reduce MAX, gmx_weight_cdf against the global max, all-gather of the 8-byte totals, one gmx_shard_step
+               (the sorted multinomial: gmx_shard_step_sorted against the step's table) per leaf
+
+    A leaf is (rows, send, recv): the [n + W*C] row whose first n values are routed (ancestors index into all of it),
+    the [W*C] send blocks, and where the all-to-all delivers (rows[n:]; None: the caller ships the blocks itself)."""
+
+    @staticmethod
+    def form_of(kind, n_per_rank, world, *, cdf_form=False, peer_capable=False, sweep=True):
+        """"peer" | "tiles" | "cdf".  sweep=False (the one-off global resample): any per-rank size takes the tile
+        statistics — gmx_shard_totals / gmx_shard_step_tiles stride over the table; a sweep's site program and its fused
+        routing hold a tile row per workgroup, hence FUSED_RESAMPLE_MAX per rank."""
+        from .smc import FUSED_RESAMPLE_MAX
+        if kind == MULTINOMIAL_SORTED:
+            # routed against the order-statistics table of all N slots (i32 words), which every rank draws in full
+            if sweep and n_per_rank * world >= 1 << 31:
+                raise NotImplementedError("resample='multinomial_sorted' across ranks: n_per_rank * world < 2^31")
+            return "cdf"
+        if cdf_form or world > 64 or (sweep and n_per_rank > FUSED_RESAMPLE_MAX):
+            return "cdf"
+        return "peer" if peer_capable else "tiles"
+
+    def __init__(self, form, kind, n, rank, world, shift, cx=None, comm=False, fused=True, sets=1):
+        """cx: the communicator (destinations of collectives come from it); comm: issue the collectives (else local
+        copies); sets=2: two sets of tile statistics (the one-launch step reads step t - 1's while it writes step t's)"""
+        be = _lib.get()
+        dev, W = be.device, world
+        self.form, self.kind, self.n, self.rank, self.world, self.shift = form, kind, int(n), rank, world, shift
+        self.cx, self.comm, self.fused = cx, bool(comm), bool(fused)
+        self.tiles = (self.n + CDF_TILE - 1) // CDF_TILE
+        self.capacity = self.land = self.sorted_tab = self.sorted_keys = None
+
+        def zeros(shape, dt):
+            return torch.zeros(shape, dtype=dt, device=dev)
+        shared = cx.alloc if cx is not None else zeros
+        self.plan = zeros((int(be.c.gmx_shard_plan_words(W)),), torch.int64)
+        self.totals_all = shared((W,), torch.int64)
+        if form == "cdf":
+            self.cdf = zeros((self.n,), torch.int64)
+            self.total_d = zeros((1,), torch.int64)
+            self.ws = zeros(((be.c.gmx_weight_cdf_workspace(self.n) + 7) // 8,), torch.int64)
+            if kind == MULTINOMIAL_SORTED:      # every rank draws the SAME table of the N global slots from the step's key
+                self.sorted_tab = zeros((int(be.c.gmx_sorted_uniforms_words(self.n * W)),), torch.int32)
+            return
+        sb = int(be.c.gmx_shard_stats_bytes(self.n))
+        pad = self.tiles + (self.tiles & 1)
+        self.stats_own = [zeros((sb,), torch.uint8) for _ in range(sets)]
+        self.stats_all = shared((W * sb,), torch.uint8)
+        self.tile_agg = [b_[:pad * 8].view(torch.int64) for b_ in self.stats_own]
+        self.tile_max = [b_[pad * 8:].view(torch.float32) for b_ in self.stats_own]
+        if form == "peer":
+            self.tag, self.status = cx.step_words()
+
+    def set_capacity(self, capacity, max_leaves=1):
+        """particles a rank may ship to ONE peer; "peer": the landing block for that many (COLLECTIVE)"""
+        self.capacity = int(capacity)
+        if self.form == "peer":
+            # what crosses ranks lands in the communicator's fine-grained landing block; the extended states (and their
+            # tails, filled by this rank's own routing launch) are ordinary memory
+            self.land, _ = self.cx.landing(self.n, self.capacity, max_leaves)
+
+    def set_sorted_keys(self, words):
+        """the resampling keys ([steps, 2] uint32, host) gmx_sorted_uniforms draws each step's table from"""
+        hk = np.ascontiguousarray(words, dtype=np.uint32)
+        self.sorted_keys = torch.from_numpy(hk.view(np.int32)).to(_lib.get().device)
+
+    def peer(self, step, leaves):
+        """the gmx_peer of `step` routing `leaves`: for that step's own launches, and for the next step's program when it
+        routes this one as its prologue"""
+        p = _lib.Peer()
+        p.land_d, p.tag_base_d, p.status_d = self.land.data_ptr(), self.tag.data_ptr(), self.status.data_ptr()
+        p.rank, p.world, p.step, p.tiles = self.rank, self.world, step, self.tiles
+        p.capacity, p.leaves = self.capacity, len(leaves)
+        return p
+
+    def bind(self, t, key, lw, m, tot, leaves, idx, *, w=0, program_stats=False, pmax=None, pmax_rows=0, deferred=False):
+        """The argument tuples of step t's exchange (all buffers persistent): log-weights `lw` -> global max `m`,
+        global total `tot`, ancestors `idx`, the leaves routed under resampling key `key`.  w: which set of tile
+        statistics; program_stats: the site program left them (and put them to the peers); pmax[:pmax_rows]: the block
+        maxima gmx_weight_cdf reduces (None: `m` holds the global max already); deferred: the next step's program
+        routes this one."""
+        P = _lib.get().ptr
+        kk = _key_words(key)
+        g, W, n, C = self.rank, self.world, self.n, self.capacity
+        b = {"keep": (kk, leaves), "entry": "cdf", "pmax": pmax, "stats": None, "put": None, "peer": None, "peer_step": None,
+             "gather": None, "totals": None, "sorted": None, "routes": []}
+        if self.form == "cdf":
+            # the CDF kernel reduces the (all-reduced) block maxima itself and records the max in `m`
+            b["stats"] = (P(lw), n, self.shift, None if pmax is None else P(pmax), pmax_rows, P(m), P(self.cdf),
+                          P(self.total_d), P(self.ws))
+            b["gather"] = (self.totals_all, self.total_d)                # 8 bytes per rank
+            head = (self.kind, kk)
+            if self.sorted_tab is not None:
+                b["entry"], head = "sorted", (P(self.sorted_tab),)
+                b["sorted"] = (P(self.sorted_keys[t]), 1, n * W, P(self.sorted_tab), 0)
+            b["routes"] = [(head + (P(self.totals_all), P(self.plan), P(tot), P(self.cdf), g, W, n, C, P(rows), P(send),
+                                    P(idx)), recv, send) for rows, send, recv in leaves]
+            return b
+        so = self.stats_own[w]
+        if not program_stats:
+            b["stats"] = (P(lw), n, self.shift, P(self.tile_max[w]), P(self.tile_agg[w]))
+        if self.form == "peer":
+            from ctypes import c_void_p
+            peer = b["peer"] = self.peer(t, leaves)
+            st_arr = (c_void_p * len(leaves))(*[rows.data_ptr() for rows, _s, _r in leaves])
+            tl_arr = (c_void_p * len(leaves))(*[recv.data_ptr() for _r, _s, recv in leaves])
+            b["keep"] += (st_arr, tl_arr)
+            if not program_stats:
+                b["put"] = (P(so), peer, n)
+            if not deferred:
+                b["peer_step"] = (self.kind, kk, P(so), peer, P(self.plan), P(tot), P(lw), P(m), self.shift, n, st_arr,
+                                  tl_arr, P(idx))
+            return b
+        b["gather"] = (self.stats_all, so)                               # 12 bytes per 1024 particles per rank
+        if self.fused and len(leaves) == 1:
+            # the one routed leaf derives the totals / global max itself (one launch less in the chain)
+            rows, send, recv = leaves[0]
+            b["entry"] = "fused"
+            b["routes"] = [((self.kind, kk, P(self.stats_all), P(self.plan), P(tot), P(lw), P(m), self.shift, g, W, n, C,
+                             P(rows), P(send), P(idx)), recv, send)]
+            return b
+        b["entry"] = "tiles"
+        b["totals"] = (P(self.stats_all), W, n, P(self.totals_all), P(m))     # global max + every rank's total
+        b["routes"] = [((self.kind, kk, P(self.totals_all), P(self.plan), P(tot), P(lw), P(so), P(m), self.shift, g, W, n, C,
+                         P(rows), P(send), P(idx)), recv, send) for rows, send, recv in leaves]
+        return b
+
+    def launch(self, b, route_only=False):
+        """issue what bind() bound; route_only: the leaves again (another capacity), statistics and totals as they are"""
+        be = _lib.get()
+        c, st, ck, form = be.c, be.stream(), be.check, self.form
+        if not route_only:
+            if form == "cdf":
+                if self.comm and b["pmax"] is not None:
+                    self.cx.all_reduce_max(b["pmax"])                # element-wise MAX of the block maxima (<= 4 KB)
+                ck(c.gmx_weight_cdf(*b["stats"], st), "gmx_weight_cdf")        # global max + local integer CDF against it
+            elif b["stats"] is not None:
+                ck(c.gmx_tile_stats(*b["stats"], st), "gmx_tile_stats")
+            if form == "peer":                  # no collective launch: puts + granule waits inside the two kernels
+                if b["put"] is not None:
+                    ck(c.gmx_peer_put_stats(*b["put"], st), "gmx_peer_put_stats")
+                if b["peer_step"] is not None:  # (None: ONE launch per step — step t is routed by the launch of step t + 1)
+                    ck(c.gmx_shard_step_peer(*b["peer_step"], st), "gmx_shard_step_peer")
+                return
+            if self.comm:
+                self.cx.all_gather(*b["gather"])
+            else:
+                b["gather"][0].copy_(b["gather"][1])
+            if b["sorted"] is not None:
+                ck(c.gmx_sorted_uniforms(*b["sorted"], st), "gmx_sorted_uniforms")       # the step's table of all N slots
+            elif b["totals"] is not None:
+                ck(c.gmx_shard_totals(*b["totals"], st), "gmx_shard_totals")
+        entry = b["entry"]
+        for args, recv, send in b["routes"]:                             # slot boundaries + routing, leaf by leaf
+            if entry == "fused":
+                ck(c.gmx_shard_step_fused(*args, st), "gmx_shard_step_fused")
+            elif entry == "tiles":
+                ck(c.gmx_shard_step_tiles(*args, st), "gmx_shard_step_tiles")
+            elif entry == "sorted":
+                ck(c.gmx_shard_step_sorted(*args, st), "gmx_shard_step_sorted")
+            else:
+                ck(c.gmx_shard_step(*args, st), "gmx_shard_step")
+            if self.comm and recv is not None:
+                self.cx.all_to_all(recv, send)                       # block s of recv <- block `me` of rank s
+
+
 class ShardedBootstrapSweep(_NoiseAhead):
     """smc.BootstrapSweep over `dist.get_world_size()` ranks, n particles per rank.
 
     Per step (the tile-statistics form): site program -> all-gather of the statistics -> gmx_shard_step_fused (the
-    totals, the slot bounds, the routing: one launch) -> all-to-all.  NOISE AHEAD as on one GPU (smc._NoiseAhead): the
+    totals, the slot bounds, the routing: one launch) -> all-to-all; which form runs and what it launches is
+    _ShardRouter's.  NOISE AHEAD as on one GPU (smc._NoiseAhead): the
     step's normal draws come from background programs on a second stream — keyed by the GLOBAL particle index, so the
     draws are the single-process ones — which matters more here than on one GPU: the chain of a sharded step is
     mostly launch boundaries and collective latency, during which the vector ALUs would idle."""
 
-    fuse_mh = False
+    fuse_mh = False          # (the noise-ahead mixin: the chained MH + extension program's move draws hang off k_mh)
+    peer_tag = property(lambda self: self.router.tag)
+    peer_status = property(lambda self: self.router.status)
 
     def __init__(self, init, step, n_per_rank: int, T: int, dist, obs_addr="y", step_extra=None, specialize=True,
                  resample="systematic", capacity=None, always_communicate=False, rejuvenate=None, state_addr="x",
@@ -122,21 +301,18 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self._finished = True    # nothing launched yet: finish() / log_ml() / state() have nothing to wait for
         # rejuvenate: the MH request of smc.BootstrapSweep(rejuvenate=...) (BASELINE config 3).  The move on
         # a resampled particle needs the particle AND the state it was extended from, so two leaves are
-        # routed (two gmx_shard_step launches and two all-to-alls per step instead of one).
+        # routed (two routing launches and two all-to-alls per step instead of one).
         self.rejuvenate, self.state_addr = rejuvenate, state_addr
         self.noise_ahead_req = noise_ahead
-        # the sorted multinomial routes against the order-statistics table of all N slots (gmx_shard_step_sorted): the
-        # CDF-array form, two routing launches
-        self.cdf_form, self.fused_req = bool(cdf_form) or self.kind == MULTINOMIAL_SORTED, bool(fused)
+        self.cdf_form, self.fused_req = bool(cdf_form), bool(fused)
         self._noise_offset, self._noise_total = self.rank * self.n, self.N
         self.fuse_sh_req, self.fuse_sh = fuse_step, False      # None: one launch per step where it applies (prepare)
         self.chain_mh_req, self.chain_mh = bool(chain_mh), False   # rejuvenate=: the move and the extension as ONE program
-
-    fuse_mh = False          # (the noise-ahead mixin: the chained MH + extension program's move draws hang off k_mh)
+        self.router = self.p_mhvm_init = self.p_mhvm_step = None
+        self.peer_mode = self.tiles_mode = False
 
     def _chain_prog(self, t):
-        if t >= 1 and self.rejuvenate is not None and getattr(self, "p_mhvm_step", None) is not None and \
-                (self.chain_mh or self.fuse_mh):
+        if t >= 1 and self.rejuvenate is not None and self.p_mhvm_step is not None and (self.chain_mh or self.fuse_mh):
             return self.p_mhvm_init if t == 1 else self.p_mhvm_step
         return self.p_init if t == 0 else self.p_step
 
@@ -170,25 +346,19 @@ class ShardedBootstrapSweep(_NoiseAhead):
             return _MG(*a, hoist_noise=bool(want_na))
         self.key = key
         self.ys = ys.to(dev).float().contiguous()
-        self.lw = torch.zeros((n,), dtype=torch.float32, device=dev)
-        self.cdf = torch.zeros((n,), dtype=torch.int64, device=dev)
-        self.maxs = torch.zeros((T,), dtype=torch.float32, device=dev)           # global max per step
-        self.totals = torch.zeros((T,), dtype=torch.int64, device=dev)            # global integer total per step
-        self.total_d = torch.zeros((1,), dtype=torch.int64, device=dev)
-        self.totals_all = None      # (allocated below, once the communicator exists: a collective's destination)
-        self.plan = torch.zeros((int(be.c.gmx_shard_plan_words(W)),), dtype=torch.int64, device=dev)
-        self.verdict = torch.zeros((1,), dtype=torch.int64, device=dev)        # gmx_sweep_verdict: 0 fine, 1 overflow, 2 failed
-        self.ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64, device=dev)
-        self.shift = cdf_shift(self.N)
         if self.comm and self.cx is None:
             from .comm import make_comm
             self.cx = make_comm(self.dist, dev)
-        self.totals_all = self.cx.alloc((W,), torch.int64) if self.cx is not None else \
-            torch.zeros((W,), dtype=torch.int64, device=dev)
-        # the fused peer exchange (comm.PeerComm): no collective launch per step — tile-statistics form only
-        from .smc import FUSED_RESAMPLE_MAX as _FRM
-        self.peer_mode = bool(getattr(self.cx, "fused", False) and self.comm and self.kind in (SYSTEMATIC, STRATIFIED)
-                              and n <= _FRM and W <= 64 and not self.cdf_form)
+        # which exchange runs — "peer": the fused peer exchange (comm.PeerComm), no collective launch per step
+        self.form = _ShardRouter.form_of(self.kind, n, W, cdf_form=self.cdf_form,
+                                         peer_capable=bool(getattr(self.cx, "fused", False) and self.comm))
+        self.peer_mode, self.tiles_mode = self.form == "peer", self.form != "cdf"
+        self.router = None                               # (made below, once it is known whether the step is one launch)
+        self.lw = torch.zeros((n,), dtype=torch.float32, device=dev)
+        self.maxs = torch.zeros((T,), dtype=torch.float32, device=dev)           # global max per step
+        self.totals = torch.zeros((T,), dtype=torch.int64, device=dev)            # global integer total per step
+        self.verdict = torch.zeros((1,), dtype=torch.int64, device=dev)        # gmx_sweep_verdict: 0 fine, 1 overflow, 2 failed
+        self.shift = cdf_shift(self.N)
         obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
         self.p_init = MinimalGenerate(self.init, (), obs0, (n,))
         # the state is the model's return value: a float scalar, or ONE vector of D floats per particle kept
@@ -202,6 +372,7 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.D = int(event[0]) if event else 1
         self._alloc_exchange()
         g = Gathered(self._src(0), self.idx)
+        self.p_mhvm_init = self.p_mhvm_step = None
         if self.rejuvenate is None:
             self.p_step = MinimalGenerate(self.step, (g,) + tuple(self.step_extra(1)), obs0, (n,))
         else:
@@ -215,7 +386,6 @@ class ShardedBootstrapSweep(_NoiseAhead):
             # the move and the extension that follows it as ONE program (static.MinimalMHGenerate, what the single-GPU
             # sweep launches per step): with the routing of the previous step as its prologue a sharded MH step is ONE
             # launch — used when that form applies (fuse_sh below), else the separate programs above
-            self.p_mhvm_init = self.p_mhvm_step = None
             if self.chain_mh_req and be.uses_streams and self.specialize:
                 from ..static import MinimalMHGenerate
                 from .smc import BootstrapSweep as _BS
@@ -246,9 +416,8 @@ class ShardedBootstrapSweep(_NoiseAhead):
         # (with an MH move the program that GATHERS is the move's — it routes step t - 1 first, two leaves per state
         #  component: x_{t-1} and what it was extended from — and the extension that follows reads the moved state locally:
         #  two launches per step instead of three; round 6)
-        leaves_routed = self.D * (2 if self.rejuvenate is not None else 1)
         want_fuse_sh = bool(self.peer_mode and be.uses_streams and self.specialize and self.kind == SYSTEMATIC
-                            and W <= 8 and W * tiles_ <= 1024 and leaves_routed <= _lib.PEER_MAX_LEAVES
+                            and W <= 8 and W * tiles_ <= 1024 and self.peer_leaves <= _lib.PEER_MAX_LEAVES
                             and n + W * self.capacity <= (1 << _lib.ANC_TAG_SHIFT) and self.fuse_sh_req is not False)
         chained = self.rejuvenate is not None and self.p_mhvm_step is not None
         self._routers = (self.p_step,) if self.rejuvenate is None else \
@@ -266,27 +435,8 @@ class ShardedBootstrapSweep(_NoiseAhead):
                     self.p_mhvm_init.comp.specialize()
                     self.p_mhvm_step.comp.specialize()
         self.partials = torch.zeros((2, (n + 255) // 256), dtype=torch.float32, device=dev)
-        # two collectives per step instead of three: the ranks all-gather their CDF TILE STATISTICS (12 bytes per
-        # 1024 particles; written by the site program itself when it can, else by gmx_tile_stats), from which
-        # every rank derives the global max and all the totals — no max all-reduce, no local CDF array
-        from .smc import FUSED_RESAMPLE_MAX
-        self.tiles_mode = (self.kind in (SYSTEMATIC, STRATIFIED) and n <= FUSED_RESAMPLE_MAX and W <= 64
-                           and not self.cdf_form)
-        if self.tiles_mode:
-            sb = int(be.c.gmx_shard_stats_bytes(n))
-            tiles = (n + CDF_TILE - 1) // CDF_TILE
-            pad = tiles + (tiles & 1)
-            self.stats_own = torch.zeros((sb,), dtype=torch.uint8, device=dev)
-            self.stats_all = self.cx.alloc((W * sb,), torch.uint8) if self.cx is not None else \
-                torch.zeros((W * sb,), dtype=torch.uint8, device=dev)
-            self.tile_agg = self.stats_own[:pad * 8].view(torch.int64)
-            self.tile_max = self.stats_own[pad * 8:].view(torch.float32)
-            # (the one-launch step reads step t - 1's log-weights / statistics while it writes step t's: two sets)
-            self.stats_own_pp = [self.stats_own, torch.zeros_like(self.stats_own)]
-            self.tile_agg_pp = [b_[:pad * 8].view(torch.int64) for b_ in self.stats_own_pp]
-            self.tile_max_pp = [b_[pad * 8:].view(torch.float32) for b_ in self.stats_own_pp]
         writers = (self.p_init,) + (self._routers if chained else (self.p_step,))      # who leaves a step's tile statistics
-        self.fuse_sh = bool(want_fuse_sh and self.tiles_mode and all(p_.comp.fuses_shard_step() for p_ in self._routers)
+        self.fuse_sh = bool(want_fuse_sh and all(p_.comp.fuses_shard_step() for p_ in self._routers)
                             and all(p_.comp.writes_tile_stats() for p_ in writers)
                             and all(p_.comp.resident_particles() >= n for p_ in self._routers))
         self.chain_mh = bool(chained and self.fuse_sh)
@@ -301,18 +451,17 @@ class ShardedBootstrapSweep(_NoiseAhead):
         if self.fuse_sh_req and not self.fuse_sh:
             raise NotImplementedError("ShardedBootstrapSweep(fuse_step=True): needs the fused peer exchange, systematic "
                                       "resampling, specialised programs that leave tile statistics, world <= 8")
+        # (the one-launch step reads step t - 1's log-weights / statistics while it writes step t's: two sets)
         self.lw_pp = [self.lw, torch.zeros_like(self.lw)] if self.fuse_sh else [self.lw, self.lw]
         if self.fuse_sh:
             self.sh_status = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.router = _ShardRouter(self.form, self.kind, n, self.rank, W, self.shift, cx=self.cx, comm=self.comm,
+                                   fused=self.fused_req, sets=2 if self.fuse_sh else 1)
+        self.router.set_capacity(self.capacity, self.peer_leaves)
+        self.plan = self.router.plan
         self._set_step_keys(key)
-        self.sorted_tab = self.sorted_keys = None
         if self.kind == MULTINOMIAL_SORTED:
-            # every rank draws the SAME table of the N global slots from the step's resampling key (integers)
-            if self.N >= 1 << 31:
-                raise NotImplementedError("resample='multinomial_sorted' across ranks: n_per_rank * world < 2^31")
-            self.sorted_tab = torch.zeros((int(be.c.gmx_sorted_uniforms_words(self.N)),), dtype=torch.int32, device=dev)
-            hk = np.stack([self.step_keys[t][1].host() for t in range(T)]).astype(np.uint32)
-            self.sorted_keys = torch.from_numpy(hk.view(np.int32)).to(dev)
+            self.router.set_sorted_keys(np.stack([self.step_keys[t][1].host() for t in range(T)]))
         if self.comm and self.world > 1 and hasattr(self.dist, "barrier"):
             # ranks leave prepare() together (hiprtc compiles are seconds apart between ranks): the bounded waits of
             # the peer-mapped exchanges only ever see the microseconds of skew a running sweep has
@@ -321,29 +470,24 @@ class ShardedBootstrapSweep(_NoiseAhead):
 
     def _alloc_exchange(self):
         dev, n, W, C = _lib.get().device, self.n, self.world, self.capacity
-        if getattr(self, "peer_mode", False):
-            # what crosses ranks lands in the communicator's fine-grained landing block; the extended states (and their
-            # tails, filled by this rank's own routing launch) are ordinary memory
-            self.peer_leaves = self.D * (2 if self.rejuvenate is not None else 1)
-            if self.peer_leaves > _lib.PEER_MAX_LEAVES:
-                raise NotImplementedError("ShardedBootstrapSweep over the fused peer exchange: at most "
-                                          f"{_lib.PEER_MAX_LEAVES} routed leaves (GMX_PEER_MAX_LEAVES)")
-            self.peer_land, _ = self.cx.landing(n, C, self.peer_leaves)              # COLLECTIVE
-            if not hasattr(self, "peer_tag"):
-                self.peer_tag, self.peer_status = self.cx.step_words()
+        # routed leaves per step: every component of the state and, with an MH move, of what it was extended from
+        self.peer_leaves = self.D * (2 if self.rejuvenate is not None else 1)
+        if self.peer_mode and self.peer_leaves > _lib.PEER_MAX_LEAVES:
+            raise NotImplementedError("ShardedBootstrapSweep over the fused peer exchange: at most "
+                                      f"{_lib.PEER_MAX_LEAVES} routed leaves (GMX_PEER_MAX_LEAVES)")
+        if self.router is not None:                      # (the overflow re-run: the landing block for the new capacity)
+            self.router.set_capacity(C, self.peer_leaves)
         # extended state, double-buffered: [ n local | W*C received ]; ancestors index into it
         # destinations of collectives come from the communicator (peer-mapped memory under GENMI_COMM=p2p)
-        mk = (lambda shape, dt=torch.float32: self.cx.alloc(shape, dt)) if (self.cx is not None and not getattr(self, "peer_mode", False)) else \
+        mk = (lambda shape, dt=torch.float32: self.cx.alloc(shape, dt)) if (self.cx is not None and not self.peer_mode) else \
             (lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev))
         self.xrows = [mk((self.D, n + W * C)) for _ in range(2)]
-        self.xext = [r[0] for r in self.xrows]                    # component 0 (THE state when it is a scalar)
-        self.send = torch.zeros((self.D, W * C), dtype=torch.float32, device=dev)
+        self.send = torch.zeros((self.peer_leaves, W * C), dtype=torch.float32, device=dev)      # one row per routed leaf
         self.idx = torch.zeros((n,), dtype=torch.int32, device=dev)
         if self.rejuvenate is not None:
-            # aext[t % 2][:n] = the MH-moved, resampled state step t is extended from; its tail receives the
+            # arows[t % 2][:, :n] = the MH-moved, resampled state step t is extended from; its tail receives the
             # remote copies of it when it travels as the second routed leaf of the NEXT resampling
             self.arows = [mk((self.D, n + W * C)) for _ in range(2)]
-            self.send2 = torch.zeros((self.D, W * C), dtype=torch.float32, device=dev)
         self._bound = [None] * self.T
 
     def _asrc(self, tb, local=False):
@@ -355,236 +499,114 @@ class ShardedBootstrapSweep(_NoiseAhead):
         """what the step model sees as the previous state (before the gather): [n + W*C] or [n + W*C, D]"""
         return self.xrows[tb][0] if not self.event else self.xrows[tb].t()
 
+    def _leaves(self, t):
+        """what step t's resampling routes, in issue order: every component of x_t, then (an MH move, t >= 1) every
+        component of the state it was extended from — _ShardRouter's (rows, send, recv)"""
+        rows = list(self.xrows[t % 2])
+        if self.rejuvenate is not None and t >= 1:
+            rows += list(self.arows[t % 2])
+        return [(r, self.send[i], r[self.n:]) for i, r in enumerate(rows)]
+
     # ------------------------------------------------------------------
-    def _bind_step(self, t):
-        """Everything step t launches, bound once (all buffers are persistent): the site-program
-        launch arguments plus the argument tuples of the resampling entry points."""
-        be = _lib.get()
-        n, g, W, C = self.n, self.rank, self.world, self.capacity
-        k_prop, k_res, _ = self.step_keys[t]
+    def _programs(self, t):
+        """Which programs step t launches, on which leaves, into which buffers: (mh, prog, leaves, launch key, bufs) —
+        init; the plain step; the chained MH move + extension (one program); or the separate MH move, `mh` = its own
+        (prog, leaves, key, bufs), then the extension.  (The log-weight buffer is the caller's to set.)"""
+        n = self.n
+        k_prop, _k_res, k_mh = self.step_keys[t]
         obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-        cur = self.xext[t % 2]
         mh = None
-        shard_in = None
-        if self.fuse_sh and t >= 1:
-            # the launch that gathers ROUTES step t - 1 first: that step's log-weights, statistics, states and resampling key
-            pw = (t - 1) % 2
-            prev_rows = [self.xrows[pw][d] for d in range(self.D)]
-            if self.rejuvenate is not None and t - 1 >= 1:         # second routed leaf: what x_{t-1} was extended from
-                prev_rows += [self.arows[pw][d] for d in range(self.D)]
-            kh_ = self.step_keys[t - 1][1].host()
-            p_prev = _lib.Peer()
-            p_prev.land_d, p_prev.tag_base_d, p_prev.status_d = (self.peer_land.data_ptr(), self.peer_tag.data_ptr(),
-                                                                 self.peer_status.data_ptr())
-            p_prev.rank, p_prev.world, p_prev.step, p_prev.tiles = g, W, t - 1, (n + CDF_TILE - 1) // CDF_TILE
-            p_prev.capacity, p_prev.leaves = C, len(prev_rows)
-            shard_in = dict(lw=self.lw_pp[pw], stats_own=self.stats_own_pp[pw], plan=self.plan, total_out=self.totals[t - 1:t],
-                            max_out=self.maxs[t - 1:t], status=self.sh_status, shift=self.shift, tag=1 + (t - 1) % _lib.ANC_TAG_MAX,
-                            key=(int(kh_[0]), int(kh_[1])), peer=p_prev, state=prev_rows,
-                            tail=[r_[n:] for r_ in prev_rows])
-        if t == 0:
-            prog = self.p_init
-            leaves = prog.leaves((), obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves((), obs)
-        elif self.rejuvenate is None:
-            prog = self.p_step
-            a_ = (Gathered(self._src((t - 1) % 2), self.idx),) + tuple(self.step_extra(t))
+        if t == 0 or self.rejuvenate is None:
+            prog = self.p_init if t == 0 else self.p_step
+            a_ = () if t == 0 else (Gathered(self._src((t - 1) % 2), self.idx),) + tuple(self.step_extra(t))
             leaves = prog.leaves(a_, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a_, obs)
-        elif self.chain_mh:
-            # ONE program: the MH move on the resampled particles of step t - 1 (keys split(k_mh, N)[g*n + i]), then the
-            # extension to step t from the moved state (keys split(k_prop, N)[g*n + i]: OP_KSPLITU of two launch values)
-            ch = ChoiceMap.empty().set(self.obs_addr, self.ys[t - 1]).set(self.state_addr,
-                                                                          Gathered(self._src((t - 1) % 2), self.idx))
-            ex_t = tuple(self.step_extra(t))
-            kw = k_prop.host()
-            if t == 1:
-                prog = self.p_mhvm_init
-                leaves = prog.leaves((), ch, self.rejuvenate, ex_t, obs, (int(kw[0]), int(kw[1])),
-                                     self._noise_leaves(t, prog) if self.noise_ahead else ())
-            else:
-                prog = self.p_mhvm_step
-                leaves = prog.leaves((Gathered(self._asrc((t - 1) % 2), self.idx),) + tuple(self.step_extra(t - 1)), ch,
-                                     self.rejuvenate, ex_t, obs, (int(kw[0]), int(kw[1])),
-                                     self._noise_leaves(t, prog) if self.noise_ahead else ())
-            k_prop = self.step_keys[t][2]          # the launch key of the chained program is the MOVE's
         else:
-            # the MH move on the resampled particles of step t-1, keys split(k_mh, N)[g*n + i]
+            # the MH move on the resampled particles of step t - 1 (keys split(k_mh, N)[g*n + i]) ...
             ch = ChoiceMap.empty().set(self.obs_addr, self.ys[t - 1]).set(self.state_addr,
                                                                           Gathered(self._src((t - 1) % 2), self.idx))
-            if t == 1:
-                mprog, mleaves = self.p_mh_init, self.p_mh_init.leaves((), ch, self.rejuvenate)
+            a_ = () if t == 1 else (Gathered(self._asrc((t - 1) % 2), self.idx),) + tuple(self.step_extra(t - 1))
+            if self.chain_mh:
+                # ... and, in the SAME program, the extension to step t from the moved state (keys split(k_prop, N)
+                # [g*n + i]: OP_KSPLITU of two launch values); the launch key of the chained program is the MOVE's
+                prog = self.p_mhvm_init if t == 1 else self.p_mhvm_step
+                kw = k_prop.host()
+                leaves = prog.leaves(a_, ch, self.rejuvenate, tuple(self.step_extra(t)), obs, (int(kw[0]), int(kw[1])),
+                                     self._noise_leaves(t, prog) if self.noise_ahead else ())
+                k_prop = k_mh
             else:
-                mprog = self.p_mh_step
-                mleaves = mprog.leaves((Gathered(self._asrc((t - 1) % 2), self.idx),) + tuple(self.step_extra(t - 1)), ch,
-                                       self.rejuvenate)
-            mbufs = [None] * len(mprog.comp.outputs)
-            mbufs[mprog.ro[1]] = self.arows[t % 2][:, :n]
-            mbufs[mprog.ao[1]] = self.accept.reshape(1, n)
-            mh = (mprog.comp, mprog.comp.bind(mleaves, (n,), lazy_split(self.step_keys[t][2], self.N),
-                                             out_buffers=mbufs, index_offset=g * n, shard_in=shard_in), mleaves)
-            shard_in = None                       # (the move routed: the extension below reads its output locally)
-            prog = self.p_step
-            leaves = prog.leaves((self._asrc(t % 2, local=True),) + tuple(self.step_extra(t)), obs)
+                mprog = self.p_mh_init if t == 1 else self.p_mh_step
+                mbufs = [None] * len(mprog.comp.outputs)
+                mbufs[mprog.ro[1]] = self.arows[t % 2][:, :n]
+                mbufs[mprog.ao[1]] = self.accept.reshape(1, n)
+                mh = (mprog, mprog.leaves(a_, ch, self.rejuvenate), k_mh, mbufs)
+                prog = self.p_step                   # ... then the extension reads the move's output locally
+                leaves = prog.leaves((self._asrc(t % 2, local=True),) + tuple(self.step_extra(t)), obs)
         bufs = [None] * len(prog.comp.outputs)
-        rows_t = self.xrows[t % 2]
-        bufs[prog.ro[1]] = rows_t[:, :n]                 # [D, n] window of the [D, n + W*C] rows
+        bufs[prog.ro[1]] = self.xrows[t % 2][:, :n]      # [D, n] window of the [D, n + W*C] rows
         if self.chain_mh and t >= 1:
             bufs[prog.mo[1]] = self.arows[t % 2][:, :n]     # the moved state step t was extended from
             bufs[prog.ao[1]] = self.accept.reshape(1, n)
-        w_ = t % 2 if self.fuse_sh else 0                # (one launch per step: two sets of log-weights / statistics)
-        lw_t = self.lw_pp[w_]
-        bufs[prog.wo[1]] = lw_t.reshape(1, n)
-        # keys of the GLOBAL particle index: split(k_prop, N)[g*n + i]
+        return mh, prog, leaves, k_prop, bufs
+
+    def _shard_in(self, t):
+        """the prologue of step t's gathering launch in the one-launch form: it ROUTES step t - 1 first — that step's
+        log-weights, statistics, leaves and resampling key"""
+        pw = (t - 1) % 2
+        prev = self._leaves(t - 1)
+        kh_ = self.step_keys[t - 1][1].host()
+        return dict(lw=self.lw_pp[pw], stats_own=self.router.stats_own[pw], plan=self.plan, total_out=self.totals[t - 1:t],
+                    max_out=self.maxs[t - 1:t], status=self.sh_status, shift=self.shift,
+                    tag=1 + (t - 1) % _lib.ANC_TAG_MAX, key=(int(kh_[0]), int(kh_[1])), peer=self.router.peer(t - 1, prev),
+                    state=[rows for rows, _s, _r in prev], tail=[recv for _r, _s, recv in prev])
+
+    def _bind_step(self, t):
+        """Everything step t launches, bound once (all buffers are persistent): the site programs' launch arguments
+        and the router's for the exchange that follows."""
+        be, R = _lib.get(), self.router
+        n, g = self.n, self.rank
+        mh, prog, leaves, key, bufs = self._programs(t)
+        w = t % 2 if self.fuse_sh else 0                 # (one launch per step: two sets of log-weights / statistics)
+        lw = self.lw_pp[w]
+        bufs[prog.wo[1]] = lw.reshape(1, n)
         writes_stats = self.tiles_mode and prog.comp.writes_tile_stats()
-        peer = None
-        if self.peer_mode:
-            peer = _lib.Peer()
-            peer.land_d, peer.tag_base_d, peer.status_d = self.peer_land.data_ptr(), self.peer_tag.data_ptr(), self.peer_status.data_ptr()
-            peer.rank, peer.world, peer.step, peer.tiles = g, W, t, (n + CDF_TILE - 1) // CDF_TILE
-            peer.capacity = C
-            peer.leaves = self.D * (2 if (self.rejuvenate is not None and t >= 1) else 1)
-        if writes_stats:        # the workgroup maxima land in the statistics block (red_out plane 0), the sums beside them
-            st_w = t % 2 if self.fuse_sh else 0
-            vm = prog.comp.bind(leaves, (n,), lazy_split(k_prop, self.N),
-                                red_out=self.tile_max_pp[st_w] if self.fuse_sh else self.tile_max, out_buffers=bufs,
-                                index_offset=g * n,
-                                tile_stats=((self.tile_agg_pp[st_w] if self.fuse_sh else self.tile_agg), self.shift),
-                                peer=peer, shard_in=shard_in)
-        else:
-            vm = prog.comp.bind(leaves, (n,), lazy_split(k_prop, self.N), red_out=self.partials, out_buffers=bufs,
-                                index_offset=g * n)
-        kk = _key_words(k_res)
-        m = self.maxs[t:t + 1]
-        tot = self.totals[t:t + 1]
-        P = be.ptr
         rows = int(be.c.gmx_program_grid(prog.comp.handle, n))        # block maxima the site program writes
-        pmax = self.partials[0, :rows]
-        step2 = recv2 = None
-        if self.rejuvenate is not None and t >= 1:       # second routed leaf (per component): what x_t was extended from
-            cur_a = self.arows[t % 2]
-            step2 = [((self.kind, kk) if self.kind != MULTINOMIAL_SORTED else (P(self.sorted_tab),)) +
-                     (P(self.totals_all), P(self.plan), P(tot), P(self.cdf), g, W, n, C, P(cur_a[d]),
-                      P(self.send2[d]), P(self.idx)) for d in range(self.D)]
-            recv2 = [cur_a[d][n:] for d in range(self.D)]
-        tiles = None
-        if self.tiles_mode:
-            mk = lambda row, snd: (self.kind, kk, P(self.totals_all), P(self.plan), P(tot), P(self.lw), P(self.stats_own),
-                                   P(m), self.shift, g, W, n, C, P(row), P(snd), P(self.idx))
-            mkf = lambda row, snd: (self.kind, kk, P(self.stats_all), P(self.plan), P(tot), P(self.lw), P(m), self.shift,
-                                    g, W, n, C, P(row), P(snd), P(self.idx))
-            fused_ok = W <= 64 and self.fused_req
-            pk = None
-            if peer is not None:
-                from ctypes import c_void_p as _vp
-                rows_l = [rows_t[d] for d in range(self.D)]
-                if self.rejuvenate is not None and t >= 1:
-                    rows_l += [self.arows[t % 2][d] for d in range(self.D)]
-                L = len(rows_l)
-                st_arr = (_vp * L)(*[r.data_ptr() for r in rows_l])
-                tl_arr = (_vp * L)(*[r[n:].data_ptr() for r in rows_l])
-                so_t = self.stats_own_pp[t % 2] if self.fuse_sh else self.stats_own
-                pk = {"peer": peer, "put_stats": None if writes_stats else (P(so_t), peer, n),
-                      "step": (self.kind, kk, P(so_t), peer, P(self.plan), P(tot), P(lw_t), P(m), self.shift, n,
-                               st_arr, tl_arr, P(self.idx)), "keep": (rows_l, st_arr, tl_arr)}
-            tiles = {"peer": pk,
-                     "stats": None if writes_stats else (P(self.lw), n, self.shift, P(self.tile_max), P(self.tile_agg)),
-                     "totals": (P(self.stats_all), W, n, P(self.totals_all), P(m)),
-                     # the first routed leaf derives the totals / global max itself (one launch less in the chain);
-                     # further leaves of the same step reuse them
-                     "fused": mkf(rows_t[0], self.send[0]) if fused_ok else None,
-                     "steps": [mk(rows_t[d], self.send[d]) for d in range(self.D)],
-                     "step2": [mk(self.arows[t % 2][d], self.send2[d]) for d in range(self.D)]
-                     if (self.rejuvenate is not None and t >= 1) else None}
-        return {
-            "tiles": tiles,
-            "prog": prog.comp, "vm": vm, "mh": mh, "step2": step2, "recv2": recv2,
-            "pmax": pmax, "keep": (kk, tot, leaves, m),
-            # the CDF kernel reduces the (all-reduced) block maxima itself and records the max in maxs[t]
-            "cdf": (P(self.lw), n, self.shift, P(pmax), rows, P(m), P(self.cdf), P(self.total_d), P(self.ws)),
-            # one routed leaf per state component: the same plan, D launches + D all-to-alls
-            "steps": [((self.kind, kk) if self.sorted_tab is None else (P(self.sorted_tab),)) +
-                      (P(self.totals_all), P(self.plan), P(tot), P(self.cdf), g, W, n, C,
-                       P(rows_t[d]), P(self.send[d]), P(self.idx)) for d in range(self.D)],
-            "sorted": None if self.sorted_tab is None else (P(self.sorted_keys[t]), 1, self.N, P(self.sorted_tab), 0),
-            "recvs": [rows_t[d][n:] for d in range(self.D)],
-        }
+        route = R.bind(t, self.step_keys[t][1], lw, self.maxs[t:t + 1], self.totals[t:t + 1], self._leaves(t), self.idx, w=w,
+                       program_stats=writes_stats, pmax=self.partials[0, :rows], pmax_rows=rows,
+                       deferred=self.fuse_sh and t + 1 < self.T)
+        shard_in = self._shard_in(t) if self.fuse_sh and t >= 1 else None
+        # keys of the GLOBAL particle index: split(key, N)[g*n + i]
+        if mh is not None:
+            mprog, mleaves, mkey, mbufs = mh
+            mh = (mprog.comp, mprog.comp.bind(mleaves, (n,), lazy_split(mkey, self.N), out_buffers=mbufs,
+                                              index_offset=g * n, shard_in=shard_in), mleaves)
+            shard_in = None                       # (the move routed: the extension reads its output locally)
+        if writes_stats:        # the workgroup maxima land in the statistics block (red_out plane 0), the sums beside them
+            vm = prog.comp.bind(leaves, (n,), lazy_split(key, self.N), red_out=R.tile_max[w], out_buffers=bufs,
+                                index_offset=g * n, tile_stats=(R.tile_agg[w], self.shift), peer=route["peer"],
+                                shard_in=shard_in)
+        else:
+            vm = prog.comp.bind(leaves, (n,), lazy_split(key, self.N), red_out=self.partials, out_buffers=bufs,
+                                index_offset=g * n)
+        return {"mh": mh, "prog": prog.comp, "vm": vm, "route": route, "keep": leaves}
 
     def _step(self, t):
-        be = _lib.get()
         b = self._bound[t]
         if b is None:
             b = self._bound[t] = self._bind_step(t)
-        c, st = be.c, be.stream()
         if b["mh"] is not None:
             b["mh"][0].launch(b["mh"][1])                               # MH move on the resampled particles
         b["prog"].launch(b["vm"])                                      # x_t, lw_t, block maxima
-        if b["tiles"] is not None:
-            tl = b["tiles"]
-            if tl["stats"] is not None:
-                be.check(c.gmx_tile_stats(*tl["stats"], st), "gmx_tile_stats")
-            if tl["peer"] is not None:          # no collective launch: puts + granule waits inside the two kernels
-                pk = tl["peer"]
-                if pk["put_stats"] is not None:
-                    be.check(c.gmx_peer_put_stats(*pk["put_stats"], st), "gmx_peer_put_stats")
-                if self.fuse_sh and t + 1 < self.T:
-                    return                      # ONE launch per step: step t is routed by the launch of step t + 1
-                be.check(c.gmx_shard_step_peer(*pk["step"], st), "gmx_shard_step_peer")
-                return
-            if self.comm:
-                self.cx.all_gather(self.stats_all, self.stats_own)          # 12 bytes per 1024 particles per rank
-            else:
-                self.stats_all.copy_(self.stats_own)
-            more = self.D > 1 or tl["step2"] is not None
-            if tl["fused"] is None or more:
-                be.check(c.gmx_shard_totals(*tl["totals"], st), "gmx_shard_totals")    # global max + every rank's total
-            for d in range(self.D):
-                if d == 0 and tl["fused"] is not None and not more:
-                    be.check(c.gmx_shard_step_fused(*tl["fused"], st), "gmx_shard_step_fused")
-                else:
-                    be.check(c.gmx_shard_step_tiles(*tl["steps"][d], st), "gmx_shard_step_tiles")
-                if self.comm:
-                    self.cx.all_to_all(b["recvs"][d], self.send[d])
-            if tl["step2"] is not None:
-                for d in range(self.D):
-                    be.check(c.gmx_shard_step_tiles(*tl["step2"][d], st), "gmx_shard_step_tiles")
-                    if self.comm:
-                        self.cx.all_to_all(b["recv2"][d], self.send2[d])
-            return
-        if self.comm:
-            self.cx.all_reduce_max(b["pmax"])                            # element-wise MAX of the block maxima (<= 4 KB)
-        be.check(c.gmx_weight_cdf(*b["cdf"], st), "gmx_weight_cdf")    # global max + local integer CDF against it
-        if self.comm:
-            self.cx.all_gather(self.totals_all, self.total_d)            # 8 bytes per rank
-        else:
-            self.totals_all.copy_(self.total_d)
-        shard_step = c.gmx_shard_step
-        if b["sorted"] is not None:
-            be.check(c.gmx_sorted_uniforms(*b["sorted"], st), "gmx_sorted_uniforms")     # the step's table of all N slots
-            shard_step = c.gmx_shard_step_sorted
-        for d in range(self.D):
-            be.check(shard_step(*b["steps"][d], st), "gmx_shard_step")       # slot boundaries + routing
-            if self.comm:
-                self.cx.all_to_all(b["recvs"][d], self.send[d])          # block s of recv <- block `me` of rank s
-        if b["step2"] is not None:
-            for d in range(self.D):
-                be.check(shard_step(*b["step2"][d], st), "gmx_shard_step")
-                if self.comm:
-                    self.cx.all_to_all(b["recv2"][d], self.send2[d])
+        self.router.launch(b["route"])
 
     def kernel_timers(self):
         """The site-program launch of a mid-sweep step (no collectives): bench.py's roofline kernel."""
         t = max(1, self.T // 2)
 
         def vm():
-            n = self.n
-            obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-            prog = self.p_step
-            a_ = (Gathered(self._src((t - 1) % 2), self.idx),) + tuple(self.step_extra(t))
-            leaves = prog.leaves(a_, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a_, obs)
-            bufs = [None] * len(prog.comp.outputs)
-            bufs[prog.ro[1]] = self.xrows[t % 2][:, :n]
-            bufs[prog.wo[1]] = self.lw.reshape(1, n)
-            prog.comp.run(leaves, (n,), lazy_split(self.step_keys[t][0], self.N), red_out=self.partials,
-                          out_buffers=bufs, index_offset=self.rank * n)
+            _mh, prog, leaves, key, bufs = self._programs(t)
+            bufs[prog.wo[1]] = self.lw.reshape(1, self.n)
+            prog.comp.run(leaves, (self.n,), lazy_split(key, self.N), red_out=self.partials, out_buffers=bufs,
+                          index_offset=self.rank * self.n)
         return {"k_vm": vm}
 
     def enqueue(self):
@@ -723,7 +745,7 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
                                 stats: dict | None = None, cdf_form=False):
     """BASELINE config 4 across ranks: `ImportanceK(target, k_particles = world * k_per_rank).run_smc(key)`
     with rank g holding particles [g*k, (g+1)*k) (same key tree: keys split(sub, K)[g*k + i], so the
-    ensemble is the single-process one), then ONE global resampling with ONE plan for the whole trace:
+    ensemble is the single-process one), then ONE global resampling with ONE plan for the whole trace (_ShardRouter):
 
       1. tile statistics of the local log-weights (gmx_tile_stats)         -> all-gather (12 B per 1024 particles)
       2. gmx_shard_totals: global max + every rank's integer total; gmx_shard_step_tiles routes ONE 4-byte leaf:
@@ -741,7 +763,7 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
     Returns (ParticleCollection of this rank's k resampled particles, this rank's pre-resampling log-weights).
     COLLECTIVE: every rank calls it."""
     _check_shard_alignment(int(k_per_rank), dist.get_world_size())
-    from .smc import _KINDS, FUSED_RESAMPLE_MAX, LogMLOffset, ParticleCollection, trace_map
+    from .smc import _KINDS, LogMLOffset, ParticleCollection, trace_map
     from ..engine import materialize
     be = _lib.get()
     dev = be.device
@@ -759,46 +781,20 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
     key, sub = split(key)                                            # smc.py:299
     trs, lw = target.importance(lazy_split(sub, n, offset=g * n), ChoiceMap.empty())
     lw = lw.float().contiguous()
-    shift = cdf_shift(K)
-    kk = _key_words(key)                                             # resampling key: the algorithm's leftover `key`
+    shift = cdf_shift(K)                                             # (resampling key: the algorithm's leftover `key`)
     mx = torch.empty((1,), dtype=torch.float32, device=dev)
-    calloc = (lambda shape, dt: comm.alloc(shape, dt)) if (comm is not None and hasattr(comm.inner, "alloc")) else \
-        (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev))          # destinations of collectives
-    totals_all = calloc((W,), torch.int64)
     gtotal = torch.zeros((1,), dtype=torch.int64, device=dev)
-    # (the tile-statistics plan takes any per-rank size: gmx_shard_totals / gmx_shard_step_tiles stride over the table)
-    tiles_form = kind in (0, 1) and W <= 64 and not cdf_form
-    if tiles_form:
-        nbytes = int(be.c.gmx_shard_stats_bytes(n))
-        tiles = (n + 1023) // 1024
-        pad = tiles + (tiles & 1)
-        stats_own = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-        stats_all = calloc((W * nbytes,), torch.uint8)
-        be.check(be.c.gmx_tile_stats(be.ptr(lw), n, shift, be.ptr(stats_own[pad * 8:]), be.ptr(stats_own), be.stream()),
-                 "gmx_tile_stats")
-        if W > 1:
-            comm.all_gather(stats_all, stats_own)
-        else:
-            stats_all.copy_(stats_own)
-        be.check(be.c.gmx_shard_totals(be.ptr(stats_all), W, n, be.ptr(totals_all), be.ptr(mx), be.stream()),
-                 "gmx_shard_totals")
-        cdf = None
-    else:
-        # global max (deterministic LSE kernel's max output), local CDF against it, totals
+    router = _ShardRouter(_ShardRouter.form_of(kind, n, W, cdf_form=cdf_form, sweep=False), kind, n, g, W, shift,
+                          cx=comm, comm=W > 1, fused=False)
+    if router.form == "cdf":
+        # global max (deterministic LSE kernel's max output); the router: local CDF against it, totals
         dummy = torch.empty((1,), dtype=torch.float32, device=dev)
         rows_ws = torch.empty(((be.c.gmx_logsumexp_workspace(1, n) + 3) // 4,), dtype=torch.int32, device=dev)
         be.check(be.c.gmx_logsumexp(be.ptr(lw), 1, n, be.ptr(dummy), be.ptr(mx), be.ptr(rows_ws), be.stream()), "gmx_logsumexp")
         if W > 1:
             comm.all_reduce_max(mx)
-        cdf = torch.empty((n,), dtype=torch.int64, device=dev)
-        total = torch.zeros((1,), dtype=torch.int64, device=dev)
-        ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64, device=dev)
-        be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, shift, None, 0, be.ptr(mx), be.ptr(cdf), be.ptr(total), be.ptr(ws),
-                                     be.stream()), "gmx_weight_cdf")
-        if W > 1:
-            comm.all_gather(totals_all, total)
-        else:
-            totals_all.copy_(total)
+        if kind == MULTINOMIAL_SORTED:        # every rank draws the same table of the K global slots from the key
+            router.set_sorted_keys(key.host().reshape(1, 2))
 
     lazy_out = W == 1
     # ---- every per-particle leaf of the trace as 4-byte rows [R, n] ----
@@ -831,39 +827,26 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
 
     # (ONE rank ships nothing: no send blocks to size, no overflow to ask the device about — and no host sync)
     C = 1 if W == 1 else max(1, min(int(capacity) if capacity else max(4096, n // 32), n))
-    sorted_tab = None
+    local_index = torch.arange(n, dtype=torch.int32, device=dev)                      # the ONE routed leaf
+    again = False
     while True:
-        plan = torch.zeros((int(be.c.gmx_shard_plan_words(W)),), dtype=torch.int64, device=dev)
         next_idx = torch.zeros((n,), dtype=torch.int32, device=dev)
         send_idx = torch.zeros((W * C,), dtype=torch.int32, device=dev)              # unused capacity: particle 0 (valid)
-        local_index = torch.arange(n, dtype=torch.int32, device=dev)                  # the ONE routed leaf
-        if tiles_form:
-            be.check(be.c.gmx_shard_step_tiles(kind, kk, be.ptr(totals_all), be.ptr(plan), be.ptr(gtotal), be.ptr(lw),
-                                               be.ptr(stats_own), be.ptr(mx), shift, g, W, n, C, be.ptr(local_index),
-                                               be.ptr(send_idx), be.ptr(next_idx), be.stream()), "gmx_shard_step_tiles")
-        elif kind == MULTINOMIAL_SORTED:      # every rank draws the same table of the K global slots from the key
-            if sorted_tab is None:
-                sorted_tab = torch.zeros((int(be.c.gmx_sorted_uniforms_words(K)),), dtype=torch.int32, device=dev)
-                kd = torch.tensor([int(kk[0]), int(kk[1])], dtype=torch.int64).to(torch.int32).to(dev)
-                be.check(be.c.gmx_sorted_uniforms(be.ptr(kd), 1, K, be.ptr(sorted_tab), 0, be.stream()), "gmx_sorted_uniforms")
-            be.check(be.c.gmx_shard_step_sorted(be.ptr(sorted_tab), be.ptr(totals_all), be.ptr(plan), be.ptr(gtotal),
-                                                be.ptr(cdf), g, W, n, C, be.ptr(local_index), be.ptr(send_idx),
-                                                be.ptr(next_idx), be.stream()), "gmx_shard_step_sorted")
-        else:
-            be.check(be.c.gmx_shard_step(kind, kk, be.ptr(totals_all), be.ptr(plan), be.ptr(gtotal), be.ptr(cdf), g, W,
-                                         n, C, be.ptr(local_index), be.ptr(send_idx), be.ptr(next_idx), be.stream()),
-                     "gmx_shard_step")
+        router.set_capacity(C)
+        if again:
+            router.plan.zero_()
+        router.launch(router.bind(0, key, lw, mx, gtotal, [(local_index, send_idx, None)], next_idx), route_only=again)
         if W == 1:
             break
-        flag = plan[2:3].clone()
+        flag = router.plan[2:3].clone()
         comm.all_reduce_max(flag)
         if int(flag.item()) == 0:
             break
-        C = n                                                        # always sufficient
+        C, again = n, True                                           # always sufficient
     # ---- pack by destination, ONE all-to-all, one gather ----
     if W > 1 and R:
         packed = table[:, send_idx.long()].reshape(R, W, C).permute(1, 0, 2).contiguous()          # [W, R, C]
-        recv = calloc(tuple(packed.shape), packed.dtype)
+        recv = comm.alloc(tuple(packed.shape), packed.dtype)                                       # a collective's destination
         comm.all_to_all(recv.view(-1), packed.view(-1))
         # the local ancestors by ONE gather of the table; the few slots whose ancestor arrived from another rank are then
         # filled from the received blocks (no [R, n + W * C] copy of the whole table in between)
@@ -898,7 +881,7 @@ def sharded_importance_resample(target, k_per_rank: int, key: Key, dist, kind="s
         new = trace_map(trs, lambda v: rebuild(materialize(v)))
     if stats is not None:
         stats.update(collectives=dict(comm.counts) if comm is not None else {}, rows=R, capacity=C,
-                     form="tile statistics" if tiles_form else "cdf array")
+                     form="tile statistics" if router.form == "tiles" else "cdf array")
     off = LogMLOffset().plus(mx, gtotal, shift, K)
     out = ParticleCollection(new, None, True, off, n_zero=n)
     return out, lw

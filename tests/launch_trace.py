@@ -251,6 +251,143 @@ def trace_sharded(be):
     return {"launch_finish": out}
 
 
+class _Solo:
+    @staticmethod
+    def get_rank(): return 0
+    @staticmethod
+    def get_world_size(): return 1
+
+
+class _comm_env:
+    """GENMI_COMM for the duration of a case ("none": unset)"""
+
+    def __init__(self, comm):
+        self.comm = comm
+
+    def __enter__(self):
+        self.old = os.environ.pop("GENMI_COMM", None)
+        if self.comm != "none":
+            os.environ["GENMI_COMM"] = self.comm
+
+    def __exit__(self, *exc):
+        os.environ.pop("GENMI_COMM", None)
+        if self.old is not None:
+            os.environ["GENMI_COMM"] = self.old
+
+
+SHARD_N, SHARD_T = 3072, 4            # three tiles (a table of more than one row, an odd count: the padding); init, the
+                                      # first MH step and the steady state
+
+
+def _sharded_model(model):
+    """(init, step, constructor keywords, observations, seed) of the sharded cases' models"""
+    import genjax_amd as G
+    from genjax_amd import numpy as jnp, workloads
+    from tests import parity
+    T = SHARD_T
+    if model == "lgssm":
+        return workloads.make_lgssm(G) + ({}, workloads.lgssm_data(T), 3)
+    if model == "nlssm_mh":          # config 3: two routed leaves
+        req = G.StaticRequest({"x": G.Rejuvenate(G.normal, lambda chm: (chm.get_value(), 0.5))})
+        return workloads.make_nlssm(G) + (dict(rejuvenate=req, step_extra=lambda t: (float(t),)), workloads.nlssm_data(T), 7)
+    if model == "tracker":           # a vector state, D = 2: one routed leaf per component
+        return parity.make_tracker(G, lambda a, b: jnp.stack([a, b])) + ({}, parity.tracker_data(T), 5)
+    if model == "vec_mh":            # D = 2 and an MH move: 2 * D leaves
+        req = G.StaticRequest({"x": G.Rejuvenate(G.normal, lambda chm: (chm.get_value(), 0.2))})
+        return parity.make_vec_mh(G, lambda *v: jnp.stack(list(v)), jnp.ones(2)) + (
+            dict(rejuvenate=req, step_extra=lambda t: (float(t),)), parity.tracker_data(T), 11)
+    raise KeyError(model)
+
+
+def sharded_cases(backend):
+    """name -> (model, GENMI_COMM or "none", ShardedBootstrapSweep keywords, captured); world size 1, the collectives
+    issued whenever a communicator is named.  The mirror never specialises or fuses the sharded step, so the one-launch
+    step and the chained MH form are in the device's list only — which is short (the GPU suite's time budget)."""
+    cases = {}
+    if backend == "gpu":
+        cases["sharded/lgssm/peer/default"] = ("lgssm", "peer", {}, False)
+        cases["sharded/lgssm/peer/fuse_step0"] = ("lgssm", "peer", {"fuse_step": False}, False)
+        cases["sharded/nlssm_mh/peer/default"] = ("nlssm_mh", "peer", {}, False)
+        cases["sharded/lgssm/p2p/default"] = ("lgssm", "p2p", {}, False)
+        cases["sharded/nlssm_mh/p2p/default"] = ("nlssm_mh", "p2p", {}, False)
+        cases["sharded/lgssm/none/cdf_form"] = ("lgssm", "none", {"cdf_form": True}, False)
+        cases["sharded/lgssm/none/multinomial_sorted"] = ("lgssm", "none", {"resample": "multinomial_sorted"}, False)
+        cases["sharded/tracker/none/default"] = ("tracker", "none", {}, False)
+        cases["sharded/lgssm/peer/captured"] = ("lgssm", "peer", {}, True)
+        return cases
+    variants = {"default": {}, "cdf_form": {"cdf_form": True}, "unfused": {"fused": False},
+                "stratified": {"resample": "stratified"}, "multinomial_sorted": {"resample": "multinomial_sorted"},
+                "na1": {"noise_ahead": True}}
+    for comm in ("none", "p2p", "peer"):
+        for v, kw in variants.items():
+            cases[f"sharded/lgssm/{comm}/{v}"] = ("lgssm", comm, {"noise_ahead": False, **kw}, False)
+    for comm, kw in (("none", {}), ("peer", {}), ("none", {"cdf_form": True}), ("p2p", {"cdf_form": True})):
+        cases[f"sharded/nlssm_mh/{comm}/{'cdf_form' if kw else 'default'}"] = ("nlssm_mh", comm, {"noise_ahead": False, **kw}, False)
+    for comm in ("none", "p2p", "peer"):
+        cases[f"sharded/tracker/{comm}/default"] = ("tracker", comm, {"noise_ahead": False}, False)
+    cases["sharded/vec_mh/none/default"] = ("vec_mh", "none", {"noise_ahead": False}, False)
+    return cases
+
+
+def trace_sharded_case(be, model, comm, kw, captured):
+    """{"form": which exchange form prepare() chose, "launch_finish": [...]} after one untraced run (captured:
+    "capture_launch_launch", as trace_captured)"""
+    from genjax_amd.inference.sharded import ShardedBootstrapSweep
+    rec = install(be)
+    with _comm_env(comm):
+        init, step, mkw, ys, seed = _sharded_model(model)
+        sw = ShardedBootstrapSweep(init, step, SHARD_N, SHARD_T, _Solo, always_communicate=comm != "none", specialize=True,
+                                   **mkw, **kw).prepare(_key(seed), torch.from_numpy(ys))
+        form = {k: getattr(sw, k) for k in ("tiles_mode", "peer_mode", "fuse_sh", "chain_mh", "noise_ahead", "capacity")}
+        sw.launch()
+        sw.finish()
+        rec.start(identity=True)
+        if captured:
+            sw.capture()
+            sw.launch()
+            sw.launch()
+        else:
+            sw.launch()
+        sw.finish()
+        out = rec.stop()
+        assert sw.reruns == 0
+        sw.close()
+    return {"form": form, "capture_launch_launch" if captured else "launch_finish": out}
+
+
+IMPORTANCE_CASES = {"sharded_importance/default": {}, "sharded_importance/cdf_form": {"cdf_form": True},
+                    "sharded_importance/multinomial_sorted": {"kind": "multinomial_sorted"}}
+
+
+def trace_sharded_importance(be, kw):
+    """sharded_importance_resample on the 8-schools target of tests/dist_worker.py, 3072 particles on the one rank"""
+    import genjax_amd as G
+    from genjax_amd import ChoiceMapBuilder as C, numpy as jnp
+    from genjax_amd.inference.sharded import sharded_importance_resample
+    from tests import parity
+
+    @G.gen
+    def schools():
+        mu = G.normal(0.0, 5.0) @ "mu"
+        log_tau = G.normal(0.0, 1.0) @ "log_tau"
+        theta = G.normal(mu * jnp.ones(8), jnp.exp(log_tau) * jnp.ones(8)) @ "theta"
+        _ = G.normal(theta, jnp.array(parity.SCHOOL_SIGMA)) @ "y"
+        return theta
+    target = G.Target(schools, (), C["y"].set(parity.SCHOOL_Y))
+    rec = install(be)
+    with _comm_env("none"):
+        sharded_importance_resample(target, SHARD_N, _key(2), _Solo, **kw)
+        info = {}
+        rec.start(identity=False)
+        sharded_importance_resample(target, SHARD_N, _key(2), _Solo, stats=info, **kw)
+        out = rec.stop()
+    _sync(be)
+    # (a one-off sizes its workspaces between its launches — a prepared sweep does in prepare(), outside the record;
+    #  the size queries launch nothing and are left out: WHERE a buffer is sized is not what this record pins)
+    out = [c for c in out if not c[0].endswith(("_workspace", "_words", "_bytes"))]
+    return {"form": info["form"], "calls": out}
+
+
 def _sync(be):
     if be.uses_streams:
         torch.cuda.synchronize()
@@ -314,7 +451,7 @@ def case_names(backend):
     names = list(sweep_cases()) + ["sharded", "one_offs"]
     if backend == "gpu":
         names += [f"captured/{k}" for k in CAPTURED]
-    return names
+    return names + list(sharded_cases(backend)) + (list(IMPORTANCE_CASES) if backend == "cpu" else [])
 
 
 def trace_case(be, name):
@@ -323,6 +460,10 @@ def trace_case(be, name):
     try:
         if name == "sharded":
             return trace_sharded(be)
+        if name.startswith("sharded/"):
+            return trace_sharded_case(be, *sharded_cases("gpu" if be.uses_streams else "cpu")[name])
+        if name in IMPORTANCE_CASES:
+            return trace_sharded_importance(be, IMPORTANCE_CASES[name])
         if name == "one_offs":
             return trace_one_offs(be)
         if name.startswith("captured/"):
@@ -343,7 +484,11 @@ def check_case(be, backend, name):
     want = load_golden(backend)["cases"][name]
     got = json.loads(json.dumps(trace_case(be, name)))
     assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    if "form" in want:           # a silent change of form is a failure with a name, not a diff of calls
+        assert got["form"] == want["form"], f"{name}: form {got['form']}, recorded at the parent: {want['form']}"
     for part in want:
+        if part == "form":
+            continue
         a, b = got[part], want[part]
         for i, (x, y) in enumerate(zip(a, b)):
             assert x == y, f"{name} / {part}: call {i} is {x}, recorded at the parent: {y}"
