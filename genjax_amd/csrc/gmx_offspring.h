@@ -76,6 +76,10 @@ __device__ __forceinline__ int64_t sorted_below_exact(const sorted_ctx& X, uint6
 // Every load is issued before anything waits (unconditional, clamped addresses), wave-level reductions and scans are
 // DPP (gmx_block.h), the slot ranges are straight-line f64 code with one cold exact path.
 #define RS_TPB 1
+// a branch on a workgroup-uniform condition whose body is a few vector instructions: left alone, hipcc turns it into
+// selects on the scalar condition (every lane issues both sides — measured: MORE vector instructions than the per-lane
+// compare it replaced); an empty volatile asm in the body cannot be speculated, so the scalar branch stays a branch
+#define GMX_KEEP_BRANCH asm volatile("")
 #define RS_BLOCK (GMX_BLOCK * RS_TPB)
 #define RS_WAVES (RS_BLOCK / GMX_WAVE)
 static_assert(RS_MAX_TILES % RS_BLOCK == 0, "tile table shape");
@@ -157,9 +161,14 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   if (!PREF) {
 #pragma unroll
     for (int r = 0; r < PERN; ++r) {
-      const int t = r * RS_BLOCK + (int)threadIdx.x;
-      ta[r] = (t < n_tiles) ? ta[r] : 0ull;
-      tm[r] = (t < n_tiles) ? tm[r] : -gmx_inf();
+      // only the table's last row can run past n_tiles (uniform): the others keep what they loaded (a row that does
+      // not exist holds 0 / -inf from above)
+      if (r * RS_BLOCK < n_tiles && (r + 1) * RS_BLOCK > n_tiles) {
+        GMX_KEEP_BRANCH;
+        const int t = r * RS_BLOCK + (int)threadIdx.x;
+        ta[r] = (t < n_tiles) ? ta[r] : 0ull;
+        tm[r] = (t < n_tiles) ? tm[r] : -gmx_inf();
+      }
     }
   }
   const int32_t k_b = gmx_tile_exp(tmax_mine);
@@ -209,8 +218,12 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
         const int t = r * RS_BLOCK + (int)threadIdx.x;
         const uint64_t G = gmx_tile_scale(ta[r], gmx_tile_exp(tm[r]), K);
         all += G;
-        below += (t < first_tile) ? G : 0ull;
-        if (t >= first_tile && t < first_tile + RS_TPB) s_g[t - first_tile] = G;      // t >= n_tiles: G = 0
+        // workgroup-uniform: a row wholly in front of this block's first tile counts whole, a row wholly at or behind
+        // it not at all — only the row `first_tile` lies in compares per lane (sums of u64: any order, same integers)
+        if ((r + 1) * RS_BLOCK <= first_tile) { GMX_KEEP_BRANCH; below += G; }
+        else if (r * RS_BLOCK < first_tile) { GMX_KEEP_BRANCH; below += (t < first_tile) ? G : 0ull; }
+        if constexpr (RS_TPB > 1)
+          if (t >= first_tile && t < first_tile + RS_TPB) s_g[t - first_tile] = G;      // t >= n_tiles: G = 0
       }
     }
     below = wave_sum_u64(below);
@@ -219,8 +232,10 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) { prefix += s_below[w]; total += s_all[w]; }
+    if constexpr (RS_TPB > 1) {
 #pragma unroll
-    for (int j = 0; j < RS_TPB; ++j) prefix += (j < grp) ? s_g[j] : 0ull;
+      for (int j = 0; j < RS_TPB; ++j) prefix += (j < grp) ? s_g[j] : 0ull;
+    }
   }
   if (blk == 0 && threadIdx.x == 0) { *total_out = total; *max_out = M; }
   if (!tile_ok) return;                                  // a whole tile group past the end (uniform per wave; no barrier follows)
@@ -256,9 +271,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   if constexpr (SORTED) {
     // the evaluations side by side: every guide read issued before any is used, then every slot probe — written one
     // evaluation after the other, the (rare) walk past the probed slots orders the loads: ten dependent round trips.
-    // cv[0] (the lower edge of the thread's first source) is the previous thread's cv[4]: lanes take it from their
-    // neighbour below, lane 0 of waves 1 .. 3 from the wave before through LDS (after the cold path, so a corrected
-    // value travels), and only wave 0 evaluates its own (the tile's first edge).
+    // (cv[0]: only wave 0 evaluates its own — see below)
     uint32_t mv[CDF_VEC_OT + 1], gv[CDF_VEC_OT + 1], lov[CDF_VEC_OT + 1], hiv[CDF_VEC_OT + 1], kv[CDF_VEC_OT + 1];
     auto eval = [&](const int c0, const int c1) {
 #pragma unroll
@@ -321,14 +334,18 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   } else {
 #pragma unroll
     for (int c = 1; c <= CDF_VEC_OT; ++c) R[c] = below_est(cv[c]);
-    R[0] = below_est(cv[0]);
+    R[0].j = 0; R[0].near = false;
+    if (__builtin_amdgcn_readfirstlane(wave) == 0) R[0] = below_est(cv[0]);        // wave-uniform: a scalar branch
   }
 #pragma unroll
   for (int c = 1; c <= CDF_VEC_OT; ++c) {
     e[c] = R[c].j;
     near_bits |= R[c].near ? (1u << c) : 0u;
   }
-  // lower bound of the thread's first source = upper bound of the previous thread's last one; lane 0 evaluates its own
+  // lower bound of the thread's first source (cv[0]) = upper bound of the previous thread's last one (its cv[4]): lanes take
+  // it from their neighbour below, lane 0 of waves 1 .. 3 from the wave before through LDS (s_edge: published after the
+  // cold path, so a corrected value travels; read behind the barrier that precedes the slot fill), and only lane 0 of
+  // wave 0 uses an evaluation of its own (the tile's first edge)
   {
     const sb_est r = R[0];
     near_bits |= (lane == 0 && r.near) ? 1u : 0u;
@@ -355,12 +372,8 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     const uint32_t up = wave_shr1_u32((uint32_t)e[CDF_VEC_OT], (uint32_t)fixed0);
     e[0] = (lane == 0) ? fixed0 : (int32_t)up;
   }
-  if constexpr (SORTED) {        // lane 0 of waves 1 .. 3: the (settled) upper edge of the wave before
-    __shared__ int32_t s_edge[RS_WAVES];
-    if (lane == 63) s_edge[wave] = e[CDF_VEC_OT];
-    __syncthreads();
-    if (lane == 0 && wave > 0) e[0] = s_edge[wave - 1];
-  }
+  __shared__ int32_t s_edge[RS_WAVES];
+  if (lane == 63) s_edge[wave] = e[CDF_VEC_OT];      // the (settled) upper edge of this wave, for lane 0 of the next
   // Sources past n have e[c] = n = e of the last real source, so they own no slot.
   const int32_t e4 = e[4];
   const int32_t src0 = (int32_t)i0;
@@ -373,6 +386,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   reinterpret_cast<uint4*>(s_mark)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
   reinterpret_cast<uint4*>(s_mark)[threadIdx.x + RS_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
+  if (lane == 0 && wave > 0) e[0] = s_edge[wave - 1];
   const int32_t T0 = __builtin_amdgcn_readfirstlane(s_rng[0]), T1 = __builtin_amdgcn_readfirstlane(s_rng[1]);
   for (int32_t base = T0; base < T1; base += RS_FILL_SLOTS) {      // block-uniform trip count (1 unless the tile owns > 2048 slots)
     if (base != T0) {
@@ -451,10 +465,14 @@ gmx_tile_table_pass(const float* __restrict__ tmax, const uint64_t* __restrict__
   for (int c = 0; c < C; ++c) {
     const int lo = c * G, hi = (lo + G < n_tiles) ? lo + G : n_tiles, mine = lo + blk;
     uint64_t tot = 0, part = 0;
-    for (int t = lo + (int)threadIdx.x; t < hi; t += RS_BLOCK) {
-      const uint64_t g_ = gmx_tile_scale(agg[t], gmx_tile_exp(tmax[t]), K);
-      tot += g_;
-      part += (t < mine) ? g_ : 0ull;
+    for (int tb = lo; tb < hi; tb += RS_BLOCK) {      // a row of 256 entries: wholly in front of `mine` / straddling it / behind
+      const int t = tb + (int)threadIdx.x;
+      if (t < hi) {
+        const uint64_t g_ = gmx_tile_scale(agg[t], gmx_tile_exp(tmax[t]), K);
+        tot += g_;
+        if (tb + RS_BLOCK <= mine) { GMX_KEEP_BRANCH; part += g_; }          // (workgroup-uniform)
+        else if (tb < mine) { GMX_KEEP_BRANCH; part += (t < mine) ? g_ : 0ull; }
+      }
     }
     tot = wave_sum_u64(tot);
     part = wave_sum_u64(part);
