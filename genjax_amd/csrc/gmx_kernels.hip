@@ -3609,6 +3609,81 @@ extern "C" int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int6
 }
 
 // ---------------------------------------------------------------------------
+// row-wise resampling: many independent rows, each resampled as gmx_resample resamples it alone (gmx_resample_rows.h)
+// ---------------------------------------------------------------------------
+#include "gmx_resample_rows.h"
+static_assert(GMX_ROWS_MAX_N == (int64_t)RS_MAX_TILES * RS_TILE && GMX_TP_MAX_TILES == RS_MAX_TILES,
+              "gmx_resample_rows takes the rows the per-row fused path takes");
+
+extern "C" size_t gmx_resample_rows_workspace(int kind, int64_t rows, int64_t n) { return gmx_resample_rows_bytes_(kind, rows, n); }
+
+extern "C" int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                                 int64_t index_stride, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
+                                 int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("gmx_resample_rows: null argument%s");
+  switch (gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride)) {
+    case 0: break;
+    case 2: return gmx_fail("gmx_resample_rows: GMX_RESAMPLE_MULTINOMIAL_TILED and GMX_RESAMPLE_MULTINOMIAL_SORTED have no row "
+                            "form (systematic, stratified or multinomial)%s");
+    case 3: return gmx_fail("gmx_resample_rows: unknown kind %s%lld", "", (long long)kind);
+    case 4: return gmx_fail("gmx_resample_rows: index_stride = %s%lld does not keep rows * index_stride below 2^31", "",
+                            (long long)index_stride);
+    default:
+      if (rows < 1 || rows > 0x7fffffffLL) return gmx_fail("gmx_resample_rows: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
+      if (ld < n) return gmx_fail("gmx_resample_rows: ld = %s%lld is smaller than n", "", (long long)ld);
+      return gmx_fail("gmx_resample_rows: n = %s%lld is outside [1, 2^21]", "", (long long)n);
+  }
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows: workspace_d must be 8-byte aligned%s");
+  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) ||
+      ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
+    return gmx_fail("gmx_resample_rows: a pointer is not aligned to its element%s");
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  auto* status = (unsigned long long*)status_d;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+#define GMX_ROWS_SMALL2(KIND, W_)                                                                                      \
+  hipLaunchKernelGGL((k_rows_small<KIND, W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
+                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status)
+#define GMX_ROWS_SMALL(KIND)                                                                                           \
+  do {                                                                                                                 \
+    if (n <= 256) GMX_ROWS_SMALL2(KIND, 1);                                                                            \
+    else if (n <= 512) GMX_ROWS_SMALL2(KIND, 2);                                                                       \
+    else GMX_ROWS_SMALL2(KIND, 4);                                                                                     \
+  } while (0)
+    if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_SMALL(GMX_RESAMPLE_SYSTEMATIC);
+    else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_SMALL(GMX_RESAMPLE_STRATIFIED);
+    else GMX_ROWS_SMALL(GMX_RESAMPLE_MULTINOMIAL);
+#undef GMX_ROWS_SMALL
+#undef GMX_ROWS_SMALL2
+    GMX_HIP(hipGetLastError());
+    return 0;
+  }
+  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
+  uint64_t* agg = (uint64_t*)workspace_d;
+  uint64_t* cdf = agg + rows * tiles;
+  float* tmax = (float*)(cdf + (kind == GMX_RESAMPLE_MULTINOMIAL ? rows * n : 0));
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
+    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
+    const dim3 grid((unsigned)tiles, (unsigned)cnt), block(GMX_ROWS_BLOCK);
+    hipLaunchKernelGGL(k_pick_stats, grid, block, 0, st, lw_d, n, ld, tiles, row0, scale, tmax, agg);
+#define GMX_ROWS_TILE(KIND)                                                                                            \
+  hipLaunchKernelGGL((k_rows_tile<KIND>), grid, block, 0, st, keys_d, lw_d, n, ld, (int)tiles, row0, index_stride, scale, \
+                     (const float*)tmax, (const uint64_t*)agg, max_d, total_d, ancestors_d, cdf, status)
+    if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_TILE(GMX_RESAMPLE_SYSTEMATIC);
+    else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_TILE(GMX_RESAMPLE_STRATIFIED);
+    else {
+      GMX_ROWS_TILE(GMX_RESAMPLE_MULTINOMIAL);
+      hipLaunchKernelGGL(k_rows_mn, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0, st,
+                         keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
+    }
+#undef GMX_ROWS_TILE
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------
 struct gmx_graph { hipGraph_t graph; hipGraphExec_t exec; };

@@ -1,0 +1,308 @@
+// Resampling of many independent rows (include/genmi.h "Row-wise exact-integer draws": gmx_resample_rows): row r of a
+// [rows, n] matrix of log-weights is resampled under keys[r] exactly as gmx_resample resamples it alone — the two-level
+// block-floating-point integer CDF over tiles of 1024 columns OF THE ROW, shift = 62 - ceil(log2 n), 23-bit uniforms, 128-bit
+// comparisons.  Everything after the per-element exp is integer arithmetic and every slot is decided by the DEFINITION
+// (the first column whose CDF value passes the slot's threshold: a binary search over the tile's CDF in LDS), so the
+// ancestors do not depend on the grid or on the form.
+//   n <= 1024   k_rows_small<kind, W>: ONE launch, no workspace traffic.  A row is one CDF tile: its maximum, its weights,
+//               their scan and the slot searches stay in registers / LDS.  PACKING: a thread holds 4 consecutive columns
+//               (one 16-byte load), so a row takes W = 1, 2 or 4 waves (n <= 256, <= 512, <= 1024) and a 256-thread
+//               workgroup holds 4 / W rows: four rows of up to 256 columns, two of up to 512, one of up to 1024.
+//   n > 1024    k_pick_stats (gmx_backward.h) per (row, tile), then k_rows_tile<kind>, one workgroup per (row, tile): the
+//               row's tile prefixes, total and (M, K) from its <= 2048 tile statistics (gmx_tile_prefix_block, into LDS),
+//               the tile's 1024 CDF values rebuilt into LDS, and — systematic / stratified — the slots the tile owns,
+//               [f(prefix_b), f(prefix_b + G_b)), f(c) = #{ j : P_j < c D }, searched in that LDS tile.  No CDF array.
+//   iid multinomial past one tile: a slot's threshold falls anywhere in the row, so k_rows_tile writes the row's CDF into
+//               the workspace ([rows, n] u64) and k_rows_mn searches it per slot (a third launch).
+// Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
+// host compiler: the two ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
+// multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
+// for gmx_pick_rows; gmx_vm.h includes this file there.  That loop validates its arguments as the HIP entry point does but
+// leaves no message.
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include "gmx_backward.h"              /* GMX_PICK_TILE, gmx_pick_rows_shift_; under hipcc k_pick_stats, pick_load4 */
+
+#define GMX_ROWS_MAX_N (2048 * 1024)   /* RS_MAX_TILES tiles: what the per-row fused path takes */
+
+// workspace: agg u64 [rows * tiles] | cdf u64 [rows * n] (iid multinomial only) | tmax f32 [rows * tiles]; nothing for n <= 1024
+static inline size_t gmx_resample_rows_bytes_(int kind, int64_t rows, int64_t n) {
+  if (rows < 1 || n <= GMX_PICK_TILE || n > GMX_ROWS_MAX_N) return 16;
+  const uint64_t cells = (uint64_t)rows * (uint64_t)((n + GMX_PICK_TILE - 1) / GMX_PICK_TILE);
+  const uint64_t cdf = kind == 2 /* GMX_RESAMPLE_MULTINOMIAL */ ? (uint64_t)rows * (uint64_t)n * 8u : 0u;
+  return (size_t)((cells * 12u + cdf + 15u) & ~(uint64_t)15u);
+}
+// 0: fine.  1: a size out of range.  2: an ordered multinomial.  3: an unknown kind.  4: the stride overflows int32.
+static inline int gmx_resample_rows_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
+  if (kind == 3 || kind == 4) return 2;
+  if (kind < 0 || kind > 2) return 3;
+  if (rows < 1 || rows > 0x7fffffffLL || n < 1 || n > GMX_ROWS_MAX_N || ld < n) return 1;
+  if (index_stride < 0) return 4;
+  if (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
+                           (rows - 1) * index_stride + n - 1 >= (1LL << 31))) return 4;
+  return 0;
+}
+
+#if defined(__HIPCC__)
+#include "gmx_resample.h"              /* gmx_block.h, gmx_rng.h, u128 / mul64 / slot_threshold */
+
+#define GMX_ROWS_BLOCK 256
+
+// Slot j's ancestor inside ONE ascending run of CDF values cdf[0 .. cnt): the first i whose value passes the slot's
+// threshold, cnt when none does.  systematic / stratified: cdf_i D > P_j = (j 2^23 + u_j) total, D = n 2^23 (k_offspring's
+// predicate); multinomial: cdf_i >= ceil(total (2^23 - u_j) / 2^23) (k_ancestors_mn's integer form).  total >= 1.
+template <int KIND>
+__device__ __forceinline__ int32_t rows_slot_search(const uint64_t* cdf, int32_t cnt, gmx_key key, uint64_t u0, int64_t j,
+                                                    uint64_t total, uint64_t D) {
+  int32_t lo = 0, hi = cnt;
+  if (KIND == GMX_RESAMPLE_MULTINOMIAL) {
+    const uint64_t u = (uint64_t)(gmx_bits32(key, (uint64_t)j) >> 9);
+    const u128 P = mul64(total, (1ull << 23) - u);                 // >= 1
+    const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
+    const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
+    const uint64_t Thr = (phi << 41) | (plo >> 23);                // ceil(P / 2^23), in [1, total]
+    while (lo < hi) {
+      const int32_t mid = lo + ((hi - lo) >> 1);
+      if (cdf[mid] >= Thr) hi = mid; else lo = mid + 1;
+    }
+  } else {
+    const u128 P = slot_threshold(KIND, key, u0, j, total);
+    while (lo < hi) {
+      const int32_t mid = lo + ((hi - lo) >> 1);
+      if (gt128(mul64(cdf[mid], D), P)) hi = mid; else lo = mid + 1;
+    }
+  }
+  return lo;
+}
+
+// f(c) = #{ j in [0, n) : P_j < c D } for the ordered kinds (P_j increases with j): the exact predicate, bisected
+template <int KIND>
+__device__ __forceinline__ int64_t rows_slots_below(gmx_key key, uint64_t u0, uint64_t c, uint64_t D, uint64_t total, int64_t n) {
+  const u128 X = mul64(c, D);
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (gt128(X, slot_threshold(KIND, key, u0, mid, total))) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Four ancestors of consecutive slots base .. base + 3 of a row: one 16-byte store where the address allows
+__device__ __forceinline__ void rows_store4(int32_t* __restrict__ row, int64_t base, int64_t n, const int32_t v[4]) {
+  if (base + 4 <= n && (((uintptr_t)(row + base)) & 15u) == 0u) {
+    *reinterpret_cast<int4*>(row + base) = make_int4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (base + c < n) row[base + c] = v[c];
+  }
+}
+
+// n <= 1024: W waves per row, 4 / W rows per workgroup; thread gt of a row's group holds columns (and slots) 4 gt .. 4 gt + 3.
+// Every thread reaches every barrier (a group past the last row works on the last row again and writes nothing).
+template <int KIND, int W>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_small(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld,
+             int64_t index_stride, float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out,
+             int32_t* __restrict__ anc, unsigned long long* __restrict__ status) {
+  static_assert(W == 1 || W == 2 || W == 4, "waves per row");
+  constexpr int RPW = 4 / W, GT = 64 * W;
+  __shared__ float s_max[4];
+  __shared__ uint64_t s_scan[4];
+  __shared__ uint64_t s_cdf[GMX_PICK_TILE];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int grp = tid / GT, gt = tid % GT;
+  const int64_t r_ = (int64_t)blockIdx.x * RPW + grp;
+  const bool live = r_ < rows;
+  const int64_t r = live ? r_ : rows - 1;
+  const float* __restrict__ row = lw + r * ld;
+  const int64_t base = (int64_t)gt * 4;
+  float x[4];
+  pick_load4(row, base, n, x);
+  const float m = wave_max(gmx_rmax(gmx_rmax(x[0], x[1]), gmx_rmax(x[2], x[3])));
+  if (lane == 0) s_max[wave] = m;
+  __syncthreads();
+  float M = s_max[grp * W];
+#pragma unroll
+  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  const float ref = gmx_tile_ref(gmx_tile_exp(M));       // one tile: K = k_b, cdf_i = the tile-local inclusive sum
+  uint64_t q[4], run = 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    run += (base + c < n) ? weight_fixed(x[c], ref, scale) : 0ull;
+    q[c] = run;
+  }
+  const uint64_t inc = wave_scan_u64(run);
+  if (lane == 63) s_scan[wave] = inc;
+  __syncthreads();
+  uint64_t woff = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const uint64_t v = s_scan[grp * W + w];
+    total += v;
+    woff += (grp * W + w < wave) ? v : 0ull;
+  }
+  const uint64_t loc = woff + (inc - run);
+  uint64_t* cdf = s_cdf + grp * (GT * 4);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) cdf[base + c] = loc + q[c];
+  __syncthreads();
+  if (!live) return;                                     // (no barrier follows)
+  if (gt == 0) {
+    max_out[r] = M;
+    total_out[r] = total;
+    if (total == 0ull) atomicAdd(status, 1ull);
+  }
+  gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
+  const uint64_t u0 = KIND == GMX_RESAMPLE_SYSTEMATIC ? (uint64_t)(gmx_bits32(key, 0ull) >> 9) : 0ull;
+  const uint64_t D = (uint64_t)n << 23;
+  const int32_t add = (int32_t)(r * index_stride);
+  int32_t out[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int32_t i = (int32_t)n - 1;                          // no mass at all: the last column, as gmx_resample answers
+    if (total != 0ull && base + c < n) {
+      i = rows_slot_search<KIND>(cdf, (int32_t)n, key, u0, base + c, total, D);
+      i = i < (int32_t)n ? i : (int32_t)n - 1;
+    }
+    out[c] = i + add;
+  }
+  rows_store4(anc + r * n, base, n, out);
+}
+
+// n > 1024: blockIdx.x the tile, blockIdx.y the row (row0 + y).  tmax / agg: k_pick_stats' [rows, n_tiles] statistics.
+// cdf_i = prefix_b + ((tile-local inclusive sum) >> (K - k_b)), as k_weight_cdf writes it.
+template <int KIND>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_tile(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int64_t n, int64_t ld, int n_tiles, int64_t row0,
+            int64_t index_stride, float scale, const float* __restrict__ tmax, const uint64_t* __restrict__ agg,
+            float* __restrict__ max_out, uint64_t* __restrict__ total_out, int32_t* __restrict__ anc,
+            uint64_t* __restrict__ cdf_out, unsigned long long* __restrict__ status) {
+  __shared__ float lds4[4];
+  __shared__ uint64_t lds8[4];
+  __shared__ uint64_t s_pref[GMX_TP_MAX_TILES + 16];
+  __shared__ uint64_t s_cdf[GMX_PICK_TILE];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = (int)blockIdx.x;
+  const int64_t r = row0 + (int64_t)blockIdx.y;
+  const float* __restrict__ tm = tmax + r * n_tiles;
+  const int64_t col0 = (int64_t)b * GMX_PICK_TILE, base = col0 + (int64_t)tid * 4;
+  float x[4];
+  pick_load4(lw + r * ld, base, n, x);
+  const float tmax_mine = tm[b];
+  gmx_tile_prefix_block(tm, agg + r * n_tiles, n_tiles, s_pref, lds4, lds8);
+  const int32_t k_b = gmx_tile_exp(tmax_mine);
+  const float ref_b = gmx_tile_ref(k_b);
+  uint64_t q[4], run = 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    run += (base + c < n) ? weight_fixed(x[c], ref_b, scale) : 0ull;
+    q[c] = run;
+  }
+  const uint64_t inc = wave_scan_u64(run);
+  __syncthreads();                                       // s_pref is written; lds8 has been read
+  if (lane == 63) lds8[wave] = inc;
+  __syncthreads();
+  uint64_t woff = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) woff += (w < wave) ? lds8[w] : 0ull;
+  const uint64_t loc = woff + (inc - run);
+  const uint64_t prefix = s_pref[b], total = s_pref[n_tiles], mk = s_pref[n_tiles + 1];
+  const int32_t K = (int32_t)(uint32_t)(mk >> 32);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) s_cdf[tid * 4 + c] = prefix + gmx_tile_scale(loc + q[c], k_b, K);
+  __syncthreads();
+  if (b == 0 && tid == 0) {
+    max_out[r] = gmx_u2f((uint32_t)mk);
+    total_out[r] = total;
+    if (total == 0ull) atomicAdd(status, 1ull);
+  }
+  const int32_t add = (int32_t)(r * index_stride);
+  int32_t* __restrict__ arow = anc + r * n;
+  if (KIND == GMX_RESAMPLE_MULTINOMIAL) {                // the row's CDF for k_rows_mn (a row without mass: all zero)
+    uint64_t* __restrict__ crow = cdf_out + r * n;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (base + c < n) crow[base + c] = s_cdf[tid * 4 + c];
+    return;
+  }
+  if (total == 0ull) {                                   // no mass at all: every slot maps to the last column
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (base + c < n) arow[base + c] = (int32_t)(n - 1) + add;
+    return;
+  }
+  gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
+  const uint64_t u0 = KIND == GMX_RESAMPLE_SYSTEMATIC ? (uint64_t)(gmx_bits32(key, 0ull) >> 9) : 0ull;
+  const uint64_t D = (uint64_t)n << 23;
+  const uint64_t upper = s_cdf[GMX_PICK_TILE - 1];      // prefix_b + G_b (columns past n carry nothing)
+  if (upper == prefix) return;                           // an empty tile owns no slot
+  const int64_t T0 = rows_slots_below<KIND>(key, u0, prefix, D, total, n);
+  const int64_t T1 = rows_slots_below<KIND>(key, u0, upper, D, total, n);
+  const int64_t left = n - col0;
+  const int32_t cnt = left < GMX_PICK_TILE ? (int32_t)left : GMX_PICK_TILE;
+  for (int64_t j = T0 + tid; j < T1; j += GMX_ROWS_BLOCK) {
+    int32_t i = rows_slot_search<KIND>(s_cdf, cnt, key, u0, j, total, D);
+    i = i < cnt ? i : cnt - 1;
+    arow[j] = (int32_t)col0 + i + add;
+  }
+}
+
+// iid multinomial past one tile: slot j of row r searches the row's CDF array.  blockIdx.x: 256 slots, blockIdx.y: the row.
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_mn(const uint32_t* __restrict__ keys, const uint64_t* __restrict__ cdf, int64_t n, int64_t row0, int64_t index_stride,
+          const uint64_t* __restrict__ total_in, int32_t* __restrict__ anc) {
+  const int64_t r = row0 + (int64_t)blockIdx.y;
+  const int64_t j = (int64_t)blockIdx.x * GMX_ROWS_BLOCK + (int64_t)threadIdx.x;
+  if (j >= n) return;
+  const uint64_t total = total_in[r];
+  int32_t i = (int32_t)n - 1;
+  if (total != 0ull) {
+    gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
+    i = rows_slot_search<GMX_RESAMPLE_MULTINOMIAL>(cdf + r * n, (int32_t)n, key, 0ull, j, total, 0ull);
+    i = i < (int32_t)n ? i : (int32_t)n - 1;
+  }
+  anc[r * n + j] = i + (int32_t)(r * index_stride);
+}
+
+#elif defined(__cplusplus) && !defined(__HIPCC_RTC__)
+#include <vector>
+#include "genmi.h"
+#include "gmx_math.h"
+// (`used`: emitted, and so exported by a shared library, although nothing in the translation unit calls them)
+
+extern "C" __attribute__((used)) inline size_t gmx_resample_rows_workspace(int kind, int64_t rows, int64_t n) {
+  return gmx_resample_rows_bytes_(kind, rows, n);
+}
+
+extern "C" __attribute__((used)) inline int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n,
+                                        int64_t ld, int64_t index_stride, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
+                                        int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d) return 1;
+  if (gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride)) return 1;
+  const int shift = gmx_pick_rows_shift_(n);
+  std::vector<float> row((size_t)n);                             // (the per-row path asks for an aligned row)
+  std::vector<uint64_t> cdf(kind == GMX_RESAMPLE_MULTINOMIAL ? (size_t)n : 0);
+  std::vector<uint64_t> ws((gmx_resample_workspace(n) + 7) / 8 + 2);
+  for (int64_t r = 0; r < rows; ++r) {
+    const float* src = lw_d + r * ld;
+    float M = -gmx_inf();
+    for (int64_t i = 0; i < n; ++i) { row[(size_t)i] = src[i]; M = gmx_rmax(M, src[i]); }
+    uint64_t total = 0;
+    int32_t* out = ancestors_d + r * n;
+    if (kind == GMX_RESAMPLE_MULTINOMIAL) {
+      if (gmx_weight_cdf(row.data(), n, shift, nullptr, 0, &M, cdf.data(), &total, ws.data(), stream)) return 1;
+      if (gmx_ancestors(kind, keys_d + 2 * r, cdf.data(), n, 0, &total, n, 0, n, out, stream)) return 1;
+    } else if (gmx_resample(kind, keys_d + 2 * r, row.data(), n, shift, nullptr, 0, &M, &total, out, ws.data(), stream)) {
+      return 1;
+    }
+    max_d[r] = M;
+    total_d[r] = total;
+    if (total == 0) status_d[0] += 1;
+    const int32_t add = (int32_t)(r * index_stride);
+    for (int64_t i = 0; i < n; ++i) out[i] += add;
+  }
+  return 0;
+}
+#endif

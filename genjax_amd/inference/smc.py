@@ -125,7 +125,8 @@ class ParticleCollection:
     @property
     def log_weights(self):
         if self._lw is None:
-            self._lw = torch.zeros((self._n_zero,), dtype=torch.float32, device=_lib.get().device)
+            shape = tuple(self._n_zero) if isinstance(self._n_zero, (tuple, list)) else (self._n_zero,)      # (a batched collection: [R, n])
+            self._lw = torch.zeros(shape, dtype=torch.float32, device=_lib.get().device)
         return self._lw
 
     @log_weights.setter
@@ -148,11 +149,14 @@ class ParticleCollection:
         return self.get_particle(idx), self.log_weights[idx]
 
     def get_log_marginal_likelihood_estimate(self):
-        """logsumexp(lw) - log N (smc.py:96-97) [+ accumulated offset]."""
+        """logsumexp(lw) - log N (smc.py:96-97) [+ accumulated offset]; a batched collection: the per-row estimate."""
         n = self.log_weights.shape[-1]
         est = engine.elementwise(_sub_const, engine.logsumexp_rows(self.log_weights), math.log(n))
         if self.log_ml_offset is not None:
-            est = engine.elementwise(_add, est, self.log_ml_offset.value())
+            off = self.log_ml_offset.value()
+            if isinstance(off, np.ndarray):        # one offset per row: added in float32, as the 1-D path adds its one
+                off = torch.from_numpy(off.astype(np.float32)).to(est.device).reshape(est.shape)
+            est = engine.elementwise(_add, est, off)
         return est
 
     def sample_index(self, key: Key):
@@ -432,13 +436,19 @@ _KINDS = {"systematic": SYSTEMATIC, "stratified": STRATIFIED, "multinomial": MUL
 _TILE_KINDS = (SYSTEMATIC, STRATIFIED, MULTINOMIAL_TILED, MULTINOMIAL_SORTED)      # from log-weights + tile statistics, n <= 2^21
 
 
-def cdf_reference(m) -> float:
+def cdf_reference(m):
     """The log-weight an integer CDF total is relative to: total * 2^-shift = sum_i exp(lw_i - cdf_reference(max lw)).
     = ceil(max lw / ln 2) * ln 2 in float32 arithmetic (gmx_tile_exp / gmx_tile_ref in csrc/gmx_math.h: the
-    exponent K of the block-floating-point CDF), evaluated on the host for the evidence terms."""
+    exponent K of the block-floating-point CDF), evaluated on the host for the evidence terms.  A float for one maximum;
+    a float64 array, element by element the same numbers, for an array of them (one per row of gmx_resample_rows)."""
     lim = 1 << 29
     inv_ln2 = np.frombuffer(np.uint32(0x3FB8AA3B).tobytes(), np.float32)[0]
     ln2 = np.frombuffer(np.uint32(0x3F317218).tobytes(), np.float32)[0]
+    if np.ndim(m) > 0:
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = np.asarray(m, dtype=np.float32) * inv_ln2
+            k = np.ceil(np.clip(np.where(t > -np.float32(lim), t, -np.float32(lim)), -np.float32(lim), np.float32(lim)))
+        return (k.astype(np.float32) * ln2).astype(np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
         t = np.float32(m) * inv_ln2
     if not (t > -np.float32(lim)):
@@ -466,12 +476,28 @@ class LogMLOffset:
       sum_t [ M_t + log(total_t * 2^-shift) - log N ]."""
 
     def __init__(self, terms=()):
-        self.terms = list(terms)      # (max_d f32[1], total_d u64-as-i64[1], shift, n)
+        self.terms = list(terms)      # (max_d f32[1], total_d u64-as-i64[1], shift, n); a batched collection: [R] each
 
     def plus(self, max_d, total_d, shift, n):
         return LogMLOffset(self.terms + [(max_d, total_d, shift, n)])
 
-    def value(self) -> float:
+    def value(self):
+        """a float; with [R] terms (smc.resample on a batched collection) float64 [R], row r the float the same terms of
+        row r alone give"""
+        if any(max_d.numel() > 1 for max_d, _, _, _ in self.terms):
+            ms = [cdf_reference(max_d.reshape(-1).cpu().numpy()) for max_d, _, _, _ in self.terms]
+            tots = [total_d.reshape(-1).cpu().numpy().view(np.uint64) for _, total_d, _, _ in self.terms]
+            out = np.zeros((max(m.size for m in ms),), dtype=np.float64)
+            for r in range(out.size):
+                acc = 0.0
+                for m, tot, (_, _, shift, n) in zip(ms, tots, self.terms):
+                    tr = int(tot[r % tot.size])
+                    if tr == 0:              # no particle of the row carried any mass
+                        acc = -math.inf
+                        break
+                    acc += float(m[r % m.size]) + math.log(tr) - shift * math.log(2.0) - math.log(n)
+                out[r] = acc
+            return out
         acc = 0.0
         for max_d, total_d, shift, n in self.terms:
             m = float(max_d.reshape(-1)[0].item())
@@ -696,7 +722,7 @@ def resample(key: Key, collection: ParticleCollection, kind="systematic", n_out=
     its kernel; weights reset to 0 and the evidence moves into log_ml_offset."""
     lw = collection.get_log_weights()
     if lw.ndim != 1:
-        raise NotImplementedError("resample: batched collections")
+        return _resample_batched(key, collection, kind, n_out)
     kind = _KINDS[kind] if isinstance(kind, str) else int(kind)
     n = lw.numel()
     if _Resampler.form_of(kind, n, n_out) != "cdf":
@@ -712,6 +738,77 @@ def resample(key: Key, collection: ParticleCollection, kind="systematic", n_out=
     return out
 
 
+ROW_KINDS = (SYSTEMATIC, STRATIFIED, MULTINOMIAL)      # what gmx_resample_rows takes
+ROWS_N_MAX = FUSED_RESAMPLE_MAX
+
+
+def resample_rows(kind, keys: Key, lw: torch.Tensor, index_stride: int = 0, *, out=None, workspace=None):
+    """gmx_resample_rows: R independent rows in one call.  lw [R, n] float32 (contiguous), keys of shape (R,) ->
+    (ancestors int32 [R, n] — row-local, or into the flat [R * n] store with index_stride = n —, total [R], max [R],
+    shift, status [1]: the number of rows without mass).  out = (anc, total, max, status) and workspace: persistent
+    buffers of a sweep instead of fresh ones (status is then NOT zeroed here)."""
+    be = _lib.get()
+    R, n = lw.shape
+    kd = keys if isinstance(keys, torch.Tensor) else keys.data()
+    if out is None:
+        anc = torch.empty((R, n), dtype=torch.int32, device=lw.device)
+        total = torch.empty((R,), dtype=torch.int64, device=lw.device)
+        mx = torch.empty((R,), dtype=torch.float32, device=lw.device)
+        status = torch.zeros((1,), dtype=torch.int64, device=lw.device)
+    else:
+        anc, total, mx, status = out
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(int(kind), R, n)) + 7) // 8,), dtype=torch.int64,
+                                device=lw.device)
+    be.check(be.c.gmx_resample_rows(int(kind), be.ptr(kd), be.ptr(lw), R, n, n, int(index_stride), be.ptr(mx), be.ptr(total),
+                                    be.ptr(anc), be.ptr(status), be.ptr(workspace), be.stream()), "gmx_resample_rows")
+    return anc, total, mx, cdf_shift(n), status
+
+
+def _row_kind(kind, who):
+    kind = _KINDS[kind] if isinstance(kind, str) else int(kind)
+    if kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):
+        raise NotImplementedError(f"{who}: 'multinomial_tiled' / 'multinomial_sorted' have no row form "
+                                  "(use 'systematic', 'stratified' or 'multinomial')")
+    if kind not in ROW_KINDS:
+        raise ValueError(f"{who}: unknown resampling kind {kind}")
+    return kind
+
+
+def _resample_batched(keys: Key, collection: ParticleCollection, kind, n_out) -> ParticleCollection:
+    """smc.resample on a collection of R independent particle systems (log_weights [R, n], keys of shape (R,)): row r
+    is resampled under keys[r] as the 1-D path resamples it alone — ONE gmx_resample_rows call with index_stride = n and
+    ONE gmx_gather of every (R, n) leaf over its flat [R * n] view (materialised).  `ancestors` are row-local [R, n]."""
+    lw = collection.get_log_weights()
+    if lw.ndim != 2:
+        raise NotImplementedError(f"resample: log_weights of shape {tuple(lw.shape)} (one batch axis over the particles)")
+    R, n = (int(v) for v in lw.shape)
+    if tuple(keys.shape) != (R,):
+        raise ValueError(f"resample: log_weights of shape {(R, n)} need keys of shape {(R,)}, one per row; got keys of "
+                         f"shape {tuple(keys.shape)}")
+    kind = _row_kind(kind, "resample on a batched collection")
+    if n_out not in (None, n):
+        raise NotImplementedError(f"resample on a batched collection: n_out != n (n_out = {n_out}, n = {n})")
+    if n > ROWS_N_MAX or R * n >= 2 ** 31:
+        raise NotImplementedError(f"resample on a batched collection: n <= 2^21 and R * n < 2^31 (R = {R}, n = {n})")
+    lw = lw.float().contiguous()
+    flat, total, mx, shift, _ = resample_rows(kind, keys, lw, index_stride=n)
+    found = []
+
+    def pick(v):
+        if tuple(v.shape[:2]) == (R, n):
+            v = engine.materialize(v)
+            found.append(v.reshape((R * n,) + tuple(v.shape[2:])))
+        return v
+    trace_map(collection.get_particles(), pick)
+    moved = iter(engine.gather_leaves(found, flat)) if found else iter(())
+    particles = trace_map(collection.get_particles(), lambda v: next(moved) if tuple(v.shape[:2]) == (R, n) else v)
+    off = (collection.log_ml_offset or LogMLOffset()).plus(mx, total, shift, n)
+    out = ParticleCollection(particles, None, True, off, n_zero=(R, n))          # weights reset to 0, lazily
+    out.ancestors = flat - (torch.arange(R, dtype=torch.int32, device=flat.device) * n).reshape(R, 1)
+    return out
+
+
 def extend(key: Key, collection: ParticleCollection, step, step_args, observations: ChoiceMap) -> ParticleCollection:
     """Bootstrap extension by one step: every particle i runs
     `step.importance(split(key, N)[i], observations, step_args_i)` and
@@ -719,7 +816,9 @@ def extend(key: Key, collection: ParticleCollection, step, step_args, observatio
     restricted to the new step's sites).  `step_args` is a tuple, or a callable
     mapping the previous particles' trace to the tuple."""
     zero = collection.weights_are_zero()
-    n = collection._n_zero if zero else collection.get_log_weights().shape[0]
+    n = collection._n_zero if zero else collection.get_log_weights().shape[-1]
+    if isinstance(n, (tuple, list)):       # a batched collection: (R, n) — `key` then holds R keys, split(key, n) is (R, n)
+        n = n[-1]
     args = step_args(collection.get_particles()) if callable(step_args) else tuple(step_args)
     keys = split(key, n)
     from ..static import StaticGenerativeFunction, run_gfi
@@ -1754,3 +1853,191 @@ class BootstrapSweep(_NoiseAhead):
         """(x_T particles before the last resampling, log-weights, last ancestors)."""
         self._check_valid()
         return self.x[(self.T - 1) % 2], self.lw_pp[(self.T - 1) % 2 if self.fuse else 0], self.anc
+
+
+class BootstrapBank(_NoiseAhead):
+    """R independent bootstrap particle filters of n particles each as ONE chain of launches (the reference's
+    `jax.vmap(smc_run)(keys)`: replicate keys for the variance of the evidence estimate, a grid or a chain over model
+    parameters): per step ONE site program over the R * n particles and ONE gmx_resample_rows call (every row under its
+    own key, n <= 1024: a single launch), no host read of a device value in between — the whole sweep is capturable.
+
+    Key schedule: row r follows BootstrapSweep's under keys[r] — step key = fold_in(keys[r], t); (k_prop, k_res, _) =
+    split(step key, 3); particle i of the row draws under split(k_prop, n)[i] (derived in the program from the row's key:
+    GMX_KEY_ROWSPLIT, no key launch); the row is resampled under k_res.  The T x R proposal / resampling keys are
+    derived on the host and uploaded once by prepare().
+
+    Contract: row r of state() and log_ml()[r] equal, bit for bit, what BootstrapSweep(init, step, n, T, ...).prepare(
+    keys[r], ys) gives launched on its own.
+
+    The programs are built as the sweep builds them (static.MinimalGenerate), over the flat R * n particle axis; the
+    next step gathers through GLOBAL ancestors (gmx_resample_rows with index_stride = n) over the flat state store.
+    `params`: a tuple of float32 [R] tensors, one value per filter; the models are called as init(*params_r) and
+    step(x_prev, *step_extra(t), *params_r).  Each is expanded ONCE, in prepare(), to a persistent [R * n] per-particle
+    leaf (4 bytes per particle and parameter read by every step; nothing is launched for it inside the sweep) — the
+    engine's launch-uniform leaves have no per-row form.  ys: [T], shared by the filters."""
+
+    def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
+                 step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
+                 noise_ahead=None, fuse_resample=None, comm=None):
+        for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
+                            ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
+                            ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
+                            ("comm= (sharding over several GPUs)", comm is not None)):
+            if given:
+                raise NotImplementedError(f"BootstrapBank: {name} is not supported (use BootstrapSweep per filter)")
+        self.init, self.step = init, step
+        self.n, self.R, self.T = int(n_particles), int(n_filters), int(T)
+        if self.n < 1 or self.R < 1 or self.T < 1:
+            raise ValueError("BootstrapBank: n_particles, n_filters and T must be positive")
+        self.kind = _row_kind(resample, "BootstrapBank(resample=)")
+        if self.n > ROWS_N_MAX:
+            raise NotImplementedError(f"BootstrapBank: n_particles = {self.n} > 2^21 (gmx_resample_rows)")
+        if self.R * self.n >= 2 ** 31:
+            raise NotImplementedError(f"BootstrapBank: R * n >= 2^31 (R = {self.R}, n = {self.n}): the ancestors index the "
+                                      "flat [R * n] store in int32")
+        self.obs_addr, self.state_addr = obs_addr, state_addr
+        self.step_extra = step_extra or (lambda t: ())
+        self.params = tuple(params) if params is not None else ()
+        self.specialize = specialize
+
+    def prepare(self, keys: Key, ys: torch.Tensor):
+        from ..random import _derive_host
+        from ..static import MinimalGenerate
+        be = _lib.get()
+        self._drop_graph()
+        R, n, T = self.R, self.n, self.T
+        N = R * n
+        dev = be.device
+        if tuple(keys.shape) != (R,):
+            raise ValueError(f"BootstrapBank.prepare: {R} filters need keys of shape {(R,)}, got {tuple(keys.shape)}")
+        ys = torch.as_tensor(ys)
+        if ys.ndim != 1:
+            raise NotImplementedError(f"BootstrapBank.prepare: per-filter observations (ys of [R, T]; got "
+                                      f"{tuple(ys.shape)}) are not supported: ys is [T], shared by the filters")
+        self.keys = keys
+        self.ys = ys.to(dev).float().contiguous()
+        assert self.ys.numel() >= T
+        # the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys
+        kh = np.asarray(keys.host(), dtype=np.uint32).reshape(R, 2)
+        prop, res = np.empty((T, R, 2), np.uint32), np.empty((T, R, 2), np.uint32)
+        for t in range(T):
+            ks = _derive_host(_derive_host(kh, np.uint64(t))[:, None, :], np.arange(3, dtype=np.uint64))
+            prop[t], res[t] = ks[:, 0], ks[:, 1]
+        self.keys_prop = torch.from_numpy(prop.view(np.int32)).to(dev)
+        self.keys_res = torch.from_numpy(res.view(np.int32)).to(dev)
+        self.lw = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.anc = torch.zeros((R, n), dtype=torch.int32, device=dev)          # indices into the flat [R * n] store
+        self.maxs = torch.zeros((T, R), dtype=torch.float32, device=dev)
+        self.totals = torch.zeros((T, R), dtype=torch.int64, device=dev)
+        self.status = torch.zeros((1,), dtype=torch.int64, device=dev)         # rows without mass, over the last sweep
+        self.shift = cdf_shift(n)
+        self.ws = torch.zeros(((int(be.c.gmx_resample_rows_workspace(self.kind, R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
+        self.params_full = []
+        for p in self.params:
+            p = torch.as_tensor(p)
+            if tuple(p.shape) != (R,):
+                raise ValueError(f"BootstrapBank: params are [R] = {(R,)} tensors, one value per filter; got {tuple(p.shape)}")
+            self.params_full.append(p.to(dev).float().reshape(R, 1).expand(R, n).contiguous().reshape(N))
+        pf = tuple(self.params_full)
+        obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
+        self.p_init = MinimalGenerate(self.init, pf, obs0, (N,))
+        ro, outs_ = self.p_init.ro, self.p_init.comp.outputs
+        self.tuple_state = None
+        if ro[0] in ("tuple", "list") and ro[1] and all(o[0] == "out" and outs_[o[1]][0] == "f32" and outs_[o[1]][1] == ()
+                                                          for o in ro[1]):
+            self.tuple_state = type(()) if ro[0] == "tuple" else type([])
+            event, D = (), len(ro[1])
+        else:
+            if ro[0] != "out":
+                raise NotImplementedError("BootstrapBank: the step model must return one array (scalar or vector "
+                                          "state) or a tuple of float scalars")
+            dt, event, _slots = outs_[ro[1]]
+            if dt != "f32" or len(event) > 1:
+                raise NotImplementedError("BootstrapBank: the state must be a float scalar or a float vector")
+            D = int(np.prod(event, dtype=np.int64)) if event else 1
+        self.event = tuple(event)
+        self.x_store = [torch.zeros((D, N), dtype=torch.float32, device=dev) for _ in range(2)]
+        if self.tuple_state is not None:
+            self.x = [self.tuple_state(s_[d] for d in range(D)) for s_ in self.x_store]
+        else:
+            self.x = [s_.reshape(N) if not event else s_.t() for s_ in self.x_store]
+        self.p_step = MinimalGenerate(self.step, (self._gathered(0),) + tuple(self.step_extra(1)) + pf, obs0, (N,))
+        if self.specialize:
+            self.p_init.comp.specialize()
+            self.p_step.comp.specialize()
+        self.partials = torch.zeros((2, (N + 255) // 256), dtype=torch.float32, device=dev)
+        return self
+
+    def _gathered(self, which):
+        anc = self.anc.reshape(-1)
+        if self.tuple_state is not None:
+            return self.tuple_state(Gathered(row, anc) for row in self.x[which])
+        return Gathered(self.x[which], anc)
+
+    def _launch_vm(self, t):
+        N = self.R * self.n
+        obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
+        pf = tuple(self.params_full)
+        if t == 0:
+            prog = self.p_init
+            leaves = prog.leaves(pf, obs)
+        else:
+            prog = self.p_step
+            leaves = prog.leaves((self._gathered((t - 1) % 2),) + tuple(self.step_extra(t)) + pf, obs)
+        bufs = [None] * len(prog.comp.outputs)
+        if self.tuple_state is not None:
+            for d, o in enumerate(prog.ro[1]):
+                bufs[o[1]] = self.x_store[t % 2][d:d + 1]
+        else:
+            bufs[prog.ro[1]] = self.x_store[t % 2]
+        bufs[prog.wo[1]] = self.lw.reshape(1, N)
+        # particle i of row r draws under split(k_prop[r], n)[i]: derived in the program from the row's key
+        key = Key(lazy=("rowsplit", Key(dev=self.keys_prop[t]), self.n))
+        prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
+
+    def _resample(self, t):
+        resample_rows(self.kind, self.keys_res[t], self.lw.reshape(self.R, self.n), index_stride=self.n,
+                      out=(self.anc, self.totals[t], self.maxs[t], self.status), workspace=self.ws)
+
+    def enqueue(self):
+        """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (no syncs, no
+        allocations, no host read of a device value)"""
+        self.status.zero_()
+        for t in range(self.T):
+            self._launch_vm(t)
+            self._resample(t)
+
+    def launch(self):
+        be = _lib.get()
+        if self.graph is None:
+            self.enqueue()
+        else:
+            be.check(be.c.gmx_graph_launch(self.graph, be.stream()), "gmx_graph_launch")
+
+    def log_ml(self) -> np.ndarray:
+        """float64 [R]: row r is BootstrapSweep.log_ml() of that filter — sum_t [ ref(M_t) + log(total_t 2^-shift) - log n ]
+        from the [T, R] evidence terms, finished in float64 on the host (synchronises)."""
+        m = cdf_reference(self.maxs.cpu().numpy())                                  # [T, R] float64
+        tot = self.totals.cpu().numpy().view(np.uint64).astype(np.float64)
+        out = np.empty((self.R,), dtype=np.float64)
+        for r in range(self.R):
+            tr = np.ascontiguousarray(tot[:, r])
+            if np.any(tr == 0):              # a step where no particle of the row carried any mass
+                out[r] = -math.inf
+            else:
+                out[r] = float(np.sum(np.ascontiguousarray(m[:, r]) + np.log(tr) - self.shift * math.log(2.0) - math.log(self.n)))
+        return out
+
+    def state(self):
+        """(x_T before the last resampling: [R, n], [R, n, D] or a tuple of [R, n]; log-weights [R, n]; the last ancestors,
+        int32 [R, n], row-local)"""
+        R, n = self.R, self.n
+        w = (self.T - 1) % 2
+        if self.tuple_state is not None:
+            x = self.tuple_state(row.reshape(R, n) for row in self.x[w])
+        elif self.event:
+            x = self.x[w].reshape(R, n, self.x[w].shape[-1])
+        else:
+            x = self.x[w].reshape(R, n)
+        local = self.anc - (torch.arange(R, dtype=torch.int32, device=self.anc.device) * n).reshape(R, 1)
+        return x, self.lw.reshape(R, n), local

@@ -637,12 +637,36 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
  *                   Rows are ld >= n elements apart and may start at any 4-byte boundary; element offsets are 64-bit.
  *                   Limits: 1 <= rows < 2^31, 1 <= n < 2^31; workspace_d: gmx_pick_rows_workspace(rows, n) bytes, 8-byte
  *                   aligned, contents irrelevant on entry.
+ *   gmx_resample_rows   (additive, ABI still v8.  Reference call site: jax.vmap of a resampling step over keys — R
+ *                   independent particle systems, e.g. jax.vmap(smc_run)(keys).)  Row r of ancestors_d ([rows, n], rows n
+ *                   elements apart) minus r * index_stride, with max_d[r] and total_d[r], is what the per-row path gives
+ *                   for that row alone: gmx_resample(kind, keys[r], lw_d + r * ld, n, 62 - ceil(log2 n), ...) — the same
+ *                   block-floating-point integer CDF over tiles of 1024 columns OF THE ROW, the same 128-bit comparisons,
+ *                   the same 23-bit uniforms from keys[r]; integers throughout after the per-element exp, so the answer
+ *                   does not depend on the grid.  n_out = n.  index_stride = 0: row-local indices; index_stride = n:
+ *                   indices into the flat [rows * n] store (one gmx_gather over all rows); a non-zero stride with
+ *                   rows * index_stride >= 2^31 is refused.  kind: GMX_RESAMPLE_SYSTEMATIC, _STRATIFIED or _MULTINOMIAL
+ *                   (iid slot order); the two ordered multinomials are refused by name.  n <= 1024: ONE launch, nothing in
+ *                   the workspace (a row is one CDF tile; a 256-thread workgroup holds four rows of up to 256 columns,
+ *                   two of up to 512 or one of up to 1024).  n > 1024: two launches (tile statistics per (row, tile);
+ *                   one workgroup per (row, tile) that rebuilds its tile and assigns the slots it owns from the row's
+ *                   prefix) and no CDF array; the iid multinomial keeps a [rows, n] u64 CDF in the workspace and takes a
+ *                   third launch.  A row whose total is 0 gets the per-row path's answer (every slot n - 1) and adds 1
+ *                   to *status_d (a vector atomic add; the caller zeroes it); its neighbours are unaffected.  Rows are
+ *                   ld >= n elements apart and may start at any 4-byte boundary; element offsets are 64-bit.
+ *                   Limits: 1 <= rows < 2^31, 1 <= n <= 2^21; workspace_d: gmx_resample_rows_workspace(kind, rows, n)
+ *                   bytes, 8-byte aligned, contents irrelevant on entry.
  * A null pointer or an out-of-range size returns non-zero before anything is launched.
  * ---------------------------------------------------------------------- */
 size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
 int gmx_pick_rows(const uint32_t* keys_d /* [rows, 2] */, const float* logits_d, int64_t rows, int64_t n,
                   int64_t ld /* elements between rows, >= n */, int32_t* out_d /* [rows] */, int64_t* status_d /* [1] */,
                   void* workspace_d, gmx_stream stream);
+size_t gmx_resample_rows_workspace(int kind, int64_t rows, int64_t n);
+int gmx_resample_rows(int kind, const uint32_t* keys_d /* [rows, 2] */, const float* lw_d, int64_t rows, int64_t n,
+                      int64_t ld /* elements between rows, >= n */, int64_t index_stride, float* max_d /* [rows] */,
+                      uint64_t* total_d /* [rows] */, int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [1] */,
+                      void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
