@@ -41,8 +41,7 @@ import torch
 from .. import _lib
 from ..core.choice_map import ChoiceMap
 from ..random import Key, lazy_split, split
-from ..engine import Gathered
-from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _NoiseAhead, _key_words, cdf_reference, cdf_shift
+from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _StateStore, _Sweep, _key_words, cdf_shift, evidence_terms
 
 
 def systematic_slot_bounds(offsets, total: int, n_total: int, u0: int):
@@ -253,17 +252,17 @@ class _ShardRouter:
                 self.cx.all_to_all(recv, send)                       # block s of recv <- block `me` of rank s
 
 
-class ShardedBootstrapSweep(_NoiseAhead):
+class ShardedBootstrapSweep(_Sweep):
     """smc.BootstrapSweep over `dist.get_world_size()` ranks, n particles per rank.
 
     Per step (the tile-statistics form): site program -> all-gather of the statistics -> gmx_shard_step_fused (the
     totals, the slot bounds, the routing: one launch) -> all-to-all; which form runs and what it launches is
-    _ShardRouter's.  NOISE AHEAD as on one GPU (smc._NoiseAhead): the
+    _ShardRouter's.  NOISE AHEAD as on one GPU (smc._Sweep): the
     step's normal draws come from background programs on a second stream — keyed by the GLOBAL particle index, so the
     draws are the single-process ones — which matters more here than on one GPU: the chain of a sharded step is
     mostly launch boundaries and collective latency, during which the vector ALUs would idle."""
 
-    fuse_mh = False          # (the noise-ahead mixin: the chained MH + extension program's move draws hang off k_mh)
+    chained = property(lambda self: self.chain_mh)
     peer_tag = property(lambda self: self.router.tag)
     peer_status = property(lambda self: self.router.status)
 
@@ -311,16 +310,10 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.router = self.p_mhvm_init = self.p_mhvm_step = None
         self.peer_mode = self.tiles_mode = False
 
-    def _chain_prog(self, t):
-        if t >= 1 and self.rejuvenate is not None and self.p_mhvm_step is not None and (self.chain_mh or self.fuse_mh):
-            return self.p_mhvm_init if t == 1 else self.p_mhvm_step
-        return self.p_init if t == 0 else self.p_step
-
     def _chain_step(self, t, skip_vm=False):
         self._step(t)
 
     def prepare(self, key: Key, ys: torch.Tensor):
-        from ..static import MinimalGenerate as _MG
         be = _lib.get()
         n, T, dev, W = self.n, self.T, be.device, self.world
         # noise ahead: on request, or by default on a device with streams (specialised programs)
@@ -337,15 +330,11 @@ class ShardedBootstrapSweep(_NoiseAhead):
                                       "extension program as the one-launch sharded step (the fused peer exchange, "
                                       "specialised programs)")
         self.noise_ahead = False
-        self.fuse_mh = False
         self._noise_progs = {}
         self.__dict__.pop("_noise_run_cache", None)
         self._drop_graph()                               # prepared again: the graph captured for the previous run goes
-
-        def MinimalGenerate(*a):
-            return _MG(*a, hoist_noise=bool(want_na))
         self.key = key
-        self.ys = ys.to(dev).float().contiguous()
+        self._set_observations(ys)
         if self.comm and self.cx is None:
             from .comm import make_comm
             self.cx = make_comm(self.dist, dev)
@@ -359,45 +348,33 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.totals = torch.zeros((T,), dtype=torch.int64, device=dev)            # global integer total per step
         self.verdict = torch.zeros((1,), dtype=torch.int64, device=dev)        # gmx_sweep_verdict: 0 fine, 1 overflow, 2 failed
         self.shift = cdf_shift(self.N)
-        obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
-        self.p_init = MinimalGenerate(self.init, (), obs0, (n,))
+        self.batch = self.window = n
+        self._build_init(bool(want_na))
         # the state is the model's return value: a float scalar, or ONE vector of D floats per particle kept
-        # struct-of-arrays ([D, n + W*C]) so every component is one routed 4-byte leaf
-        if self.p_init.ro[0] != "out":
-            raise NotImplementedError("ShardedBootstrapSweep: the step model must return one array (scalar or vector state)")
-        dt, event, _slots = self.p_init.comp.outputs[self.p_init.ro[1]]
-        if dt != "f32" or len(event) > 1:
-            raise NotImplementedError("ShardedBootstrapSweep: the state must be a float scalar or a float vector")
-        self.event = tuple(event)
-        self.D = int(event[0]) if event else 1
-        self._alloc_exchange()
-        g = Gathered(self._src(0), self.idx)
-        self.p_mhvm_init = self.p_mhvm_step = None
-        if self.rejuvenate is None:
-            self.p_step = MinimalGenerate(self.step, (g,) + tuple(self.step_extra(1)), obs0, (n,))
-        else:
-            from ..static import MinimalMH
+        # struct-of-arrays ([D, n + W*C]) so every component is one routed 4-byte leaf.  Extended state, double-buffered:
+        # [ n local | W*C received ]; ancestors index into it; destinations of collectives come from the communicator
+        # (peer-mapped memory under GENMI_COMM=p2p)
+        shared = self.cx is not None and not self.peer_mode
+        mk = (lambda shape: self.cx.alloc(shape, torch.float32)) if shared else None
+        width = n + W * self.capacity
+        self.store = _StateStore(self.p_init, width, "ShardedBootstrapSweep", tuples=False, alloc=mk)
+        self.event, self.D = self.store.event, self.store.D
+        self.moved = None
+        if self.rejuvenate is not None:
+            # store t % 2 of `moved`, [:, :n] = the MH-moved, resampled state step t is extended from; its tail receives
+            # the remote copies of it when it travels as the second routed leaf of the NEXT resampling
+            self.moved = _StateStore(self.p_init, width, "ShardedBootstrapSweep", tuples=False, alloc=mk)
             self.accept = torch.zeros((n,), dtype=torch.bool, device=dev)
-            self.p_step = MinimalGenerate(self.step, (self._asrc(0, local=True),) + tuple(self.step_extra(1)), obs0, (n,))
-            ch = obs0.set(self.state_addr, g)
-            self.p_mh_init = MinimalMH(self.init, (), ch, self.rejuvenate, (n,))
-            self.p_mh_step = MinimalMH(self.step, (Gathered(self._asrc(0), self.idx),) + tuple(self.step_extra(1)), ch,
-                                       self.rejuvenate, (n,))
-            # the move and the extension that follows it as ONE program (static.MinimalMHGenerate, what the single-GPU
-            # sweep launches per step): with the routing of the previous step as its prologue a sharded MH step is ONE
-            # launch — used when that form applies (fuse_sh below), else the separate programs above
-            if self.chain_mh_req and be.uses_streams and self.specialize:
-                from ..static import MinimalMHGenerate
-                from .smc import BootstrapSweep as _BS
-                ex1 = tuple(self.step_extra(1))
-                hn = tuple(_BS.NOISE_ROOTS_MH.split(",")) if want_na else False      # the move's proposal + accept draws
-                self.p_mhvm_init = MinimalMHGenerate(self.init, (), ch, self.rejuvenate, self.step, ex1, obs0, (n,),
-                                                     hoist_noise=hn)
-                self.p_mhvm_step = MinimalMHGenerate(self.step, (Gathered(self._asrc(0), self.idx),) + ex1, ch,
-                                                     self.rejuvenate, self.step, ex1, obs0, (n,), hoist_noise=hn)
+        self._alloc_exchange()
+        # the move and the extension that follows it as ONE program (what the single-GPU sweep launches per step): with
+        # the routing of the previous step as its prologue a sharded MH step is ONE launch — used when that form applies
+        # (fuse_sh below), else the separate programs
+        from .smc import BootstrapSweep as _BS
+        hn = tuple(_BS.NOISE_ROOTS_MH.split(",")) if want_na else False      # the move's proposal + accept draws
+        self._build_steps(bool(want_na), bool(want_na), chain=bool(self.chain_mh_req and be.uses_streams and self.specialize),
+                          chain_hoist=hn)
         if want_na and self.rejuvenate is not None:
             if self.p_mhvm_step is not None and self.p_mhvm_step.noise:
-                self.fuse_mh = True
                 self._noise_setup((self.p_init, self.p_mhvm_init, self.p_mhvm_step), n, T, dev)
             else:
                 self._mh_na_failed = True
@@ -475,78 +452,22 @@ class ShardedBootstrapSweep(_NoiseAhead):
         if self.peer_mode and self.peer_leaves > _lib.PEER_MAX_LEAVES:
             raise NotImplementedError("ShardedBootstrapSweep over the fused peer exchange: at most "
                                       f"{_lib.PEER_MAX_LEAVES} routed leaves (GMX_PEER_MAX_LEAVES)")
-        if self.router is not None:                      # (the overflow re-run: the landing block for the new capacity)
-            self.router.set_capacity(C, self.peer_leaves)
-        # extended state, double-buffered: [ n local | W*C received ]; ancestors index into it
-        # destinations of collectives come from the communicator (peer-mapped memory under GENMI_COMM=p2p)
-        mk = (lambda shape, dt=torch.float32: self.cx.alloc(shape, dt)) if (self.cx is not None and not self.peer_mode) else \
-            (lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev))
-        self.xrows = [mk((self.D, n + W * C)) for _ in range(2)]
+        if self.router is not None:                      # (the overflow re-run: the landing block and the stores for the
+            self.router.set_capacity(C, self.peer_leaves)         #  new capacity)
+            for store in (self.store, self.moved):
+                if store is not None:
+                    store.allocate(n + W * C)
         self.send = torch.zeros((self.peer_leaves, W * C), dtype=torch.float32, device=dev)      # one row per routed leaf
-        self.idx = torch.zeros((n,), dtype=torch.int32, device=dev)
-        if self.rejuvenate is not None:
-            # arows[t % 2][:, :n] = the MH-moved, resampled state step t is extended from; its tail receives the
-            # remote copies of it when it travels as the second routed leaf of the NEXT resampling
-            self.arows = [mk((self.D, n + W * C)) for _ in range(2)]
+        self.idx = self.index = torch.zeros((n,), dtype=torch.int32, device=dev)
         self._bound = [None] * self.T
-
-    def _asrc(self, tb, local=False):
-        """the MH-moved state of buffer tb as the model sees it: [n + W*C] (or [.., D]); local=True: this rank's n rows"""
-        rows = self.arows[tb][:, :self.n] if local else self.arows[tb]
-        return rows[0] if not self.event else rows.t()
-
-    def _src(self, tb):
-        """what the step model sees as the previous state (before the gather): [n + W*C] or [n + W*C, D]"""
-        return self.xrows[tb][0] if not self.event else self.xrows[tb].t()
 
     def _leaves(self, t):
         """what step t's resampling routes, in issue order: every component of x_t, then (an MH move, t >= 1) every
         component of the state it was extended from — _ShardRouter's (rows, send, recv)"""
-        rows = list(self.xrows[t % 2])
+        rows = self.store.leaves(t % 2)
         if self.rejuvenate is not None and t >= 1:
-            rows += list(self.arows[t % 2])
+            rows += self.moved.leaves(t % 2)
         return [(r, self.send[i], r[self.n:]) for i, r in enumerate(rows)]
-
-    # ------------------------------------------------------------------
-    def _programs(self, t):
-        """Which programs step t launches, on which leaves, into which buffers: (mh, prog, leaves, launch key, bufs) —
-        init; the plain step; the chained MH move + extension (one program); or the separate MH move, `mh` = its own
-        (prog, leaves, key, bufs), then the extension.  (The log-weight buffer is the caller's to set.)"""
-        n = self.n
-        k_prop, _k_res, k_mh = self.step_keys[t]
-        obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-        mh = None
-        if t == 0 or self.rejuvenate is None:
-            prog = self.p_init if t == 0 else self.p_step
-            a_ = () if t == 0 else (Gathered(self._src((t - 1) % 2), self.idx),) + tuple(self.step_extra(t))
-            leaves = prog.leaves(a_, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a_, obs)
-        else:
-            # the MH move on the resampled particles of step t - 1 (keys split(k_mh, N)[g*n + i]) ...
-            ch = ChoiceMap.empty().set(self.obs_addr, self.ys[t - 1]).set(self.state_addr,
-                                                                          Gathered(self._src((t - 1) % 2), self.idx))
-            a_ = () if t == 1 else (Gathered(self._asrc((t - 1) % 2), self.idx),) + tuple(self.step_extra(t - 1))
-            if self.chain_mh:
-                # ... and, in the SAME program, the extension to step t from the moved state (keys split(k_prop, N)
-                # [g*n + i]: OP_KSPLITU of two launch values); the launch key of the chained program is the MOVE's
-                prog = self.p_mhvm_init if t == 1 else self.p_mhvm_step
-                kw = k_prop.host()
-                leaves = prog.leaves(a_, ch, self.rejuvenate, tuple(self.step_extra(t)), obs, (int(kw[0]), int(kw[1])),
-                                     self._noise_leaves(t, prog) if self.noise_ahead else ())
-                k_prop = k_mh
-            else:
-                mprog = self.p_mh_init if t == 1 else self.p_mh_step
-                mbufs = [None] * len(mprog.comp.outputs)
-                mbufs[mprog.ro[1]] = self.arows[t % 2][:, :n]
-                mbufs[mprog.ao[1]] = self.accept.reshape(1, n)
-                mh = (mprog, mprog.leaves(a_, ch, self.rejuvenate), k_mh, mbufs)
-                prog = self.p_step                   # ... then the extension reads the move's output locally
-                leaves = prog.leaves((self._asrc(t % 2, local=True),) + tuple(self.step_extra(t)), obs)
-        bufs = [None] * len(prog.comp.outputs)
-        bufs[prog.ro[1]] = self.xrows[t % 2][:, :n]      # [D, n] window of the [D, n + W*C] rows
-        if self.chain_mh and t >= 1:
-            bufs[prog.mo[1]] = self.arows[t % 2][:, :n]     # the moved state step t was extended from
-            bufs[prog.ao[1]] = self.accept.reshape(1, n)
-        return mh, prog, leaves, k_prop, bufs
 
     def _shard_in(self, t):
         """the prologue of step t's gathering launch in the one-launch form: it ROUTES step t - 1 first — that step's
@@ -655,12 +576,8 @@ class ShardedBootstrapSweep(_NoiseAhead):
         return super().capture()
 
     def launch(self):
-        if self.graph is not None:
-            be = _lib.get()
-            self._finished = False
-            be.check(be.c.gmx_graph_launch(self.graph, be.stream()), "gmx_graph_launch")
-        else:
-            self.enqueue()
+        self._finished = False
+        super().launch()
 
     def finish(self):
         """Read the overflow flag (one sync per sweep; COLLECTIVE — every rank calls it, which
@@ -704,18 +621,15 @@ class ShardedBootstrapSweep(_NoiseAhead):
         self.finish()
         acc = 0.0
         for m, tot in zip(self.maxs.cpu().tolist(), self.totals.cpu().numpy().view(np.uint64).tolist()):
-            if tot == 0:
-                return -math.inf
-            acc += cdf_reference(m) + math.log(tot) - self.shift * math.log(2.0) - math.log(self.N)
+            acc += evidence_terms(m, tot, self.shift, self.N)
+            if acc == -math.inf:
+                break
         return acc
 
     def state(self):
         """this rank's resampled particles after the last step (global slots [g*n, (g+1)*n))"""
         self.finish()
-        from ..engine import gather_leaves
-        rows = self.xrows[(self.T - 1) % 2]
-        got = gather_leaves([rows[d] for d in range(self.D)], self.idx)
-        return got[0] if not self.event else torch.stack(got, dim=1)
+        return self.store.take((self.T - 1) % 2, self.idx)
 
 
 class CountingComm:

@@ -440,26 +440,34 @@ def cdf_reference(m):
     """The log-weight an integer CDF total is relative to: total * 2^-shift = sum_i exp(lw_i - cdf_reference(max lw)).
     = ceil(max lw / ln 2) * ln 2 in float32 arithmetic (gmx_tile_exp / gmx_tile_ref in csrc/gmx_math.h: the
     exponent K of the block-floating-point CDF), evaluated on the host for the evidence terms.  A float for one maximum;
-    a float64 array, element by element the same numbers, for an array of them (one per row of gmx_resample_rows)."""
-    lim = 1 << 29
+    a float64 array for an array of them (one per row of gmx_resample_rows)."""
+    lim = np.float32(1 << 29)
     inv_ln2 = np.frombuffer(np.uint32(0x3FB8AA3B).tobytes(), np.float32)[0]
     ln2 = np.frombuffer(np.uint32(0x3F317218).tobytes(), np.float32)[0]
-    if np.ndim(m) > 0:
-        with np.errstate(invalid="ignore", over="ignore"):
-            t = np.asarray(m, dtype=np.float32) * inv_ln2
-            k = np.ceil(np.clip(np.where(t > -np.float32(lim), t, -np.float32(lim)), -np.float32(lim), np.float32(lim)))
-        return (k.astype(np.float32) * ln2).astype(np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
-        t = np.float32(m) * inv_ln2
-    if not (t > -np.float32(lim)):
-        k = -lim
-    elif t > np.float32(lim):
-        k = lim
-    else:
-        k = int(t)
-        if np.float32(k) < t:
-            k += 1
-    return float(np.float32(k) * ln2)
+        t = np.asarray(m, dtype=np.float32) * inv_ln2
+        k = np.ceil(np.clip(np.where(t > -lim, t, -lim), -lim, lim))      # (NaN: the lower clamp, as the kernels')
+    ref = (k.astype(np.float32) * ln2).astype(np.float64)
+    return ref if np.ndim(m) > 0 else float(ref)
+
+
+def evidence_terms(maxs, totals, shift, n):
+    """The evidence a resampling step contributes, ref(M) + log(total) - shift ln 2 - log n in float64, -inf where the
+    total is 0 (no particle carried any mass): an array for arrays of maxima and totals (the totals as the int64 words the
+    kernels leave: read as uint64), a float for one maximum and one Python-integer total.
+
+    The callers sum the terms, each in its own order, and the last bit of a sum depends on it: np.sum over the T
+    contiguous terms of a sweep (BootstrapSweep.log_ml; BootstrapBank.log_ml per row), a sequential `acc +=` over the
+    steps in LogMLOffset.value and ShardedBootstrapSweep.log_ml.  The sequential callers hand over one step at a time
+    and get math.log of the integer; the array callers get np.log — the two differ in the last bit for about 2 totals
+    in 100 000, so neither caller can take the other's."""
+    ref = cdf_reference(maxs)
+    if np.ndim(totals) == 0:
+        tot = int(totals) & 0xFFFFFFFFFFFFFFFF
+        return ref + math.log(tot) - shift * math.log(2.0) - math.log(n) if tot else -math.inf
+    tot = np.asarray(totals).view(np.uint64).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(tot == 0, -np.inf, ref + np.log(tot) - shift * math.log(2.0) - math.log(n))
 
 
 def cdf_shift(n_total: int) -> int:
@@ -485,26 +493,20 @@ class LogMLOffset:
         """a float; with [R] terms (smc.resample on a batched collection) float64 [R], row r the float the same terms of
         row r alone give"""
         if any(max_d.numel() > 1 for max_d, _, _, _ in self.terms):
-            ms = [cdf_reference(max_d.reshape(-1).cpu().numpy()) for max_d, _, _, _ in self.terms]
+            ms = [max_d.reshape(-1).cpu().numpy() for max_d, _, _, _ in self.terms]
             tots = [total_d.reshape(-1).cpu().numpy().view(np.uint64) for _, total_d, _, _ in self.terms]
             out = np.zeros((max(m.size for m in ms),), dtype=np.float64)
             for r in range(out.size):
-                acc = 0.0
                 for m, tot, (_, _, shift, n) in zip(ms, tots, self.terms):
-                    tr = int(tot[r % tot.size])
-                    if tr == 0:              # no particle of the row carried any mass
-                        acc = -math.inf
+                    out[r] += evidence_terms(m[r % m.size], int(tot[r % tot.size]), shift, n)
+                    if out[r] == -math.inf:      # no particle of the row carried any mass
                         break
-                    acc += float(m[r % m.size]) + math.log(tr) - shift * math.log(2.0) - math.log(n)
-                out[r] = acc
             return out
         acc = 0.0
         for max_d, total_d, shift, n in self.terms:
-            m = float(max_d.reshape(-1)[0].item())
-            tot = int(total_d.reshape(-1)[0].item()) & 0xFFFFFFFFFFFFFFFF
-            if tot == 0:                 # no particle carried any mass: the evidence estimate is 0
-                return -math.inf
-            acc += cdf_reference(m) + math.log(tot) - shift * math.log(2.0) - math.log(n)
+            acc += evidence_terms(max_d.reshape(-1)[0].item(), total_d.reshape(-1)[0].item(), shift, n)
+            if acc == -math.inf:         # no particle carried any mass: the evidence estimate is 0
+                break
         return acc
 
 
@@ -916,14 +918,102 @@ def capture(loop_fn, *args, warmup: int = 1, noise_ahead=None) -> CapturedLoop:
     return CapturedLoop(loop_fn, *args, warmup=warmup, noise_ahead=noise_ahead)
 
 
-class _NoiseAhead:
-    """The noise-ahead machinery shared by BootstrapSweep and sharded.ShardedBootstrapSweep: background
-    programs that draw the chain programs' hoisted normal / uniform values on a second stream, a group of steps ahead.
-    The host class provides n, T, specialize, fuse_mh, `_chain_prog(t)` (the site program of step t),
-    `_chain_step(t, skip_vm)` (everything step t launches on the chain) and `enqueue()`; `_noise_total` /
-    `_noise_offset`: the keys of this shard are children offset .. offset + n - 1 of split(k, total) (a single GPU:
-    total = n, offset = 0).  Also what the two sweeps do alike besides: the per-step key schedule, capturing enqueue()
-    into a graph and dropping that graph."""
+class _StateStore:
+    """THE place that knows a sweep's state layout.  The state is the init program's return value — a float scalar,
+    ONE vector of D floats, or (tuples=True) a tuple / list of D float scalars — kept struct-of-arrays in two [D, width]
+    stores (step t writes store t % 2 and reads the other through the ancestors), every row one output of the site
+    program and one gathered input of the next step.  `who` names the sweep in the refusals; alloc(shape): the
+    allocator of the stores (default: zeros on the device)."""
+
+    def __init__(self, prog, width, who, tuples=True, alloc=None):
+        ro, outs = prog.ro, prog.comp.outputs
+        self.tuple_state = None
+        if tuples and ro[0] in ("tuple", "list") and ro[1] and all(
+                o[0] == "out" and outs[o[1]][0] == "f32" and outs[o[1]][1] == () for o in ro[1]):
+            self.tuple_state = type(()) if ro[0] == "tuple" else type([])
+            event, D = (), len(ro[1])
+        else:
+            if ro[0] != "out":
+                raise NotImplementedError(f"{who}: the step model must return one array (scalar or vector state)"
+                                          + (" or a tuple of float scalars" if tuples else ""))
+            dt, event, _slots = outs[ro[1]]
+            if dt != "f32" or len(event) > 1:
+                raise NotImplementedError(f"{who}: the state must be a float scalar or a float vector")
+            D = int(event[0]) if event else 1
+        self.event, self.D = tuple(event), D
+        self._alloc = alloc or (lambda shape: torch.zeros(shape, dtype=torch.float32, device=_lib.get().device))
+        self.allocate(width)
+
+    def allocate(self, width):
+        """the pair of [D, width] stores (again: another width)"""
+        self.rows = [self._alloc((self.D, int(width))) for _ in range(2)]
+        self._views = {}
+
+    def view(self, which, n=None):
+        """store `which` as the model sees it — [width], [width, D] or a tuple of [width] rows; n: its first n columns"""
+        v = self._views.get((which, n))
+        if v is None:
+            s = self.rows[which] if n is None else self.rows[which][:, :n]
+            if self.tuple_state is not None:
+                v = self.tuple_state(s[d] for d in range(self.D))
+            else:
+                v = s[0] if not self.event else s.t()
+            self._views[(which, n)] = v
+        return v
+
+    def gathered(self, which, index):
+        """view(which)[index] as a model argument (lazy: the gather is fused into the program that reads it)"""
+        v = self.view(which)
+        if self.tuple_state is not None:
+            return self.tuple_state(Gathered(row, index) for row in v)
+        return Gathered(v, index)
+
+    def bind(self, bufs, prog, which, n=None, moved=False):
+        """the rows of store `which` (n: their first n columns) as the output buffers of prog's return value (moved=True:
+        of the MH-moved state a chained program returns besides)"""
+        s = self.rows[which] if n is None else self.rows[which][:, :n]
+        o = prog.mo if moved else prog.ro
+        if self.tuple_state is not None:
+            for d, od in enumerate(o[1]):
+                bufs[od[1]] = s[d:d + 1]
+        else:
+            bufs[o[1]] = s
+
+    def leaves(self, which):
+        """the D rows of store `which`, each a leaf the sharded exchange routes"""
+        return list(self.rows[which])
+
+    def per_filter(self, which, R, n):
+        """store `which` over R * n particles as R filters see it: [R, n], [R, n, D] or a tuple of [R, n]"""
+        v = self.view(which)
+        if self.tuple_state is not None:
+            return self.tuple_state(row.reshape(R, n) for row in v)
+        return v.reshape((R, n) + self.event)
+
+    def take(self, which, index):
+        """view(which)[index], materialised: [len(index)] or [len(index), D] (ONE gmx_gather over the rows)"""
+        got = engine.gather_leaves(self.leaves(which), index)
+        return got[0] if not self.event else torch.stack(got, dim=1)
+
+
+class _Sweep:
+    """What BootstrapSweep, BootstrapBank and sharded.ShardedBootstrapSweep do alike: the per-step key schedule, the
+    site programs and the table of what step t launches (`_programs`), capturing enqueue() into a graph, replaying and
+    dropping it, and the noise-ahead machinery: background programs that draw the chain programs' hoisted
+    normal / uniform values on a second stream, a group of steps ahead.
+
+    What differs between the sweeps is handed over as values, set by the host class's prepare():
+      batch         particles per launch (n; the bank: R * n)
+      store, moved  the _StateStore of the state and (rejuvenate=) of the MH-moved state step t is extended from
+      index         the ancestors the previous state is gathered through
+      window        None, or the n columns of a wider store the programs write (the sharded [n | received] rows)
+      tail          trailing model arguments (the bank's per-particle parameters)
+      chained       the MH move and the extension run as ONE program
+      step_keys[t]  (proposal, resampling, MH move) keys of step t; how a launch key is split over the particles is the
+                    host class's own
+    The host class also provides n, T, specialize, `_chain_step(t, skip_vm)` (everything step t launches on the chain)
+    and `enqueue()`; `_noise_total` / `_noise_offset`: the keys of this shard are children offset .. offset + n - 1 of
+    split(k, total) (a single GPU: total = n, offset = 0)."""
 
     NOISE_LDS_PAD = 56000      # bytes of unused LDS per noise workgroup: two of them per CU (160 KB)
     NOISE_GROUP = 10           # steps per group of noise launches (the noise runs one group ahead of the chain)
@@ -931,6 +1021,110 @@ class _NoiseAhead:
     _noise_offset = 0
     _noise_total = None
     graph = None
+    window = moved = rejuvenate = None
+    tail = ()
+    chained = noise_ahead = False
+
+    def _set_observations(self, ys):
+        self.ys = ys.to(_lib.get().device).float().contiguous()
+        self._obs_maps = {}
+
+    def _obs(self, t):
+        """step t's observation as the constraint of its programs (made once per prepared run, not per launch)"""
+        obs = self._obs_maps.get(t)
+        if obs is None:
+            obs = self._obs_maps[t] = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
+        return obs
+
+    def _build_init(self, hoist=False):
+        from ..static import MinimalGenerate
+        self.p_init = MinimalGenerate(self.init, self.tail, self._obs(0), (self.batch,), hoist_noise=hoist)
+
+    def _build_steps(self, hoist=False, step_hoist=False, chain=False, chain_hoist=False):
+        """The step programs, once p_init and the stores exist: p_step — without a move it gathers the previous state
+        (noise hoisted: `hoist`), with one it reads the moved state in place (`step_hoist`) —; rejuvenate=: the move alone,
+        p_mh_init / p_mh_step, and (chain) the move and the extension that follows it as ONE program, p_mhvm_init /
+        p_mhvm_step (static.MinimalMHGenerate: same keys, same draws, same bits; one launch boundary and one trip of the
+        moved state through memory less; `chain_hoist`: which of its draws are hoisted)"""
+        from ..static import MinimalGenerate, MinimalMH, MinimalMHGenerate
+        obs0, ex, b = self._obs(0), tuple(self.step_extra(1)), (self.batch,)
+        prev = self.store.gathered(0, self.index)
+        self.p_mhvm_init = self.p_mhvm_step = None
+        if self.rejuvenate is None:
+            self.p_step = MinimalGenerate(self.step, (prev,) + ex + self.tail, obs0, b, hoist_noise=hoist)
+            return
+        self.p_step = MinimalGenerate(self.step, (self.moved.view(0, self.window),) + ex, obs0, b, hoist_noise=step_hoist)
+        ch = obs0.set(self.state_addr, prev)
+        was = (self.moved.gathered(0, self.index),) + ex
+        self.p_mh_init = MinimalMH(self.init, (), ch, self.rejuvenate, b)
+        self.p_mh_step = MinimalMH(self.step, was, ch, self.rejuvenate, b)
+        if chain:
+            self.p_mhvm_init = MinimalMHGenerate(self.init, (), ch, self.rejuvenate, self.step, ex, obs0, b,
+                                                 hoist_noise=chain_hoist)
+            self.p_mhvm_step = MinimalMHGenerate(self.step, was, ch, self.rejuvenate, self.step, ex, obs0, b,
+                                                 hoist_noise=chain_hoist)
+
+    def _chain_prog(self, t):
+        """the site program of step t on the chain"""
+        if t == 0:
+            return self.p_init
+        if self.chained:
+            return self.p_mhvm_init if t == 1 else self.p_mhvm_step
+        return self.p_step
+
+    def _programs(self, t, alone=False):
+        """Which programs step t launches, on which leaves, under which key, into which buffers: (mh, prog, leaves, launch
+        key, bufs) — init; the plain step; the chained MH move + extension (one program); or the separate MH move, `mh`
+        = its own (prog, leaves, key, bufs), then the extension.  alone=True: the extension without its move, whatever
+        the form (kernel_timers).  The log-weight buffer, and how the key is split, are the caller's to set."""
+        n = self.n
+        k_prop, _k_res, k_mh = self.step_keys[t]
+        obs = self._obs(t)
+        mh, key, moves = None, k_prop, False
+        if t == 0 or self.rejuvenate is None:
+            prog = self.p_init if t == 0 else self.p_step
+            a_ = self.tail if t == 0 else \
+                (self.store.gathered((t - 1) % 2, self.index),) + tuple(self.step_extra(t)) + self.tail
+            leaves = prog.leaves(a_, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a_, obs)
+        elif self.chained and not alone:
+            # the MH move on the resampled particles of step t - 1: reads x_{t-1}[index] and, for t >= 2, the moved state
+            # x_{t-1} was extended from; and, in the SAME program, the extension to step t from the moved state (keys
+            # split(k_prop, ..): OP_KSPLITU of two launch values); the launch key of the chained program is the MOVE's
+            prog = self.p_mhvm_init if t == 1 else self.p_mhvm_step
+            kw = k_prop.host()
+            leaves = prog.leaves(*self._move_leaves(t), tuple(self.step_extra(t)), obs, (int(kw[0]), int(kw[1])),
+                                 self._noise_leaves(t, prog) if self.noise_ahead else ())
+            key, moves = k_mh, True
+        else:
+            if not alone:
+                mprog = self.p_mh_init if t == 1 else self.p_mh_step
+                mbufs = [None] * len(mprog.comp.outputs)
+                self.moved.bind(mbufs, mprog, t % 2, self.window)
+                mbufs[mprog.ao[1]] = self.accept.reshape(1, n)
+                mh = (mprog, mprog.leaves(*self._move_leaves(t)), k_mh, mbufs)
+            prog = self.p_step                       # ... then the extension reads the move's output in place
+            a_ = (self.moved.view(t % 2, self.window),) + tuple(self.step_extra(t))
+            leaves = prog.leaves(a_, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a_, obs)
+        bufs = [None] * len(prog.comp.outputs)
+        self.store.bind(bufs, prog, t % 2, self.window)
+        if moves:
+            self.moved.bind(bufs, prog, t % 2, self.window, moved=True)     # the moved state step t was extended from
+            bufs[prog.ao[1]] = self.accept.reshape(1, n)
+        return mh, prog, leaves, key, bufs
+
+    def _move_leaves(self, t):
+        """(arguments, choices, request) of the MH move of step t >= 1: on x_{t-1}[index] under step t - 1's observation"""
+        ch = self._obs(t - 1).set(self.state_addr, self.store.gathered((t - 1) % 2, self.index))
+        a_ = () if t == 1 else (self.moved.gathered((t - 1) % 2, self.index),) + tuple(self.step_extra(t - 1))
+        return a_, ch, self.rejuvenate
+
+    def launch(self):
+        """replay the captured graph, or else enqueue()"""
+        if self.graph is None:
+            self.enqueue()
+        else:
+            be = _lib.get()
+            be.check(be.c.gmx_graph_launch(self.graph, be.stream()), "gmx_graph_launch")
 
     def _set_step_keys(self, key):
         """step key = fold_in(run key, t); (k_prop, k_res, k_mh) = split(step key, 3) — on the host"""
@@ -1048,7 +1242,7 @@ class _NoiseAhead:
             P = self._chain_prog(ta)
             half, row_a = self.noise_slot[ta]
             rows = tb - ta
-            mh = self.fuse_mh and ta >= 1
+            mh = self.chained and ta >= 1
             for root, q, idx in self._noise_progs[id(P)]:
                 ks = [self.step_keys[t][2] if (mh and root == "LDKEY") else self.step_keys[t][0] for t in range(ta, tb)]
                 if rows == 1 or rows * n >= 2 ** 31 - 4096:
@@ -1076,7 +1270,7 @@ class _NoiseAhead:
         (k_prop; the chained MH + extension program: k_mh), root KSPLITU from the extension's key k_prop"""
         P = self._chain_prog(t)
         views = self._noise_views(t, len(P.noise))
-        mh = self.fuse_mh and t >= 1
+        mh = self.chained and t >= 1
         for root, q, idx in self._noise_progs[id(P)]:
             k = self.step_keys[t][2] if (mh and root == "LDKEY") else self.step_keys[t][0]
             q.run((self.n,), self._noise_split(k), [views[k_] for k_ in idx])
@@ -1335,7 +1529,7 @@ class SweepHistory:
         return mean[:, 0] if (self._tuple is None and not self._event) else mean
 
 
-class BootstrapSweep(_NoiseAhead):
+class BootstrapSweep(_Sweep):
     """A whole bootstrap particle filter (T steps, resampling every step) as a
     fixed sequence of launches on one stream, capturable into a hipGraph — two launches per step:
 
@@ -1405,7 +1599,6 @@ class BootstrapSweep(_NoiseAhead):
         self.fuse_req = fuse_resample
 
     def prepare(self, key: Key, ys: torch.Tensor):
-        from ..static import MinimalGenerate as _MG, NoiseProgram
         be = _lib.get()
         # a sweep object may be prepared again (another key, other observations): nothing bound for the previous run
         # survives — the background launches' key rows in particular (found by the unbiasedness test on the GPU: a
@@ -1424,13 +1617,10 @@ class BootstrapSweep(_NoiseAhead):
                                       "program (chain_mh=False)")
         self.noise_ahead = False
         self._noise_progs = {}
-
-        def MinimalGenerate(*a):
-            return _MG(*a, hoist_noise=bool(want_na))
         n, T = self.n, self.T
         dev = be.device
         self.key = key
-        self.ys = ys.to(dev).float().contiguous()
+        self._set_observations(ys)
         assert self.ys.numel() >= T
         self.lw = torch.zeros((n,), dtype=torch.float32, device=dev)
         self.anc = torch.zeros((n,), dtype=torch.int32, device=dev)
@@ -1441,65 +1631,27 @@ class BootstrapSweep(_NoiseAhead):
         # known whether the site programs leave the statistics)
         self.fused = _Resampler.form_of(self.kind, n, sweep=True) == "tiles"
         self.fuse = False
-        obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
-        self.p_init = MinimalGenerate(self.init, (), obs0, (n,))
-        # the state is the model's return value: a scalar, or ONE vector of D floats per particle, stored
-        # struct-of-arrays as [D, n] and seen by models (and by state()) as the [n, D] view
-        ro = self.p_init.ro
-        outs_ = self.p_init.comp.outputs
-        self.tuple_state = None
-        if ro[0] in ("tuple", "list") and ro[1] and all(o[0] == "out" and outs_[o[1]][0] == "f32" and outs_[o[1]][1] == ()
-                                                          for o in ro[1]):
-            # a TUPLE of float scalars (the latent sites a step hands to the next one): D rows of one [D, n] store,
-            # every row its own output of the site program and its own gathered input of the next step
-            self.tuple_state = type(()) if ro[0] == "tuple" else type([])
-            if self.rejuvenate is not None:
+        self.batch, self.index = n, self.anc
+        self._build_init(bool(want_na))
+        # the state is the model's return value, stored struct-of-arrays as [D, n] and seen by models (and by state())
+        # as the [n] / [n, D] / tuple-of-rows view
+        self.store = _StateStore(self.p_init, n, "BootstrapSweep")
+        self.tuple_state, self.event, D = self.store.tuple_state, self.store.event, self.store.D
+        hn = False
+        if self.rejuvenate is not None:
+            if self.tuple_state is not None:
                 raise NotImplementedError("BootstrapSweep(rejuvenate=...): a tuple state is not supported (return one "
                                           "array, or use smc.resample / rejuvenate / extend under smc.capture)")
-            event, D = (), len(ro[1])
-        else:
-            if ro[0] != "out":
-                raise NotImplementedError("BootstrapSweep: the step model must return one array (scalar or vector "
-                                          "state) or a tuple of float scalars")
-            dt, event, _slots = outs_[ro[1]]
-            if dt != "f32" or len(event) > 1:
-                raise NotImplementedError("BootstrapSweep: the state must be a float scalar or a float vector")
-            D = int(np.prod(event, dtype=np.int64)) if event else 1
-        self.event = tuple(event)
-        self.x_store = [torch.zeros((D, n), dtype=torch.float32, device=dev) for _ in range(2)]
-        if self.tuple_state is not None:
-            self.x = [self.tuple_state(s_[d] for d in range(D)) for s_ in self.x_store]
-        else:
-            self.x = [s_.reshape(n) if not event else s_.t() for s_ in self.x_store]
-        g = self._gathered(0)
-        if self.rejuvenate is None:
-            self.p_step = MinimalGenerate(self.step, (g,) + tuple(self.step_extra(1)), obs0, (n,))
-        else:
-            from ..static import MinimalMH
-            # xm[t % 2]: the MH-moved, resampled state the extension of step t starts from
-            self.xm_store = [torch.zeros((D, n), dtype=torch.float32, device=dev) for _ in range(2)]
-            self.xm = [s_.reshape(n) if not event else s_.t() for s_ in self.xm_store]
+            # store t % 2 of `moved`: the MH-moved, resampled state the extension of step t starts from
+            self.moved = _StateStore(self.p_init, n, "BootstrapSweep")
             self.accept = torch.zeros((n,), dtype=torch.bool, device=dev)
-            self.p_step = _MG(self.step, (self.xm[0],) + tuple(self.step_extra(1)), obs0, (n,))
-            ch = obs0.set(self.state_addr, g)
-            self.p_mh_init = MinimalMH(self.init, (), ch, self.rejuvenate, (n,))
-            self.p_mh_step = MinimalMH(self.step, (Gathered(self.xm[0], self.anc),) + tuple(self.step_extra(1)), ch,
-                                       self.rejuvenate, (n,))
-        # the MH move and the extension that follows it as ONE program / one launch per step (static.MinimalMHGenerate:
-        # same keys, same draws, same bits; one launch boundary and one trip of the moved state through memory less).
-        self.p_mhvm_init = self.p_mhvm_step = None
-        if self.rejuvenate is not None and self.chain_mh:
-            from ..static import MinimalMHGenerate
-            ex = tuple(self.step_extra(1))
             # which draws of the chained program go to the background stream: the two streams should carry about the
             # same vector work (noise_roots: "all", "LDKEY" = the move's proposal + accept draws, "KSPLITU" = the
             # extension's draw)
             roots = self.noise_roots
             hn = False if not want_na else (True if roots == "all" else tuple(roots.split(",")))
-            self.p_mhvm_init = MinimalMHGenerate(self.init, (), ch, self.rejuvenate, self.step, ex, obs0, (n,),
-                                                 hoist_noise=hn)
-            self.p_mhvm_step = MinimalMHGenerate(self.step, (Gathered(self.xm[0], self.anc),) + ex, ch, self.rejuvenate,
-                                                 self.step, ex, obs0, (n,), hoist_noise=hn)
+        # (with rejuvenate=, the extension alone, p_step, draws in place whatever the chained program does)
+        self._build_steps(bool(want_na), False, chain=self.chain_mh, chain_hoist=hn)
         # the chain's programs by step: t = 0, t = 1, t >= 2
         chain_progs = (self.p_init, self.p_step, self.p_step) if self.rejuvenate is None else \
             (self.p_init, self.p_mhvm_init, self.p_mhvm_step)
@@ -1598,40 +1750,30 @@ class BootstrapSweep(_NoiseAhead):
         be = _lib.get()
         w = t % 2 if self.fuse else 0
         tag = 1 + t % _lib.ANC_TAG_MAX if tagged else 0
-        be.check(be.c.gmx_history_record(be.ptr(self.x_store[t % 2]), self.x_store[0].shape[0], be.ptr(self.lw_pp[w]),
+        be.check(be.c.gmx_history_record(be.ptr(self.store.rows[t % 2]), self.store.D, be.ptr(self.lw_pp[w]),
                                          be.ptr(self.anc), self.n, tag, be.ptr(self.hist_xs[t]), be.ptr(self.hist_lws[t]),
                                          be.ptr(self.hist_ancs[t]), be.ptr(self.hist_status), be.stream()),
                  "gmx_history_record")
 
-    def _gathered(self, which):
-        """the resampled state x[which][anc] as the step model's first argument (lazy: the gather is fused)"""
-        if self.tuple_state is not None:
-            return self.tuple_state(Gathered(row, self.anc) for row in self.x[which])
-        return Gathered(self.x[which], self.anc)
+    chained = property(lambda self: self.fuse_mh)
 
-    def _launch_vm(self, t):
+    def _launch_step(self, t, skip_vm=False, alone=False):
+        """step t's programs (_programs) with what is the single-GPU sweep's own: the log-weights and block maxima of set
+        t % 2 (the one-launch form alternates two), the tile statistics, and — a one-launch step that gathers — the
+        resampling of step t - 1 as its prologue.  skip_vm: the separate MH move only; alone: the extension only."""
         n = self.n
-        k_prop = self.step_keys[t][0]
-        obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-        if t == 0:
-            prog = self.p_init
-            leaves = prog.leaves((), obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves((), obs)
-        else:
-            g = self._gathered((t - 1) % 2) if self.rejuvenate is None else self.xm[t % 2]
-            prog = self.p_step
-            a = (g,) + tuple(self.step_extra(t))
-            leaves = prog.leaves(a, obs, self._noise_leaves(t, prog)) if self.noise_ahead else prog.leaves(a, obs)
-        bufs = [None] * len(prog.comp.outputs)
-        if self.tuple_state is not None:
-            for d, o in enumerate(prog.ro[1]):
-                bufs[o[1]] = self.x_store[t % 2][d:d + 1]
-        else:
-            bufs[prog.ro[1]] = self.x_store[t % 2]
+        mh, prog, leaves, key, bufs = self._programs(t, alone)
+        if mh is not None:
+            mprog, mleaves, mkey, mbufs = mh
+            mprog.comp.run(mleaves, (n,), lazy_split(mkey, n), out_buffers=mbufs)
+        if skip_vm:
+            return
         w = t % 2 if self.fuse else 0
         bufs[prog.wo[1]] = self.lw_pp[w].reshape(1, n)
-        prog.comp.run(leaves, (n,), lazy_split(k_prop, n), red_out=self.partials_pp[w], out_buffers=bufs,
+        gathers = t >= 1 and (self.rejuvenate is None or not alone)
+        prog.comp.run(leaves, (n,), lazy_split(key, n), red_out=self.partials_pp[w], out_buffers=bufs,
                       tile_stats=(self.tile_agg_pp[w], self.shift) if self.tile_stats else None,
-                      resample_in=self._resample_in(t) if (self.fuse and t >= 1 and self.rejuvenate is None) else None)
+                      resample_in=self._resample_in(t) if (self.fuse and gathers) else None)
 
     def _resample_in(self, t):
         """gmx_run_args.rs of the launch of step t (>= 1) that gathers: resample step t-1's weights first"""
@@ -1640,60 +1782,6 @@ class BootstrapSweep(_NoiseAhead):
         return dict(lw=self.lw_pp[w], tile_max=self.partials_pp[w], tile_agg=self.tile_agg_pp[w], shift=self.shift,
                     key=(int(kh[0]), int(kh[1])), tag=1 + (t - 1) % _lib.ANC_TAG_MAX, max_out=self.maxs[t - 1:t],
                     total_out=self.totals[t - 1:t], status=self.rs_status)
-
-    def _chain_prog(self, t):
-        if t == 0:
-            return self.p_init
-        if self.fuse_mh:
-            return self.p_mhvm_init if t == 1 else self.p_mhvm_step
-        return self.p_step
-
-    def _launch_mh(self, t):
-        """The MH move on the resampled particles of step t-1 (t >= 1): reads x_{t-1}[anc] and, for
-        t >= 2, the state xm[(t-1) % 2][anc] that x_{t-1} was extended from; writes xm[t % 2]."""
-        n = self.n
-        k_mh = self.step_keys[t][2]
-        ch = ChoiceMap.empty().set(self.obs_addr, self.ys[t - 1]).set(self.state_addr,
-                                                                      Gathered(self.x[(t - 1) % 2], self.anc))
-        if t == 1:
-            prog, leaves = self.p_mh_init, self.p_mh_init.leaves((), ch, self.rejuvenate)
-        else:
-            prog = self.p_mh_step
-            a = Gathered(self.xm[(t - 1) % 2], self.anc)
-            leaves = prog.leaves((a,) + tuple(self.step_extra(t - 1)), ch, self.rejuvenate)
-        bufs = [None] * len(prog.comp.outputs)
-        bufs[prog.ro[1]] = self.xm_store[t % 2]
-        bufs[prog.ao[1]] = self.accept.reshape(1, n)
-        prog.comp.run(leaves, (n,), lazy_split(k_mh, n), out_buffers=bufs)
-
-    def _launch_mhvm(self, t):
-        """step t >= 1 as ONE launch: the MH move on the resampled particles of step t-1 (as _launch_mh), then the
-        extension to step t (as _launch_vm) from the moved state"""
-        n = self.n
-        k_mh, k_prop = self.step_keys[t][2], self.step_keys[t][0]
-        ch = ChoiceMap.empty().set(self.obs_addr, self.ys[t - 1]).set(self.state_addr,
-                                                                      Gathered(self.x[(t - 1) % 2], self.anc))
-        obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-        ex = tuple(self.step_extra(t))
-        kw = k_prop.host()
-        if t == 1:
-            prog = self.p_mhvm_init
-            leaves = prog.leaves((), ch, self.rejuvenate, ex, obs, (int(kw[0]), int(kw[1])),
-                                 self._noise_leaves(t, prog) if self.noise_ahead else ())
-        else:
-            prog = self.p_mhvm_step
-            a = Gathered(self.xm[(t - 1) % 2], self.anc)
-            leaves = prog.leaves((a,) + tuple(self.step_extra(t - 1)), ch, self.rejuvenate, ex, obs,
-                                 (int(kw[0]), int(kw[1])), self._noise_leaves(t, prog) if self.noise_ahead else ())
-        bufs = [None] * len(prog.comp.outputs)
-        bufs[prog.mo[1]] = self.xm_store[t % 2]
-        bufs[prog.ao[1]] = self.accept.reshape(1, n)
-        bufs[prog.ro[1]] = self.x_store[t % 2]
-        w = t % 2 if self.fuse else 0
-        bufs[prog.wo[1]] = self.lw_pp[w].reshape(1, n)
-        prog.comp.run(leaves, (n,), lazy_split(k_mh, n), red_out=self.partials_pp[w], out_buffers=bufs,
-                      tile_stats=(self.tile_agg_pp[w], self.shift) if self.tile_stats else None,
-                      resample_in=self._resample_in(t) if self.fuse else None)
 
     def _rows(self, t) -> int:
         """partial rows the site program of step t wrote"""
@@ -1763,13 +1851,10 @@ class BootstrapSweep(_NoiseAhead):
 
     def _chain_step(self, t, skip_vm=False):
         """everything step t launches on the chain: [the MH move], site program', then the resampler"""
-        if t >= 1 and self.rejuvenate is not None and not self.fuse_mh:
-            self._launch_mh(t)                    # (a launch of its own — one-stream form only — and not part of skip_vm)
+        separate_mh = t >= 1 and self.rejuvenate is not None and not self.fuse_mh
+        if separate_mh or not skip_vm:            # (the move as a launch of its own — one-stream form only — is not
+            self._launch_step(t, skip_vm)         #  part of skip_vm)
         if not skip_vm:
-            if t >= 1 and self.fuse_mh:
-                self._launch_mhvm(t)
-            else:
-                self._launch_vm(t)
             if self.keep_history and self.fuse and t >= 1:
                 self._record(t - 1, tagged=True)      # (this launch's prologue resampled step t - 1)
         if self.fuse and t < self.T - 1:
@@ -1791,7 +1876,7 @@ class BootstrapSweep(_NoiseAhead):
     def kernel_timers(self):
         """Representative single launches (a mid-sweep step) for per-kernel timing in bench.py."""
         t = max(1, self.T // 2)
-        out = {"k_vm": lambda: self._launch_vm(t)}
+        out = {"k_vm": lambda: self._launch_step(t, alone=True)}
         if self.noise_ahead:
             out["k_noise"] = lambda: self._launch_noise(t)
         if self.fuse:
@@ -1804,13 +1889,6 @@ class BootstrapSweep(_NoiseAhead):
             out["k_weight_cdf"] = lambda: self._resample(t, cdf_only=True)
             out["k_ancestors"] = lambda: self._resample(t, cdf_ready=True)
         return out
-
-    def launch(self):
-        be = _lib.get()
-        if self.graph is None:
-            self.enqueue()
-        else:
-            be.check(be.c.gmx_graph_launch(self.graph, be.stream()), "gmx_graph_launch")
 
     def _check_valid(self):
         """the fused resampling prologue's sticky timeout word: a workgroup that gave up waiting clamps stale words into
@@ -1843,19 +1921,18 @@ class BootstrapSweep(_NoiseAhead):
     def log_ml(self) -> float:
         """sum_t [ ref(M_t) + log(total_t * 2^-shift) - log N ] in float64 (synchronises)."""
         self._check_valid()
-        m = np.array([cdf_reference(v) for v in self.maxs.cpu().numpy()], dtype=np.float64)
-        tot = self.totals.cpu().numpy().view(np.uint64).astype(np.float64)
-        if np.any(tot == 0):             # a step where no particle carried any mass
+        terms = evidence_terms(self.maxs.cpu().numpy(), self.totals.cpu().numpy(), self.shift, self.n)
+        if np.any(np.isneginf(terms)):   # a step where no particle carried any mass
             return -math.inf
-        return float(np.sum(m + np.log(tot) - self.shift * math.log(2.0) - math.log(self.n)))
+        return float(np.sum(terms))
 
     def state(self):
         """(x_T particles before the last resampling, log-weights, last ancestors)."""
         self._check_valid()
-        return self.x[(self.T - 1) % 2], self.lw_pp[(self.T - 1) % 2 if self.fuse else 0], self.anc
+        return self.store.view((self.T - 1) % 2), self.lw_pp[(self.T - 1) % 2 if self.fuse else 0], self.anc
 
 
-class BootstrapBank(_NoiseAhead):
+class BootstrapBank(_Sweep):
     """R independent bootstrap particle filters of n particles each as ONE chain of launches (the reference's
     `jax.vmap(smc_run)(keys)`: replicate keys for the variance of the evidence estimate, a grid or a chain over model
     parameters): per step ONE site program over the R * n particles and ONE gmx_resample_rows call (every row under its
@@ -1902,7 +1979,6 @@ class BootstrapBank(_NoiseAhead):
 
     def prepare(self, keys: Key, ys: torch.Tensor):
         from ..random import _derive_host
-        from ..static import MinimalGenerate
         be = _lib.get()
         self._drop_graph()
         R, n, T = self.R, self.n, self.T
@@ -1915,7 +1991,7 @@ class BootstrapBank(_NoiseAhead):
             raise NotImplementedError(f"BootstrapBank.prepare: per-filter observations (ys of [R, T]; got "
                                       f"{tuple(ys.shape)}) are not supported: ys is [T], shared by the filters")
         self.keys = keys
-        self.ys = ys.to(dev).float().contiguous()
+        self._set_observations(ys)
         assert self.ys.numel() >= T
         # the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys
         kh = np.asarray(keys.host(), dtype=np.uint32).reshape(R, 2)
@@ -1938,106 +2014,49 @@ class BootstrapBank(_NoiseAhead):
             if tuple(p.shape) != (R,):
                 raise ValueError(f"BootstrapBank: params are [R] = {(R,)} tensors, one value per filter; got {tuple(p.shape)}")
             self.params_full.append(p.to(dev).float().reshape(R, 1).expand(R, n).contiguous().reshape(N))
-        pf = tuple(self.params_full)
-        obs0 = ChoiceMap.empty().set(self.obs_addr, self.ys[0])
-        self.p_init = MinimalGenerate(self.init, pf, obs0, (N,))
-        ro, outs_ = self.p_init.ro, self.p_init.comp.outputs
-        self.tuple_state = None
-        if ro[0] in ("tuple", "list") and ro[1] and all(o[0] == "out" and outs_[o[1]][0] == "f32" and outs_[o[1]][1] == ()
-                                                          for o in ro[1]):
-            self.tuple_state = type(()) if ro[0] == "tuple" else type([])
-            event, D = (), len(ro[1])
-        else:
-            if ro[0] != "out":
-                raise NotImplementedError("BootstrapBank: the step model must return one array (scalar or vector "
-                                          "state) or a tuple of float scalars")
-            dt, event, _slots = outs_[ro[1]]
-            if dt != "f32" or len(event) > 1:
-                raise NotImplementedError("BootstrapBank: the state must be a float scalar or a float vector")
-            D = int(np.prod(event, dtype=np.int64)) if event else 1
-        self.event = tuple(event)
-        self.x_store = [torch.zeros((D, N), dtype=torch.float32, device=dev) for _ in range(2)]
-        if self.tuple_state is not None:
-            self.x = [self.tuple_state(s_[d] for d in range(D)) for s_ in self.x_store]
-        else:
-            self.x = [s_.reshape(N) if not event else s_.t() for s_ in self.x_store]
-        self.p_step = MinimalGenerate(self.step, (self._gathered(0),) + tuple(self.step_extra(1)) + pf, obs0, (N,))
+        # particle i of row r draws under split(k_prop[r], n)[i]: derived in the program from the row's key
+        self.step_keys = [(Key(lazy=("rowsplit", Key(dev=self.keys_prop[t]), n)), self.keys_res[t], None) for t in range(T)]
+        self.batch, self.index, self.tail = N, self.anc.reshape(-1), tuple(self.params_full)
+        self._build_init()
+        self.store = _StateStore(self.p_init, N, "BootstrapBank")
+        self.tuple_state, self.event = self.store.tuple_state, self.store.event
+        self._build_steps()
         if self.specialize:
             self.p_init.comp.specialize()
             self.p_step.comp.specialize()
         self.partials = torch.zeros((2, (N + 255) // 256), dtype=torch.float32, device=dev)
         return self
 
-    def _gathered(self, which):
-        anc = self.anc.reshape(-1)
-        if self.tuple_state is not None:
-            return self.tuple_state(Gathered(row, anc) for row in self.x[which])
-        return Gathered(self.x[which], anc)
-
-    def _launch_vm(self, t):
-        N = self.R * self.n
-        obs = ChoiceMap.empty().set(self.obs_addr, self.ys[t])
-        pf = tuple(self.params_full)
-        if t == 0:
-            prog = self.p_init
-            leaves = prog.leaves(pf, obs)
-        else:
-            prog = self.p_step
-            leaves = prog.leaves((self._gathered((t - 1) % 2),) + tuple(self.step_extra(t)) + pf, obs)
-        bufs = [None] * len(prog.comp.outputs)
-        if self.tuple_state is not None:
-            for d, o in enumerate(prog.ro[1]):
-                bufs[o[1]] = self.x_store[t % 2][d:d + 1]
-        else:
-            bufs[prog.ro[1]] = self.x_store[t % 2]
-        bufs[prog.wo[1]] = self.lw.reshape(1, N)
-        # particle i of row r draws under split(k_prop[r], n)[i]: derived in the program from the row's key
-        key = Key(lazy=("rowsplit", Key(dev=self.keys_prop[t]), self.n))
-        prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
-
     def _resample(self, t):
-        resample_rows(self.kind, self.keys_res[t], self.lw.reshape(self.R, self.n), index_stride=self.n,
+        resample_rows(self.kind, self.step_keys[t][1], self.lw.reshape(self.R, self.n), index_stride=self.n,
                       out=(self.anc, self.totals[t], self.maxs[t], self.status), workspace=self.ws)
 
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (no syncs, no
         allocations, no host read of a device value)"""
+        N = self.R * self.n
         self.status.zero_()
         for t in range(self.T):
-            self._launch_vm(t)
+            _mh, prog, leaves, key, bufs = self._programs(t)
+            bufs[prog.wo[1]] = self.lw.reshape(1, N)
+            prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
             self._resample(t)
-
-    def launch(self):
-        be = _lib.get()
-        if self.graph is None:
-            self.enqueue()
-        else:
-            be.check(be.c.gmx_graph_launch(self.graph, be.stream()), "gmx_graph_launch")
 
     def log_ml(self) -> np.ndarray:
         """float64 [R]: row r is BootstrapSweep.log_ml() of that filter — sum_t [ ref(M_t) + log(total_t 2^-shift) - log n ]
         from the [T, R] evidence terms, finished in float64 on the host (synchronises)."""
-        m = cdf_reference(self.maxs.cpu().numpy())                                  # [T, R] float64
-        tot = self.totals.cpu().numpy().view(np.uint64).astype(np.float64)
+        terms = evidence_terms(self.maxs.cpu().numpy(), self.totals.cpu().numpy(), self.shift, self.n)      # [T, R]
         out = np.empty((self.R,), dtype=np.float64)
         for r in range(self.R):
-            tr = np.ascontiguousarray(tot[:, r])
-            if np.any(tr == 0):              # a step where no particle of the row carried any mass
-                out[r] = -math.inf
-            else:
-                out[r] = float(np.sum(np.ascontiguousarray(m[:, r]) + np.log(tr) - self.shift * math.log(2.0) - math.log(self.n)))
+            tr = np.ascontiguousarray(terms[:, r])
+            # (-inf: a step where no particle of the row carried any mass)
+            out[r] = -math.inf if np.any(np.isneginf(tr)) else float(np.sum(tr))
         return out
 
     def state(self):
         """(x_T before the last resampling: [R, n], [R, n, D] or a tuple of [R, n]; log-weights [R, n]; the last ancestors,
         int32 [R, n], row-local)"""
         R, n = self.R, self.n
-        w = (self.T - 1) % 2
-        if self.tuple_state is not None:
-            x = self.tuple_state(row.reshape(R, n) for row in self.x[w])
-        elif self.event:
-            x = self.x[w].reshape(R, n, self.x[w].shape[-1])
-        else:
-            x = self.x[w].reshape(R, n)
+        x = self.store.per_filter((self.T - 1) % 2, R, n)
         local = self.anc - (torch.arange(R, dtype=torch.int32, device=self.anc.device) * n).reshape(R, 1)
         return x, self.lw.reshape(R, n), local

@@ -6,10 +6,12 @@ never from the tree under test: the generator refuses to write while `git status
 A tree exported from a commit without its git metadata (`git archive`, a copy to a GPU box) has nothing to ask; there
 the commit it was exported from is named with --exported-from and goes into the file.
 
-  python tests/golden/make_launch_trace.py [--gpu] [--exported-from COMMIT] [--out FILE] [--only PREFIX]
+  python tests/golden/make_launch_trace.py [--gpu] [--exported-from COMMIT] [--out FILE] [--only PREFIX [PREFIX ...]]
 
---only PREFIX records the cases whose names start with PREFIX and no others (the device record holds the "sharded/"
-cases only: the GPU suite's time budget has no room for all of them).
+--only records the cases whose names start with one of the prefixes and no others (the device record holds the forms
+that only exist with streams, the state-layout and the bank cases: the GPU suite's time budget has no room for all).
+The mirror's "state/" and "bank/" cases are in a file of their own, made at a later parent than the rest:
+  --only state/ bank/ --out tests/golden/launch_trace_cpu_state.json
 """
 import argparse
 import json
@@ -41,7 +43,7 @@ def main():
     ap.add_argument("--gpu", action="store_true")
     ap.add_argument("--exported-from", default=None)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="", metavar="PREFIX")
+    ap.add_argument("--only", nargs="+", default=[""], metavar="PREFIX")
     a = ap.parse_args()
     commit = source_commit(a.exported_from)
     from tests import launch_trace as L
@@ -54,7 +56,7 @@ def main():
         import tests.hostsim as hs
         be = hs.install()
     cases = {}
-    for name in [n for n in L.case_names(backend) if n.startswith(a.only)]:
+    for name in [n for n in L.case_names(backend) if n.startswith(tuple(a.only))]:
         cases[name] = L.trace_case(be, name)
         print(name, {k: len(v) for k, v in cases[name].items()}, flush=True)
     out = a.out or L.GOLDEN[backend]

@@ -22,6 +22,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = {"cpu": os.path.join(HERE, "golden", "launch_trace_cpu.json"),
           "gpu": os.path.join(HERE, "golden", "launch_trace_gpu.json")}
+# (the "state/" and "bank/" cases of the mirror were recorded later, at another parent: a file of their own)
+LATER = {"cpu": [os.path.join(HERE, "golden", "launch_trace_cpu_state.json")], "gpu": []}
 KINDS = ("systematic", "stratified", "multinomial", "multinomial_tiled", "multinomial_sorted")
 TILE_KINDS = ("systematic", "stratified", "multinomial_tiled", "multinomial_sorted")
 
@@ -183,6 +185,61 @@ def sweep_cases():
     return cases
 
 
+def _state_sweep(which, n=1500, T=3, **kw):
+    """a vector state [n, 2] (history_checks.make_tracker) / a tuple of two scalars (make_pair): D = 2 rows of the store"""
+    def make():
+        import genjax_amd as G
+        from genjax_amd import numpy as jnp
+        from genjax_amd.inference.smc import BootstrapSweep
+        from tests import history_checks as H
+        init, step = H.make_pair(G) if which == "tuple" else H.make_tracker(G, lambda a, b: jnp.stack([a, b]))
+        return BootstrapSweep(init, step, n, T, **kw).prepare(_key(17), torch.from_numpy(H.state_data()))
+    return make
+
+
+def state_cases():
+    cases = {}
+    for which in ("vector", "tuple"):
+        for fuse in (False, True):
+            cases[f"state/{which}/fuse{int(fuse)}"] = _state_sweep(which, specialize=True, noise_ahead=False, fuse_resample=fuse)
+    cases["state/vector/history"] = _state_sweep("vector", specialize=True, noise_ahead=False, fuse_resample=False, history=True)
+    cases["state/vector/interpreted"] = _state_sweep("vector", specialize=False, noise_ahead=False, fuse_resample=False)
+    return cases
+
+
+BANK_R, BANK_T = 3, 3
+
+
+def bank_cases():
+    """name -> a function that builds and prepares a BootstrapBank of BANK_R filters"""
+    def bank(model, n, **kw):
+        def make():
+            import genjax_amd as G
+            from genjax_amd import numpy as jnp, workloads
+            from genjax_amd.inference.smc import BootstrapBank
+            from tests import bank_checks as B, history_checks as H
+            ys = torch.from_numpy(workloads.lgssm_data(BANK_T))
+            if model == "lgssm":
+                init, step = workloads.make_lgssm(G)
+            elif model == "vector":
+                init, step = H.make_tracker(G, lambda a, b: jnp.stack([a, b]))
+            elif model == "tuple":
+                init, step = H.make_pair(G)
+            else:                       # the process-noise scale as a [R] parameter of init and step
+                init, step = B.make_lgssm_sx(G, True)
+                kw["params"] = (torch.tensor(B.PARAM_SX[:BANK_R], dtype=torch.float32),)
+            return BootstrapBank(init, step, n, BANK_R, BANK_T, specialize=True, **kw).prepare(
+                G.split(_key(4242), BANK_R), ys)
+        return make
+    cases = {}
+    for kind in ("systematic", "stratified", "multinomial"):
+        for n in (200, 1500):
+            cases[f"bank/{kind}/n{n}"] = bank("lgssm", n, resample=kind)
+    for model in ("vector", "tuple", "params"):
+        cases[f"bank/systematic/{model}"] = bank(model, 1500)
+    return cases
+
+
 CAPTURED = ("systematic", "multinomial_tiled")          # (GPU half only: the mirror has no graph capture)
 
 
@@ -199,6 +256,21 @@ def trace_sweep(be, make):
         out[name] = rec.stop()
     _sync(be)
     assert out["enqueue"] == out.pop("enqueue_again"), "two enqueues of one prepared sweep issued different calls"
+    return out
+
+
+def trace_bank(be, make):
+    """{"enqueue": [...]} of one prepared bank, as trace_sweep (a bank has no skip_vm form)"""
+    rec = install(be)
+    bank = make()
+    bank.enqueue()
+    out = {}
+    for name in ("enqueue", "enqueue_again"):
+        rec.start(identity=True)
+        bank.enqueue()
+        out[name] = rec.stop()
+    _sync(be)
+    assert out["enqueue"] == out.pop("enqueue_again"), "two enqueues of one prepared bank issued different calls"
     return out
 
 
@@ -451,7 +523,8 @@ def case_names(backend):
     names = list(sweep_cases()) + ["sharded", "one_offs"]
     if backend == "gpu":
         names += [f"captured/{k}" for k in CAPTURED]
-    return names + list(sharded_cases(backend)) + (list(IMPORTANCE_CASES) if backend == "cpu" else [])
+    names += list(sharded_cases(backend)) + (list(IMPORTANCE_CASES) if backend == "cpu" else [])
+    return names + list(state_cases()) + list(bank_cases())
 
 
 def trace_case(be, name):
@@ -468,6 +541,10 @@ def trace_case(be, name):
             return trace_one_offs(be)
         if name.startswith("captured/"):
             return trace_captured(be, name.split("/", 1)[1])
+        if name.startswith("bank/"):
+            return trace_bank(be, bank_cases()[name])
+        if name.startswith("state/"):
+            return trace_sweep(be, state_cases()[name])
         return trace_sweep(be, sweep_cases()[name])
     finally:
         gc.enable()
@@ -476,7 +553,11 @@ def trace_case(be, name):
 
 def load_golden(backend):
     with open(GOLDEN[backend]) as fh:
-        return json.load(fh)
+        record = json.load(fh)
+    for path in LATER[backend]:
+        with open(path) as fh:
+            record["cases"].update(json.load(fh)["cases"])
+    return record
 
 
 def check_case(be, backend, name):

@@ -1892,3 +1892,47 @@ def test_support_matrix_is_current():
     for name, size, batch, cells in rows:
         line = f"| {name} | {size} | {batch} | " + " | ".join(cells) + " |"
         assert line in committed, line
+
+
+def _cdf_reference_scalar(m):
+    """the scalar form smc.cdf_reference had beside its array form: int(t), + 1 where that fell below t, in Python"""
+    lim = 1 << 29
+    inv_ln2 = np.frombuffer(np.uint32(0x3FB8AA3B).tobytes(), np.float32)[0]
+    ln2 = np.frombuffer(np.uint32(0x3F317218).tobytes(), np.float32)[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.float32(m) * inv_ln2
+    if not (t > -np.float32(lim)):
+        k = -lim
+    elif t > np.float32(lim):
+        k = lim
+    else:
+        k = int(t)
+        if np.float32(k) < t:
+            k += 1
+    return float(np.float32(k) * ln2)
+
+
+def test_cdf_reference_of_one_maximum_is_the_array_form():
+    """smc.cdf_reference keeps ONE implementation (arrays; a scalar goes through it and comes back a float): the same
+    numbers as the scalar form it had, on 200 615 float32 inputs — draws of N(0, 50^2), every k * ln2f (where ceil sits
+    on its edge), the specials, the denormal ends and both sides of the 2^29 clamp.  The same bits too, but for the sign
+    of a zero: a maximum in (-ln 2, 0) gives ceil = -0.0 where int() gave 0 — and an evidence term adds log(total) to
+    it, which is never -0.0, so no sum can tell the two apart."""
+    from genjax_amd.inference.smc import cdf_reference
+    ln2 = np.frombuffer(np.uint32(0x3F317218).tobytes(), np.float32)[0]
+    fmax = np.finfo(np.float32).max
+    xs = np.concatenate([
+        (np.random.default_rng(29).normal(size=200000) * 50.0).astype(np.float32),
+        (np.arange(-300, 300).astype(np.float32) * ln2).astype(np.float32),
+        np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e30, -1e30, fmax, -fmax, 1e-45, 1.1754942e-38,
+                  3.7e8, -3.7e8, 3.8e8, -3.8e8], dtype=np.float32)])
+    assert xs.size == 200615
+    want = np.array([_cdf_reference_scalar(v) for v in xs], dtype=np.float64)
+    got = cdf_reference(xs)
+    assert got.dtype == np.float64 and not np.isnan(got).any() and np.array_equal(got, want)
+    assert np.array_equal(got.view(np.int64)[want != 0], want.view(np.int64)[want != 0])
+    for v in xs[::997].tolist() + xs[-15:].tolist():           # one at a time: a float, the same number
+        one = cdf_reference(v)
+        assert type(one) is float and one == _cdf_reference_scalar(v)
+    for tot in (1, 2, 12345, 2 ** 61):                          # ... and the same evidence term, to the bit
+        assert math.copysign(1.0, -0.0 + math.log(tot)) == math.copysign(1.0, 0.0 + math.log(tot)) == 1.0

@@ -2,9 +2,10 @@
 parent of the commit that gave inference/smc.py ONE resampling launcher and ONE step loop
 (tests/golden/make_launch_trace.py): same calls, same order, same integers, same sharing of buffers — on the C-ABI's
 CPU mirror.  The "sharded/" and "sharded_importance/" cases were recorded at the parent of the commit that gave
-inference/sharded.py its _ShardRouter.  (The device's record — `make_launch_trace.py --gpu --only sharded/` for the
-sharded cases alone: the one-launch step and the chained MH form, which the mirror never runs, and the captured sweep —
-has to be made on an MI355X at that parent commit; none is committed yet.)"""
+inference/sharded.py its _ShardRouter; the "state/" and "bank/" cases at the parent of the commit that gave the sweeps
+one _StateStore and one table of step programs.  (The device's record — the one-launch step, the chained MH form and the
+captured sweeps, which the mirror never runs, with the state and bank cases — was made on an MI355X at that last
+parent: tests/test_launch_trace_gpu.py.)"""
 import pytest
 
 from tests import launch_trace as L
