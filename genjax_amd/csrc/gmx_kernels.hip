@@ -3674,10 +3674,80 @@ extern "C" int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* 
     else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_TILE(GMX_RESAMPLE_STRATIFIED);
     else {
       GMX_ROWS_TILE(GMX_RESAMPLE_MULTINOMIAL);
-      hipLaunchKernelGGL(k_rows_mn, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0, st,
+      hipLaunchKernelGGL(k_rows_mn<false>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0, st,
                          keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
     }
 #undef GMX_ROWS_TILE
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// the iid multinomial with slot n - 1 of every row pinned (conditional SMC): n <= 1024 ONE launch; past it the pins, then
+// the unpinned chain with the last slot forced in k_rows_mn
+extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                                        int64_t index_stride, const float* pin_lw_d, const float* pin_x_d, float* x_d,
+                                        int32_t D, int64_t x_ld, int64_t x_row_stride, float* max_d, uint64_t* total_d,
+                                        int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("gmx_resample_rows_pinned: null argument%s");
+  switch (gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride)) {
+    case 0: break;
+    case 4: return gmx_fail("gmx_resample_rows_pinned: index_stride = %s%lld does not keep rows * index_stride below 2^31", "",
+                            (long long)index_stride);
+    default:
+      if (rows < 1 || rows > 0x7fffffffLL)
+        return gmx_fail("gmx_resample_rows_pinned: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
+      if (ld < n) return gmx_fail("gmx_resample_rows_pinned: ld = %s%lld is smaller than n", "", (long long)ld);
+      return gmx_fail("gmx_resample_rows_pinned: n = %s%lld is outside [1, 2^21]", "", (long long)n);
+  }
+  switch (gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride)) {
+    case 0: break;
+    case 5: return gmx_fail("gmx_resample_rows_pinned: D = %s%lld is outside [0, 65533]", "", (long long)D);
+    default:
+      if (x_row_stride < 0)
+        return gmx_fail("gmx_resample_rows_pinned: x_row_stride = %s%lld is negative", "", (long long)x_row_stride);
+      return gmx_fail("gmx_resample_rows_pinned: x_ld = %s%lld does not hold (rows - 1) * x_row_stride + n columns (or is "
+                      "2^46 or more)", "", (long long)x_ld);
+  }
+  if (D > 0 && !pin_x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (pin_x_d with D > 0)%s");
+  if (D > 0 && !x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (x_d with D > 0)%s");
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows_pinned: workspace_d must be 8-byte aligned%s");
+  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) ||
+      ((uintptr_t)pin_lw_d & 3) || ((uintptr_t)pin_x_d & 3) || ((uintptr_t)x_d & 3) || ((uintptr_t)total_d & 7) ||
+      ((uintptr_t)status_d & 7))
+    return gmx_fail("gmx_resample_rows_pinned: a pointer is not aligned to its element%s");
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  auto* status = (unsigned long long*)status_d;
+  rows_pin pin;
+  pin.lw = pin_lw_d; pin.x = pin_x_d; pin.x_out = x_d; pin.D = D; pin.x_ld = x_ld; pin.x_row_stride = x_row_stride;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+#define GMX_ROWS_PINNED(W_)                                                                                            \
+  hipLaunchKernelGGL((k_rows_small_pinned<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
+                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, pin)
+    if (n <= 256) GMX_ROWS_PINNED(1);
+    else if (n <= 512) GMX_ROWS_PINNED(2);
+    else GMX_ROWS_PINNED(4);
+#undef GMX_ROWS_PINNED
+    GMX_HIP(hipGetLastError());
+    return 0;
+  }
+  hipLaunchKernelGGL(k_rows_pin, dim3((unsigned)((rows + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)(D + 1)),
+                     dim3(GMX_ROWS_BLOCK), 0, st, lw_d, rows, n, ld, pin);
+  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
+  uint64_t* agg = (uint64_t*)workspace_d;
+  uint64_t* cdf = agg + rows * tiles;
+  float* tmax = (float*)(cdf + rows * n);
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
+    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
+    const dim3 grid((unsigned)tiles, (unsigned)cnt), block(GMX_ROWS_BLOCK);
+    hipLaunchKernelGGL(k_pick_stats, grid, block, 0, st, (const float*)lw_d, n, ld, tiles, row0, scale, tmax, agg);
+    hipLaunchKernelGGL((k_rows_tile<GMX_RESAMPLE_MULTINOMIAL>), grid, block, 0, st, keys_d, (const float*)lw_d, n, ld,
+                       (int)tiles, row0, index_stride, scale, (const float*)tmax, (const uint64_t*)agg, max_d, total_d,
+                       ancestors_d, cdf, status);
+    hipLaunchKernelGGL(k_rows_mn<true>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0,
+                       st, keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
   }
   GMX_HIP(hipGetLastError());
   return 0;

@@ -14,8 +14,12 @@
 //               [f(prefix_b), f(prefix_b + G_b)), f(c) = #{ j : P_j < c D }, searched in that LDS tile.  No CDF array.
 //   iid multinomial past one tile: a slot's threshold falls anywhere in the row, so k_rows_tile writes the row's CDF into
 //               the workspace ([rows, n] u64) and k_rows_mn searches it per slot (a third launch).
+//   pinned (gmx_resample_rows_pinned, conditional SMC): the iid multinomial with column n - 1 of every row replaced by a
+//               retained particle's weight (written back), its D state words written into the caller's store, and slot
+//               n - 1 answering n - 1.  n <= 1024: k_rows_small_pinned<W>, the same body with the pin compiled in — still
+//               ONE launch; n > 1024: k_rows_pin writes the pins first, then the chain above with k_rows_mn<true>.
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
-// host compiler: the two ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
+// host compiler: the ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
 // multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
 // for gmx_pick_rows; gmx_vm.h includes this file there.  That loop validates its arguments as the HIP entry point does but
 // leaves no message.
@@ -41,6 +45,16 @@ static inline int gmx_resample_rows_refusal_(int kind, int64_t rows, int64_t n, 
   if (index_stride < 0) return 4;
   if (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
                            (rows - 1) * index_stride + n - 1 >= (1LL << 31))) return 4;
+  return 0;
+}
+// gmx_resample_rows_pinned's own arguments (after the above).  0: fine.  5: D out of range.  6: x_ld / x_row_stride do not
+// keep column n - 1 of every row inside a [D, x_ld] store.
+#define GMX_ROWS_PIN_MAX_D 65533       /* D + 1 is a grid's y extent */
+static inline int gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n, int32_t D, int64_t x_ld, int64_t x_row_stride) {
+  if (D < 0 || D > GMX_ROWS_PIN_MAX_D) return 5;
+  if (D == 0) return 0;
+  if (x_row_stride < 0 || x_ld < n || x_ld >= (1LL << 46)) return 6;          // (D * x_ld stays below 2^62)
+  if (rows > 1 && x_row_stride > (x_ld - n) / (rows - 1)) return 6;           // x_ld >= (rows - 1) * x_row_stride + n
   return 0;
 }
 
@@ -99,14 +113,31 @@ __device__ __forceinline__ void rows_store4(int32_t* __restrict__ row, int64_t b
   }
 }
 
+// What gmx_resample_rows_pinned adds to a row (conditional SMC: slot n - 1 of every row is the retained particle)
+struct rows_pin {
+  const float* lw;      // [rows]: row r's column n - 1 takes lw[r] (written back into the matrix)
+  const float* x;       // [D, rows]: ... and its D state words, into
+  float* x_out;         //   x_out[d * x_ld + r * x_row_stride + n - 1]
+  int32_t D;
+  int64_t x_ld, x_row_stride;
+};
+// a row of the matrix as the kernel reads it: nothing else writes it — unless the kernel itself writes the pin back
+template <bool PIN> struct rows_row_ptr { typedef const float* __restrict__ type; };
+template <> struct rows_row_ptr<true> { typedef const float* type; };
+
 // n <= 1024: W waves per row, 4 / W rows per workgroup; thread gt of a row's group holds columns (and slots) 4 gt .. 4 gt + 3.
 // Every thread reaches every barrier (a group past the last row works on the last row again and writes nothing).
-template <int KIND, int W>
-__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
-k_rows_small(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld,
-             int64_t index_stride, float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out,
-             int32_t* __restrict__ anc, unsigned long long* __restrict__ status) {
+// PIN (the iid multinomial only): the thread that holds column n - 1 takes the pinned weight into its registers before the
+// row's maximum is reduced, writes it back into the matrix and answers n - 1 for slot n - 1 whatever the search found; the
+// row's group writes the D pinned state words.  No barrier and no LDS of its own; without PIN nothing of it is compiled.
+template <int KIND, int W, bool PIN>
+__device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ keys, typename rows_row_ptr<PIN>::type lw,
+                                                int64_t rows, int64_t n, int64_t ld, int64_t index_stride, float scale,
+                                                float* __restrict__ max_out, uint64_t* __restrict__ total_out,
+                                                int32_t* __restrict__ anc, unsigned long long* __restrict__ status,
+                                                const rows_pin& pin) {
   static_assert(W == 1 || W == 2 || W == 4, "waves per row");
+  static_assert(!PIN || KIND == GMX_RESAMPLE_MULTINOMIAL, "forcing a slot is a conditional draw under iid slots only");
   constexpr int RPW = 4 / W, GT = 64 * W;
   __shared__ float s_max[4];
   __shared__ uint64_t s_scan[4];
@@ -116,10 +147,27 @@ k_rows_small(const uint32_t* __restrict__ keys, const float* __restrict__ lw, in
   const int64_t r_ = (int64_t)blockIdx.x * RPW + grp;
   const bool live = r_ < rows;
   const int64_t r = live ? r_ : rows - 1;
-  const float* __restrict__ row = lw + r * ld;
+  typename rows_row_ptr<PIN>::type row = lw + r * ld;
   const int64_t base = (int64_t)gt * 4;
   float x[4];
+  float p = 0.0f;
+  float px = 0.0f;
+  if (PIN) {                                             // (issued ahead of the row's load: one wait for all of them)
+    p = pin.lw[r];
+    if (live && gt < pin.D) px = pin.x[(int64_t)gt * rows + r];
+  }
   pick_load4(row, base, n, x);
+  if (PIN && live) {                                     // the D state words, by the row's thread group
+    const int64_t at = r * pin.x_row_stride + n - 1;
+    if (gt < pin.D) pin.x_out[(int64_t)gt * pin.x_ld + at] = px;
+    for (int32_t d = gt + GT; d < pin.D; d += GT) pin.x_out[(int64_t)d * pin.x_ld + at] = pin.x[(int64_t)d * rows + r];
+  }
+  if (PIN && base <= n - 1 && n - 1 < base + 4) {        // the one thread of the group that holds column n - 1
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (base + c == n - 1) x[c] = p;
+    if (live) const_cast<float*>(lw)[r * ld + n - 1] = p;
+  }
   const float m = wave_max(gmx_rmax(gmx_rmax(x[0], x[1]), gmx_rmax(x[2], x[3])));
   if (lane == 0) s_max[wave] = m;
   __syncthreads();
@@ -166,9 +214,39 @@ k_rows_small(const uint32_t* __restrict__ keys, const float* __restrict__ lw, in
       i = rows_slot_search<KIND>(cdf, (int32_t)n, key, u0, base + c, total, D);
       i = i < (int32_t)n ? i : (int32_t)n - 1;
     }
+    if (PIN && base + c == n - 1) i = (int32_t)n - 1;    // slot n - 1 descends from slot n - 1 (its uniform is its own)
     out[c] = i + add;
   }
   rows_store4(anc + r * n, base, n, out);
+}
+
+template <int KIND, int W>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_small(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld,
+             int64_t index_stride, float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out,
+             int32_t* __restrict__ anc, unsigned long long* __restrict__ status) {
+  rows_small_body<KIND, W, false>(keys, lw, rows, n, ld, index_stride, scale, max_out, total_out, anc, status, rows_pin{});
+}
+
+// (`lw` is read and written: not __restrict__)
+template <int W>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_small_pinned(const uint32_t* __restrict__ keys, float* lw, int64_t rows, int64_t n, int64_t ld, int64_t index_stride,
+                    float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out, int32_t* __restrict__ anc,
+                    unsigned long long* __restrict__ status, rows_pin pin) {
+  rows_small_body<GMX_RESAMPLE_MULTINOMIAL, W, true>(keys, lw, rows, n, ld, index_stride, scale, max_out, total_out, anc,
+                                                     status, pin);
+}
+
+// n > 1024, pinned: the pins into the matrix and the state store before the row's statistics are taken.  blockIdx.x: 256
+// rows, blockIdx.y: the state word d < D, or (y = D) the weight.
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin pin) {
+  const int64_t r = (int64_t)blockIdx.x * GMX_ROWS_BLOCK + (int64_t)threadIdx.x;
+  if (r >= rows) return;
+  const int32_t d = (int32_t)blockIdx.y;
+  if (d == pin.D) lw[r * ld + n - 1] = pin.lw[r];
+  else pin.x_out[(int64_t)d * pin.x_ld + r * pin.x_row_stride + n - 1] = pin.x[(int64_t)d * rows + r];
 }
 
 // n > 1024: blockIdx.x the tile, blockIdx.y the row (row0 + y).  tmax / agg: k_pick_stats' [rows, n_tiles] statistics.
@@ -250,6 +328,8 @@ k_rows_tile(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int
 }
 
 // iid multinomial past one tile: slot j of row r searches the row's CDF array.  blockIdx.x: 256 slots, blockIdx.y: the row.
+// PIN: slot n - 1 answers n - 1 (gmx_resample_rows_pinned).
+template <bool PIN>
 __global__ void __launch_bounds__(GMX_ROWS_BLOCK)
 k_rows_mn(const uint32_t* __restrict__ keys, const uint64_t* __restrict__ cdf, int64_t n, int64_t row0, int64_t index_stride,
           const uint64_t* __restrict__ total_in, int32_t* __restrict__ anc) {
@@ -258,7 +338,7 @@ k_rows_mn(const uint32_t* __restrict__ keys, const uint64_t* __restrict__ cdf, i
   if (j >= n) return;
   const uint64_t total = total_in[r];
   int32_t i = (int32_t)n - 1;
-  if (total != 0ull) {
+  if (total != 0ull && !(PIN && j == n - 1)) {
     gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
     i = rows_slot_search<GMX_RESAMPLE_MULTINOMIAL>(cdf + r * n, (int32_t)n, key, 0ull, j, total, 0ull);
     i = i < (int32_t)n ? i : (int32_t)n - 1;
@@ -303,6 +383,25 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows(int kind, const ui
     const int32_t add = (int32_t)(r * index_stride);
     for (int64_t i = 0; i < n; ++i) out[i] += add;
   }
+  return 0;
+}
+
+// the definition, in order: the pins into the matrix and the store, the unconditional draw on the pinned weights, slot n - 1
+extern "C" __attribute__((used)) inline int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                                               int64_t index_stride, const float* pin_lw_d, const float* pin_x_d, float* x_d,
+                                               int32_t D, int64_t x_ld, int64_t x_row_stride, float* max_d, uint64_t* total_d,
+                                               int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d) return 1;
+  if (gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride)) return 1;
+  if (gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride)) return 1;
+  if (D > 0 && (!pin_x_d || !x_d)) return 1;
+  for (int64_t r = 0; r < rows; ++r) {
+    lw_d[r * ld + n - 1] = pin_lw_d[r];
+    for (int64_t d = 0; d < D; ++d) x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r];
+  }
+  if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
+                        status_d, workspace_d, stream)) return 1;
+  for (int64_t r = 0; r < rows; ++r) ancestors_d[r * n + n - 1] = (int32_t)(n - 1 + r * index_stride);
   return 0;
 }
 #endif

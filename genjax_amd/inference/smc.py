@@ -767,6 +767,40 @@ def resample_rows(kind, keys: Key, lw: torch.Tensor, index_stride: int = 0, *, o
     return anc, total, mx, cdf_shift(n), status
 
 
+def resample_rows_pinned(keys: Key, lw: torch.Tensor, pin_lw: torch.Tensor, pin_x=None, x=None, index_stride: int = 0,
+                         x_row_stride=None, *, out=None, workspace=None):
+    """gmx_resample_rows_pinned: the iid multinomial of resample_rows with slot n - 1 of every row pinned (conditional SMC).
+    lw [R, n] float32 (contiguous; column n - 1 is OVERWRITTEN with pin_lw [R]), pin_x [D, R] -> column r * x_row_stride +
+    n - 1 of every row of the struct-of-arrays store x [D, x_ld] (x_row_stride: n by default; pin_x = x = None: no
+    state).  Returns what resample_rows returns; ancestors[r, n - 1] = n - 1 + r * index_stride, the other slots are the
+    unconditional draw on the pinned weights, bit for bit."""
+    be = _lib.get()
+    R, n = lw.shape
+    kd = keys if isinstance(keys, torch.Tensor) else keys.data()
+    if (pin_x is None) != (x is None):
+        raise ValueError("resample_rows_pinned: pin_x and x come together (the retained states and the store they go into)")
+    D, x_ld = (0, 0) if x is None else (int(v) for v in x.shape)
+    if x is not None and tuple(pin_x.shape) != (D, R):
+        raise ValueError(f"resample_rows_pinned: pin_x is [D, R] = {(D, R)} for a store of {D} rows; got {tuple(pin_x.shape)}")
+    if tuple(pin_lw.shape) != (R,):
+        raise ValueError(f"resample_rows_pinned: pin_lw is [R] = {(R,)}; got {tuple(pin_lw.shape)}")
+    if out is None:
+        anc = torch.empty((R, n), dtype=torch.int32, device=lw.device)
+        total = torch.empty((R,), dtype=torch.int64, device=lw.device)
+        mx = torch.empty((R,), dtype=torch.float32, device=lw.device)
+        status = torch.zeros((1,), dtype=torch.int64, device=lw.device)
+    else:
+        anc, total, mx, status = out
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(MULTINOMIAL, R, n)) + 7) // 8,), dtype=torch.int64,
+                                device=lw.device)
+    be.check(be.c.gmx_resample_rows_pinned(be.ptr(kd), be.ptr(lw), R, n, n, int(index_stride), be.ptr(pin_lw), be.ptr(pin_x),
+                                           be.ptr(x), D, x_ld, n if x_row_stride is None else int(x_row_stride), be.ptr(mx),
+                                           be.ptr(total), be.ptr(anc), be.ptr(status), be.ptr(workspace), be.stream()),
+             "gmx_resample_rows_pinned")
+    return anc, total, mx, cdf_shift(n), status
+
+
 def _row_kind(kind, who):
     kind = _KINDS[kind] if isinstance(kind, str) else int(kind)
     if kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):
@@ -1977,8 +2011,18 @@ class BootstrapBank(_Sweep):
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
 
-    def prepare(self, keys: Key, ys: torch.Tensor):
+    def _key_tables(self, keys: Key):
+        """the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys (int32 words)"""
         from ..random import _derive_host
+        R, T = self.R, self.T
+        kh = np.asarray(keys.host(), dtype=np.uint32).reshape(R, 2)
+        prop, res = np.empty((T, R, 2), np.uint32), np.empty((T, R, 2), np.uint32)
+        for t in range(T):
+            ks = _derive_host(_derive_host(kh, np.uint64(t))[:, None, :], np.arange(3, dtype=np.uint64))
+            prop[t], res[t] = ks[:, 0], ks[:, 1]
+        return prop.view(np.int32), res.view(np.int32)
+
+    def prepare(self, keys: Key, ys: torch.Tensor):
         be = _lib.get()
         self._drop_graph()
         R, n, T = self.R, self.n, self.T
@@ -1993,14 +2037,9 @@ class BootstrapBank(_Sweep):
         self.keys = keys
         self._set_observations(ys)
         assert self.ys.numel() >= T
-        # the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys
-        kh = np.asarray(keys.host(), dtype=np.uint32).reshape(R, 2)
-        prop, res = np.empty((T, R, 2), np.uint32), np.empty((T, R, 2), np.uint32)
-        for t in range(T):
-            ks = _derive_host(_derive_host(kh, np.uint64(t))[:, None, :], np.arange(3, dtype=np.uint64))
-            prop[t], res[t] = ks[:, 0], ks[:, 1]
-        self.keys_prop = torch.from_numpy(prop.view(np.int32)).to(dev)
-        self.keys_res = torch.from_numpy(res.view(np.int32)).to(dev)
+        prop, res = self._key_tables(keys)
+        self.keys_prop = torch.from_numpy(prop).to(dev)
+        self.keys_res = torch.from_numpy(res).to(dev)
         self.lw = torch.zeros((N,), dtype=torch.float32, device=dev)
         self.anc = torch.zeros((R, n), dtype=torch.int32, device=dev)          # indices into the flat [R * n] store
         self.maxs = torch.zeros((T, R), dtype=torch.float32, device=dev)
@@ -2060,3 +2099,254 @@ class BootstrapBank(_Sweep):
         x = self.store.per_filter((self.T - 1) % 2, R, n)
         local = self.anc - (torch.arange(R, dtype=torch.int32, device=self.anc.device) * n).reshape(R, 1)
         return x, self.lw.reshape(R, n), local
+
+
+class ConditionalBank(BootstrapBank):
+    """R independent CONDITIONAL bootstrap particle filters of n particles each (conditional SMC, the kernel of particle
+    Gibbs: Andrieu, Doucet & Holenstein 2010) as one chain of launches: BootstrapBank's programs, stores and key schedule,
+    with slot n - 1 of every chain pinned to a retained trajectory — at every step t it holds the retained state
+    ref_x[t, :, r] and its observation weight ref_lw[t, r], and it always descends from slot n - 1; the other n - 1 slots
+    are resampled as usual (gmx_resample_rows_pinned: n <= 1024, one launch per step).  Every step is recorded
+    (gmx_history_record over the flat R * n particles), so a new trajectory per chain is one exact-integer draw from the
+    final weights (gmx_pick_rows) and one walk through the recorded ancestors (gmx_lineage).
+
+    Resampling is the iid multinomial, fixed: its slots are independent, so "draw the other slots as always, force the last
+    one" IS the conditional resampling distribution.  Forcing a slot of a systematic, stratified or ordered scheme is not
+    a valid conditional draw; those kinds are refused by name.
+
+    With nothing retained a sweep is, row for row and bit for bit, BootstrapBank(resample="multinomial") under the same
+    keys (plain gmx_resample_rows), recorded.
+
+      cb.prepare(keys, ys, retained=None)   keys (R,), ys [T]; every buffer is allocated here
+      cb.launch()                           one sweep (the captured graph when there is one)
+      traj = cb.draw(key)                   ONE key: one trajectory per chain from the last sweep
+      cb.retain()                           the last draw becomes the retained path (device copies, in place)
+      cb.rekey(keys)                        a new (R,) key batch into the existing key tables, in place
+      cb.set_retained(x_ref)                a caller's own path(s), in draw()'s layout; weights from the model
+      cb.run(key, ys, iters, retained=None) the particle-Gibbs driver: [iters, R, T, ...]
+
+    The recorded weight of a particle IS its observation weight under the same ys and params, so a retained path that came
+    from a sweep needs no model evaluation.  log_ml() with a retained path is the CONDITIONAL sweep's normaliser estimate
+    (the retained particle is in every step's sum), not the unbiased estimate of an unconditional filter.
+
+    capture() fixes the form (conditional or not): going from "nothing retained" to "retained" drops the graph; rekey()
+    and retain() on a captured conditional sweep only change buffer contents, which the graph reads when replayed.
+
+    Not here: ancestor sampling, rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations.
+    Memory: the history slabs take T * (D + 2) * R * n * 4 bytes."""
+
+    def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
+                 specialize=True, state_addr="x", state_sites=None, resample="multinomial"):
+        kind = _KINDS.get(resample, None) if isinstance(resample, str) else int(resample)
+        if kind != MULTINOMIAL:
+            name = resample if isinstance(resample, str) else next((k for k, v in _KINDS.items() if v == kind), resample)
+            raise NotImplementedError(f"ConditionalBank(resample={name!r}): forcing a slot is only a valid conditional draw "
+                                      "under iid multinomial resampling (resample=\"multinomial\", the only kind)")
+        super().__init__(init, step, n_particles, n_chains, T, obs_addr=obs_addr, resample="multinomial",
+                         step_extra=step_extra, params=params, specialize=specialize, state_addr=state_addr)
+        self.state_sites = None if state_sites is None else tuple(state_sites)
+        self.conditional = False
+
+    def prepare(self, keys: Key, ys: torch.Tensor, retained=None):
+        super().prepare(keys, ys)
+        be = _lib.get()
+        dev = be.device
+        R, n, T, D = self.R, self.n, self.T, self.store.D
+        N = R * n
+        self.D = D
+        self.conditional = False
+        self._last = None
+        # the retained path in gmx_lineage's own `traj` layout (m = R), and its observation weights
+        self.ref_x = torch.zeros((T, D, R), dtype=torch.float32, device=dev)
+        self.ref_lw = torch.zeros((T, R), dtype=torch.float32, device=dev)
+        # row t of each slab: step t's particles [D, N] / log-weights / FLAT ancestors (the resampling after step t)
+        self.hist_xs = torch.zeros((T, D, N), dtype=torch.float32, device=dev)
+        self.hist_lws = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        self.hist_ancs = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        self.hist_status = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.pick_ws = torch.zeros(((int(be.c.gmx_pick_rows_workspace(R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
+        self._views = SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state)
+        if retained is not None:
+            self.set_retained(retained)
+        return self
+
+    def _set_conditional(self, flag):
+        if bool(flag) != self.conditional:
+            self._drop_graph()             # a captured graph holds the launches of the other form
+            self.conditional = bool(flag)
+
+    def _resample(self, t):
+        if not self.conditional:
+            return super()._resample(t)
+        resample_rows_pinned(self.step_keys[t][1], self.lw.reshape(self.R, self.n), self.ref_lw[t], self.ref_x[t],
+                             self.store.rows[t % 2], index_stride=self.n, x_row_stride=self.n,
+                             out=(self.anc, self.totals[t], self.maxs[t], self.status), workspace=self.ws)
+
+    def enqueue(self):
+        """every launch of the sweep on the current stream, per step: the site program over the R * n particles,
+        gmx_resample_rows_pinned (nothing retained: gmx_resample_rows), gmx_history_record — in this order, so that the
+        record holds the pins and the next step's gather extends every child of slot n - 1 from the retained state.  No
+        syncs, no allocations, no host read of a device value."""
+        be = _lib.get()
+        N = self.R * self.n
+        self.status.zero_()
+        for t in range(self.T):
+            _mh, prog, leaves, key, bufs = self._programs(t)
+            bufs[prog.wo[1]] = self.lw.reshape(1, N)
+            prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
+            self._resample(t)
+            be.check(be.c.gmx_history_record(be.ptr(self.store.rows[t % 2]), self.D, be.ptr(self.lw), be.ptr(self.anc), N, 0,
+                                             be.ptr(self.hist_xs[t]), be.ptr(self.hist_lws[t]), be.ptr(self.hist_ancs[t]),
+                                             be.ptr(self.hist_status), be.stream()), "gmx_history_record")
+
+    def rekey(self, keys: Key):
+        """a new (R,) key batch: the proposal / resampling key tables are rewritten IN PLACE (BootstrapBank.prepare's
+        derivation), so a captured graph replays under the new keys"""
+        if tuple(keys.shape) != (self.R,):
+            raise ValueError(f"ConditionalBank.rekey: {self.R} chains need keys of shape {(self.R,)}, got {tuple(keys.shape)}")
+        prop, res = self._key_tables(keys)
+        self.keys_prop.copy_(torch.from_numpy(prop))
+        self.keys_res.copy_(torch.from_numpy(res))
+        self.keys = keys
+        return self
+
+    def draw(self, key: Key):
+        """One trajectory per chain from the last sweep (synchronises): k[r] = gmx_pick_rows of chain r's final log-weights
+        under split(key, R)[r]; one gmx_lineage walk from the flat indices k + r * n through the recorded ancestors.
+        Returns SweepHistory.trajectories()' layout — [R, T], [R, T, D] or a tuple of [R, T] — and keeps the trajectories
+        and the recorded weights along them for retain()."""
+        if tuple(key.shape) != ():
+            raise ValueError("ConditionalBank.draw takes ONE key")
+        be = _lib.get()
+        dev = self.hist_xs.device
+        R, n, T, D = self.R, self.n, self.T, self.D
+        k = torch.empty((R,), dtype=torch.int32, device=dev)
+        status = torch.zeros((2,), dtype=torch.int64, device=dev)       # rows without mass; indices outside the history
+        lw_last = self.hist_lws[T - 1]
+        be.check(be.c.gmx_pick_rows(be.ptr(split(key, R).data()), be.ptr(lw_last), R, n, n, be.ptr(k), be.ptr(status[0:]),
+                                    be.ptr(self.pick_ws), be.stream()), "gmx_pick_rows")
+        start = (k + torch.arange(R, dtype=torch.int32, device=dev) * n).contiguous()
+        paths = torch.empty((T, R), dtype=torch.int32, device=dev)
+        traj = torch.empty((T, D, R), dtype=torch.float32, device=dev)
+        be.check(be.c.gmx_lineage(be.ptr(self.hist_ancs), be.ptr(self.hist_xs), T, D, R * n, be.ptr(start), R, be.ptr(paths),
+                                  be.ptr(traj), be.ptr(status[1:]), be.stream()), "gmx_lineage")
+        lw_path = self.hist_lws.gather(1, paths.long())
+        empty, bad = (int(v) for v in status.tolist())
+        if empty:
+            raise FloatingPointError(f"ConditionalBank.draw: the final weights of {empty} of the {R} chains carry no mass")
+        if bad or int(self.hist_status.item()):
+            raise IndexError(f"ConditionalBank.draw: {bad} index(es) outside [0, {R * n}) on the walk through the recorded "
+                             "ancestors: they were clamped, nothing outside the history was read")
+        self._last = (traj, lw_path, paths, k)
+        return self._views._state_view(traj, 1)
+
+    def retain(self):
+        """the last draw() becomes the retained path: two device copies into ref_x / ref_lw, in place"""
+        if self._last is None:
+            raise RuntimeError("ConditionalBank.retain: nothing drawn yet (draw(key) after a launch())")
+        self._set_conditional(True)
+        self.ref_x.copy_(self._last[0])
+        self.ref_lw.copy_(self._last[1])
+        return self
+
+    def _paths_to_rows(self, x_ref):
+        """a path per chain in draw()'s layout -> [T, D, R]"""
+        R, T, D = self.R, self.T, self.D
+        dev = self.ref_x.device
+        if self.tuple_state is not None:
+            ok = isinstance(x_ref, (tuple, list)) and len(x_ref) == D and all(tuple(torch.as_tensor(v).shape) == (R, T) for v in x_ref)
+            want = f"a {self.tuple_state.__name__} of {D} arrays of shape {(R, T)}"
+            rows = (lambda: torch.stack([torch.as_tensor(v).to(dev).float().t() for v in x_ref], dim=1))
+        elif not self.event:
+            ok = not isinstance(x_ref, (tuple, list)) and tuple(torch.as_tensor(x_ref).shape) == (R, T)
+            want = f"an array of shape {(R, T)}"
+            rows = (lambda: torch.as_tensor(x_ref).to(dev).float().t().reshape(T, 1, R))
+        else:
+            ok = not isinstance(x_ref, (tuple, list)) and tuple(torch.as_tensor(x_ref).shape) == (R, T, D)
+            want = f"an array of shape {(R, T, D)}"
+            rows = (lambda: torch.as_tensor(x_ref).to(dev).float().permute(1, 2, 0))
+        if not ok:
+            got = [tuple(torch.as_tensor(v).shape) for v in x_ref] if isinstance(x_ref, (tuple, list)) else \
+                tuple(torch.as_tensor(x_ref).shape)
+            raise ValueError(f"ConditionalBank.set_retained: the retained paths are {want} (R chains, T steps: draw()'s "
+                             f"layout); got {got}")
+        return rows().contiguous()
+
+    def set_retained(self, x_ref):
+        """A caller's own retained path per chain, in draw()'s layout.  Its weights come from the model, at set-up time (one
+        launch of R particles per step, none of it in the sweep): ref_lw[t] is the OBSERVATION site's score of step t's
+        model — init for t = 0, else step called with (x_ref[t-1], *step_extra(t), *params) — constrained on the state
+        sites and the observation (importance, then project on obs_addr; not the importance weight, which also holds the
+        transition density).  state_sites (the constructor's): the address of each state component, in order; default
+        (state_addr,), required for D > 1.  The model may have no latent site besides them and the observation."""
+        from ..core.choice_map import Selection
+        from ..random import key as _key
+        if not hasattr(self, "ref_x"):
+            raise RuntimeError("ConditionalBank.set_retained: prepare(keys, ys) first")
+        R, T, D = self.R, self.T, self.D
+        sites = self.state_sites
+        if sites is None:
+            if D > 1:
+                raise NotImplementedError("ConditionalBank.set_retained: a state of more than one component needs "
+                                          "state_sites= (the address of each component, in order)")
+            sites = (self.state_addr,)
+        if len(sites) != D:
+            raise ValueError(f"ConditionalBank.set_retained: state_sites names {len(sites)} addresses for a state of {D} "
+                             "components")
+        rows = self._paths_to_rows(x_ref)
+        dev = rows.device
+        params = tuple(torch.as_tensor(p).to(dev).float() for p in self.params)
+        keys = split(_key(0), R)                   # (nothing is left to draw)
+        sel = Selection.at[self.obs_addr]
+        ref_lw = torch.empty((T, R), dtype=torch.float32, device=dev)
+        for t in range(T):
+            con = self._obs(t)
+            for d, a in enumerate(sites):
+                con = con.set(a, rows[t, d])
+            if t == 0:
+                model, args = self.init, params
+            else:
+                prev = self._views._state_view(rows[t - 1:t], 0)
+                prev = type(prev)(v[0] for v in prev) if self.tuple_state is not None else prev[0]
+                model, args = self.step, (prev,) + tuple(self.step_extra(t)) + params
+            tr, _w = model.importance(keys, con, args)
+            extra = [a for a in tr.subtraces if a not in sites and a != self.obs_addr]
+            if extra:
+                raise NotImplementedError(
+                    f"ConditionalBank.set_retained: the {'init' if t == 0 else 'step'} model samples {extra[0]!r}, which is "
+                    f"neither one of the state's sites {tuple(sites)!r} nor the observation {self.obs_addr!r}: the retained "
+                    "path does not say what it was")
+            ref_lw[t] = engine.materialize(model.project(keys, tr, sel)).reshape(R)
+        self._set_conditional(True)
+        self.ref_x.copy_(rows)
+        self.ref_lw.copy_(ref_lw)
+        return self
+
+    def run(self, key: Key, ys=None, iters: int = 1, retained=None):
+        """The particle-Gibbs driver: `iters` conditional sweeps, each followed by a draw that becomes the next sweep's
+        retained path.  Schedule (build-defined, as the sweeps' key schedules are): for k = 0 .. iters - 1
+
+            (k_sweep, k_draw) = split(fold_in(key, k), 2)
+            rekey(split(k_sweep, R)); launch(); draw(k_draw); retain()
+
+        With nothing retained (no `retained`, no earlier retain() / set_retained()) iteration 0 is an unconditional sweep.
+        ys given: the bank is prepared for it first (prepare(split(key, R), ys, retained)); ys = None keeps a prepared bank
+        — its observations, its retained path and its captured graph.  Returns the stacked draws: [iters, R, T],
+        [iters, R, T, D] or a tuple of [iters, R, T]."""
+        if tuple(key.shape) != ():
+            raise ValueError("ConditionalBank.run takes ONE key")
+        if ys is not None:
+            self.prepare(split(key, self.R), ys, retained)
+        elif retained is not None:
+            self.set_retained(retained)
+        out = []
+        for k in range(int(iters)):
+            ks = split(fold_in(key, k), 2)
+            self.rekey(split(ks[0], self.R))
+            self.launch()
+            x = self.draw(ks[1])
+            self.retain()
+            out.append(x)                  # (views of this draw's own buffer)
+        if self.tuple_state is not None:
+            return self.tuple_state(torch.stack([o[d] for o in out]) for d in range(self.D))
+        return torch.stack(out)

@@ -656,6 +656,29 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
  *                   ld >= n elements apart and may start at any 4-byte boundary; element offsets are 64-bit.
  *                   Limits: 1 <= rows < 2^31, 1 <= n <= 2^21; workspace_d: gmx_resample_rows_workspace(kind, rows, n)
  *                   bytes, 8-byte aligned, contents irrelevant on entry.
+ *   gmx_resample_rows_pinned   (additive, ABI still v8.  Reference call site: none of its own — conditional SMC over a
+ *                   Scan model, vmapped over chains: the resampling step of particle Gibbs, Andrieu, Doucet & Holenstein
+ *                   2010.)  The iid multinomial of gmx_resample_rows with slot n - 1 of every row pinned to a retained
+ *                   particle.  For every row r, in this order:
+ *                     1. lw_d[r * ld + n - 1] = pin_lw_d[r]  (WRITTEN BACK: the caller's log-weights hold the pin);
+ *                     2. d < D: x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r]  (the retained state into
+ *                        a struct-of-arrays [D, x_ld] store whose row r starts x_row_stride columns after row r - 1);
+ *                     3. max_d, total_d, status_d and ancestors_d are exactly gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL,
+ *                        ...) on the matrix after step 1;
+ *                     4. except ancestors_d[r * n + n - 1] = (n - 1) + r * index_stride, always (a row without mass
+ *                        included, where every slot is n - 1 anyway).
+ *                   Slot n - 1's uniform stays its own (uniforms are counter-based: slot j draws bits32(keys[r], j)), so
+ *                   the other n - 1 slots are bit for bit the unconditional draw on the pinned weights; iid slots are
+ *                   independent, which is what makes the forced slot an exact conditional draw — there is no pinned form of
+ *                   the systematic / stratified / ordered kinds.  No other word of lw_d (the padding between rows
+ *                   included) or of x_d is written.  A pinned weight of -inf or NaN is any other column's; status_d
+ *                   counts the rows whose total is 0.  n <= 1024: still ONE launch (the thread that holds column n - 1
+ *                   substitutes the pin in its registers before the row's maximum is reduced; no barrier, no LDS added).
+ *                   n > 1024: one small launch that writes the pins, then gmx_resample_rows' three.
+ *                   Limits: those of gmx_resample_rows (1 <= rows < 2^31, 1 <= n <= 2^21, ld >= n, the index_stride rule);
+ *                   0 <= D <= 65533; with D > 0: x_row_stride >= 0, n <= x_ld < 2^46, x_ld >= (rows - 1) * x_row_stride + n,
+ *                   pin_x_d and x_d not null (both are ignored when D = 0); every pointer aligned to its element;
+ *                   workspace_d: gmx_resample_rows_workspace(GMX_RESAMPLE_MULTINOMIAL, rows, n) bytes.
  * A null pointer or an out-of-range size returns non-zero before anything is launched.
  * ---------------------------------------------------------------------- */
 size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
@@ -667,6 +690,12 @@ int gmx_resample_rows(int kind, const uint32_t* keys_d /* [rows, 2] */, const fl
                       int64_t ld /* elements between rows, >= n */, int64_t index_stride, float* max_d /* [rows] */,
                       uint64_t* total_d /* [rows] */, int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [1] */,
                       void* workspace_d, gmx_stream stream);
+int gmx_resample_rows_pinned(const uint32_t* keys_d /* [rows, 2] */, float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                             int64_t index_stride, const float* pin_lw_d /* [rows] */,
+                             const float* pin_x_d /* [D, rows], null iff D = 0 */, float* x_d /* [D, x_ld], null iff D = 0 */,
+                             int32_t D, int64_t x_ld, int64_t x_row_stride,
+                             float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
+                             void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —

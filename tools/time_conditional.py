@@ -1,0 +1,153 @@
+"""What pinning a slot costs.  JSON lines, appended to --out:
+
+  pinned_rows   (rows, n) in {(1024, 256), (256, 1024), (64, 4096)}, D in {1, 3}: gmx_resample_rows_pinned against
+                gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL) on the same weights, alternated: the median and the min / max
+                of --reps windows after a warm-up.  With --parent-lib the unpinned call is ALSO timed from that library (a
+                build of the commit before the pinned entry point existed): the kernel as it was.  The pinned call's
+                unpinned slots are asserted equal to the unpinned call's on the pinned weights.
+  sweep         ConditionalBank(R = 1024, n = 256, T = 100) on the LGSSM with a retained path, captured, against the
+                captured BootstrapBank(resample="multinomial") of the same shape (which records no history), and against
+                the ConditionalBank with nothing retained (which does)
+
+Clocks as found; a host clock around work that ends in a device synchronise.  Environment: SHAPES ("rows:n,..."), BR, BN,
+BT.  Needs the MI355X: there is no CPU path."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+import genjax_amd as G
+from genjax_amd import _lib, workloads
+from genjax_amd.inference import smc
+from genjax_amd.random import split
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--label", default="")
+ap.add_argument("--skip-sweep", action="store_true")
+ap.add_argument("--parent-lib", default="", help="a build of the library without the pinned entry point")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_time_conditional.jsonl"))
+args = ap.parse_args()
+assert torch.cuda.is_available(), "tools/time_conditional.py measures on the GPU only"
+be = _lib.get()
+dev = be.device
+common = {"label": args.label, "reps": args.reps, "device": torch.cuda.get_device_name(0),
+          "library": os.path.basename(_lib.LIB_PATH)}
+parent = None
+if args.parent_lib:
+    parent = ctypes.CDLL(args.parent_lib)
+    parent.gmx_resample_rows.argtypes = be.c.gmx_resample_rows.argtypes
+    assert not hasattr(parent, "gmx_resample_rows_pinned"), "--parent-lib has the pinned entry point: not the parent's build"
+
+
+def timed(fn, launches=1):
+    """seconds per call over a window of `launches` back-to-back calls"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(launches):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / launches
+
+
+def spread(ts, scale=1e3):
+    return {"median": scale * statistics.median(ts), "min": scale * min(ts), "max": scale * max(ts)}
+
+
+def emit(rec):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as fh:
+        fh.write(line + "\n")
+
+
+# ---- (a) the kernel -------------------------------------------------------------------------------------------------------
+shapes = [tuple(int(v) for v in s.split(":")) for s in os.environ.get("SHAPES", "1024:256,256:1024,64:4096").split(",")]
+kind = smc.MULTINOMIAL
+for rows, n in shapes:
+    for D in (1, 3):
+        gen = torch.Generator(device="cuda").manual_seed(11)
+        lw = torch.randn((rows, n), device=dev, generator=gen) * 3.0
+        pin_lw = torch.randn((rows,), device=dev, generator=gen)
+        pin_x = torch.randn((D, rows), device=dev, generator=gen)
+        x = torch.zeros((D, rows * n), device=dev)
+        keys_d = split(G.key(7), rows).data()
+        anc_p, anc_u, anc_o = (torch.empty((rows, n), dtype=torch.int32, device=dev) for _ in range(3))
+        mx = torch.empty((rows,), dtype=torch.float32, device=dev)
+        tot = torch.empty((rows,), dtype=torch.int64, device=dev)
+        status = torch.zeros((1,), dtype=torch.int64, device=dev)
+        ws = torch.empty(((be.c.gmx_resample_rows_workspace(kind, rows, n) + 7) // 8,), dtype=torch.int64, device=dev)
+        P, st = be.ptr, be.stream()
+
+        def pinned():
+            be.check(be.c.gmx_resample_rows_pinned(P(keys_d), P(lw), rows, n, n, n, P(pin_lw), P(pin_x), P(x), D, rows * n, n,
+                                                   P(mx), P(tot), P(anc_p), P(status), P(ws), st), "gmx_resample_rows_pinned")
+
+        def plain():
+            be.check(be.c.gmx_resample_rows(kind, P(keys_d), P(lw), rows, n, n, n, P(mx), P(tot), P(anc_u), P(status), P(ws), st),
+                     "gmx_resample_rows")
+
+        def plain_parent():
+            rc = parent.gmx_resample_rows(kind, P(keys_d), P(lw), rows, n, n, n, P(mx), P(tot), P(anc_o), P(status), P(ws), st)
+            assert rc == 0, "the parent library refused the call"
+
+        forms = {"pinned": pinned, "plain": plain}
+        if parent is not None:
+            forms["plain_parent"] = plain_parent
+        for f in forms.values():                    # (the pinned call first: the others then see the pinned weights)
+            f()
+        torch.cuda.synchronize()
+        assert torch.equal(anc_p[:, :n - 1], anc_u[:, :n - 1]), "the unpinned slots differ from the unconditional draw"
+        assert parent is None or torch.equal(anc_u, anc_o), "this build's and the parent's gmx_resample_rows disagree"
+        assert int(status.item()) == 0
+        per_window = max(10, min(2000, int(0.05 / max(timed(pinned, 10), 1e-7))))       # ~50 ms of calls per window
+        ts = {name: [] for name in forms}
+        for _ in range(args.reps):                  # alternated: every form sees the same neighbours on the machine
+            for name, f in forms.items():
+                ts[name].append(timed(f, per_window))
+        med = {name: statistics.median(v) for name, v in ts.items()}
+        emit(dict(common, tool="time_conditional", what="pinned_rows", rows=rows, n=n, D=D, calls_per_window=per_window,
+                  launches_pinned=1 if n <= 1024 else 4, launches_plain=1 if n <= 1024 else 3,
+                  us={name: spread(v, 1e6) for name, v in ts.items()},
+                  pinned_over_plain=med["pinned"] / med["plain"],
+                  pinned_over_plain_parent=(med["pinned"] / med["plain_parent"]) if parent is not None else None,
+                  unpinned_slots_equal=True))
+        del lw, x, anc_p, anc_u, anc_o
+
+# ---- (b) the sweep ----------------------------------------------------------------------------------------------------------
+if not args.skip_sweep:
+    R, n, T = int(os.environ.get("BR", 1024)), int(os.environ.get("BN", 256)), int(os.environ.get("BT", 100))
+    init, step = workloads.make_lgssm(G)
+    ys = torch.from_numpy(workloads.lgssm_data(T))
+    keys = split(G.key(314159), R)
+    bank = smc.BootstrapBank(init, step, n, R, T, resample="multinomial").prepare(keys, ys).capture()
+    free = smc.ConditionalBank(init, step, n, R, T).prepare(keys, ys).capture()
+    cond = smc.ConditionalBank(init, step, n, R, T).prepare(keys, ys)
+    cond.launch()
+    cond.draw(G.key(1))
+    cond.retain()
+    cond.capture()
+    forms = {"bootstrap_bank": bank.launch, "conditional_nothing_retained": free.launch, "conditional": cond.launch}
+    for f in forms.values():
+        f()
+    torch.cuda.synchronize()
+    assert (bank.log_ml() == free.log_ml()).all(), "nothing retained: the bank and the conditional bank disagree"
+    ts = {name: [] for name in forms}
+    for _ in range(args.reps):
+        for name, f in forms.items():
+            ts[name].append(timed(f, 3))
+    med = {name: statistics.median(v) for name, v in ts.items()}
+    emit(dict(common, tool="time_conditional", what="sweep", R=R, n=n, T=T, ms={name: spread(v) for name, v in ts.items()},
+              us_per_step={name: 1e6 * m / T for name, m in med.items()},
+              conditional_over_bank=med["conditional"] / med["bootstrap_bank"],
+              conditional_over_nothing_retained=med["conditional"] / med["conditional_nothing_retained"],
+              note="the bootstrap bank records no history; both conditional forms add one gmx_history_record per step",
+              history_bytes=T * (cond.D + 2) * R * n * 4))
