@@ -9,6 +9,10 @@ The `wrt` nodes are treated as independent inputs: propagation stops at them.  I
 ops, comparisons and table indices carry no gradient.  Density ops differentiate in closed form:
   L_NORMAL(x; m, s):  z = x/s - m/s;  d/dx = -z/s,  d/dm = z/s,  d/ds = (z*z - 1)/s
 (the derivative of TFP's  -0.5*squared_difference(x/s, m/s) - log s - 0.5*log(2 pi)).
+
+Where a derivative is a convention it is jax.grad's: abs'(+-0) = 0, maximum / minimum at a tie give each argument half,
+d pow(x, y) / d y = 0 at x = 0 < y.  One deliberate difference: L_FLIP forms only the term of the observed outcome, so its
+gradient is finite wherever its density is (jax.grad gives 0 * inf = NaN at p = 1 observed True); DESIGN.md section 3.
 """
 from __future__ import annotations
 
@@ -74,6 +78,18 @@ def grad(out: Expr, wrt: list) -> list:
     return [adj.get(w.node.idx, zero) for w in wrt]
 
 
+# ops with a derivative rule in _rule (LOOPVAR: in grad itself) ...
+DIFFERENTIABLE = frozenset({
+    "MOV", "ADD", "SUB", "MUL", "DIV", "NEG", "ABS", "EXP", "LOG", "LOG1P", "SQRT", "SQUARE", "RECIP", "SIN", "COS", "TANH",
+    "SIGMOID", "SOFTPLUS", "POW", "MIN", "MAX", "SEL", "L_NORMAL", "L_BERNL", "L_FLIP", "L_UNIFORM", "LOOPVAR"})
+# ... and the ops through which no gradient flows, by NAME: roundings, conversions, loads, comparisons, logic and integer
+# arithmetic.  Every other op (LGAMMA, L_BETA, the samplers, ...) raises NotDifferentiable.
+ZERO_GRADIENT = frozenset({
+    "FLOOR", "CEIL", "ROUND", "I2F", "F2I", "LDTAB", "LDIN", "LDINX", "UNI", "CONST", "LDIDX", "LDT",
+    "FLT", "FLE", "FGT", "FGE", "FEQ", "FNE", "IEQ", "INE", "ILT", "ILE", "IGT", "IGE",
+    "AND", "OR", "NOT", "XOR", "IADD", "ISUB", "IMUL", "INEG"})
+
+
 def _rule(n, a, push):
     op = n.op
     E = lambda node: Expr(node)
@@ -90,9 +106,9 @@ def _rule(n, a, push):
         push(n.args[0], a / y); push(n.args[1], -(a * E(n)) / y)
     elif op == "NEG":
         push(n.args[0], -a)
-    elif op == "ABS":
+    elif op == "ABS":                  # a * sign(x): 0 at +0 and -0, NaN at NaN (jax.grad's rule)
         x = E(n.args[0])
-        push(n.args[0], T.where(x < 0.0, -a, a))
+        push(n.args[0], T.where(x > 0.0, a, T.where(x < 0.0, -a, a * (x * 0.0))))
     elif op == "EXP":
         push(n.args[0], a * E(n))
     elif op == "LOG":
@@ -118,11 +134,14 @@ def _rule(n, a, push):
     elif op == "POW":
         x, y = E(n.args[0]), E(n.args[1])
         push(n.args[0], a * (y * T.power(x, y - 1.0)))
-        push(n.args[1], a * (E(n) * T.unary("LOG")(x)))
-    elif op in ("MIN", "MAX"):
+        # d/dy = x^y log x, with log(0) replaced by log(1): 0 at x = 0, y > 0 where the limit is 0 (jax's replace_zero)
+        push(n.args[1], a * (E(n) * T.unary("LOG")(T.where(x == 0.0, 1.0, x))))
+    elif op in ("MIN", "MAX"):         # at an exact tie each argument gets half the adjoint (jax's balanced rule)
         x, y = E(n.args[0]), E(n.args[1])
         first = (x < y) if op == "MIN" else (x > y)
-        push(n.args[0], T.where(first, a, 0.0)); push(n.args[1], T.where(first, 0.0, a))
+        tie, half = x == y, a * 0.5
+        push(n.args[0], T.where(first, a, T.where(tie, half, 0.0)))
+        push(n.args[1], T.where(first, 0.0, T.where(tie, half, a)))
     elif op == "SEL":
         c, x, y = n.args
         push(x, T.where(E(c), a, 0.0)); push(y, T.where(E(c), 0.0, a))
@@ -135,17 +154,16 @@ def _rule(n, a, push):
     elif op == "L_BERNL":              # x*l - softplus(l):  d/dl = x - sigmoid(l)
         x, l = n.args
         push(l, a * (T.as_float(E(x)) - T.unary("SIGMOID")(E(l))))
-    elif op == "L_FLIP":               # x log p + (1-x) log(1-p)
-        x, p = n.args
-        xf, pf = T.as_float(E(x)), E(p)
-        push(p, a * (xf / pf - (1.0 - xf) / (1.0 - pf)))
+    elif op == "L_FLIP":               # x log p + (1-x) log(1-p): only the live term is formed (at p = 1, x = True the
+        x, p = n.args                  # other one is 0/0), so the gradient is finite wherever the density is
+        pf = E(p)
+        push(p, T.where(E(x), a / pf, -(a / (1.0 - pf))))
     elif op == "L_UNIFORM":
         x, lo, hi = (E(v) for v in n.args)
         inside = T.where((x >= lo), 1.0, 0.0) * T.where((x <= hi), 1.0, 0.0)
         w = hi - lo
         push(n.args[1], a * (inside / w)); push(n.args[2], -(a * (inside / w)))
-    elif op in ("FLOOR", "CEIL", "ROUND", "I2F", "F2I", "LDTAB", "LDIN", "UNI", "CONST", "LDIDX") or \
-            op.startswith(("F", "I")) and op not in ("FLOOR",) or op in ("AND", "OR", "NOT", "XOR"):
+    elif op in ZERO_GRADIENT:
         return                          # piecewise constant / not a float function of its inputs
     else:
         raise NotDifferentiable(f"no derivative rule for {op}")
@@ -159,8 +177,10 @@ _VG_CACHE = _new_program_cache()
 
 def value_and_grad(fn):
     """`value_and_grad(fn)(*xs)`: xs are float tensors of one common batch shape; returns
-    (fn(*xs), (d fn / d x_k for each k)) computed per element in ONE launch."""
+    (fn(*xs), (d fn / d x_k for each k)) computed per element in ONE launch.  Every result is a float32 tensor of the
+    batch shape on the backend's device, a gradient that folds to a constant (d (a + b) / d b) included."""
     def run(*xs):
+        import torch
         from . import _lib
         from .engine import Compiled, Flat, Tracing, leaf_spec, resolve
         from .static import _fnkey
@@ -183,6 +203,11 @@ def value_and_grad(fn):
             _VG_CACHE[ck] = ent
         comp, oo, go = ent
         outs = comp.run(flat.leaves, batch, None)
-        _lib.get()
-        return resolve(oo, outs, flat.leaves), tuple(resolve(g, outs, flat.leaves) for g in go)
+        dev = _lib.get().device
+
+        def tensor(v):
+            if isinstance(v, torch.Tensor):
+                return v
+            return torch.full(batch, float(v), dtype=torch.float32, device=dev)
+        return tensor(resolve(oo, outs, flat.leaves)), tuple(tensor(resolve(g, outs, flat.leaves)) for g in go)
     return run

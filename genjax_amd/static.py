@@ -373,18 +373,26 @@ def _fnkey(fn):
     code = getattr(fn, "__code__", None)
     if code is None:
         return ("id", id(fn))
+    def token(v, holder):
+        try:
+            hash(v)
+            return v
+        except Exception:
+            return ("id", id(holder))
+
     cells = ()
     if fn.__closure__:
         vals = []
         for c in fn.__closure__:
             try:
-                v = c.cell_contents
-                hash(v)
-                vals.append(v)
-            except Exception:
+                vals.append(token(c.cell_contents, c))
+            except ValueError:                 # an empty cell
                 vals.append(("id", id(c)))
         cells = tuple(vals)
-    return ("fn", code, cells)
+    # the values bound as defaults are as much part of the function as its closure cells (`lambda a, ev=ev: ...` in a loop)
+    defaults = tuple(token(v, v) for v in (getattr(fn, "__defaults__", None) or ()))
+    kwdefaults = tuple((k, token(v, v)) for k, v in sorted((getattr(fn, "__kwdefaults__", None) or {}).items()))
+    return ("fn", code, cells, defaults, kwdefaults)
 
 
 class _ReqSpec:
