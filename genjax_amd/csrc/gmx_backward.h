@@ -10,25 +10,14 @@
 // Under hipcc: the two kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a
 // plain host compiler: the two ENTRY POINTS, the draw as a sequential loop over rows calling gmx_weight_cdf and
 // gmx_ancestors (both declared in genmi.h and exported by a CPU build of the C-ABI; gmx_vm.h includes this file there).
-// That loop validates its arguments as the HIP entry point does but leaves no message.
+// That loop validates its arguments as the HIP entry point does and leaves its message (gmx_sizes.h: the checks, gmx_fail).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
 
-#define GMX_PICK_TILE 1024             /* = RS_TILE: one definition tile of the CDF */
+#include "gmx_sizes.h"                 /* gmx_pick_rows_bytes_, gmx_pick_rows_shift_, gmx_pick_rows_refusal_ */
 
-// workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
-static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
-  if (rows < 1 || n < 1) return 16;
-  const uint64_t cells = (uint64_t)rows * (uint64_t)((n + GMX_PICK_TILE - 1) / GMX_PICK_TILE);
-  return (size_t)((cells * 12u + 15u) & ~(uint64_t)15u);
-}
-// shift = 62 - ceil(log2 n): a sum of n terms <= 2^shift stays below 2^62 (smc.cdf_shift)
-static inline int gmx_pick_rows_shift_(int64_t n) {
-  int need = 0;
-  while (((int64_t)1 << need) < n) ++need;
-  return 62 - need;
-}
+#define GMX_PICK_TILE GMX_TILE          /* one definition tile of the CDF */
 
 #if defined(__HIPCC__)
 #include "gmx_resample.h"              /* gmx_block.h, gmx_rng.h, u128 / mul64 */
@@ -172,8 +161,9 @@ extern "C" __attribute__((used)) inline size_t gmx_pick_rows_workspace(int64_t r
 
 extern "C" __attribute__((used)) inline int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
                                     int32_t* out_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !logits_d || !out_d || !status_d || !workspace_d) return 1;
-  if (rows < 1 || rows > 0x7fffffffLL || n < 1 || n > 0x7fffffffLL || ld < n) return 1;
+  if (!keys_d || !logits_d || !out_d || !status_d || !workspace_d) return gmx_fail("%s: null argument", "gmx_pick_rows", 0);
+  const gmx_refusal no = gmx_pick_rows_refusal_(rows, n, ld);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_pick_rows", no.v);
   const int shift = gmx_pick_rows_shift_(n);
   std::vector<uint64_t> cdf((size_t)n);
   std::vector<float> row((size_t)n);                             // (gmx_weight_cdf may ask for an aligned row)

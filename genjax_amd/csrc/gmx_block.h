@@ -15,6 +15,17 @@
 #define GMX_CHAIN_PRIO 2
 #define GMX_SETPRIO __builtin_amdgcn_s_setprio(GMX_CHAIN_PRIO);
 #include "gmx_math.h"
+// The two tile constants of gmx_sizes.h that device code needs.  That header is host code and is not embedded for hiprtc,
+// so a specialised kernel takes them from here; the hipcc build holds the two statements together.
+#define GMX_RTC_TILE 1024
+#define GMX_RTC_MAX_TILES 2048
+#if !defined(__HIPCC_RTC__)
+#include "gmx_sizes.h"
+static_assert(GMX_TILE == GMX_RTC_TILE && GMX_MAX_TILES == GMX_RTC_MAX_TILES, "gmx_block.h restates gmx_sizes.h for hiprtc");
+#else
+#define GMX_TILE GMX_RTC_TILE
+#define GMX_MAX_TILES GMX_RTC_MAX_TILES
+#endif
 
 #define GMX_BLOCK 256
 #define GMX_WAVE 64
@@ -129,10 +140,9 @@ __device__ __forceinline__ uint64_t weight_fixed(float lw, float ref, float scal
 // P_b = sum_{b' < b} A_b' >> (K - k_b'), and the total.  Thread t owns the `per` consecutive tiles [t per, (t+1) per)
 // (per = ceil(tiles / 256): 1 .. 8): a running sum in registers, one u64 wave scan, three wave offsets.
 // Every thread of the workgroup reaches both barriers.  lds: >= 4 floats and 4 u64.
-#define GMX_TP_MAX_TILES 2048
+#define GMX_TP_MAX_TILES GMX_MAX_TILES
 #define GMX_TP_PER_MAX (GMX_TP_MAX_TILES / GMX_BLOCK)
-// layout of the block (u64 words): [0, tiles) prefixes | [tiles] total | [tiles + 1] M, K | pad to a multiple of 16
-GMX_HD size_t gmx_tile_prefix_words_(int64_t n) { return (size_t)(((n + 1023) / 1024 + 2 + 15) / 16) * 16; }
+// (the layout of the block it writes: gmx_sizes.h, gmx_tile_prefix_words_)
 __device__ __forceinline__ void gmx_tile_prefix_block(const float* tmax, const uint64_t* agg, int n_tiles,
                                                       uint64_t* pref, float* lds4, uint64_t* lds8) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;

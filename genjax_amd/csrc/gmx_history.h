@@ -6,7 +6,7 @@
 // among those embedded for hiprtc).  Under a plain host compiler: the two ENTRY POINTS as sequential loops — the
 // statement of what the kernels compute that a CPU build of the C-ABI from these headers (gmx_vm.h includes this file
 // there) exports, so host logic that records and walks a history can run without a device.  Those loops validate their
-// arguments as the HIP entry points do but leave no message (a host build owns its own error string).
+// arguments as the HIP entry points do and leave their message (gmx_sizes.h: the checks, gmx_fail).
 #pragma once
 #include <stdint.h>
 
@@ -143,14 +143,15 @@ k_lineage(const int32_t* __restrict__ anc, const float* __restrict__ xs, int32_t
 #elif defined(__cplusplus) && !defined(__HIPCC_RTC__)
 #include <string.h>
 #include "genmi.h"
+#include "gmx_sizes.h"
 // (`used`: emitted, and so exported by a shared library, although nothing in the translation unit calls them)
 
 extern "C" __attribute__((used)) inline int gmx_history_record(const float* x_d, int32_t D, const float* lw_d, const uint32_t* anc_d, int64_t n,
                                          uint32_t expect_tag, float* x_out_d, float* lw_out_d, int32_t* anc_out_d,
                                          int64_t* status_d, gmx_stream) {
-  if (!x_d || !lw_d || !anc_d || !x_out_d || !lw_out_d || !anc_out_d) return 1;
-  if (D <= 0 || D > 65533 || n <= 0 || n > 0x7fffffffLL) return 1;
-  if (expect_tag > 255u || (expect_tag != 0u && (!status_d || n > (1LL << 24)))) return 1;
+  const gmx_refusal no = gmx_history_record_refusal_(D, n, expect_tag, !x_d || !lw_d || !anc_d || !x_out_d || !lw_out_d || !anc_out_d,
+                                                     status_d != nullptr);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_history_record", no.v);
   memcpy(x_out_d, x_d, (size_t)D * (size_t)n * 4);
   memcpy(lw_out_d, lw_d, (size_t)n * 4);
   for (int64_t i = 0; i < n; ++i) {
@@ -167,8 +168,8 @@ extern "C" __attribute__((used)) inline int gmx_history_record(const float* x_d,
 extern "C" __attribute__((used)) inline int gmx_lineage(const int32_t* anc_d, const float* xs_d, int32_t T, int32_t D, int64_t n,
                                   const int32_t* start_d, int64_t m, int32_t* paths_d, float* traj_d, int64_t* status_d,
                                   gmx_stream) {
-  if (!start_d || !status_d || (!paths_d && !traj_d) || (traj_d && !xs_d)) return 1;
-  if (T <= 0 || D <= 0 || n <= 0 || m <= 0 || n > 0x7fffffffLL || (T > 1 && !anc_d)) return 1;
+  const gmx_refusal no = gmx_lineage_refusal_(anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, status_d);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_lineage", no.v);
   for (int64_t j = 0; j < m; ++j) {
     int64_t p = start_d[j];
     for (int32_t t = T - 1; t >= 0; --t) {

@@ -40,12 +40,7 @@
 // ---------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-static int gmx_fail(const char* fmt, const char* a = "", long long b = 0) {
-  snprintf(g_err, sizeof(g_err), fmt, a, b);
-  return 1;
-}
+// (the error string and gmx_fail: gmx_sizes.h)
 #define GMX_HIP(call)                                                        \
   do {                                                                       \
     hipError_t _e = (call);                                                  \
@@ -54,7 +49,7 @@ static int gmx_fail(const char* fmt, const char* a = "", long long b = 0) {
 
 extern "C" int gmx_version(void) { return GMX_ABI_VERSION; }
 extern "C" size_t gmx_run_args_bytes(void) { return sizeof(gmx_run_args); }
-extern "C" const char* gmx_last_error(void) { return g_err; }
+extern "C" const char* gmx_last_error(void) { return gmx_err_; }
 
 extern "C" void gmx_threefry2x32_host(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1,
                                       uint32_t out[2]) {
@@ -627,7 +622,7 @@ extern "C" size_t gmx_specialize_dryrun(const uint32_t* blob, size_t n_words, ch
 extern "C" size_t gmx_specialize_dryrun2(const uint32_t* blob, size_t n_words, int flags, char* log_out, size_t log_cap,
                                          char* code_out, size_t code_cap) {
   gmx_program P;
-  if (parse_program(blob, n_words, P)) { if (log_out && log_cap) snprintf(log_out, log_cap, "%s", g_err); return 0; }
+  if (parse_program(blob, n_words, P)) { if (log_out && log_cap) snprintf(log_out, log_cap, "%s", gmx_err_); return 0; }
   P.fuse_rs = (flags & 1) != 0 || (flags & 8) != 0;
   P.fuse_rs_loop = (flags & 8) != 0;
   P.background = (flags & 2) != 0;
@@ -904,6 +899,7 @@ extern "C" int gmx_random_bits(const uint32_t* keys_d, int64_t n, int64_t m, uin
 // ---------------------------------------------------------------------------
 #define LSE_ITEMS 16
 #define LSE_TILE (GMX_BLOCK * LSE_ITEMS)
+static_assert(LSE_TILE == GMX_LSE_TILE, "the row reductions' workspaces (gmx_sizes.h) are per tile of LSE_TILE columns");
 
 // Special values (include/genmi.h "Log-normaliser").  The maximum m ignores NaN (gmx_rmax), so it is never NaN.  A
 // finite m takes the sequence m + log(sum exp(x - m)): a NaN in the row reaches the sum through exp.  An infinite m
@@ -989,22 +985,14 @@ k_lse_rows(const float* __restrict__ lw, int64_t rows, int64_t cols, float* __re
   }
 }
 
-#define LSE_ROWS_PATH_MAX_COLS 4096
-static inline bool lse_use_rows_path(int64_t rows, int64_t cols) {
-  return rows >= 32 && cols <= LSE_ROWS_PATH_MAX_COLS;
-}
-extern "C" size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols) {
-  if (rows <= 0 || cols <= 0 || lse_use_rows_path(rows, cols)) return 16;
-  int64_t tiles = (cols + LSE_TILE - 1) / LSE_TILE;
-  return (size_t)(rows * tiles * 2 * sizeof(float)) + 16;
-}
+extern "C" size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols) { return gmx_logsumexp_bytes_(rows, cols); }
 extern "C" int gmx_logsumexp(const float* lw_d, int64_t rows, int64_t cols, float* out_d,
                              float* out_max_d, void* workspace_d, gmx_stream stream) {
   if (rows <= 0) return 0;
   if (cols <= 0) return gmx_fail("gmx_logsumexp: cols must be positive%s");
   if (!lw_d || !out_d) return gmx_fail("gmx_logsumexp: null argument%s");
   hipStream_t st = (hipStream_t)stream;
-  if (lse_use_rows_path(rows, cols)) {
+  if (gmx_lse_rows_path_(rows, cols)) {
     int64_t blocks = (rows + 3) / 4;
     hipLaunchKernelGGL(k_lse_rows, dim3((unsigned)blocks), dim3(GMX_BLOCK), 0, st, lw_d, rows, cols,
                        out_d, out_max_d);
@@ -1122,10 +1110,7 @@ extern "C" int gmx_sum_rows_inorder(const float* x_d, int64_t rows, int64_t cols
   GMX_HIP(hipGetLastError());
   return 0;
 }
-extern "C" size_t gmx_sum_rows_workspace(int64_t rows, int64_t cols) {
-  if (rows <= 0 || cols <= 0) return 16;
-  return (size_t)(rows * ((cols + LSE_TILE - 1) / LSE_TILE) * sizeof(float)) + 16;
-}
+extern "C" size_t gmx_sum_rows_workspace(int64_t rows, int64_t cols) { return gmx_sum_rows_bytes_(rows, cols); }
 extern "C" int gmx_sum_rows(const float* x_d, int64_t rows, int64_t cols, float* out_d, void* workspace_d,
                             gmx_stream stream) {
   if (rows <= 0) return 0;
@@ -1161,7 +1146,8 @@ extern "C" int gmx_sum_rows(const float* x_d, int64_t rows, int64_t cols, float*
 #define CDF_VEC 4                      /* consecutive items per thread (one float4) */
 #endif
 #define CDF_TILE (CDF_THREADS * CDF_VEC)
-static_assert(CDF_THREADS % 256 == 0 && CDF_VEC * 256 == 1024, "a definition tile of the CDF is 1024 items = 256 threads");
+static_assert(CDF_THREADS % 256 == 0 && CDF_VEC * 256 == GMX_TILE, "a definition tile of the CDF is 1024 items = 256 threads");
+static_assert(CDF_TILE == GMX_SCAN_TILE, "gmx_weight_cdf's workspace (gmx_sizes.h) holds one descriptor per scan tile");
 #define CDF_ST_AGG 1ull
 #define CDF_ST_INC 2ull
 #define CDF_SPIN_LIMIT (1u << 22)
@@ -1175,11 +1161,7 @@ static_assert(CDF_THREADS % 256 == 0 && CDF_VEC * 256 == 1024, "a definition til
 // ordering against any other memory.  Contract: zero on entry, zero on exit.
 struct cdf_ws { uint32_t ticket; uint32_t error; uint32_t done; uint32_t pad; uint64_t desc[1]; };
 
-extern "C" size_t gmx_weight_cdf_workspace(int64_t n) {
-  int64_t tiles = (n + CDF_TILE - 1) / CDF_TILE;
-  if (tiles < 1) tiles = 1;
-  return 16 + (size_t)tiles * 8;
-}
+extern "C" size_t gmx_weight_cdf_workspace(int64_t n) { return gmx_weight_cdf_bytes_(n); }
 
 __global__ void __launch_bounds__(GMX_BLOCK)
 k_reduce_max(const float* __restrict__ partials, int64_t n_part, float* __restrict__ max_out) {
@@ -1602,7 +1584,7 @@ k_ancestors_guided(uint32_t k0, uint32_t k1, const uint64_t* __restrict__ cdf, i
   anc[s] = (int32_t)res;
 }
 
-extern "C" size_t gmx_multinomial_workspace(int64_t n_in) { return (size_t)(n_in + 4) * 4; }
+extern "C" size_t gmx_multinomial_workspace(int64_t n_in) { return gmx_multinomial_bytes_(n_in); }
 
 extern "C" int gmx_multinomial(const uint32_t key[2], const uint64_t* cdf_d, int64_t n_in, const uint64_t* total_d,
                                int64_t n_out, int32_t* ancestors_d, void* workspace_d, gmx_stream stream) {
@@ -1722,18 +1704,6 @@ k_offspring_tile(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __rest
   gmx_offspring_tile_body<kind, PER, false>(k0, k1, u0_host, lw, tmax, agg, n, n_tiles, scale, max_out, total_out, anc, uslot, 0u);
 }
 
-static int resample_shape(const char* who, int64_t n, int shift, bool any_n = false) {
-  if (n <= 0) return gmx_fail("%s: n must be positive", who);
-  if (!any_n && (n + RS_TILE - 1) / RS_TILE > RS_MAX_TILES)
-    return gmx_fail("%s: n too large for the fused path (gmx_tile_stats + gmx_tile_prefix + gmx_resample_tiles_p, or gmx_weight_cdf + gmx_ancestors)", who);
-  if (n > 0x7fffffffLL) return gmx_fail("%s: n out of range", who);
-  if (shift < 1 || shift > 62) return gmx_fail("%s: shift out of range", who);
-  int need = 0;
-  while (((int64_t)1 << need) < n) ++need;
-  if (shift + need > 62) return gmx_fail("%s: shift too large for n (overflow)", who);
-  return 0;
-}
-
 static int launch_offspring_tile(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                  const float* tile_max_d, const uint64_t* tile_agg_d, float* max_d, uint64_t* total_d,
                                  int32_t* ancestors_d, gmx_stream stream, bool pref = false, const uint32_t* u_d = nullptr) {
@@ -1768,9 +1738,8 @@ static int launch_offspring_tile(int kind, const uint32_t key[2], const float* l
 
 extern "C" int gmx_tile_stats(const float* lw_d, int64_t n, int shift, float* tile_max_d, uint64_t* tile_agg_d,
                               gmx_stream stream) {
-  if (resample_shape("gmx_tile_stats", n, shift, true)) return 1;
-  if (!lw_d || !tile_max_d || !tile_agg_d) return gmx_fail("gmx_tile_stats: null argument%s");
-  if ((uintptr_t)lw_d & 15) return gmx_fail("gmx_tile_stats: lw_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_STATS, 0, n, shift, !lw_d || !tile_max_d || !tile_agg_d, lw_d))
+    return gmx_fail(m, "gmx_tile_stats");
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
   hipLaunchKernelGGL(k_tile_stats, dim3((unsigned)tiles), dim3(RS_THREADS), 0, (hipStream_t)stream, lw_d, n,
                      gmx_pow2i(shift), tile_max_d, tile_agg_d);
@@ -1781,13 +1750,9 @@ extern "C" int gmx_tile_stats(const float* lw_d, int64_t n, int shift, float* ti
 extern "C" int gmx_resample_tiles(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                   const float* tile_max_d, const uint64_t* tile_agg_d, float* max_d,
                                   uint64_t* total_d, int32_t* ancestors_d, gmx_stream stream) {
-  if (resample_shape("gmx_resample_tiles", n, shift)) return 1;
-  if (!key || !lw_d || !tile_max_d || !tile_agg_d || !max_d || !total_d || !ancestors_d)
-    return gmx_fail("gmx_resample_tiles: null argument%s");
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED)
-    return gmx_fail("gmx_resample_tiles: kind must be systematic or stratified (use gmx_weight_cdf + gmx_ancestors)%s");
-  if (n > 0x7fffffffLL) return gmx_fail("gmx_resample_tiles: n out of range%s");
-  if ((uintptr_t)lw_d & 15) return gmx_fail("gmx_resample_tiles: lw_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES, kind, n, shift,
+                                             !key || !lw_d || !tile_max_d || !tile_agg_d || !max_d || !total_d || !ancestors_d, lw_d))
+    return gmx_fail(m, "gmx_resample_tiles");
   return launch_offspring_tile(kind, key, lw_d, n, shift, tile_max_d, tile_agg_d, max_d, total_d, ancestors_d, stream);
 }
 
@@ -2102,19 +2067,16 @@ k_mn_tile(uint32_t k0, uint32_t k1, const float* __restrict__ lw, const float* _
 }
 
 // two count buffers of (tiles + 16) words each
-extern "C" size_t gmx_multinomial_tiled_workspace(int64_t n) { return (size_t)((n + RS_TILE - 1) / RS_TILE + 16) * 8; }
+extern "C" size_t gmx_multinomial_tiled_workspace(int64_t n) { return gmx_multinomial_tiled_bytes_(n); }
 
 extern "C" int gmx_multinomial_tiled(const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                      const float* tile_max_d, const uint64_t* tile_agg_d, const uint32_t* u_d,
                                      float* max_d, uint64_t* total_d, int32_t* ancestors_d, void* workspace_d,
                                      int phase, gmx_stream stream) {
-  if (resample_shape("gmx_multinomial_tiled", n, shift)) return 1;
-  if (!key || !lw_d || !tile_max_d || !tile_agg_d || !max_d || !total_d || !ancestors_d || !workspace_d)
-    return gmx_fail("gmx_multinomial_tiled: null argument%s");
-  if (n > 0x7fffffffLL) return gmx_fail("gmx_multinomial_tiled: n out of range%s");
-  if (phase < -1 || phase > 1) return gmx_fail("gmx_multinomial_tiled: phase is -1, 0 or 1%s");
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)workspace_d & 15))
-    return gmx_fail("gmx_multinomial_tiled: lw_d and workspace_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_MN_TILED, GMX_RESAMPLE_MULTINOMIAL_TILED, n, shift,
+                                             !key || !lw_d || !tile_max_d || !tile_agg_d || !max_d || !total_d || !ancestors_d || !workspace_d,
+                                             lw_d, workspace_d, phase))
+    return gmx_fail(m, "gmx_multinomial_tiled");
   hipStream_t st = (hipStream_t)stream;
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
   const size_t words = (size_t)tiles + 16;
@@ -2184,12 +2146,9 @@ extern "C" int gmx_slot_uniforms(const uint32_t* keys_d, int rows, int64_t n, ui
 extern "C" int gmx_resample_tiles_u(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                     const float* tile_max_d, const uint64_t* tile_agg_d, const uint32_t* u_d,
                                     float* max_d, uint64_t* total_d, int32_t* ancestors_d, gmx_stream stream) {
-  if (resample_shape("gmx_resample_tiles_u", n, shift)) return 1;
-  if (!key || !lw_d || !tile_max_d || !tile_agg_d || !u_d || !max_d || !total_d || !ancestors_d)
-    return gmx_fail("gmx_resample_tiles_u: null argument%s");
-  if (kind != GMX_RESAMPLE_STRATIFIED) return gmx_fail("gmx_resample_tiles_u: stratified only (systematic draws one uniform)%s");
-  if (n > 0x7fffffffLL) return gmx_fail("gmx_resample_tiles_u: n out of range%s");
-  if ((uintptr_t)lw_d & 15) return gmx_fail("gmx_resample_tiles_u: lw_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES_U, kind, n, shift,
+                                             !key || !lw_d || !tile_max_d || !tile_agg_d || !u_d || !max_d || !total_d || !ancestors_d, lw_d))
+    return gmx_fail(m, "gmx_resample_tiles_u");
   return launch_offspring_tile(kind, key, lw_d, n, shift, tile_max_d, tile_agg_d, max_d, total_d, ancestors_d, stream,
                                false, u_d);
 }
@@ -2375,7 +2334,7 @@ k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, in
   }
 }
 
-extern "C" size_t gmx_sorted_uniforms_words(int64_t n) { return n > 0 ? gmx_sorted_layout_of(n).words : 0; }
+extern "C" size_t gmx_sorted_uniforms_words(int64_t n) { return gmx_sorted_uniforms_words_(n); }
 
 static int launch_sorted_uniforms(const uint32_t* keys_d, const uint32_t* hkey, int rows, int64_t n, uint32_t* out_d,
                                   int lds_pad, gmx_stream stream) {
@@ -2402,11 +2361,10 @@ extern "C" int gmx_sorted_uniforms(const uint32_t* keys_d, int rows, int64_t n, 
 extern "C" int gmx_resample_sorted(const uint32_t key[2], const float* lw_d, int64_t n, int shift, const float* tile_max_d,
                                    const uint64_t* tile_agg_d, uint32_t* table_d, int table_ready, float* max_d,
                                    uint64_t* total_d, int32_t* ancestors_d, gmx_stream stream) {
-  if (resample_shape("gmx_resample_sorted", n, shift)) return 1;
-  if (!key || !lw_d || !tile_max_d || !tile_agg_d || !table_d || !max_d || !total_d || !ancestors_d)
-    return gmx_fail("gmx_resample_sorted: null argument%s");
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)table_d & 15))
-    return gmx_fail("gmx_resample_sorted: lw_d and table_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_SORTED, GMX_RESAMPLE_MULTINOMIAL_SORTED, n, shift,
+                                             !key || !lw_d || !tile_max_d || !tile_agg_d || !table_d || !max_d || !total_d || !ancestors_d,
+                                             lw_d, table_d))
+    return gmx_fail(m, "gmx_resample_sorted");
   if (!table_ready && launch_sorted_uniforms(nullptr, key, 1, n, table_d, 0, stream)) return 1;
   return launch_offspring_tile(GMX_RESAMPLE_MULTINOMIAL_SORTED, key, lw_d, n, shift, tile_max_d, tile_agg_d, max_d,
                                total_d, ancestors_d, stream, false, table_d);
@@ -2417,11 +2375,10 @@ extern "C" int gmx_resample_sorted(const uint32_t key[2], const float* lw_d, int
 extern "C" int gmx_resample_sorted_p(const uint32_t key[2], const float* lw_d, int64_t n, int shift, const float* tile_max_d,
                                      const uint64_t* tile_pref_d, uint32_t* table_d, int table_ready, float* max_d,
                                      uint64_t* total_d, int32_t* ancestors_d, gmx_stream stream) {
-  if (resample_shape("gmx_resample_sorted_p", n, shift, true)) return 1;
-  if (!key || !lw_d || !tile_max_d || !tile_pref_d || !table_d || !max_d || !total_d || !ancestors_d)
-    return gmx_fail("gmx_resample_sorted_p: null argument%s");
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)table_d & 15))
-    return gmx_fail("gmx_resample_sorted_p: lw_d and table_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_SORTED_P, GMX_RESAMPLE_MULTINOMIAL_SORTED, n, shift,
+                                             !key || !lw_d || !tile_max_d || !tile_pref_d || !table_d || !max_d || !total_d || !ancestors_d,
+                                             lw_d, table_d))
+    return gmx_fail(m, "gmx_resample_sorted_p");
   if (!table_ready && launch_sorted_uniforms(nullptr, key, 1, n, table_d, 0, stream)) return 1;
   return launch_offspring_tile(GMX_RESAMPLE_MULTINOMIAL_SORTED, key, lw_d, n, shift, tile_max_d, tile_pref_d, max_d,
                                total_d, ancestors_d, stream, true, table_d);
@@ -2499,78 +2456,22 @@ extern "C" int gmx_tile_prefix(const float* tile_max_d, const uint64_t* tile_agg
 extern "C" int gmx_resample_tiles_p(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                     const float* tile_max_d, const uint64_t* tile_pref_d, float* max_d,
                                     uint64_t* total_d, int32_t* ancestors_d, gmx_stream stream) {
-  if (resample_shape("gmx_resample_tiles_p", n, shift, true)) return 1;       // any n < 2^31: a workgroup reads ONE prefix
-  if (!key || !lw_d || !tile_max_d || !tile_pref_d || !max_d || !total_d || !ancestors_d)
-    return gmx_fail("gmx_resample_tiles_p: null argument%s");
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED)
-    return gmx_fail("gmx_resample_tiles_p: kind must be systematic or stratified%s");
-  if (n > 0x7fffffffLL) return gmx_fail("gmx_resample_tiles_p: n out of range%s");
-  if ((uintptr_t)lw_d & 15) return gmx_fail("gmx_resample_tiles_p: lw_d must be 16-byte aligned%s");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES_P, kind, n, shift,       // any n < 2^31: a workgroup reads ONE prefix
+                                             !key || !lw_d || !tile_max_d || !tile_pref_d || !max_d || !total_d || !ancestors_d, lw_d))
+    return gmx_fail(m, "gmx_resample_tiles_p");
   return launch_offspring_tile(kind, key, lw_d, n, shift, tile_max_d, tile_pref_d, max_d, total_d, ancestors_d,
                                stream, true);
 }
 
-// log-weights -> ancestors: gmx_tile_stats + gmx_resample_tiles with the tile stats in the workspace.
-// max_partials_d / n_partials are accepted for compatibility and unused: the tile maxima are recomputed.
-// THE resampling entry point (include/genmi.h): log-weights -> ancestors for every kind and every n < 2^31, dispatching
-// to the staged forms a caller that already holds tile statistics uses directly.
-struct resample_ws_layout {
-  size_t agg, tmax, pref, table, mnt, cdf, cdfws, mnws, total;
-};
-static size_t ws_up(size_t x) { return (x + 255) & ~(size_t)255; }
-static resample_ws_layout resample_ws_of(int64_t n) {
-  resample_ws_layout L;
-  const size_t tiles = (size_t)((n + RS_TILE - 1) / RS_TILE);
-  size_t o = 0;
-  L.agg = o; o = ws_up(o + tiles * 8);
-  L.tmax = o; o = ws_up(o + tiles * 4);
-  L.pref = o; o = ws_up(o + gmx_tile_prefix_words(n) * 8);
-  L.table = o; o = ws_up(o + gmx_sorted_uniforms_words(n) * 4);
-  L.mnt = o; o = ws_up(o + (n <= (int64_t)RS_MAX_TILES * RS_TILE ? gmx_multinomial_tiled_workspace(n) : 0));
-  L.cdf = o; o = ws_up(o + (size_t)n * 8);
-  L.cdfws = o; o = ws_up(o + gmx_weight_cdf_workspace(n));
-  L.mnws = o; o = ws_up(o + gmx_multinomial_workspace(n));
-  L.total = o;
-  return L;
-}
-extern "C" size_t gmx_resample_workspace(int64_t n) { return n > 0 ? resample_ws_of(n).total : 0; }
+// THE resampling entry point (include/genmi.h): the workspace layout, the argument checks and the dispatch over kind and
+// size are gmx_sizes.h's (gmx_resample_dispatch_), which calls the staged entry points above
+extern "C" size_t gmx_resample_workspace(int64_t n) { return gmx_resample_bytes_(n); }
 
 extern "C" int gmx_resample(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                             const float* max_partials_d, int64_t n_partials, float* max_d,
                             uint64_t* total_d, int32_t* ancestors_d, void* workspace_d, gmx_stream stream) {
   (void)max_partials_d; (void)n_partials;
-  if (!workspace_d || !key || !lw_d || !max_d || !total_d || !ancestors_d) return gmx_fail("gmx_resample: null argument%s");
-  if ((uintptr_t)workspace_d & 15) return gmx_fail("gmx_resample: workspace_d must be 16-byte aligned%s");
-  if (n <= 0 || n > 0x7fffffffLL) return gmx_fail("gmx_resample: n out of range%s");
-  const resample_ws_layout L = resample_ws_of(n);
-  uint8_t* w = (uint8_t*)workspace_d;
-  uint64_t* agg = (uint64_t*)(w + L.agg);
-  float* tmax = (float*)(w + L.tmax);
-  const bool small = (n + RS_TILE - 1) / RS_TILE <= RS_MAX_TILES;
-  if (kind == GMX_RESAMPLE_MULTINOMIAL) {          // iid slot order: the CDF array + the guide-table search
-    uint64_t* cdf = (uint64_t*)(w + L.cdf);
-    if (gmx_tile_stats(lw_d, n, shift, tmax, agg, stream)) return 1;        // (the tile maxima: gmx_weight_cdf reduces them to the max)
-    if (gmx_weight_cdf(lw_d, n, shift, tmax, (n + RS_TILE - 1) / RS_TILE, max_d, cdf, total_d, w + L.cdfws, stream)) return 1;
-    return gmx_multinomial(key, cdf, n, total_d, n, ancestors_d, w + L.mnws, stream);
-  }
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED && kind != GMX_RESAMPLE_MULTINOMIAL_TILED &&
-      kind != GMX_RESAMPLE_MULTINOMIAL_SORTED)
-    return gmx_fail("gmx_resample: unknown kind%s");
-  if (gmx_tile_stats(lw_d, n, shift, tmax, agg, stream)) return 1;
-  if (kind == GMX_RESAMPLE_MULTINOMIAL_TILED) {
-    if (!small) return gmx_fail("gmx_resample: GMX_RESAMPLE_MULTINOMIAL_TILED takes n <= 2^21 (use GMX_RESAMPLE_MULTINOMIAL_SORTED)%s");
-    return gmx_multinomial_tiled(key, lw_d, n, shift, tmax, agg, nullptr, max_d, total_d, ancestors_d, w + L.mnt, -1, stream);
-  }
-  if (small) {
-    if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
-      return gmx_resample_sorted(key, lw_d, n, shift, tmax, agg, (uint32_t*)(w + L.table), 0, max_d, total_d, ancestors_d, stream);
-    return gmx_resample_tiles(kind, key, lw_d, n, shift, tmax, agg, max_d, total_d, ancestors_d, stream);
-  }
-  uint64_t* pref = (uint64_t*)(w + L.pref);           // past 2048 tiles: one prefix pass, then the prefix-reading forms
-  if (gmx_tile_prefix(tmax, agg, n, pref, stream)) return 1;
-  if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
-    return gmx_resample_sorted_p(key, lw_d, n, shift, tmax, pref, (uint32_t*)(w + L.table), 0, max_d, total_d, ancestors_d, stream);
-  return gmx_resample_tiles_p(kind, key, lw_d, n, shift, tmax, pref, max_d, total_d, ancestors_d, stream);
+  return gmx_resample_dispatch_(kind, key, lw_d, n, shift, max_d, total_d, ancestors_d, workspace_d, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2867,7 +2768,7 @@ k_shard_step(int kind, uint32_t k0, uint32_t k1, const uint64_t* __restrict__ to
   if (overflow) plan[GMX_PLAN_OVERFLOW] = 1;
 }
 
-extern "C" size_t gmx_shard_plan_words(int world) { return (size_t)(GMX_PLAN_BOUNDS + world + 1); }
+extern "C" size_t gmx_shard_plan_words(int world) { return gmx_shard_plan_words_(world); }
 
 static int shard_check(const char* who, int kind, const void* key, int rank, int world, int64_t n) {
   if (!key) return gmx_fail("%s: null key", who);
@@ -2957,11 +2858,7 @@ extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* t
 // tmax[tiles_pad] f32, tiles_pad = tiles rounded up to even) — ONE collective carries what the max all-reduce
 // and the totals all-gather carried.  k_shard_totals (one block) turns the gathered table into the global max
 // and every rank's integer total; k_shard_step<true> rebuilds this rank's CDF per tile in registers.
-extern "C" size_t gmx_shard_stats_bytes(int64_t n_per_rank) {
-  int64_t tiles = (n_per_rank + RS_TILE - 1) / RS_TILE;
-  tiles += tiles & 1;
-  return (size_t)tiles * 12;
-}
+extern "C" size_t gmx_shard_stats_bytes(int64_t n_per_rank) { return gmx_shard_stats_bytes_(n_per_rank); }
 
 __global__ void __launch_bounds__(GMX_BLOCK)
 k_shard_totals(const uint8_t* __restrict__ stats_all, int world, int n_tiles, size_t stride,
@@ -3113,9 +3010,7 @@ extern "C" int gmx_shard_step_fused(int kind, const uint32_t key[2], const void*
 // fused peer exchange (include/genmi.h "Fused peer exchange"): the entry points around k_shard_step_fill<.., PEER>
 // ---------------------------------------------------------------------------
 extern "C" size_t gmx_peer_landing_bytes(int world, int64_t n_per_rank, int64_t capacity, int leaves) {
-  if (world < 1 || n_per_rank < 1 || capacity < 1 || leaves < 1) return 0;
-  const int tiles = (int)((n_per_rank + RS_TILE - 1) / RS_TILE);
-  return (gmx_peer_stats_words(world, tiles) + gmx_peer_state_words(world, capacity, leaves)) * sizeof(uint64_t);
+  return gmx_peer_landing_bytes_(world, n_per_rank, capacity, leaves);
 }
 
 __global__ void k_peer_bump(uint32_t* tag_base, uint32_t T) {
@@ -3530,17 +3425,14 @@ extern "C" int gmx_mh_accept(const uint32_t* keys_d, const float* log_alpha_d, i
 // sweep history: the per-step record and the lineage walk (gmx_history.h)
 // ---------------------------------------------------------------------------
 #include "gmx_history.h"
+static_assert(GMX_HIST_TAG_SHIFT == 24u, "gmx_history_record refuses (gmx_sizes.h) what a tagged word's 24-bit index cannot hold");
 
 extern "C" int gmx_history_record(const float* x_d, int32_t D, const float* lw_d, const uint32_t* anc_d, int64_t n,
                                   uint32_t expect_tag, float* x_out_d, float* lw_out_d, int32_t* anc_out_d,
                                   int64_t* status_d, gmx_stream stream) {
-  if (!x_d || !lw_d || !anc_d || !x_out_d || !lw_out_d || !anc_out_d) return gmx_fail("gmx_history_record: null argument%s");
-  if (D <= 0 || D > 65533) return gmx_fail("gmx_history_record: D = %s%lld is outside [1, 65533]", "", (long long)D);
-  if (n <= 0 || n > 0x7fffffffLL) return gmx_fail("gmx_history_record: n = %s%lld is outside [1, 2^31)", "", (long long)n);
-  if (expect_tag > 255u) return gmx_fail("gmx_history_record: expect_tag = %s%lld is outside [0, 255]", "", (long long)expect_tag);
-  if (expect_tag != 0u && !status_d) return gmx_fail("gmx_history_record: a tag check needs status_d%s");
-  if (expect_tag != 0u && n > (1LL << GMX_HIST_TAG_SHIFT))
-    return gmx_fail("gmx_history_record: tagged ancestors hold 24-bit indices (n = %s%lld)", "", (long long)n);
+  const gmx_refusal no = gmx_history_record_refusal_(D, n, expect_tag, !x_d || !lw_d || !anc_d || !x_out_d || !lw_out_d || !anc_out_d,
+                                                     status_d != nullptr);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_history_record", no.v);
   const int64_t blocks = (n / 4 + GMX_HIST_BLOCK) / GMX_HIST_BLOCK;       // >= 1: thread 0 moves the row's head and tail
   hipLaunchKernelGGL(k_history_record, dim3((unsigned)blocks, (unsigned)(D + 2)), dim3(GMX_HIST_BLOCK), 0, (hipStream_t)stream,
                      (const uint32_t*)x_d, D, (const uint32_t*)lw_d, anc_d, n, expect_tag, (uint32_t*)x_out_d,
@@ -3551,12 +3443,8 @@ extern "C" int gmx_history_record(const float* x_d, int32_t D, const float* lw_d
 
 extern "C" int gmx_lineage(const int32_t* anc_d, const float* xs_d, int32_t T, int32_t D, int64_t n, const int32_t* start_d,
                            int64_t m, int32_t* paths_d, float* traj_d, int64_t* status_d, gmx_stream stream) {
-  if (!start_d || !status_d) return gmx_fail("gmx_lineage: null argument%s");
-  if (!paths_d && !traj_d) return gmx_fail("gmx_lineage: null argument (paths_d and traj_d)%s");
-  if (traj_d && !xs_d) return gmx_fail("gmx_lineage: null argument (xs_d with traj_d)%s");
-  if (T <= 0 || D <= 0 || n <= 0 || m <= 0) return gmx_fail("gmx_lineage: T, D, n and m must be positive%s");
-  if (T > 1 && !anc_d) return gmx_fail("gmx_lineage: null argument (anc_d)%s");
-  if (n > 0x7fffffffLL) return gmx_fail("gmx_lineage: n = %s%lld does not fit the int32 indices", "", (long long)n);
+  const gmx_refusal no = gmx_lineage_refusal_(anc_d, xs_d, T, D, n, start_d, m, paths_d, traj_d, status_d);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_lineage", no.v);
   constexpr int C = GMX_LINEAGE_CHAINS;
   const int64_t per_block = (int64_t)GMX_HIST_BLOCK * C;
   const int64_t blocks = (m + per_block - 1) / per_block;
@@ -3587,9 +3475,8 @@ extern "C" size_t gmx_pick_rows_workspace(int64_t rows, int64_t n) { return gmx_
 extern "C" int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
                              int32_t* out_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
   if (!keys_d || !logits_d || !out_d || !status_d || !workspace_d) return gmx_fail("gmx_pick_rows: null argument%s");
-  if (rows < 1 || rows > 0x7fffffffLL) return gmx_fail("gmx_pick_rows: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
-  if (n < 1 || n > 0x7fffffffLL) return gmx_fail("gmx_pick_rows: n = %s%lld is outside [1, 2^31)", "", (long long)n);
-  if (ld < n) return gmx_fail("gmx_pick_rows: ld = %s%lld is smaller than n", "", (long long)ld);
+  const gmx_refusal no = gmx_pick_rows_refusal_(rows, n, ld);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_pick_rows", no.v);
   if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_pick_rows: workspace_d must be 8-byte aligned%s");
   if (((uintptr_t)logits_d & 3) || ((uintptr_t)keys_d & 3)) return gmx_fail("gmx_pick_rows: keys_d and logits_d must be 4-byte aligned%s");
   const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
@@ -3622,18 +3509,8 @@ extern "C" int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* 
                                  int64_t* status_d, void* workspace_d, gmx_stream stream) {
   if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
     return gmx_fail("gmx_resample_rows: null argument%s");
-  switch (gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride)) {
-    case 0: break;
-    case 2: return gmx_fail("gmx_resample_rows: GMX_RESAMPLE_MULTINOMIAL_TILED and GMX_RESAMPLE_MULTINOMIAL_SORTED have no row "
-                            "form (systematic, stratified or multinomial)%s");
-    case 3: return gmx_fail("gmx_resample_rows: unknown kind %s%lld", "", (long long)kind);
-    case 4: return gmx_fail("gmx_resample_rows: index_stride = %s%lld does not keep rows * index_stride below 2^31", "",
-                            (long long)index_stride);
-    default:
-      if (rows < 1 || rows > 0x7fffffffLL) return gmx_fail("gmx_resample_rows: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
-      if (ld < n) return gmx_fail("gmx_resample_rows: ld = %s%lld is smaller than n", "", (long long)ld);
-      return gmx_fail("gmx_resample_rows: n = %s%lld is outside [1, 2^21]", "", (long long)n);
-  }
+  const gmx_refusal no = gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows", no.v);
   if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows: workspace_d must be 8-byte aligned%s");
   if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) ||
       ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
@@ -3691,25 +3568,9 @@ extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int
                                         int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
   if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
     return gmx_fail("gmx_resample_rows_pinned: null argument%s");
-  switch (gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride)) {
-    case 0: break;
-    case 4: return gmx_fail("gmx_resample_rows_pinned: index_stride = %s%lld does not keep rows * index_stride below 2^31", "",
-                            (long long)index_stride);
-    default:
-      if (rows < 1 || rows > 0x7fffffffLL)
-        return gmx_fail("gmx_resample_rows_pinned: rows = %s%lld is outside [1, 2^31)", "", (long long)rows);
-      if (ld < n) return gmx_fail("gmx_resample_rows_pinned: ld = %s%lld is smaller than n", "", (long long)ld);
-      return gmx_fail("gmx_resample_rows_pinned: n = %s%lld is outside [1, 2^21]", "", (long long)n);
-  }
-  switch (gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride)) {
-    case 0: break;
-    case 5: return gmx_fail("gmx_resample_rows_pinned: D = %s%lld is outside [0, 65533]", "", (long long)D);
-    default:
-      if (x_row_stride < 0)
-        return gmx_fail("gmx_resample_rows_pinned: x_row_stride = %s%lld is negative", "", (long long)x_row_stride);
-      return gmx_fail("gmx_resample_rows_pinned: x_ld = %s%lld does not hold (rows - 1) * x_row_stride + n columns (or is "
-                      "2^46 or more)", "", (long long)x_ld);
-  }
+  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
+  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_pinned", no.v);
   if (D > 0 && !pin_x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (pin_x_d with D > 0)%s");
   if (D > 0 && !x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (x_d with D > 0)%s");
   if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows_pinned: workspace_d must be 8-byte aligned%s");

@@ -12,10 +12,8 @@
 #define RS_THREADS 256                 /* 4 waves per tile                         */
 #endif
 #define RS_TILE (RS_THREADS * CDF_VEC_OT) /* 1024 log-weights per tile = one definition tile of the CDF */
-#ifndef RS_MAX_TILES
-#define RS_MAX_TILES 2048              /* n <= 2^21                                */
-#endif
-static_assert(RS_TILE == 1024 && RS_THREADS == GMX_BLOCK, "resampling tiles are the CDF's definition tiles");
+#define RS_MAX_TILES GMX_MAX_TILES     /* n <= 2^21                                */
+static_assert(RS_TILE == GMX_TILE && RS_THREADS == GMX_BLOCK, "resampling tiles are the CDF's definition tiles");
 static_assert(RS_MAX_TILES % GMX_BLOCK == 0, "tile table shape");
 
 // TAGGED (a site program's prologue): every ancestor is stored as {tag: bits 24..31 | index: bits 0..23} with a

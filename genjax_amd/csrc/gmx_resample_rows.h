@@ -21,42 +21,14 @@
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
 // host compiler: the ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
 // multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
-// for gmx_pick_rows; gmx_vm.h includes this file there.  That loop validates its arguments as the HIP entry point does but
-// leaves no message.
+// for gmx_pick_rows; gmx_vm.h includes this file there.  That loop validates its arguments as the HIP entry point does
+// and leaves its message (gmx_sizes.h: the checks, gmx_fail).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
-#include "gmx_backward.h"              /* GMX_PICK_TILE, gmx_pick_rows_shift_; under hipcc k_pick_stats, pick_load4 */
+#include "gmx_backward.h"              /* gmx_sizes.h, GMX_PICK_TILE; under hipcc k_pick_stats, pick_load4 */
 
-#define GMX_ROWS_MAX_N (2048 * 1024)   /* RS_MAX_TILES tiles: what the per-row fused path takes */
-
-// workspace: agg u64 [rows * tiles] | cdf u64 [rows * n] (iid multinomial only) | tmax f32 [rows * tiles]; nothing for n <= 1024
-static inline size_t gmx_resample_rows_bytes_(int kind, int64_t rows, int64_t n) {
-  if (rows < 1 || n <= GMX_PICK_TILE || n > GMX_ROWS_MAX_N) return 16;
-  const uint64_t cells = (uint64_t)rows * (uint64_t)((n + GMX_PICK_TILE - 1) / GMX_PICK_TILE);
-  const uint64_t cdf = kind == 2 /* GMX_RESAMPLE_MULTINOMIAL */ ? (uint64_t)rows * (uint64_t)n * 8u : 0u;
-  return (size_t)((cells * 12u + cdf + 15u) & ~(uint64_t)15u);
-}
-// 0: fine.  1: a size out of range.  2: an ordered multinomial.  3: an unknown kind.  4: the stride overflows int32.
-static inline int gmx_resample_rows_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
-  if (kind == 3 || kind == 4) return 2;
-  if (kind < 0 || kind > 2) return 3;
-  if (rows < 1 || rows > 0x7fffffffLL || n < 1 || n > GMX_ROWS_MAX_N || ld < n) return 1;
-  if (index_stride < 0) return 4;
-  if (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
-                           (rows - 1) * index_stride + n - 1 >= (1LL << 31))) return 4;
-  return 0;
-}
-// gmx_resample_rows_pinned's own arguments (after the above).  0: fine.  5: D out of range.  6: x_ld / x_row_stride do not
-// keep column n - 1 of every row inside a [D, x_ld] store.
-#define GMX_ROWS_PIN_MAX_D 65533       /* D + 1 is a grid's y extent */
-static inline int gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n, int32_t D, int64_t x_ld, int64_t x_row_stride) {
-  if (D < 0 || D > GMX_ROWS_PIN_MAX_D) return 5;
-  if (D == 0) return 0;
-  if (x_row_stride < 0 || x_ld < n || x_ld >= (1LL << 46)) return 6;          // (D * x_ld stays below 2^62)
-  if (rows > 1 && x_row_stride > (x_ld - n) / (rows - 1)) return 6;           // x_ld >= (rows - 1) * x_row_stride + n
-  return 0;
-}
+// (workspace size, refusals, GMX_ROWS_MAX_N, GMX_ROWS_PIN_MAX_D: gmx_sizes.h)
 
 #if defined(__HIPCC__)
 #include "gmx_resample.h"              /* gmx_block.h, gmx_rng.h, u128 / mul64 / slot_threshold */
@@ -359,8 +331,10 @@ extern "C" __attribute__((used)) inline size_t gmx_resample_rows_workspace(int k
 extern "C" __attribute__((used)) inline int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n,
                                         int64_t ld, int64_t index_stride, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
                                         int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d) return 1;
-  if (gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride)) return 1;
+  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("%s: null argument", "gmx_resample_rows", 0);
+  const gmx_refusal no = gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows", no.v);
   const int shift = gmx_pick_rows_shift_(n);
   std::vector<float> row((size_t)n);                             // (the per-row path asks for an aligned row)
   std::vector<uint64_t> cdf(kind == GMX_RESAMPLE_MULTINOMIAL ? (size_t)n : 0);
@@ -391,10 +365,14 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_pinned(const uint3
                                                int64_t index_stride, const float* pin_lw_d, const float* pin_x_d, float* x_d,
                                                int32_t D, int64_t x_ld, int64_t x_row_stride, float* max_d, uint64_t* total_d,
                                                int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d) return 1;
-  if (gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride)) return 1;
-  if (gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride)) return 1;
-  if (D > 0 && (!pin_x_d || !x_d)) return 1;
+  const char* who = "gmx_resample_rows_pinned";
+  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("%s: null argument", who, 0);
+  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
+  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (D > 0 && !pin_x_d) return gmx_fail("%s: null argument (pin_x_d with D > 0)", who, 0);
+  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
   for (int64_t r = 0; r < rows; ++r) {
     lw_d[r * ld + n - 1] = pin_lw_d[r];
     for (int64_t d = 0; d < D; ++d) x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r];

@@ -1,0 +1,248 @@
+// gmx_sizes.h — how big a workspace is, what an entry point refuses, and what gmx_resample dispatches to: stated ONCE,
+// for every build of the C-ABI of include/genmi.h (gmx_kernels.hip; the CPU mirror in tests/hostsim).
+//   the tile constants        the definition tile of the two-level integer CDF and the tile tables built on it
+//   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
+//   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
+//                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string
+//   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
+//                             and size.  It calls exported entry points only, so every build dispatches alike.
+// Plain host C++ (static inline): no HIP, no kernel, no algorithm.  hiprtc never sees this file (it is not among the
+// embedded headers): a specialised kernel gets GMX_TILE and GMX_MAX_TILES as two #defines ahead of its source.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "genmi.h"
+#include "gmx_peer.h"                  /* gmx_peer_stats_words, gmx_peer_state_words */
+#include "gmx_sorted.h"                /* gmx_sorted_layout_of */
+
+#define GMX_TILE 1024                  /* one definition tile of the CDF (include/genmi.h "Resampling") */
+#define GMX_MAX_TILES 2048             /* tiles of one table-per-workgroup resampling: n <= 2^21 */
+#define GMX_LSE_TILE 4096              /* columns per workgroup of the two-stage row reductions */
+#define GMX_LSE_ROWS_PATH_MAX_COLS 4096
+#define GMX_SCAN_TILE 4096             /* items per workgroup of gmx_weight_cdf's chained scan */
+#define GMX_ROWS_MAX_N (GMX_MAX_TILES * GMX_TILE)        /* what the per-row fused path takes */
+#define GMX_ROWS_PIN_MAX_D 65533       /* D + 1 is a grid's y extent */
+
+static inline int64_t gmx_tiles_(int64_t n) { return (n + GMX_TILE - 1) / GMX_TILE; }
+static inline int gmx_ceil_log2_(int64_t n) {
+  int need = 0;
+  while (((int64_t)1 << need) < n) ++need;
+  return need;
+}
+
+// ---- row reductions: gmx_logsumexp (one wave per row for many short rows: no workspace), gmx_sum_rows ----
+static inline bool gmx_lse_rows_path_(int64_t rows, int64_t cols) { return rows >= 32 && cols <= GMX_LSE_ROWS_PATH_MAX_COLS; }
+static inline size_t gmx_logsumexp_bytes_(int64_t rows, int64_t cols) {
+  if (rows <= 0 || cols <= 0 || gmx_lse_rows_path_(rows, cols)) return 16;
+  return (size_t)(rows * ((cols + GMX_LSE_TILE - 1) / GMX_LSE_TILE) * 2 * sizeof(float)) + 16;
+}
+static inline size_t gmx_sum_rows_bytes_(int64_t rows, int64_t cols) {
+  if (rows <= 0 || cols <= 0) return 16;
+  return (size_t)(rows * ((cols + GMX_LSE_TILE - 1) / GMX_LSE_TILE) * sizeof(float)) + 16;
+}
+
+// ---- the CDF array forms ----
+// gmx_weight_cdf: ticket, error flag, done count, pad; then one u64 descriptor per scan tile
+static inline size_t gmx_weight_cdf_bytes_(int64_t n) {
+  int64_t tiles = (n + GMX_SCAN_TILE - 1) / GMX_SCAN_TILE;
+  if (tiles < 1) tiles = 1;
+  return 16 + (size_t)tiles * 8;
+}
+static inline size_t gmx_multinomial_bytes_(int64_t n_in) { return (size_t)(n_in + 4) * 4; }     // the guide table
+// gmx_multinomial_tiled: two count buffers of (tiles + 16) words each
+static inline size_t gmx_multinomial_tiled_bytes_(int64_t n) { return (size_t)(gmx_tiles_(n) + 16) * 8; }
+// gmx_tile_prefix's block (u64 words): [0, tiles) prefixes | [tiles] total | [tiles + 1] M, K | pad to a multiple of 16
+static inline size_t gmx_tile_prefix_words_(int64_t n) { return (size_t)((gmx_tiles_(n) + 2 + 15) / 16) * 16; }
+static inline size_t gmx_sorted_uniforms_words_(int64_t n) { return n > 0 ? gmx_sorted_layout_of(n).words : 0; }
+
+// ---- sharded resampling ----
+// a rank's tile statistics: agg[tiles_pad] u64 then tmax[tiles_pad] f32, tiles_pad = tiles rounded up to even
+static inline size_t gmx_shard_stats_bytes_(int64_t n_per_rank) {
+  int64_t tiles = gmx_tiles_(n_per_rank);
+  tiles += tiles & 1;
+  return (size_t)tiles * 12;
+}
+static inline size_t gmx_shard_plan_words_(int world) { return (size_t)(GMX_PLAN_BOUNDS + world + 1); }
+static inline size_t gmx_peer_landing_bytes_(int world, int64_t n_per_rank, int64_t capacity, int leaves) {
+  if (world < 1 || n_per_rank < 1 || capacity < 1 || leaves < 1) return 0;
+  return (gmx_peer_stats_words(world, (int)gmx_tiles_(n_per_rank)) + gmx_peer_state_words(world, capacity, leaves)) *
+         sizeof(uint64_t);
+}
+
+// ---- refusals ----
+// fmt == nullptr: nothing to refuse.  Otherwise a printf format taking the entry point's name (%s), then v (%lld) where
+// the message quotes a value.
+struct gmx_refusal { const char* fmt; long long v; };
+// The error string of a build of the C-ABI (what its gmx_last_error returns) and the one way to leave a message in it:
+// `fmt` takes a string, then an integer.  Returns 1, an entry point's refusal.
+static thread_local char gmx_err_[512] = "";
+static inline int gmx_fail(const char* fmt, const char* a = "", long long b = 0) {
+  snprintf(gmx_err_, sizeof(gmx_err_), fmt, a, b);
+  return 1;
+}
+
+// the sizes every tile-form resampler takes; any_n: the forms that read ONE prefix per workgroup, not the table
+static inline const char* gmx_resample_shape_refusal_(int64_t n, int shift, bool any_n) {
+  if (n <= 0) return "%s: n must be positive";
+  if (!any_n && gmx_tiles_(n) > GMX_MAX_TILES)
+    return "%s: n too large for the fused path (gmx_tile_stats + gmx_tile_prefix + gmx_resample_tiles_p, or gmx_weight_cdf + gmx_ancestors)";
+  if (n > 0x7fffffffLL) return "%s: n out of range";
+  if (shift < 1 || shift > 62) return "%s: shift out of range";
+  if (shift + gmx_ceil_log2_(n) > 62) return "%s: shift too large for n (overflow)";      // n terms <= 2^shift stay below 2^62
+  return nullptr;
+}
+// the tile-form resamplers: shape, null arguments, the kinds (or phase) the form takes, 16-byte alignment — in that order.
+// has_null: one of the form's required pointers is null.  also16: the form's second 16-byte pointer (the order-statistics
+// table of the sorted forms, gmx_multinomial_tiled's workspace), or nullptr.
+enum gmx_tile_form { GMX_FORM_STATS, GMX_FORM_TILES, GMX_FORM_TILES_U, GMX_FORM_TILES_P, GMX_FORM_SORTED, GMX_FORM_SORTED_P,
+                     GMX_FORM_MN_TILED };
+static inline const char* gmx_tile_form_refusal_(gmx_tile_form form, int kind, int64_t n, int shift, bool has_null,
+                                                 const void* lw_d, const void* also16 = nullptr, int phase = 0) {
+  const bool any_n = form == GMX_FORM_STATS || form == GMX_FORM_TILES_P || form == GMX_FORM_SORTED_P;
+  if (const char* m = gmx_resample_shape_refusal_(n, shift, any_n)) return m;
+  if (has_null) return "%s: null argument";
+  const bool ordered = kind == GMX_RESAMPLE_SYSTEMATIC || kind == GMX_RESAMPLE_STRATIFIED;
+  if (form == GMX_FORM_TILES && !ordered) return "%s: kind must be systematic or stratified (use gmx_weight_cdf + gmx_ancestors)";
+  if (form == GMX_FORM_TILES_P && !ordered) return "%s: kind must be systematic or stratified";
+  if (form == GMX_FORM_TILES_U && kind != GMX_RESAMPLE_STRATIFIED) return "%s: stratified only (systematic draws one uniform)";
+  if (form == GMX_FORM_MN_TILED && (phase < -1 || phase > 1)) return "%s: phase is -1, 0 or 1";
+  if (((uintptr_t)lw_d & 15) || ((uintptr_t)also16 & 15)) {
+    if (form == GMX_FORM_MN_TILED) return "%s: lw_d and workspace_d must be 16-byte aligned";
+    if (form == GMX_FORM_SORTED || form == GMX_FORM_SORTED_P) return "%s: lw_d and table_d must be 16-byte aligned";
+    return "%s: lw_d must be 16-byte aligned";
+  }
+  return nullptr;
+}
+
+// ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned ----
+// gmx_pick_rows' workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
+static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
+  if (rows < 1 || n < 1) return 16;
+  const uint64_t cells = (uint64_t)rows * (uint64_t)gmx_tiles_(n);
+  return (size_t)((cells * 12u + 15u) & ~(uint64_t)15u);
+}
+// shift = 62 - ceil(log2 n): a sum of n terms <= 2^shift stays below 2^62 (smc.cdf_shift)
+static inline int gmx_pick_rows_shift_(int64_t n) { return 62 - gmx_ceil_log2_(n); }
+static inline gmx_refusal gmx_pick_rows_refusal_(int64_t rows, int64_t n, int64_t ld) {
+  if (rows < 1 || rows > 0x7fffffffLL) return {"%s: rows = %lld is outside [1, 2^31)", (long long)rows};
+  if (n < 1 || n > 0x7fffffffLL) return {"%s: n = %lld is outside [1, 2^31)", (long long)n};
+  if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  return {nullptr, 0};
+}
+// gmx_resample_rows' workspace: agg u64 [rows * tiles] | cdf u64 [rows * n] (iid multinomial only) | tmax f32 [rows * tiles];
+// nothing for n <= 1024
+static inline size_t gmx_resample_rows_bytes_(int kind, int64_t rows, int64_t n) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
+  const uint64_t cells = (uint64_t)rows * (uint64_t)gmx_tiles_(n);
+  const uint64_t cdf = kind == GMX_RESAMPLE_MULTINOMIAL ? (uint64_t)rows * (uint64_t)n * 8u : 0u;
+  return (size_t)((cells * 12u + cdf + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_refusal gmx_resample_rows_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
+  if (kind == GMX_RESAMPLE_MULTINOMIAL_TILED || kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
+    return {"%s: GMX_RESAMPLE_MULTINOMIAL_TILED and GMX_RESAMPLE_MULTINOMIAL_SORTED have no row form (systematic, stratified "
+            "or multinomial)", 0};
+  if (kind < 0 || kind > 2) return {"%s: unknown kind %lld", (long long)kind};
+  if (rows < 1 || rows > 0x7fffffffLL) return {"%s: rows = %lld is outside [1, 2^31)", (long long)rows};
+  if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  if (n < 1 || n > GMX_ROWS_MAX_N) return {"%s: n = %lld is outside [1, 2^21]", (long long)n};
+  if (index_stride < 0 || (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
+                                                (rows - 1) * index_stride + n - 1 >= (1LL << 31))))
+    return {"%s: index_stride = %lld does not keep rows * index_stride below 2^31", (long long)index_stride};
+  return {nullptr, 0};
+}
+// gmx_resample_rows_pinned's own arguments (after the above): D, and x_ld / x_row_stride keeping column n - 1 of every
+// row inside a [D, x_ld] store
+static inline gmx_refusal gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n, int32_t D, int64_t x_ld, int64_t x_row_stride) {
+  if (D < 0 || D > GMX_ROWS_PIN_MAX_D) return {"%s: D = %lld is outside [0, 65533]", (long long)D};
+  if (D == 0) return {nullptr, 0};
+  if (x_row_stride < 0) return {"%s: x_row_stride = %lld is negative", (long long)x_row_stride};
+  if (x_ld < n || x_ld >= (1LL << 46) ||                                      // (D * x_ld stays below 2^62)
+      (rows > 1 && x_row_stride > (x_ld - n) / (rows - 1)))                   // x_ld >= (rows - 1) * x_row_stride + n
+    return {"%s: x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)x_ld};
+  return {nullptr, 0};
+}
+
+// ---- sweep history ----
+static inline gmx_refusal gmx_history_record_refusal_(int32_t D, int64_t n, uint32_t expect_tag, bool has_null, bool has_status) {
+  if (has_null) return {"%s: null argument", 0};
+  if (D <= 0 || D > 65533) return {"%s: D = %lld is outside [1, 65533]", (long long)D};
+  if (n <= 0 || n > 0x7fffffffLL) return {"%s: n = %lld is outside [1, 2^31)", (long long)n};
+  if (expect_tag > 255u) return {"%s: expect_tag = %lld is outside [0, 255]", (long long)expect_tag};
+  if (expect_tag != 0u && !has_status) return {"%s: a tag check needs status_d", 0};
+  if (expect_tag != 0u && n > (1LL << 24)) return {"%s: tagged ancestors hold 24-bit indices (n = %lld)", (long long)n};
+  return {nullptr, 0};
+}
+static inline gmx_refusal gmx_lineage_refusal_(const void* anc_d, const void* xs_d, int32_t T, int32_t D, int64_t n,
+                                               const void* start_d, int64_t m, const void* paths_d, const void* traj_d,
+                                               const void* status_d) {
+  if (!start_d || !status_d) return {"%s: null argument", 0};
+  if (!paths_d && !traj_d) return {"%s: null argument (paths_d and traj_d)", 0};
+  if (traj_d && !xs_d) return {"%s: null argument (xs_d with traj_d)", 0};
+  if (T <= 0 || D <= 0 || n <= 0 || m <= 0) return {"%s: T, D, n and m must be positive", 0};
+  if (T > 1 && !anc_d) return {"%s: null argument (anc_d)", 0};
+  if (n > 0x7fffffffLL) return {"%s: n = %lld does not fit the int32 indices", (long long)n};
+  return {nullptr, 0};
+}
+
+// ---- gmx_resample: THE resampling entry point (include/genmi.h): log-weights -> ancestors for every kind and every
+// n < 2^31, dispatching to the staged forms a caller that already holds tile statistics uses directly ----
+struct gmx_resample_ws_layout {
+  size_t agg, tmax, pref, table, mnt, cdf, cdfws, mnws, total;
+};
+static inline size_t gmx_ws_up_(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline gmx_resample_ws_layout gmx_resample_ws_of_(int64_t n) {
+  gmx_resample_ws_layout L;
+  const size_t tiles = (size_t)gmx_tiles_(n);
+  size_t o = 0;
+  L.agg = o; o = gmx_ws_up_(o + tiles * 8);
+  L.tmax = o; o = gmx_ws_up_(o + tiles * 4);
+  L.pref = o; o = gmx_ws_up_(o + gmx_tile_prefix_words_(n) * 8);
+  L.table = o; o = gmx_ws_up_(o + gmx_sorted_uniforms_words_(n) * 4);
+  L.mnt = o; o = gmx_ws_up_(o + (n <= (int64_t)GMX_ROWS_MAX_N ? gmx_multinomial_tiled_bytes_(n) : 0));
+  L.cdf = o; o = gmx_ws_up_(o + (size_t)n * 8);
+  L.cdfws = o; o = gmx_ws_up_(o + gmx_weight_cdf_bytes_(n));
+  L.mnws = o; o = gmx_ws_up_(o + gmx_multinomial_bytes_(n));
+  L.total = o;
+  return L;
+}
+static inline size_t gmx_resample_bytes_(int64_t n) { return n > 0 ? gmx_resample_ws_of_(n).total : 0; }
+
+// (max_partials_d / n_partials of the entry point are accepted for compatibility and unused: the tile maxima are recomputed)
+static inline int gmx_resample_dispatch_(int kind, const uint32_t key[2], const float* lw_d, int64_t n,
+                                         int shift, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
+                                         void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_resample";
+  if (!workspace_d || !key || !lw_d || !max_d || !total_d || !ancestors_d) return gmx_fail("%s: null argument", who);
+  if ((uintptr_t)workspace_d & 15) return gmx_fail("%s: workspace_d must be 16-byte aligned", who);
+  if (n <= 0 || n > 0x7fffffffLL) return gmx_fail("%s: n out of range", who);
+  const gmx_resample_ws_layout L = gmx_resample_ws_of_(n);
+  uint8_t* w = (uint8_t*)workspace_d;
+  uint64_t* agg = (uint64_t*)(w + L.agg);
+  float* tmax = (float*)(w + L.tmax);
+  const bool small = gmx_tiles_(n) <= GMX_MAX_TILES;
+  if (kind == GMX_RESAMPLE_MULTINOMIAL) {          // iid slot order: the CDF array + the guide-table search
+    uint64_t* cdf = (uint64_t*)(w + L.cdf);
+    if (gmx_tile_stats(lw_d, n, shift, tmax, agg, stream)) return 1;        // (the tile maxima: gmx_weight_cdf reduces them to the max)
+    if (gmx_weight_cdf(lw_d, n, shift, tmax, gmx_tiles_(n), max_d, cdf, total_d, w + L.cdfws, stream)) return 1;
+    return gmx_multinomial(key, cdf, n, total_d, n, ancestors_d, w + L.mnws, stream);
+  }
+  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED && kind != GMX_RESAMPLE_MULTINOMIAL_TILED &&
+      kind != GMX_RESAMPLE_MULTINOMIAL_SORTED)
+    return gmx_fail("%s: unknown kind", who);
+  if (gmx_tile_stats(lw_d, n, shift, tmax, agg, stream)) return 1;
+  if (kind == GMX_RESAMPLE_MULTINOMIAL_TILED) {
+    if (!small) return gmx_fail("%s: GMX_RESAMPLE_MULTINOMIAL_TILED takes n <= 2^21 (use GMX_RESAMPLE_MULTINOMIAL_SORTED)", who);
+    return gmx_multinomial_tiled(key, lw_d, n, shift, tmax, agg, nullptr, max_d, total_d, ancestors_d, w + L.mnt, -1, stream);
+  }
+  if (small) {
+    if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
+      return gmx_resample_sorted(key, lw_d, n, shift, tmax, agg, (uint32_t*)(w + L.table), 0, max_d, total_d, ancestors_d, stream);
+    return gmx_resample_tiles(kind, key, lw_d, n, shift, tmax, agg, max_d, total_d, ancestors_d, stream);
+  }
+  uint64_t* pref = (uint64_t*)(w + L.pref);           // past 2048 tiles: one prefix pass, then the prefix-reading forms
+  if (gmx_tile_prefix(tmax, agg, n, pref, stream)) return 1;
+  if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
+    return gmx_resample_sorted_p(key, lw_d, n, shift, tmax, pref, (uint32_t*)(w + L.table), 0, max_d, total_d, ancestors_d, stream);
+  return gmx_resample_tiles_p(kind, key, lw_d, n, shift, tmax, pref, max_d, total_d, ancestors_d, stream);
+}

@@ -327,3 +327,26 @@ def check_filter_mean(h):
     err = np.abs(got - ref).max(axis=1)
     print("filter_mean: max |torch - numpy| per step", err, "bound", bound)
     assert np.all(err <= bound), (err, bound)
+
+
+def history_refusal_calls():
+    """(entry point, argument tuple, what the message has to name): what gmx_history_record and gmx_lineage refuse before
+    any launch"""
+    import ctypes
+    N, i64, i32, u32 = ctypes.c_void_p(0), ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
+    buf = (ctypes.c_int64 * 8)()
+    B = ctypes.cast(buf, ctypes.c_void_p)
+    calls = [
+        ("gmx_history_record", (N, i32(1), N, N, i64(10), u32(0), N, N, N, N, N), b"null argument"),
+        ("gmx_history_record", (B, i32(0), B, B, i64(10), u32(0), B, B, B, B, N), b"D = 0"),
+        ("gmx_history_record", (B, i32(1), B, B, i64(0), u32(0), B, B, B, B, N), b"n = 0"),
+        ("gmx_history_record", (B, i32(1), B, B, i64(4), u32(3), B, B, B, N, N), b"needs status_d"),      # a tag check without status
+        ("gmx_history_record", (B, i32(1), B, B, i64(4), u32(256), B, B, B, B, N), b"expect_tag = 256"),    # no such tag
+        ("gmx_lineage", (N, N, i32(3), i32(1), i64(10), N, i64(4), N, N, N, N), b"null argument"),
+        ("gmx_lineage", (B, B, i32(3), i32(1), i64(10), B, i64(4), N, N, B, N), b"paths_d and traj_d"),     # neither output
+        ("gmx_lineage", (B, N, i32(3), i32(1), i64(10), B, i64(4), N, B, B, N), b"xs_d with traj_d"),       # traj without xs
+        ("gmx_lineage", (B, B, i32(0), i32(1), i64(10), B, i64(4), B, B, B, N), b"must be positive"),       # T = 0
+        ("gmx_lineage", (B, B, i32(3), i32(1), i64(10), B, i64(-1), B, B, B, N), b"must be positive"),      # m < 0
+        ("gmx_lineage", (B, B, i32(3), i32(1), i64(10), B, i64(4), B, B, N, N), b"null argument"),          # no status word
+    ]
+    return calls, buf

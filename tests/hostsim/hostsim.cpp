@@ -6,7 +6,9 @@
 // own headers (genjax_amd/csrc/gmx_vm.h ...) compiled for the host, so CPU
 // tests diff the product's device functions against the independent oracle.
 // The scan / search / gather entry points are plain re-implementations (the
-// gfx950 kernels themselves are validated by the `-m gpu` tests).
+// gfx950 kernels themselves are validated by the `-m gpu` tests).  Workspace
+// sizes, the shared argument refusals and gmx_resample's dispatch are the
+// product's too (genjax_amd/csrc/gmx_sizes.h): the mirror states none of them.
 //
 // Nothing in genjax_amd/ refers to this file; tests install it through
 // genjax_amd._lib.install().  It is never shipped as a fallback.
@@ -17,14 +19,14 @@
 
 #include <vector>
 
+// gmx_history_record, gmx_lineage, gmx_pick_rows and gmx_resample_rows[_pinned] come from the product's headers (gmx_vm.h
+// pulls their host branches in for a plain host compiler); the error string and gmx_fail are gmx_sizes.h's
 #include "../../genjax_amd/csrc/gmx_vm.h"  // build with -I include
-
-static thread_local char g_err[512] = "";
-static int fail(const char* m) { snprintf(g_err, sizeof(g_err), "%s", m); return 1; }
+#include "../../genjax_amd/csrc/gmx_sizes.h"
 
 extern "C" int gmx_version(void) { return GMX_ABI_VERSION; }
 extern "C" size_t gmx_run_args_bytes(void) { return sizeof(gmx_run_args); }
-extern "C" const char* gmx_last_error(void) { return g_err; }
+extern "C" const char* gmx_last_error(void) { return gmx_err_; }
 extern "C" void gmx_threefry2x32_host(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]) {
   gmx_threefry2x32(k0, k1, c0, c1, &out[0], &out[1]);
 }
@@ -67,10 +69,10 @@ struct HostCtx {
 };
 
 extern "C" int gmx_program_create(const uint32_t* blob, size_t n_words, gmx_program** out) {
-  if (!blob || !out || n_words < GMX_PROG_HEADER_WORDS) return fail("program_create: bad blob");
-  if (blob[0] != GMX_PROG_MAGIC || blob[1] != GMX_PROG_VERSION) return fail("program_create: bad magic/version");
-  if (n_words != GMX_PROG_HEADER_WORDS + 2ull * blob[2] + blob[8]) return fail("program_create: bad length");
-  if (blob[3] == 0 || blob[3] > GMX_MAX_REGS) return fail("program_create: n_regs out of range");
+  if (!blob || !out || n_words < GMX_PROG_HEADER_WORDS) return gmx_fail("program_create: bad blob");
+  if (blob[0] != GMX_PROG_MAGIC || blob[1] != GMX_PROG_VERSION) return gmx_fail("program_create: bad magic/version");
+  if (n_words != GMX_PROG_HEADER_WORDS + 2ull * blob[2] + blob[8]) return gmx_fail("program_create: bad length");
+  if (blob[3] == 0 || blob[3] > GMX_MAX_REGS) return gmx_fail("program_create: n_regs out of range");
   gmx_program* p = new gmx_program;
   p->n_instr = blob[2]; p->n_regs = blob[3]; p->n_in = blob[4]; p->n_out = blob[5]; p->n_uni = blob[6]; p->n_tab = blob[7];
   p->n_const = blob[8]; p->n_dyn = blob[9];
@@ -79,10 +81,10 @@ extern "C" int gmx_program_create(const uint32_t* blob, size_t n_words, gmx_prog
   // the same index validation the HIP library performs
   for (uint32_t pc = 0; pc < p->n_instr; ++pc) {
     uint32_t w0 = p->code[2*pc]; uint32_t op = w0 & 0xff;
-    if (op >= OP__COUNT) { delete p; return fail("program_create: invalid opcode"); }
+    if (op >= OP__COUNT) { delete p; return gmx_fail("program_create: invalid opcode"); }
     uint32_t dst = (w0 >> 8) & 0xff, a = (w0 >> 16) & 0xff, b = w0 >> 24;
     bool regdst = !(op == OP_STOUT || op == OP_END || op == OP_REDMAX || op == OP_REDLSE || op == OP_LOOP || op == OP_ENDLOOP);
-    if (regdst && dst >= p->n_regs) { delete p; return fail("program_create: register out of range"); }
+    if (regdst && dst >= p->n_regs) { delete p; return gmx_fail("program_create: register out of range"); }
     (void)a; (void)b;
   }
   for (uint32_t pc = 0; pc < p->n_instr; ++pc) {
@@ -93,14 +95,14 @@ extern "C" int gmx_program_create(const uint32_t* blob, size_t n_words, gmx_prog
   *out = p; return 0;
 }
 extern "C" int gmx_program_destroy(gmx_program* p) { delete p; return 0; }
-extern "C" int gmx_program_specialize(gmx_program*) { return fail("hostsim: no specialisation"); }
+extern "C" int gmx_program_specialize(gmx_program*) { return gmx_fail("hostsim: no specialisation"); }
 extern "C" int gmx_program_is_specialized(const gmx_program*) { return 0; }
 extern "C" uint64_t gmx_program_code_hash(const gmx_program*) { return 0; }
 extern "C" int gmx_program_despecialize(gmx_program*, const char*) { return 0; }        // (never specialised here)
 extern "C" int64_t gmx_jit_rejected_count(void) { return 0; }
 extern "C" int gmx_program_set_background(gmx_program* p, uint32_t lds_pad) {     // scheduling only: nothing to mirror
-  if (!p) return fail("gmx_program_set_background: null program");
-  if (lds_pad > 160u * 1024u) return fail("gmx_program_set_background: lds_pad above the 160 KB of a CU");
+  if (!p) return gmx_fail("gmx_program_set_background: null program");
+  if (lds_pad > 160u * 1024u) return gmx_fail("gmx_program_set_background: lds_pad above the 160 KB of a CU");
   return 0;
 }
 // Like the specialised 4-particles-per-thread kernel, a program with exactly one OP_REDMAX runs in workgroups of
@@ -121,7 +123,7 @@ static bool hs_gathers(const gmx_program* p) {
   return false;
 }
 extern "C" int gmx_program_set_fuse_resample(gmx_program* p) {
-  if (!p) return fail("gmx_program_set_fuse_resample: null program");
+  if (!p) return gmx_fail("gmx_program_set_fuse_resample: null program");
   p->fuse_rs = true;
   return 0;
 }
@@ -131,7 +133,6 @@ extern "C" int64_t gmx_program_resident_particles(const gmx_program* p) { return
 extern "C" int gmx_program_set_fuse_resample_loop(gmx_program* p) { return gmx_program_set_fuse_resample(p); }   // (the mirror runs tiles in turn anyway)
 extern "C" int gmx_program_fuses_resample(const gmx_program* p) { return p && p->fuse_rs && hs_tile_mode(p) && hs_gathers(p) ? 1 : 0; }
 extern "C" int64_t gmx_program_grid(const gmx_program* p, int64_t n) { return hs_tile_mode(p) ? (n + 1023) / 1024 : (n + 255) / 256; }
-static uint64_t hs_weight_fixed(float lw, float ref, float scale);
 
 static float butterfly_sum64(const float* v) {
   float t[64]; memcpy(t, v, sizeof(t));
@@ -149,24 +150,24 @@ static void hs_peer_put_tile(uint64_t* land, uint32_t tag, int world, int tiles,
   __atomic_store_n(row + 2, gmx_granule(gmx_f2u(tmax), tag), __ATOMIC_RELAXED);
 }
 extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_args* A_in, gmx_stream) {
-  if (!p || !A_in) return fail("program_run: null");
+  if (!p || !A_in) return gmx_fail("program_run: null");
   gmx_run_args patched = *A_in;
   for (uint32_t k = 0; k < p->n_const; ++k) patched.uni[p->n_dyn + k] = p->consts[k];
   const gmx_run_args* A = &patched;
-  for (uint32_t s = 0; s < p->n_in; ++s) if (!A->in_d[s]) return fail("program_run: null input slot");
-  for (uint32_t s = 0; s < p->n_out; ++s) if (!A->out_d[s]) return fail("program_run: null output slot");
+  for (uint32_t s = 0; s < p->n_in; ++s) if (!A->in_d[s]) return gmx_fail("program_run: null input slot");
+  for (uint32_t s = 0; s < p->n_out; ++s) if (!A->out_d[s]) return gmx_fail("program_run: null output slot");
   std::vector<int32_t> rs_anc;
   if (A->rs.lw_d) {          // resample the previous step first: gmx_resample_tiles, tagged ancestors, gather through them
     const gmx_resample_in& q = A->rs;
-    if (!gmx_program_fuses_resample(p)) return fail("program_run: rs is set but this program cannot resample in its own launch");
+    if (!gmx_program_fuses_resample(p)) return gmx_fail("program_run: rs is set but this program cannot resample in its own launch");
     if (!q.tile_max_d || !q.tile_agg_d || !q.max_out_d || !q.total_out_d || !q.status_d || !A->ancestors_d)
-      return fail("program_run: rs has a null pointer");
-    if (q.tag < 1u || q.tag > 255u) return fail("program_run: rs.tag must be in [1, 255]");
-    if ((n + 1023) / 1024 > 1024) return fail("program_run: rs: n <= 2^20");
+      return gmx_fail("program_run: rs has a null pointer");
+    if (q.tag < 1u || q.tag > 255u) return gmx_fail("program_run: rs.tag must be in [1, 255]");
+    if ((n + 1023) / 1024 > 1024) return gmx_fail("program_run: rs: n <= 2^20");
     if (A->tile_agg_d == q.tile_agg_d || (const float*)A->red_out_d == q.tile_max_d)
-      return fail("program_run: rs reads the tile statistics this launch writes (use two sets)");
+      return gmx_fail("program_run: rs reads the tile statistics this launch writes (use two sets)");
     for (uint32_t s_ = 0; s_ < p->n_out; ++s_)
-      if ((const void*)A->out_d[s_] == (const void*)q.lw_d) return fail("program_run: rs.lw_d is also an output of this launch");
+      if ((const void*)A->out_d[s_] == (const void*)q.lw_d) return gmx_fail("program_run: rs.lw_d is also an output of this launch");
     const uint32_t key[2] = {q.key0, q.key1};
     rs_anc.resize((size_t)n);
     if (gmx_resample_tiles(GMX_RESAMPLE_SYSTEMATIC, key, q.lw_d, n, q.shift, q.tile_max_d, q.tile_agg_d, q.max_out_d,
@@ -176,7 +177,7 @@ extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_ar
     patched.ancestors_d = rs_anc.data();       // the program's gathers see the indices
   }
   const bool tile = hs_tile_mode(p);
-  if (A->tile_agg_d && !tile) return fail("program_run: tile_agg_d is set but this program cannot write tile statistics");
+  if (A->tile_agg_d && !tile) return gmx_fail("program_run: tile_agg_d is set but this program cannot write tile statistics");
   const int G = tile ? 1024 : 256;                 // particles per workgroup
   int64_t grid = (n + G - 1) / G;
   std::vector<float> red((size_t)G);
@@ -216,18 +217,14 @@ extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_ar
 }
 
 // ---- logsumexp (sequential; float tolerance vs the device tree) ----
-// (the size the device asks for: 16 bytes on its one-wave-per-row path, two floats per (row, tile of 4096) otherwise)
-extern "C" size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols) {
-  if (rows <= 0 || cols <= 0 || (rows >= 32 && cols <= 4096)) return 16;
-  return (size_t)(rows * ((cols + 4095) / 4096) * 2 * sizeof(float)) + 16;
-}
+extern "C" size_t gmx_logsumexp_workspace(int64_t rows, int64_t cols) { return gmx_logsumexp_bytes_(rows, cols); }
 // special values as the device's kernels (csrc/gmx_kernels.hip, include/genmi.h): an infinite maximum gives m, or NaN
 // when the row holds a NaN; the refusal of more than 65535 rows on the two-stage path is the device's too
 extern "C" int gmx_logsumexp(const float* lw, int64_t rows, int64_t cols, float* out, float* out_max, void*, gmx_stream) {
   if (rows <= 0) return 0;
-  if (cols <= 0) return fail("gmx_logsumexp: cols must be positive");
-  if (!lw || !out) return fail("gmx_logsumexp: null argument");
-  if (!(rows >= 32 && cols <= 4096) && rows > 65535) return fail("gmx_logsumexp: too many long rows");
+  if (cols <= 0) return gmx_fail("gmx_logsumexp: cols must be positive");
+  if (!lw || !out) return gmx_fail("gmx_logsumexp: null argument");
+  if (!gmx_lse_rows_path_(rows, cols) && rows > 65535) return gmx_fail("gmx_logsumexp: too many long rows");
   for (int64_t r = 0; r < rows; ++r) {
     const float* x = lw + r * cols;
     float m = -gmx_inf();
@@ -249,7 +246,7 @@ static float hs_block_sum(const float* v256) {
 }
 extern "C" int gmx_sum_rows_inorder(const float* x, int64_t rows, int64_t cols, int64_t sr, int64_t sc, float* out, gmx_stream) {
   if (rows <= 0) return 0;
-  if (cols < 0 || !x || !out) return fail("sum_rows_inorder: bad argument");
+  if (cols < 0 || !x || !out) return gmx_fail("sum_rows_inorder: bad argument");
   for (int64_t r = 0; r < rows; ++r) {
     float acc = 0.0f;
     for (int64_t c = 0; c < cols; ++c) acc += x[r * sr + c * sc];
@@ -257,22 +254,19 @@ extern "C" int gmx_sum_rows_inorder(const float* x, int64_t rows, int64_t cols, 
   }
   return 0;
 }
-extern "C" size_t gmx_sum_rows_workspace(int64_t rows, int64_t cols) {
-  if (rows <= 0 || cols <= 0) return 16;
-  return (size_t)(rows * ((cols + 4095) / 4096) * sizeof(float)) + 16;
-}
+extern "C" size_t gmx_sum_rows_workspace(int64_t rows, int64_t cols) { return gmx_sum_rows_bytes_(rows, cols); }
 extern "C" int gmx_sum_rows(const float* x, int64_t rows, int64_t cols, float* out, void* ws, gmx_stream) {
   if (rows <= 0) return 0;
-  if (cols <= 0 || !x || !out || !ws) return fail("gmx_sum_rows: bad argument");
-  if (rows > 65535) return fail("gmx_sum_rows: too many rows");
-  const int64_t tiles = (cols + 4095) / 4096;
+  if (cols <= 0 || !x || !out || !ws) return gmx_fail("gmx_sum_rows: bad argument");
+  if (rows > 65535) return gmx_fail("gmx_sum_rows: too many rows");
+  const int64_t tiles = (cols + GMX_LSE_TILE - 1) / GMX_LSE_TILE;
   float* part = (float*)ws;
   for (int64_t r = 0; r < rows; ++r) {
     for (int64_t tile = 0; tile < tiles; ++tile) {
       float v[256];
       for (int t = 0; t < 256; ++t) {
         float s = 0.0f;
-        for (int k = 0; k < 16; ++k) { const int64_t j = tile * 4096 + (int64_t)k * 256 + t; s += j < cols ? x[r * cols + j] : 0.0f; }
+        for (int k = 0; k < 16; ++k) { const int64_t j = tile * GMX_LSE_TILE + (int64_t)k * 256 + t; s += j < cols ? x[r * cols + j] : 0.0f; }
         v[t] = s;
       }
       part[r * tiles + tile] = hs_block_sum(v);
@@ -287,39 +281,65 @@ extern "C" int gmx_sum_rows(const float* x, int64_t rows, int64_t cols, float* o
 extern "C" int gmx_ancestors(int kind, const uint32_t key[2], const uint64_t* cdf, int64_t n_in, uint64_t off,
                              const uint64_t* total_d, int64_t n_out_total, int64_t slot_offset, int64_t n_slots,
                              int32_t* anc, gmx_stream);
-extern "C" int gmx_reduce_max(const float* parts, int64_t n, float* max_d, gmx_stream) {
-  float m = -gmx_inf(); for (int64_t j = 0; j < n; ++j) m = gmx_rmax(m, parts[j]); *max_d = m; return 0;
+static float hs_max(const float* v, int64_t n) {
+  float m = -gmx_inf();
+  for (int64_t j = 0; j < n; ++j) m = gmx_rmax(m, v[j]);
+  return m;
 }
-extern "C" size_t gmx_weight_cdf_workspace(int64_t n) { return 8 + (size_t)((n + 1023) / 1024) * 8; }
-// the two-level integer CDF (include/genmi.h "Resampling"): tiles of 1024 consecutive indices
-static const int64_t HS_TILE = 1024;
+extern "C" int gmx_reduce_max(const float* parts, int64_t n, float* max_d, gmx_stream) { *max_d = hs_max(parts, n); return 0; }
+extern "C" size_t gmx_weight_cdf_workspace(int64_t n) { return gmx_weight_cdf_bytes_(n); }
 // the device's own function (csrc/gmx_math.h): the mirror checks it against the oracle's floor(exp(.) * 2^shift)
 static uint64_t hs_weight_fixed(float lw, float ref, float scale) {
   return gmx_exp_fixed(lw - ref, (int)(gmx_f2u(scale) >> 23) - 127);
 }
-extern "C" int gmx_weight_cdf(const float* lw, int64_t n, int shift, const float* parts, int64_t n_parts, float* max_d,
-                              uint64_t* cdf, uint64_t* total, void*, gmx_stream) {
-  if (n <= 0) return fail("weight_cdf: n");
-  int need = 0; while (((int64_t)1 << need) < n) ++need;
-  if (shift + need > 62) return fail("weight_cdf: shift too large");
-  if (parts) { float m = -gmx_inf(); for (int64_t j = 0; j < n_parts; ++j) m = gmx_rmax(m, parts[j]); *max_d = m; }
-  const float M = *max_d, scale = gmx_pow2i(shift);
-  const int32_t K = gmx_tile_exp(M);
-  uint64_t prefix = 0;
-  for (int64_t lo = 0; lo < n; lo += HS_TILE) {
-    const int64_t hi = lo + HS_TILE < n ? lo + HS_TILE : n;
+// the statistics of the two-level integer CDF (include/genmi.h "Resampling"; tiles of GMX_TILE consecutive indices):
+// m_b = the tile's maximum, A_b = sum floor(exp(lw - k_b ln 2) * 2^shift)
+static void hs_tile_stats(const float* lw, int64_t n, int shift, float* tmax, uint64_t* agg) {
+  const float scale = gmx_pow2i(shift);
+  for (int64_t lo = 0, b = 0; lo < n; lo += GMX_TILE, ++b) {
+    const int64_t hi = lo + GMX_TILE < n ? lo + GMX_TILE : n;
     float m = -gmx_inf();
     for (int64_t i = lo; i < hi; ++i) m = gmx_rmax(m, lw[i]);
-    const int32_t k = gmx_tile_exp(m);
+    const float ref = gmx_tile_ref(gmx_tile_exp(m));
+    uint64_t run = 0;
+    for (int64_t i = lo; i < hi; ++i) run += hs_weight_fixed(lw[i], ref, scale);
+    tmax[b] = m; agg[b] = run;
+  }
+}
+// THE rebuild of a shard's CDF from its log-weights and tile maxima, relative to the exponent K:
+//   cdf_i = P_b + ((the tile-local inclusive sum up to i) >> (K - k_b)),  b = the tile of i.
+// The prefixes P_b run over the tile sums `agg` (A_b >> (K - k_b)) — or are read from the prefix block `pref` of
+// gmx_tile_prefix (agg == nullptr).  Returns the total.  pref_ok: every prefix of the block is what the log-weights give.
+static uint64_t hs_cdf(const float* lw, int64_t n, int shift, const float* tmax, int32_t K, const uint64_t* agg,
+                       const uint64_t* pref, uint64_t* cdf, bool* pref_ok = nullptr) {
+  const float scale = gmx_pow2i(shift);
+  const int64_t tiles = gmx_tiles_(n);
+  uint64_t prefix = 0;
+  if (pref_ok) *pref_ok = true;
+  for (int64_t b = 0; b < tiles; ++b) {
+    const int64_t lo = b * GMX_TILE, hi = lo + GMX_TILE < n ? lo + GMX_TILE : n;
+    const int32_t k = gmx_tile_exp(tmax[b]);
     const float ref = gmx_tile_ref(k);
+    if (!agg) prefix = pref[b];
     uint64_t run = 0;
     for (int64_t i = lo; i < hi; ++i) {
       run += hs_weight_fixed(lw[i], ref, scale);
       cdf[i] = prefix + gmx_tile_scale(run, k, K);
     }
-    prefix += gmx_tile_scale(run, k, K);
+    if (agg) prefix += gmx_tile_scale(agg[b], k, K);
+    else if (pref_ok && prefix + gmx_tile_scale(run, k, K) != pref[b + 1]) *pref_ok = false;
   }
-  *total = prefix;
+  return agg ? prefix : pref[tiles];
+}
+extern "C" int gmx_weight_cdf(const float* lw, int64_t n, int shift, const float* parts, int64_t n_parts, float* max_d,
+                              uint64_t* cdf, uint64_t* total, void*, gmx_stream) {
+  if (n <= 0) return gmx_fail("weight_cdf: n");
+  if (shift + gmx_ceil_log2_(n) > 62) return gmx_fail("weight_cdf: shift too large");
+  if (parts) *max_d = hs_max(parts, n_parts);
+  std::vector<float> tmax((size_t)gmx_tiles_(n));
+  std::vector<uint64_t> agg((size_t)gmx_tiles_(n));
+  hs_tile_stats(lw, n, shift, tmax.data(), agg.data());
+  *total = hs_cdf(lw, n, shift, tmax.data(), gmx_tile_exp(*max_d), agg.data(), nullptr, cdf);
   return 0;
 }
 typedef unsigned __int128 u128;
@@ -346,63 +366,36 @@ extern "C" int gmx_ancestors(int kind, const uint32_t key[2], const uint64_t* cd
   }
   return 0;
 }
-extern "C" size_t gmx_resample_workspace(int64_t) { return 2048 * 12; }
+extern "C" size_t gmx_resample_workspace(int64_t n) { return gmx_resample_bytes_(n); }
 extern "C" int gmx_tile_stats(const float* lw, int64_t n, int shift, float* tmax, uint64_t* agg, gmx_stream) {
-  if (n <= 0 || !lw || !tmax || !agg) return fail("tile_stats: bad argument");
-  const float scale = gmx_pow2i(shift);
-  for (int64_t lo = 0, b = 0; lo < n; lo += HS_TILE, ++b) {
-    const int64_t hi = lo + HS_TILE < n ? lo + HS_TILE : n;
-    float m = -gmx_inf();
-    for (int64_t i = lo; i < hi; ++i) m = gmx_rmax(m, lw[i]);
-    const float ref = gmx_tile_ref(gmx_tile_exp(m));
-    uint64_t run = 0;
-    for (int64_t i = lo; i < hi; ++i) run += hs_weight_fixed(lw[i], ref, scale);
-    tmax[b] = m; agg[b] = run;
-  }
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_STATS, 0, n, shift, !lw || !tmax || !agg, lw)) return gmx_fail(m, "gmx_tile_stats");
+  hs_tile_stats(lw, n, shift, tmax, agg);
   return 0;
 }
-extern "C" size_t gmx_multinomial_workspace(int64_t n_in) { return (size_t)(n_in + 4) * 4; }
+extern "C" size_t gmx_multinomial_workspace(int64_t n_in) { return gmx_multinomial_bytes_(n_in); }
 // the mirror states the definition: the per-slot search of gmx_ancestors
 extern "C" int gmx_multinomial(const uint32_t key[2], const uint64_t* cdf, int64_t n_in, const uint64_t* total, int64_t n_out,
                                int32_t* anc, void* ws, gmx_stream st) {
-  if (!ws) return fail("multinomial: null workspace");
+  if (!ws) return gmx_fail("multinomial: null workspace");
   return gmx_ancestors(GMX_RESAMPLE_MULTINOMIAL, key, cdf, n_in, 0, total, n_out, 0, n_out, anc, st);
 }
 // the mirror rebuilds the global CDF from log-weights + tile stats and searches it per slot
 extern "C" int gmx_resample_tiles(int kind, const uint32_t key[2], const float* lw, int64_t n, int shift, const float* tmax,
                                   const uint64_t* agg, float* max_d, uint64_t* total, int32_t* anc, gmx_stream st) {
-  if (kind == GMX_RESAMPLE_MULTINOMIAL) return fail("resample: kind");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE;
-  float M = -gmx_inf();
-  for (int64_t b = 0; b < tiles; ++b) M = gmx_rmax(M, tmax[b]);
-  const float scale = gmx_pow2i(shift);
-  const int32_t K = gmx_tile_exp(M);
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES, kind, n, shift, !key || !lw || !tmax || !agg || !max_d || !total || !anc, lw))
+    return gmx_fail(m, "gmx_resample_tiles");
   std::vector<uint64_t> cdf((size_t)n);
-  uint64_t prefix = 0;
-  for (int64_t b = 0; b < tiles; ++b) {
-    const int64_t lo = b * HS_TILE, hi = lo + HS_TILE < n ? lo + HS_TILE : n;
-    const int32_t k = gmx_tile_exp(tmax[b]);
-    const float ref = gmx_tile_ref(k);
-    uint64_t run = 0;
-    for (int64_t i = lo; i < hi; ++i) {
-      run += hs_weight_fixed(lw[i], ref, scale);
-      cdf[(size_t)i] = prefix + gmx_tile_scale(run, k, K);
-    }
-    prefix += gmx_tile_scale(agg[b], k, K);
-  }
-  *max_d = M; *total = prefix;
+  *max_d = hs_max(tmax, gmx_tiles_(n));
+  *total = hs_cdf(lw, n, shift, tmax, gmx_tile_exp(*max_d), agg, nullptr, cdf.data());
   return gmx_ancestors(kind, key, cdf.data(), n, 0, total, n, 0, n, anc, st);
 }
 // tile statistics -> tile prefixes (sequential statement of gmx_block.h: gmx_tile_prefix_block)
-extern "C" size_t gmx_tile_prefix_words(int64_t n) {       // prefixes | total | M, K | pad to 16
-  return (size_t)(((n + HS_TILE - 1) / HS_TILE + 2 + 15) / 16) * 16;
-}
+extern "C" size_t gmx_tile_prefix_words(int64_t n) { return gmx_tile_prefix_words_(n); }
 extern "C" int gmx_tile_prefix(const float* tmax, const uint64_t* agg, int64_t n, uint64_t* pref, gmx_stream) {
-  if (n <= 0 || !tmax || !agg || !pref) return fail("tile_prefix: bad argument");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE;
-  if (n > 0x7fffffffLL) return fail("tile_prefix: n out of range");
-  float M = -gmx_inf();
-  for (int64_t b = 0; b < tiles; ++b) M = gmx_rmax(M, tmax[b]);
+  if (n <= 0 || !tmax || !agg || !pref) return gmx_fail("tile_prefix: bad argument");
+  const int64_t tiles = gmx_tiles_(n);
+  if (n > 0x7fffffffLL) return gmx_fail("tile_prefix: n out of range");
+  const float M = hs_max(tmax, tiles);
   const int32_t K = gmx_tile_exp(M);
   uint64_t run = 0;
   for (int64_t b = 0; b < tiles; ++b) { pref[b] = run; run += gmx_tile_scale(agg[b], gmx_tile_exp(tmax[b]), K); }
@@ -414,50 +407,40 @@ extern "C" int gmx_tile_prefix(const float* tmax, const uint64_t* agg, int64_t n
 // statistics-free definition (the CDF rebuilt from the log-weights alone) on the way
 extern "C" int gmx_resample_tiles_p(int kind, const uint32_t key[2], const float* lw, int64_t n, int shift, const float* tmax,
                                     const uint64_t* pref, float* max_d, uint64_t* total, int32_t* anc, gmx_stream st) {
-  if (kind == GMX_RESAMPLE_MULTINOMIAL) return fail("resample: kind");
-  if (!lw || !tmax || !pref || !max_d || !total || !anc) return fail("resample_tiles_p: bad argument");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE;
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES_P, kind, n, shift, !key || !lw || !tmax || !pref || !max_d || !total || !anc, lw))
+    return gmx_fail(m, "gmx_resample_tiles_p");
+  const int64_t tiles = gmx_tiles_(n);
   const float M = gmx_u2f((uint32_t)pref[tiles + 1]);
   const int32_t K = (int32_t)(uint32_t)(pref[tiles + 1] >> 32);
-  if (K != gmx_tile_exp(M)) return fail("resample_tiles_p: (M, K) of the prefix block disagree");
-  const float scale = gmx_pow2i(shift);
+  if (K != gmx_tile_exp(M)) return gmx_fail("resample_tiles_p: (M, K) of the prefix block disagree");
   std::vector<uint64_t> cdf((size_t)n);
-  for (int64_t b = 0; b < tiles; ++b) {
-    const int64_t lo = b * HS_TILE, hi = lo + HS_TILE < n ? lo + HS_TILE : n;
-    const int32_t k = gmx_tile_exp(tmax[b]);
-    const float ref = gmx_tile_ref(k);
-    uint64_t run = 0;
-    for (int64_t i = lo; i < hi; ++i) {
-      run += hs_weight_fixed(lw[i], ref, scale);
-      cdf[(size_t)i] = pref[b] + gmx_tile_scale(run, k, K);
-    }
-    const uint64_t next = pref[b] + gmx_tile_scale(run, k, K);
-    if (next != pref[b + 1]) return fail("resample_tiles_p: the prefixes do not match the log-weights");
-  }
-  *max_d = M; *total = pref[tiles];
+  bool ok;
+  *max_d = M; *total = hs_cdf(lw, n, shift, tmax, K, nullptr, pref, cdf.data(), &ok);
+  if (!ok) return gmx_fail("resample_tiles_p: the prefixes do not match the log-weights");
   return gmx_ancestors(kind, key, cdf.data(), n, 0, total, n, 0, n, anc, st);
 }
 // two-stage multinomial resampling (include/genmi.h: gmx_multinomial_tiled) — the sequential statement
-extern "C" size_t gmx_multinomial_tiled_workspace(int64_t n) { return (size_t)((n + HS_TILE - 1) / HS_TILE + 16) * 8; }
+extern "C" size_t gmx_multinomial_tiled_workspace(int64_t n) { return gmx_multinomial_tiled_bytes_(n); }
 extern "C" int gmx_multinomial_tiled(const uint32_t key[2], const float* lw, int64_t n, int shift, const float* tmax,
                                      const uint64_t* agg, const uint32_t* u_d, float* max_d, uint64_t* total_d,
                                      int32_t* anc, void* ws, int phase, gmx_stream) {
-  if (!key || !lw || !tmax || !agg || !max_d || !total_d || !anc || !ws || n <= 0 || shift < 1 || phase < -1 || phase > 1)
-    return fail("multinomial_tiled: bad argument");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE;
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_MN_TILED, GMX_RESAMPLE_MULTINOMIAL_TILED, n, shift,
+                                             !key || !lw || !tmax || !agg || !max_d || !total_d || !anc || !ws, lw, ws, phase))
+    return gmx_fail(m, "gmx_multinomial_tiled");
+  const int64_t tiles = gmx_tiles_(n);
   // the two-buffer protocol of the device entry, checked: the buffer of this phase must arrive zero
   uint32_t* buf = (uint32_t*)ws + (phase == 1 ? tiles + 16 : 0);
   uint32_t* other = (uint32_t*)ws + (phase == 1 ? 0 : tiles + 16);
   if (phase >= 0)
     for (int64_t b = 0; b < tiles; ++b)
-      if (buf[b]) return fail("multinomial_tiled: the count buffer of this phase is not zero (alternate the phases)");
+      if (buf[b]) return gmx_fail("multinomial_tiled: the count buffer of this phase is not zero (alternate the phases)");
   struct Leave { uint32_t* o; int64_t t; ~Leave() { for (int64_t b = 0; b < t; ++b) o[b] = 0; } } leave{other, tiles};
-  float M = -gmx_inf();
-  for (int64_t b = 0; b < tiles; ++b) M = gmx_rmax(M, tmax[b]);
+  const float M = hs_max(tmax, tiles);
   const int32_t K = gmx_tile_exp(M);
-  std::vector<uint64_t> cend((size_t)tiles), G((size_t)tiles);
+  std::vector<uint64_t> cend((size_t)tiles), G((size_t)tiles), cdf((size_t)n);
   uint64_t total = 0;
   for (int64_t b = 0; b < tiles; ++b) { G[b] = gmx_tile_scale(agg[b], gmx_tile_exp(tmax[b]), K); total += G[b]; cend[b] = total; }
+  hs_cdf(lw, n, shift, tmax, K, agg, nullptr, cdf.data());
   *max_d = M; *total_d = total;
   if (total == 0) { for (int64_t i = 0; i < n; ++i) anc[i] = (int32_t)(n - 1); return 0; }
   gmx_key k; k.k0 = key[0]; k.k1 = key[1];
@@ -466,37 +449,33 @@ extern "C" int gmx_multinomial_tiled(const uint32_t key[2], const float* lw, int
   for (int64_t b = 0; b < tiles; ++b) counts[b] = 0;
   for (int64_t j = 0; j < n; ++j) {
     const uint32_t u = gmx_bits32(k1, (uint64_t)j) >> 9;
-    if (u_d && u_d[j] != u) return fail("multinomial_tiled: u_d is not split(key, 2)[0]'s slot uniforms");
+    if (u_d && u_d[j] != u) return gmx_fail("multinomial_tiled: u_d is not split(key, 2)[0]'s slot uniforms");
     const uint64_t P = (uint64_t)(((u128)u * (u128)total) >> 23);
     int64_t lo = 0, hi = tiles;
     while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (cend[mid] > P) hi = mid; else lo = mid + 1; }
     ++counts[lo];
   }
-  const float scale = gmx_pow2i(shift);
   int64_t pos = 0;
   for (int64_t b = 0; b < tiles; ++b) {
-    const int64_t lo_i = b * HS_TILE, hi_i = lo_i + HS_TILE < n ? lo_i + HS_TILE : n;
-    const int32_t kb_e = gmx_tile_exp(tmax[b]);
-    const float ref = gmx_tile_ref(kb_e);
-    std::vector<uint64_t> loc((size_t)(hi_i - lo_i));
-    uint64_t run = 0;
-    for (int64_t i = lo_i; i < hi_i; ++i) { run += hs_weight_fixed(lw[i], ref, scale); loc[(size_t)(i - lo_i)] = gmx_tile_scale(run, kb_e, K); }
+    const int64_t lo_i = b * GMX_TILE, hi_i = lo_i + GMX_TILE < n ? lo_i + GMX_TILE : n;
+    const uint64_t* loc = cdf.data() + lo_i;              // the tile's own CDF: cdf_i - before
+    const uint64_t before = cend[b] - G[b];
     const gmx_key kb = gmx_fold_in(k2, (uint32_t)b);
     for (uint32_t r = 0; r < counts[b]; ++r) {
       const uint32_t v = gmx_bits32(kb, (uint64_t)r) >> 9;
       const uint64_t Q = (uint64_t)(((u128)v * (u128)G[b]) >> 23);
       int64_t a = 0, z = hi_i - lo_i;
-      while (a < z) { int64_t mid = (a + z) >> 1; if (loc[(size_t)mid] > Q) z = mid; else a = mid + 1; }
+      while (a < z) { int64_t mid = (a + z) >> 1; if (loc[mid] - before > Q) z = mid; else a = mid + 1; }
       anc[pos++] = (int32_t)(lo_i + a);
     }
   }
-  if (pos != n) return fail("multinomial_tiled: the tile counts do not add up to n");
+  if (pos != n) return gmx_fail("multinomial_tiled: the tile counts do not add up to n");
   return 0;
 }
 // the stratified resampler's uniforms ahead of time, and the resampler that reads them (the mirror checks that what it
 // is handed IS what the resampling would draw, then resamples as usual)
 extern "C" int gmx_slot_uniforms(const uint32_t* keys, int rows, int64_t n, uint32_t* out, int lds_pad, gmx_stream) {
-  if (!keys || !out || rows < 1 || n <= 0 || lds_pad < 0) return fail("slot_uniforms: bad argument");
+  if (!keys || !out || rows < 1 || n <= 0 || lds_pad < 0) return gmx_fail("slot_uniforms: bad argument");
   for (int r = 0; r < rows; ++r) {
     gmx_key k; k.k0 = keys[2 * r]; k.k1 = keys[2 * r + 1];
     for (int64_t j = 0; j < n; ++j) out[(int64_t)r * n + j] = gmx_bits32(k, (uint64_t)j) >> 9;
@@ -506,18 +485,18 @@ extern "C" int gmx_slot_uniforms(const uint32_t* keys, int rows, int64_t n, uint
 extern "C" int gmx_resample_tiles_u(int kind, const uint32_t key[2], const float* lw, int64_t n, int shift, const float* tmax,
                                     const uint64_t* agg, const uint32_t* u, float* max_d, uint64_t* total, int32_t* anc,
                                     gmx_stream st) {
-  if (kind != GMX_RESAMPLE_STRATIFIED) return fail("resample_tiles_u: stratified only");
-  if (!key || !u) return fail("resample_tiles_u: bad argument");
+  if (const char* m = gmx_tile_form_refusal_(GMX_FORM_TILES_U, kind, n, shift, !key || !lw || !tmax || !agg || !u || !max_d || !total || !anc, lw))
+    return gmx_fail(m, "gmx_resample_tiles_u");
   gmx_key k; k.k0 = key[0]; k.k1 = key[1];
   for (int64_t j = 0; j < n; ++j)
-    if (u[j] != (gmx_bits32(k, (uint64_t)j) >> 9)) return fail("resample_tiles_u: u_d is not this key's slot uniforms");
+    if (u[j] != (gmx_bits32(k, (uint64_t)j) >> 9)) return gmx_fail("resample_tiles_u: u_d is not this key's slot uniforms");
   return gmx_resample_tiles(kind, key, lw, n, shift, tmax, agg, max_d, total, anc, st);
 }
 // multinomial resampling with sorted uniforms (csrc/gmx_sorted.h): the table from its definition, sequentially; the
 // resampler rebuilds the CDF and merges it with the sums read back from the TABLE (so a wrong table gives wrong ancestors),
 // after checking the table against the key when it was handed one
 #include "../../genjax_amd/csrc/gmx_sorted.h"
-extern "C" size_t gmx_sorted_uniforms_words(int64_t n) { return n > 0 ? gmx_sorted_layout_of(n).words : 0; }
+extern "C" size_t gmx_sorted_uniforms_words(int64_t n) { return gmx_sorted_uniforms_words_(n); }
 static void hs_sorted_row(gmx_key k, int64_t n, uint32_t* row) {
   const gmx_sorted_layout L = gmx_sorted_layout_of(n);
   uint64_t* tsum = (uint64_t*)(row + L.off_tsum);
@@ -545,7 +524,7 @@ static void hs_sorted_row(gmx_key k, int64_t n, uint32_t* row) {
   }
 }
 extern "C" int gmx_sorted_uniforms(const uint32_t* keys, int rows, int64_t n, uint32_t* out, int lds_pad, gmx_stream) {
-  if (!keys || !out || rows < 1 || n <= 0 || lds_pad < 0) return fail("sorted_uniforms: bad argument");
+  if (!keys || !out || rows < 1 || n <= 0 || lds_pad < 0) return gmx_fail("sorted_uniforms: bad argument");
   const size_t words = gmx_sorted_layout_of(n).words;
   for (int r = 0; r < rows; ++r) {
     gmx_key k; k.k0 = keys[2 * r]; k.k1 = keys[2 * r + 1];
@@ -557,8 +536,9 @@ extern "C" int gmx_sorted_uniforms(const uint32_t* keys, int rows, int64_t n, ui
 static int hs_resample_sorted(const uint32_t key[2], const float* lw, int64_t n, int shift, const float* tmax,
                               const uint64_t* agg, bool prefixes, uint32_t* table, int table_ready, float* max_d, uint64_t* total,
                               int32_t* anc) {
-  if (!key || !lw || !tmax || !agg || !table || !max_d || !total || !anc || n <= 0 || (!prefixes && n > 2048 * HS_TILE))
-    return fail("resample_sorted: bad argument");
+  if (const char* m = gmx_tile_form_refusal_(prefixes ? GMX_FORM_SORTED_P : GMX_FORM_SORTED, GMX_RESAMPLE_MULTINOMIAL_SORTED, n, shift,
+                                             !key || !lw || !tmax || !agg || !table || !max_d || !total || !anc, lw, table))
+    return gmx_fail(m, prefixes ? "gmx_resample_sorted_p" : "gmx_resample_sorted");
   gmx_key k; k.k0 = key[0]; k.k1 = key[1];
   const gmx_sorted_layout L = gmx_sorted_layout_of(n);
   if (table_ready) {
@@ -569,28 +549,13 @@ static int hs_resample_sorted(const uint32_t key[2], const float* lw, int64_t n,
     if (memcmp(want.data(), table, (size_t)L.tiles * GMX_SORTED_TILE * 4) ||
         memcmp(want.data() + L.off_guide, table + L.off_guide, (gtop + 1) * 4) ||
         memcmp(want.data() + L.off_toff, table + L.off_toff, ((size_t)L.tiles + 1) * 8) || want[L.off_sh] != table[L.off_sh])
-      return fail("resample_sorted: table_d is not this key's order-statistics table");
+      return gmx_fail("resample_sorted: table_d is not this key's order-statistics table");
   } else {
     hs_sorted_row(k, n, table);
   }
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE;
-  float M = -gmx_inf();
-  for (int64_t b = 0; b < tiles; ++b) M = gmx_rmax(M, tmax[b]);
-  const float scale = gmx_pow2i(shift);
-  const int32_t K = gmx_tile_exp(M);
+  const float M = hs_max(tmax, gmx_tiles_(n));
   std::vector<uint64_t> cdf((size_t)n);
-  uint64_t prefix = 0;
-  for (int64_t b = 0; b < tiles; ++b) {
-    const int64_t lo = b * HS_TILE, hi = lo + HS_TILE < n ? lo + HS_TILE : n;
-    const int32_t kb = gmx_tile_exp(tmax[b]);
-    const float ref = gmx_tile_ref(kb);
-    uint64_t run = 0;
-    for (int64_t i = lo; i < hi; ++i) {
-      run += hs_weight_fixed(lw[i], ref, scale);
-      cdf[(size_t)i] = prefix + gmx_tile_scale(run, kb, K);
-    }
-    prefix = prefixes ? (b + 1 < tiles ? agg[b + 1] : agg[tiles]) : prefix + gmx_tile_scale(agg[b], kb, K);
-  }
+  const uint64_t prefix = hs_cdf(lw, n, shift, tmax, gmx_tile_exp(M), prefixes ? nullptr : agg, prefixes ? agg : nullptr, cdf.data());
   *max_d = M; *total = prefix;
   if (prefix == 0) { for (int64_t j = 0; j < n; ++j) anc[j] = (int32_t)(n - 1); return 0; }
   const uint64_t* toff = (const uint64_t*)(table + L.off_toff);
@@ -615,11 +580,10 @@ extern "C" int gmx_resample_sorted_p(const uint32_t key[2], const float* lw, int
                                      int32_t* anc, gmx_stream) {
   return hs_resample_sorted(key, lw, n, shift, tmax, pref, true, table, table_ready, max_d, total, anc);
 }
+// the product's dispatch over the mirror's entry points (csrc/gmx_sizes.h)
 extern "C" int gmx_resample(int kind, const uint32_t key[2], const float* lw, int64_t n, int shift, const float*,
                             int64_t, float* max_d, uint64_t* total, int32_t* anc, void* ws, gmx_stream st) {
-  uint64_t* agg = (uint64_t*)ws; float* tmax = (float*)(agg + 2048);
-  if (gmx_tile_stats(lw, n, shift, tmax, agg, st)) return 1;
-  return gmx_resample_tiles(kind, key, lw, n, shift, tmax, agg, max_d, total, anc, st);
+  return gmx_resample_dispatch_(kind, key, lw, n, shift, max_d, total, anc, ws, st);
 }
 // ---- global resampling across ranks: destination-centric restatement ----
 static int64_t hs_slots_below(int kind, gmx_key k, uint64_t c, uint64_t total, int64_t N) {
@@ -635,10 +599,10 @@ static int64_t hs_slots_below(int kind, gmx_key k, uint64_t c, uint64_t total, i
   }
   return lo;
 }
-extern "C" size_t gmx_shard_plan_words(int world) { return (size_t)(GMX_PLAN_BOUNDS + world + 1); }
+extern "C" size_t gmx_shard_plan_words(int world) { return gmx_shard_plan_words_(world); }
 extern "C" int gmx_shard_plan(int kind, const uint32_t key[2], const uint64_t* totals, int rank, int world, int64_t n,
                               int64_t* plan, uint64_t* total_out, gmx_stream) {
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED) return fail("shard_plan: kind");
+  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED) return gmx_fail("shard_plan: kind");
   gmx_key k; k.k0 = key[0]; k.k1 = key[1];
   int64_t N = n * world;
   uint64_t total = 0, off = 0;
@@ -653,9 +617,22 @@ extern "C" int gmx_shard_plan(int kind, const uint32_t key[2], const uint64_t* t
   if (total_out) *total_out = total;
   return 0;
 }
+// the slots of this rank whose ancestor is remote: an index into the receive area the exchange fills (the k-th slot
+// that rank s sources here sits at n + s * cap + k), or the overflow flag
+static void hs_remote_slots(int64_t* plan, int rank, int world, int64_t n, int64_t cap, int32_t* next_idx) {
+  const int64_t* bounds = plan + GMX_PLAN_BOUNDS;
+  const int64_t base = (int64_t)rank * n;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t jj = base + i;
+    int s = 0; while (s + 1 < world && bounds[s + 1] <= jj) ++s;
+    if (s == rank) continue;
+    const int64_t first = bounds[s] > base ? bounds[s] : base, k = jj - first;
+    if (k < cap) next_idx[i] = (int32_t)(n + (int64_t)s * cap + k); else { next_idx[i] = 0; plan[GMX_PLAN_OVERFLOW] = 1; }
+  }
+}
 extern "C" int gmx_shard_route(int kind, const uint32_t key[2], int64_t* plan, const uint64_t* cdf, int rank, int world,
                                int64_t n, int64_t cap, const void* state_v, void* send_v, int32_t* next_idx, gmx_stream st) {
-  if (cap < 1 || cap > n) return fail("shard_route: capacity");
+  if (cap < 1 || cap > n) return gmx_fail("shard_route: capacity");
   const uint32_t* state = (const uint32_t*)state_v; uint32_t* send = (uint32_t*)send_v;
   const int64_t* bounds = plan + GMX_PLAN_BOUNDS;
   const int64_t N = n * world, base = (int64_t)rank * n, S = bounds[rank], E = bounds[rank + 1];
@@ -671,13 +648,7 @@ extern "C" int gmx_shard_route(int kind, const uint32_t key[2], int64_t* plan, c
       if (k < cap) send[d * cap + k] = state[a]; else plan[GMX_PLAN_OVERFLOW] = 1;
     }
   }
-  for (int64_t i = 0; i < n; ++i) {
-    int64_t jj = base + i;
-    int s = 0; while (s + 1 < world && bounds[s + 1] <= jj) ++s;
-    if (s == rank) continue;
-    int64_t first = bounds[s] > base ? bounds[s] : base, k = jj - first;
-    if (k < cap) next_idx[i] = (int32_t)(n + (int64_t)s * cap + k); else { next_idx[i] = 0; plan[GMX_PLAN_OVERFLOW] = 1; }
-  }
+  hs_remote_slots(plan, rank, world, n, cap, next_idx);
   return 0;
 }
 extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* totals, int64_t* plan, uint64_t* total_out,
@@ -693,7 +664,7 @@ extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* t
 extern "C" int gmx_shard_step_sorted(const uint32_t* table, const uint64_t* totals, int64_t* plan, uint64_t* total_out,
                                      const uint64_t* cdf, int rank, int world, int64_t n, int64_t cap,
                                      const void* state_v, void* send_v, int32_t* next_idx, gmx_stream) {
-  if (cap < 1 || cap > n) return fail("shard_step_sorted: capacity");
+  if (cap < 1 || cap > n) return gmx_fail("shard_step_sorted: capacity");
   const int64_t N = n * world, base = (int64_t)rank * n;
   const gmx_sorted_layout L = gmx_sorted_layout_of(N);
   const uint64_t* toff = (const uint64_t*)(table + L.off_toff);
@@ -725,19 +696,13 @@ extern "C" int gmx_shard_step_sorted(const uint32_t* table, const uint64_t* tota
     if (d == rank) next_idx[j - base] = (int32_t)i;
     else { int64_t first = S > d * n ? S : d * n, k = j - first; if (k < cap) send[d * cap + k] = state[i]; else plan[GMX_PLAN_OVERFLOW] = 1; }
   }
-  for (int64_t q = 0; q < n; ++q) {
-    int64_t jj = base + q;
-    int s = 0; while (s + 1 < world && bounds[s + 1] <= jj) ++s;
-    if (s == rank) continue;
-    int64_t first = bounds[s] > base ? bounds[s] : base, k = jj - first;
-    if (k < cap) next_idx[q] = (int32_t)(n + (int64_t)s * cap + k); else { next_idx[q] = 0; plan[GMX_PLAN_OVERFLOW] = 1; }
-  }
+  hs_remote_slots(plan, rank, world, n, cap, next_idx);
   return 0;
 }
-extern "C" size_t gmx_shard_stats_bytes(int64_t n) { int64_t t = (n + HS_TILE - 1) / HS_TILE; t += t & 1; return (size_t)t * 12; }
+extern "C" size_t gmx_shard_stats_bytes(int64_t n) { return gmx_shard_stats_bytes_(n); }
 extern "C" int gmx_shard_totals(const void* stats_all, int world, int64_t n, uint64_t* totals, float* max_d, gmx_stream) {
-  if (!stats_all || !totals || !max_d) return fail("shard_totals: null argument");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE, pad = tiles + (tiles & 1);
+  if (!stats_all || !totals || !max_d) return gmx_fail("shard_totals: null argument");
+  const int64_t tiles = gmx_tiles_(n), pad = tiles + (tiles & 1);
   const size_t stride = gmx_shard_stats_bytes(n);
   float M = -gmx_inf();
   for (int r = 0; r < world; ++r) {
@@ -759,29 +724,19 @@ extern "C" int gmx_shard_totals(const void* stats_all, int world, int64_t n, uin
 extern "C" int gmx_shard_step_tiles(int kind, const uint32_t key[2], const uint64_t* totals, int64_t* plan, uint64_t* total_out,
                                     const float* lw, const void* stats_own, const float* max_d, int shift, int rank, int world,
                                     int64_t n, int64_t cap, const void* state, void* send, int32_t* next_idx, gmx_stream st) {
-  if (!lw || !stats_own || !max_d) return fail("shard_step_tiles: null argument");
-  const int64_t tiles = (n + HS_TILE - 1) / HS_TILE, pad = tiles + (tiles & 1);
+  if (!lw || !stats_own || !max_d) return gmx_fail("shard_step_tiles: null argument");
+  const int64_t tiles = gmx_tiles_(n), pad = tiles + (tiles & 1);
   const uint64_t* ag = (const uint64_t*)stats_own;
   const float* tm = (const float*)((const uint8_t*)stats_own + pad * 8);
-  const int32_t K = gmx_tile_exp(*max_d);
-  const float scale = gmx_pow2i(shift);
   std::vector<uint64_t> cdf((size_t)n);
-  uint64_t prefix = 0;
-  for (int64_t b = 0; b < tiles; ++b) {
-    const int64_t lo = b * HS_TILE, hi = lo + HS_TILE < n ? lo + HS_TILE : n;
-    const int32_t k = gmx_tile_exp(tm[b]);
-    const float ref = gmx_tile_ref(k);
-    uint64_t run = 0;
-    for (int64_t i = lo; i < hi; ++i) { run += hs_weight_fixed(lw[i], ref, scale); cdf[(size_t)i] = prefix + gmx_tile_scale(run, k, K); }
-    prefix += gmx_tile_scale(ag[b], k, K);
-  }
+  hs_cdf(lw, n, shift, tm, gmx_tile_exp(*max_d), ag, nullptr, cdf.data());
   return gmx_shard_step(kind, key, totals, plan, total_out, cdf.data(), rank, world, n, cap, state, send, next_idx, st);
 }
 // the one-launch form: the totals from the gathered table, then the step with this rank's own block of it
 extern "C" int gmx_shard_step_fused(int kind, const uint32_t key[2], const void* stats_all, int64_t* plan, uint64_t* total_out,
                                     const float* lw, float* max_out, int shift, int rank, int world, int64_t n, int64_t cap,
                                     const void* state, void* send, int32_t* next_idx, gmx_stream st) {
-  if (!stats_all || !max_out || world < 1 || world > 64) return fail("shard_step_fused: bad argument");
+  if (!stats_all || !max_out || world < 1 || world > 64) return gmx_fail("shard_step_fused: bad argument");
   std::vector<uint64_t> totals((size_t)world);
   if (gmx_shard_totals(stats_all, world, n, totals.data(), max_out, st)) return 1;
   const void* own = (const uint8_t*)stats_all + (size_t)rank * gmx_shard_stats_bytes(n);
@@ -792,31 +747,30 @@ extern "C" int gmx_shard_step_fused(int kind, const uint32_t key[2], const void*
 #include <sched.h>
 #include <time.h>
 extern "C" size_t gmx_peer_landing_bytes(int world, int64_t n, int64_t cap, int leaves) {
-  if (world < 1 || n < 1 || cap < 1 || leaves < 1) return 0;
-  return (gmx_peer_stats_words(world, (int)((n + HS_TILE - 1) / HS_TILE)) + gmx_peer_state_words(world, cap, leaves)) * 8;
+  return gmx_peer_landing_bytes_(world, n, cap, leaves);
 }
 extern "C" int gmx_peer_bump(uint32_t* tag_base, int32_t T, gmx_stream) {
-  if (!tag_base || T < 1) return fail("peer_bump: bad argument");
+  if (!tag_base || T < 1) return gmx_fail("peer_bump: bad argument");
   *tag_base += (uint32_t)T;
   return 0;
 }
 extern "C" int gmx_sweep_verdict(const int64_t* overflow, const uint64_t* const* status, int32_t n_status, int64_t* verdict,
                                  gmx_stream) {
-  if (!overflow || !verdict || n_status < 0 || n_status > 4 || (n_status && !status)) return fail("sweep_verdict: bad argument");
+  if (!overflow || !verdict || n_status < 0 || n_status > 4 || (n_status && !status)) return gmx_fail("sweep_verdict: bad argument");
   bool bad = false;
   for (int k = 0; k < n_status; ++k) bad = bad || (status[k] && *status[k] != 0);
   *verdict = bad ? 2 : *overflow;
   return 0;
 }
 static int hs_peer_check(const gmx_peer& P, int64_t n) {
-  if (!P.land_d || !P.tag_base_d || !P.status_d) return fail("peer: null pointer");
-  if (P.world < 1 || P.world > 64 || P.rank < 0 || P.rank >= P.world || P.step < 0) return fail("peer: rank / world / step out of range");
-  if (n <= 0 || P.tiles != (int32_t)((n + HS_TILE - 1) / HS_TILE)) return fail("peer: tiles must be ceil(n / 1024)");
-  if (P.capacity < 1 || P.capacity > n || P.leaves < 1 || P.leaves > GMX_PEER_MAX_LEAVES) return fail("peer: capacity / leaves out of range");
+  if (!P.land_d || !P.tag_base_d || !P.status_d) return gmx_fail("peer: null pointer");
+  if (P.world < 1 || P.world > 64 || P.rank < 0 || P.rank >= P.world || P.step < 0) return gmx_fail("peer: rank / world / step out of range");
+  if (n <= 0 || P.tiles != (int32_t)(gmx_tiles_(n))) return gmx_fail("peer: tiles must be ceil(n / 1024)");
+  if (P.capacity < 1 || P.capacity > n || P.leaves < 1 || P.leaves > GMX_PEER_MAX_LEAVES) return gmx_fail("peer: capacity / leaves out of range");
   return 0;
 }
 extern "C" int gmx_peer_put_stats(const void* stats_own, gmx_peer P, int64_t n, gmx_stream) {
-  if (!stats_own) return fail("peer_put_stats: null argument");
+  if (!stats_own) return gmx_fail("peer_put_stats: null argument");
   if (hs_peer_check(P, n)) return 1;
   const int pad = P.tiles + (P.tiles & 1);
   const uint64_t* ag = (const uint64_t*)stats_own;
@@ -840,7 +794,7 @@ static bool hs_peer_wait(const uint64_t* g, uint32_t tag, uint32_t* data, const 
 extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* stats_own, gmx_peer P, int64_t* plan,
                                    uint64_t* total_out, const float* lw, float* max_out, int shift, int64_t n,
                                    const void* const* state_rows, void* const* tail_rows, int32_t* next_idx, gmx_stream st) {
-  if (!stats_own || !plan || !lw || !max_out || !state_rows || !tail_rows || !next_idx) return fail("shard_step_peer: null argument");
+  if (!stats_own || !plan || !lw || !max_out || !state_rows || !tail_rows || !next_idx) return gmx_fail("shard_step_peer: null argument");
   if (hs_peer_check(P, n)) return 1;
   const int W = P.world, me = P.rank, tiles = P.tiles, pad = tiles + (tiles & 1);
   const int64_t cap = P.capacity;
@@ -860,7 +814,7 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
       uint32_t lo, hi, mb;
       if (!hs_peer_wait(row, tag, &lo, t0) || !hs_peer_wait(row + 1, tag, &hi, t0) || !hs_peer_wait(row + 2, tag, &mb, t0)) {
         P.status_d[0] = 1; plan[GMX_PLAN_OVERFLOW] = 1;
-        return fail("shard_step_peer: a peer's statistics did not arrive within 60 s");
+        return gmx_fail("shard_step_peer: a peer's statistics did not arrive within 60 s");
       }
       ag[b] = (uint64_t)lo | ((uint64_t)hi << 32);
       tm[b] = gmx_u2f(mb);
@@ -870,7 +824,7 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
   if (gmx_shard_totals(all.data(), W, n, totals.data(), max_out, st)) return 1;
   std::vector<uint32_t> send((size_t)W * (size_t)cap);
   for (int l = 0; l < P.leaves; ++l) {
-    if (!state_rows[l] || !tail_rows[l]) return fail("shard_step_peer: a leaf pointer is null");
+    if (!state_rows[l] || !tail_rows[l]) return gmx_fail("shard_step_peer: a leaf pointer is null");
     if (gmx_shard_step_tiles(kind, key, totals.data(), plan, total_out, lw, stats_own, max_out, shift, me, W, n, cap,
                              state_rows[l], send.data(), next_idx, st)) return 1;
     // what this rank ships to d: the slots of d's shard whose ancestor lives here, [max(bounds[me], d n), min(bounds[me+1], (d+1) n))
@@ -897,7 +851,7 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
         uint32_t v;
         if (!hs_peer_wait(land_own + gmx_peer_state_at(tag, W, tiles, cap, P.leaves, l, s, k), tag, &v, t0)) {
           P.status_d[0] = 1;
-          return fail("shard_step_peer: a peer's states did not arrive within 60 s");
+          return gmx_fail("shard_step_peer: a peer's states did not arrive within 60 s");
         }
         tail[(size_t)s * (size_t)cap + (size_t)k] = v;
       }
@@ -916,16 +870,16 @@ static_assert(sizeof(hs_shm) <= GMX_P2P_HANDLE_BYTES, "handle");
 #include <map>
 static std::map<void*, hs_shm> g_shm;
 extern "C" int gmx_p2p_alloc(size_t bytes, void** ptr_out, void* handle_out) {
-  if (!ptr_out || !handle_out || !bytes) return fail("p2p_alloc: bad argument");
+  if (!ptr_out || !handle_out || !bytes) return gmx_fail("p2p_alloc: bad argument");
   static int counter = 0;
   hs_shm h; memset(&h, 0, sizeof(h));
   snprintf(h.name, sizeof(h.name), "/gmx_p2p_%d_%d_%ld", (int)getpid(), counter++, (long)time(nullptr));
   h.bytes = bytes;
   int fd = shm_open(h.name, O_CREAT | O_EXCL | O_RDWR, 0600);
-  if (fd < 0 || ftruncate(fd, (off_t)bytes) != 0) return fail("p2p_alloc: shm_open / ftruncate failed");
+  if (fd < 0 || ftruncate(fd, (off_t)bytes) != 0) return gmx_fail("p2p_alloc: shm_open / ftruncate failed");
   void* p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
   close(fd);
-  if (p == MAP_FAILED) return fail("p2p_alloc: mmap failed");
+  if (p == MAP_FAILED) return gmx_fail("p2p_alloc: mmap failed");
   memset(p, 0, bytes);
   memset(handle_out, 0, GMX_P2P_HANDLE_BYTES);
   memcpy(handle_out, &h, sizeof(h));
@@ -934,13 +888,13 @@ extern "C" int gmx_p2p_alloc(size_t bytes, void** ptr_out, void* handle_out) {
   return 0;
 }
 extern "C" int gmx_p2p_open(const void* handle, void** ptr_out) {
-  if (!handle || !ptr_out) return fail("p2p_open: null argument");
+  if (!handle || !ptr_out) return gmx_fail("p2p_open: null argument");
   hs_shm h; memcpy(&h, handle, sizeof(h));
   int fd = shm_open(h.name, O_RDWR, 0600);
-  if (fd < 0) return fail("p2p_open: shm_open failed");
+  if (fd < 0) return gmx_fail("p2p_open: shm_open failed");
   void* p = mmap(nullptr, h.bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
   close(fd);
-  if (p == MAP_FAILED) return fail("p2p_open: mmap failed");
+  if (p == MAP_FAILED) return gmx_fail("p2p_open: mmap failed");
   hs_shm m = h; m.name[0] = 0;                   // a mapping of somebody else's segment: not ours to unlink
   g_shm[p] = m;
   *ptr_out = p;
@@ -959,8 +913,8 @@ extern "C" int gmx_p2p_free(void* p) {
 extern "C" int gmx_p2p_exchange(const void* src, size_t src_stride, void* const* land_peers, const void* land_local, void* out,
                                 uint64_t* const* flag_peers, uint64_t* flags_local, uint64_t* state, int rank, int world,
                                 size_t bytes, gmx_stream) {
-  if (!src || !land_peers || !land_local || !out || !flag_peers || !flags_local || !state) return fail("p2p_exchange: null argument");
-  if (world < 1 || world > 64 || rank < 0 || rank >= world) return fail("p2p_exchange: rank / world out of range");
+  if (!src || !land_peers || !land_local || !out || !flag_peers || !flags_local || !state) return gmx_fail("p2p_exchange: null argument");
+  if (world < 1 || world > 64 || rank < 0 || rank >= world) return gmx_fail("p2p_exchange: rank / world out of range");
   if (!bytes) return 0;
   const uint64_t epoch = state[0] + 1;
   const size_t half = (size_t)(epoch & 1) * (size_t)world * bytes;
@@ -973,7 +927,7 @@ extern "C" int gmx_p2p_exchange(const void* src, size_t src_stride, void* const*
     while (__atomic_load_n(flags_local + d, __ATOMIC_ACQUIRE) < epoch) {
       sched_yield();
       timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-      if (t1.tv_sec - t0.tv_sec > 60) { state[1] = 1; return fail("p2p_exchange: a peer did not arrive within 60 s"); }
+      if (t1.tv_sec - t0.tv_sec > 60) { state[1] = 1; return gmx_fail("p2p_exchange: a peer did not arrive within 60 s"); }
     }
     memcpy((uint8_t*)out + (size_t)d * bytes, (const uint8_t*)land_local + half + (size_t)d * bytes, bytes);
   }
@@ -1009,9 +963,9 @@ extern "C" int gmx_mh_accept(const uint32_t* keys, const float* la, int64_t n, u
 }
 // graphs / timers: pass-through stubs (no streams on the host)
 struct gmx_graph { int dummy; };
-extern "C" int gmx_capture_begin(gmx_stream) { return fail("hostsim: graph capture unavailable"); }
-extern "C" int gmx_capture_end(gmx_stream, gmx_graph**) { return fail("hostsim: graph capture unavailable"); }
-extern "C" int gmx_graph_launch(gmx_graph*, gmx_stream) { return fail("hostsim: graph capture unavailable"); }
+extern "C" int gmx_capture_begin(gmx_stream) { return gmx_fail("hostsim: graph capture unavailable"); }
+extern "C" int gmx_capture_end(gmx_stream, gmx_graph**) { return gmx_fail("hostsim: graph capture unavailable"); }
+extern "C" int gmx_graph_launch(gmx_graph*, gmx_stream) { return gmx_fail("hostsim: graph capture unavailable"); }
 extern "C" int gmx_graph_destroy(gmx_graph*) { return 0; }
 struct gmx_timer { int dummy; };
 extern "C" int gmx_timer_create(gmx_timer** out) { *out = new gmx_timer; return 0; }

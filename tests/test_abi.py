@@ -176,3 +176,197 @@ def test_entry_points_reject_null_arguments_before_any_launch():
         rc = getattr(lib, name)(*args)
         assert rc != 0, name
         assert name.encode() in lib.gmx_last_error(), (name, lib.gmx_last_error())
+
+
+def _hip_and_mirror():
+    """the HIP library and the CPU mirror, both loaded here (size exports and refusals make no HIP call)"""
+    import tests.hostsim as hs
+    so = os.path.join(ROOT, "genjax_amd", "lib", "libgenmi_hip.so")
+    if not os.path.exists(so):
+        import __graft_entry__ as g
+        g.build_hip()
+    libs = ctypes.CDLL(so), ctypes.CDLL(hs.build())
+    for lib in libs:
+        lib.gmx_last_error.restype = ctypes.c_char_p
+    return libs
+
+
+def test_mirror_and_hip_library_state_the_same_sizes():
+    """every gmx_*_workspace / _bytes / _words export, on both libraries, over sizes around each tile edge: one statement
+    (csrc/gmx_sizes.h), so equal everywhere"""
+    import itertools
+    i64, i32 = ctypes.c_int64, ctypes.c_int
+    ns = [0, 1, 1023, 1024, 1025, 4096, 2 ** 21, 2 ** 21 + 1, 10 ** 7]
+    shapes = list(itertools.product([0, 1, 31, 32, 65535, 70000], [0, 1, 4096, 4097, 100000]))
+    grid = {
+        "gmx_logsumexp_workspace": ([i64, i64], shapes),
+        "gmx_sum_rows_workspace": ([i64, i64], shapes),
+        "gmx_weight_cdf_workspace": ([i64], [(n,) for n in ns]),
+        "gmx_multinomial_workspace": ([i64], [(n,) for n in ns]),
+        "gmx_multinomial_tiled_workspace": ([i64], [(n,) for n in ns]),
+        "gmx_tile_prefix_words": ([i64], [(n,) for n in ns]),
+        "gmx_sorted_uniforms_words": ([i64], [(n,) for n in ns]),
+        "gmx_resample_workspace": ([i64], [(n,) for n in ns]),
+        "gmx_shard_stats_bytes": ([i64], [(n,) for n in ns]),
+        "gmx_shard_plan_words": ([i32], [(w,) for w in (0, 1, 2, 8, 64)]),
+        "gmx_peer_landing_bytes": ([i32, i64, i64, i32], list(itertools.product((0, 1, 2, 8, 64), ns, (1, 64), (1, 3)))),
+        "gmx_pick_rows_workspace": ([i64, i64], list(itertools.product((1, 7), ns))),
+        "gmx_resample_rows_workspace": ([i32, i64, i64], list(itertools.product((0, 1, 2), (1, 7), ns))),
+    }
+    hip, mirror = _hip_and_mirror()
+    differ = []
+    for name, (argtypes, cases) in grid.items():
+        for lib in (hip, mirror):
+            getattr(lib, name).restype = ctypes.c_size_t
+            getattr(lib, name).argtypes = argtypes
+        for args in cases:
+            a, b = getattr(hip, name)(*args), getattr(mirror, name)(*args)
+            if a != b:
+                differ.append((name, args, a, b))
+    assert not differ, differ[:10]
+    assert hip.gmx_weight_cdf_workspace(1) == 24 and hip.gmx_resample_workspace(1) == 10240      # (the layouts did not move)
+
+
+def _refusal_cases():
+    """(entry point, argument tuple, what the message has to name) for the refusals csrc/gmx_sizes.h states: every one is
+    decided before a pointer is read, so one small aligned buffer stands for all of them"""
+    from tests import bank_checks, conditional_checks, history_checks
+    N, i64, i32 = ctypes.c_void_p(0), ctypes.c_int64, ctypes.c_int
+    buf = (ctypes.c_int64 * 8)()
+    at = (ctypes.addressof(buf) + 15) & ~15
+    B, B4 = ctypes.c_void_p(at), ctypes.c_void_p(at + 4)
+    key = ctypes.cast(B, ctypes.POINTER(ctypes.c_uint32))
+    big = 2 ** 21 + 1
+
+    # the tile-form resamplers as (name, args(kind, n, shift, lw, other pointers), a kind the form takes)
+    forms = {
+        "gmx_tile_stats": lambda kind, n, shift, lw, p: (lw, i64(n), i32(shift), p, p, N),
+        "gmx_resample_tiles": lambda kind, n, shift, lw, p: (i32(kind), key if p else None, lw, i64(n), i32(shift), p, p, p, p, p, N),
+        "gmx_resample_tiles_u": lambda kind, n, shift, lw, p: (i32(kind), key if p else None, lw, i64(n), i32(shift), p, p, p, p, p, p, N),
+        "gmx_resample_tiles_p": lambda kind, n, shift, lw, p: (i32(kind), key if p else None, lw, i64(n), i32(shift), p, p, p, p, p, N),
+        "gmx_resample_sorted": lambda kind, n, shift, lw, p: (key if p else None, lw, i64(n), i32(shift), p, p, p, i32(0), p, p, p, N),
+        "gmx_resample_sorted_p": lambda kind, n, shift, lw, p: (key if p else None, lw, i64(n), i32(shift), p, p, p, i32(0), p, p, p, N),
+        "gmx_multinomial_tiled": lambda kind, n, shift, lw, p: (key if p else None, lw, i64(n), i32(shift), p, p, p, p, p, p, p, i32(-1), N),
+    }
+    good = {"gmx_resample_tiles_u": 1}
+    cases = []
+    for name, args in forms.items():
+        k = good.get(name, 0)
+        cases += [(name, args(k, 0, 40, B, B), b"n must be positive"),
+                  (name, args(k, 10, 0, B, B), b"shift out of range"),
+                  (name, args(k, 10, 63, B, B), b"shift out of range"),
+                  (name, args(k, 1025, 52, B, B), b"shift too large for n"),
+                  (name, args(k, 10, 40, B, N), b"null argument"),
+                  (name, args(k, 10, 40, B4, B), b"16-byte aligned")]
+        if name not in ("gmx_tile_stats", "gmx_resample_tiles_p", "gmx_resample_sorted_p"):
+            cases.append((name, args(k, big, 40, B, B), b"n too large for the fused path"))
+    cases += [("gmx_resample_tiles", forms["gmx_resample_tiles"](2, 10, 40, B, B), b"kind must be systematic or stratified"),
+              ("gmx_resample_tiles_p", forms["gmx_resample_tiles_p"](4, 10, 40, B, B), b"kind must be systematic or stratified"),
+              ("gmx_resample_tiles_u", forms["gmx_resample_tiles_u"](0, 10, 40, B, B), b"stratified only"),
+              ("gmx_multinomial_tiled", forms["gmx_multinomial_tiled"](0, 10, 40, B, B)[:-2] + (i32(2), N), b"phase is -1, 0 or 1"),
+              ("gmx_resample", (i32(9), key, B, i64(10), i32(40), N, i64(0), B, B, B, B, N), b"unknown kind"),
+              ("gmx_resample", (i32(0), key, B, i64(0), i32(40), N, i64(0), B, B, B, B, N), b"n out of range"),
+              ("gmx_resample", (i32(0), key, N, i64(10), i32(40), N, i64(0), B, B, B, B, N), b"null argument"),
+              ("gmx_resample", (i32(0), key, B, i64(10), i32(40), N, i64(0), B, B, B, B4, N), b"workspace_d must be 16-byte aligned")]
+    rows, keep1 = bank_checks.rows_refusal_calls()
+    pinned, keep2 = conditional_checks.pinned_refusal_calls()
+    hist, keep3 = history_checks.history_refusal_calls()
+    cases += [("gmx_resample_rows", a, why) for a, why in rows] + [("gmx_resample_rows_pinned", a, why) for a, why in pinned]
+    cases += [c for c in hist if c[0] == "gmx_history_record"]
+    Bp = ctypes.cast(buf, ctypes.c_void_p)
+    cases += [("gmx_pick_rows", (Bp, Bp, i64(2), i64(10), i64(9), Bp, Bp, Bp, N), b"ld = 9"),
+              ("gmx_pick_rows", (Bp, Bp, i64(0), i64(10), i64(10), Bp, Bp, Bp, N), b"rows = 0"),
+              ("gmx_lineage", hist[-2][1], b"must be positive")]
+    return cases, (buf, keep1, keep2, keep3)
+
+
+def test_mirror_refusals_carry_the_entry_points_message():
+    """what both libraries refuse alike (csrc/gmx_sizes.h), the mirror refuses in the device library's words: the entry
+    point and the reason in gmx_last_error(), the same bytes on both.  The mirror is asked first; the HIP library only
+    sees a call the mirror refused (nothing here may reach a launch)."""
+    hip, mirror = _hip_and_mirror()
+    cases, _keep = _refusal_cases()
+    assert len(cases) >= 100
+    for name, args, why in cases:
+        assert getattr(mirror, name)(*args) != 0, (name, why)
+        said = mirror.gmx_last_error()
+        assert said.startswith(name.encode() + b":") and why in said, (name, why, said)
+        assert getattr(hip, name)(*args) != 0, (name, why)
+        assert hip.gmx_last_error() == said, (name, hip.gmx_last_error(), said)
+
+
+def _mirror_resample(be, kind, key, lw):
+    import torch
+    n = lw.numel()
+    from genjax_amd.inference import smc
+    mx, tot = torch.zeros(1), torch.zeros(1, dtype=torch.int64)
+    anc = torch.full((n,), -1, dtype=torch.int32)
+    ws = torch.zeros(((be.c.gmx_resample_workspace(n) + 7) // 8,), dtype=torch.int64)
+    be.check(be.c.gmx_resample(kind, key, be.ptr(lw), n, smc.cdf_shift(n), None, 0, be.ptr(mx), be.ptr(tot), be.ptr(anc),
+                               be.ptr(ws), None), "gmx_resample")
+    return mx, tot, anc
+
+
+def _resample_inputs():
+    import numpy as np
+    import torch
+    n = 1025                                  # two tiles, the second holding one particle
+    lw = torch.from_numpy(np.random.default_rng(77).normal(size=n).astype(np.float32) * 3.0)
+    return n, lw, (ctypes.c_uint32 * 2)(0x1234567, 0x89abcde)
+
+
+def test_mirror_resample_multinomial_is_weight_cdf_and_ancestors(hostsim):
+    """kind MULTINOMIAL through the product's dispatch (gmx_tile_stats + gmx_weight_cdf + gmx_multinomial) gives the
+    ancestors of gmx_weight_cdf + gmx_ancestors"""
+    import torch
+    from genjax_amd.inference import smc
+    be = hostsim
+    n, lw, key = _resample_inputs()
+    mx, tot, anc = _mirror_resample(be, smc.MULTINOMIAL, key, lw)
+    m2, t2 = lw.max().reshape(1).clone(), torch.zeros(1, dtype=torch.int64)
+    cdf, a2 = torch.zeros(n, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int32)
+    ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64)
+    be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, smc.cdf_shift(n), None, 0, be.ptr(m2), be.ptr(cdf), be.ptr(t2), be.ptr(ws), None),
+             "gmx_weight_cdf")
+    be.check(be.c.gmx_ancestors(smc.MULTINOMIAL, key, be.ptr(cdf), n, 0, be.ptr(t2), n, 0, n, be.ptr(a2), None), "gmx_ancestors")
+    assert torch.equal(anc, a2) and torch.equal(tot, t2) and torch.equal(mx, m2)
+    assert int(anc.min()) >= 0 and int(anc.max()) < n and len(set(anc.tolist())) > 10
+
+
+def test_mirror_resample_multinomial_tiled_is_the_two_stage_form(hostsim):
+    """kind MULTINOMIAL_TILED through the product's dispatch gives the ancestors of gmx_tile_stats +
+    gmx_multinomial_tiled(phase = -1)"""
+    import torch
+    from genjax_amd.inference import smc
+    be = hostsim
+    n, lw, key = _resample_inputs()
+    mx, tot, anc = _mirror_resample(be, smc.MULTINOMIAL_TILED, key, lw)
+    shift = smc.cdf_shift(n)
+    tmax, agg = torch.zeros(2), torch.zeros(2, dtype=torch.int64)
+    be.check(be.c.gmx_tile_stats(be.ptr(lw), n, shift, be.ptr(tmax), be.ptr(agg), None), "gmx_tile_stats")
+    m2, t2, a2 = torch.zeros(1), torch.zeros(1, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int32)
+    ws = torch.zeros(((be.c.gmx_multinomial_tiled_workspace(n) + 7) // 8,), dtype=torch.int64)
+    be.check(be.c.gmx_multinomial_tiled(key, be.ptr(lw), n, shift, be.ptr(tmax), be.ptr(agg), None, be.ptr(m2), be.ptr(t2),
+                                        be.ptr(a2), be.ptr(ws), -1, None), "gmx_multinomial_tiled")
+    assert torch.equal(anc, a2) and torch.equal(tot, t2) and torch.equal(mx, m2)
+    assert int(anc.min()) >= 0 and int(anc.max()) < n and len(set(anc.tolist())) > 10
+
+
+def test_mirror_resample_past_2048_tiles_takes_the_prefix_forms(hostsim):
+    """n = 2^21 + 1 (2049 tiles): the dispatch goes through gmx_tile_prefix + gmx_resample_tiles_p, whose mirror checks
+    the prefixes against the log-weights — the ancestors of the array form (gmx_weight_cdf + gmx_ancestors)"""
+    import numpy as np
+    import torch
+    from genjax_amd.inference import smc
+    be = hostsim
+    n = 2 ** 21 + 1
+    lw = torch.from_numpy(np.random.default_rng(78).normal(size=n).astype(np.float32))
+    key = (ctypes.c_uint32 * 2)(5, 6)
+    mx, tot, anc = _mirror_resample(be, smc.SYSTEMATIC, key, lw)
+    m2, t2 = lw.max().reshape(1).clone(), torch.zeros(1, dtype=torch.int64)
+    cdf, a2 = torch.zeros(n, dtype=torch.int64), torch.full((n,), -1, dtype=torch.int32)
+    ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64)
+    be.check(be.c.gmx_weight_cdf(be.ptr(lw), n, smc.cdf_shift(n), None, 0, be.ptr(m2), be.ptr(cdf), be.ptr(t2), be.ptr(ws), None),
+             "gmx_weight_cdf")
+    be.check(be.c.gmx_ancestors(smc.SYSTEMATIC, key, be.ptr(cdf), n, 0, be.ptr(t2), n, 0, n, be.ptr(a2), None), "gmx_ancestors")
+    assert torch.equal(anc, a2) and torch.equal(tot, t2) and torch.equal(mx, m2)
