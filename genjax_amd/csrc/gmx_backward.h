@@ -72,16 +72,20 @@ k_pick_stats(const float* __restrict__ logits, int64_t n, int64_t ld, int64_t n_
 // it; the draw is the first i with cdf_i >= Thr, Thr = ceil(total (2^23 - u) / 2^23) (k_ancestors_mn's integer form of
 // cdf_i 2^23 >= total (2^23 - u)).  cdf is non-decreasing, so that i = #{ i : cdf_i < Thr }: the tiles whose inclusive
 // prefix is below Thr are counted first, then the columns of the one tile that reaches it.
+// Row r's answer, plus r * index_stride, goes to out[r * out_stride + out_offset] (gmx_pick_rows: 1, 0 and no stride;
+// gmx_resample_rows_as: slot n - 1 of row r of the ancestor matrix).
 __global__ void __launch_bounds__(GMX_PICK_BLOCK)
 k_pick_row(const uint32_t* __restrict__ keys, const float* __restrict__ logits, int64_t n, int64_t ld, int64_t n_tiles,
            float scale, const float* __restrict__ tmax, const uint64_t* __restrict__ agg, int32_t* __restrict__ out,
-           unsigned long long* __restrict__ status) {
+           int64_t out_stride, int64_t out_offset, int64_t index_stride, unsigned long long* __restrict__ status) {
   __shared__ float lds4[4];
   __shared__ uint64_t lds8[4];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t r = (int64_t)blockIdx.x;
   const float* __restrict__ tm = tmax + r * n_tiles;
   const uint64_t* __restrict__ ta = agg + r * n_tiles;
+  int32_t* __restrict__ dst = out + (r * out_stride + out_offset);
+  const int32_t add = (int32_t)(r * index_stride);
   float M = -gmx_inf();
   for (int64_t t = tid; t < n_tiles; t += GMX_PICK_BLOCK) M = gmx_rmax(M, tm[t]);
   M = block_max(M, lds4);
@@ -90,7 +94,7 @@ k_pick_row(const uint32_t* __restrict__ keys, const float* __restrict__ logits, 
   for (int64_t t = tid; t < n_tiles; t += GMX_PICK_BLOCK) part += gmx_tile_scale(ta[t], gmx_tile_exp(tm[t]), K);   // (K - k_b may pass 63)
   const uint64_t total = pick_block_sum(part, lds8);
   if (total == 0ull) {                   // no mass at all: the last column, as gmx_ancestors answers, and counted
-    if (tid == 0) { out[r] = (int32_t)(n - 1); atomicAdd(status, 1ull); }
+    if (tid == 0) { *dst = (int32_t)(n - 1) + add; atomicAdd(status, 1ull); }
     return;
   }
   gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
@@ -147,7 +151,7 @@ k_pick_row(const uint32_t* __restrict__ keys, const float* __restrict__ logits, 
   if (tid == 0) {
     int64_t i = b * GMX_PICK_TILE + (int64_t)lower;
     if (i > n - 1) i = n - 1;
-    out[r] = (int32_t)i;
+    *dst = (int32_t)i + add;
   }
 }
 

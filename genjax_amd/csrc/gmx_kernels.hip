@@ -3490,7 +3490,8 @@ extern "C" int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int6
                        tiles, row0, scale, tmax, agg);
   }
   hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
-                     (const float*)tmax, (const uint64_t*)agg, out_d, (unsigned long long*)status_d);
+                     (const float*)tmax, (const uint64_t*)agg, out_d, (int64_t)1, (int64_t)0, (int64_t)0,
+                     (unsigned long long*)status_d);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -3560,6 +3561,14 @@ extern "C" int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* 
   return 0;
 }
 
+// k_rows_pin's grid x: 256 threads per workgroup over the rows and (with a broadcast) the quads of rows * n particles; its
+// threads stride, so the extent is capped
+static unsigned gmx_rows_pin_blocks_(int64_t rows, int64_t quads) {
+  const int64_t items = rows > quads ? rows : quads;
+  const int64_t blocks = (items + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK;
+  return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));
+}
+
 // the iid multinomial with slot n - 1 of every row pinned (conditional SMC): n <= 1024 ONE launch; past it the pins, then
 // the unpinned chain with the last slot forced in k_rows_mn
 extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int64_t rows, int64_t n, int64_t ld,
@@ -3594,8 +3603,8 @@ extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int
     GMX_HIP(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(k_rows_pin, dim3((unsigned)((rows + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)(D + 1)),
-                     dim3(GMX_ROWS_BLOCK), 0, st, lw_d, rows, n, ld, pin);
+  hipLaunchKernelGGL(k_rows_pin, dim3(gmx_rows_pin_blocks_(rows, 0), (unsigned)(D + 1)), dim3(GMX_ROWS_BLOCK), 0, st, lw_d,
+                     rows, n, ld, pin, (const float*)nullptr, (float*)nullptr, (int64_t)0);
   const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
   uint64_t* agg = (uint64_t*)workspace_d;
   uint64_t* cdf = agg + rows * tiles;
@@ -3610,6 +3619,78 @@ extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int
     hipLaunchKernelGGL(k_rows_mn<true>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0,
                        st, keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
   }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// the pins alone (steps 1 and 2 of gmx_resample_rows_pinned), and a second state broadcast over every particle of its row:
+// ONE launch
+extern "C" int gmx_rows_pin(float* lw_d, int64_t rows, int64_t n, int64_t ld, const float* pin_lw_d, const float* pin_x_d,
+                            float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride, const float* next_x_d, float* next_d,
+                            int64_t next_ld, gmx_stream stream) {
+  if (!lw_d || !pin_lw_d) return gmx_fail("gmx_rows_pin: null argument%s");
+  const gmx_refusal no = gmx_rows_pin_refusal_(rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr, next_ld);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_rows_pin", no.v);
+  if (D > 0 && !pin_x_d) return gmx_fail("gmx_rows_pin: null argument (pin_x_d with D > 0)%s");
+  if (D > 0 && !x_d) return gmx_fail("gmx_rows_pin: null argument (x_d with D > 0)%s");
+  if (D > 0 && next_x_d && !next_d) return gmx_fail("gmx_rows_pin: null argument (next_d with next_x_d)%s");
+  if (((uintptr_t)lw_d & 3) || ((uintptr_t)pin_lw_d & 3) || ((uintptr_t)pin_x_d & 3) || ((uintptr_t)x_d & 3) ||
+      ((uintptr_t)next_x_d & 3) || ((uintptr_t)next_d & 3))
+    return gmx_fail("gmx_rows_pin: a pointer is not aligned to its element%s");
+  rows_pin pin;
+  pin.lw = pin_lw_d; pin.x = pin_x_d; pin.x_out = x_d; pin.D = D; pin.x_ld = x_ld; pin.x_row_stride = x_row_stride;
+  const bool spread = D > 0 && next_x_d != nullptr;
+  hipLaunchKernelGGL(k_rows_pin, dim3(gmx_rows_pin_blocks_(rows, spread ? (rows * n + 3) / 4 : 0), (unsigned)(D + 1)),
+                     dim3(GMX_ROWS_BLOCK), 0, (hipStream_t)stream, lw_d, rows, n, ld, pin, spread ? next_x_d : nullptr,
+                     next_d, next_ld);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t gmx_resample_rows_as_workspace(int64_t rows, int64_t n) { return gmx_resample_rows_as_bytes_(rows, n); }
+
+// the iid multinomial with slot n - 1 of every row re-drawn from a second matrix of logits (ancestor sampling): n <= 1024
+// ONE launch; past it gmx_resample_rows' chain, then gmx_pick_rows' two kernels writing slot n - 1 of every row
+extern "C" int gmx_resample_rows_as(const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                                    int64_t index_stride, const uint32_t* as_keys_d, const float* as_lw_d, int64_t as_ld,
+                                    float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
+                                    void* workspace_d, gmx_stream stream) {
+  if (!keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("gmx_resample_rows_as: null argument%s");
+  const gmx_refusal no = gmx_resample_rows_as_refusal_(rows, n, ld, index_stride, as_ld);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_as", no.v);
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows_as: workspace_d must be 8-byte aligned%s");
+  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)as_lw_d & 3) || ((uintptr_t)as_keys_d & 3) ||
+      ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) || ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
+    return gmx_fail("gmx_resample_rows_as: a pointer is not aligned to its element%s");
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  auto* status = (unsigned long long*)status_d;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+    rows_as as;
+    as.keys = as_keys_d; as.lw = as_lw_d; as.ld = as_ld; as.status = status + 1;
+#define GMX_ROWS_AS(W_)                                                                                                \
+  hipLaunchKernelGGL((k_rows_small_as<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, st, \
+                     keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, as)
+    if (n <= 256) GMX_ROWS_AS(1);
+    else if (n <= 512) GMX_ROWS_AS(2);
+    else GMX_ROWS_AS(4);
+#undef GMX_ROWS_AS
+    GMX_HIP(hipGetLastError());
+    return 0;
+  }
+  if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
+                        status_d, workspace_d, stream)) return 1;
+  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
+  uint64_t* agg = (uint64_t*)((uint8_t*)workspace_d + gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n));
+  float* tmax = (float*)(agg + rows * tiles);
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
+    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
+    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, as_lw_d, n, as_ld,
+                       tiles, row0, scale, tmax, agg);
+  }
+  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, as_keys_d, as_lw_d, n, as_ld, tiles, scale,
+                     (const float*)tmax, (const uint64_t*)agg, ancestors_d, n, n - 1, index_stride, status + 1);
   GMX_HIP(hipGetLastError());
   return 0;
 }

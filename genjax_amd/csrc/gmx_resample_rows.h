@@ -18,6 +18,12 @@
 //               retained particle's weight (written back), its D state words written into the caller's store, and slot
 //               n - 1 answering n - 1.  n <= 1024: k_rows_small_pinned<W>, the same body with the pin compiled in — still
 //               ONE launch; n > 1024: k_rows_pin writes the pins first, then the chain above with k_rows_mn<true>.
+//   pins alone (gmx_rows_pin): k_rows_pin, which can also broadcast a second [D, rows] state over every particle of its
+//               row (ancestor sampling: the NEXT retained state as a per-particle leaf).
+//   ancestor sampling (gmx_resample_rows_as): the iid multinomial, then slot n - 1 of every row re-drawn from a second matrix
+//               of logits as gmx_pick_rows draws it.  n <= 1024: k_rows_small_as<W>, the same body with that draw compiled
+//               in — still ONE launch, no barrier added; n > 1024: the chain above, then k_pick_stats and k_pick_row
+//               (gmx_backward.h) on the second matrix, k_pick_row writing slot n - 1 of the row.
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
 // host compiler: the ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
 // multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
@@ -93,6 +99,13 @@ struct rows_pin {
   int32_t D;
   int64_t x_ld, x_row_stride;
 };
+// What gmx_resample_rows_as adds to a row (ancestor sampling: slot n - 1 of every row is one draw from a second matrix)
+struct rows_as {
+  const uint32_t* keys;          // [rows, 2]: row r's draw is under keys[r], counter 0
+  const float* lw;               // the ancestor logits, rows ld elements apart
+  int64_t ld;
+  unsigned long long* status;    // counts the rows whose ancestor logits carry no mass
+};
 // a row of the matrix as the kernel reads it: nothing else writes it — unless the kernel itself writes the pin back
 template <bool PIN> struct rows_row_ptr { typedef const float* __restrict__ type; };
 template <> struct rows_row_ptr<true> { typedef const float* type; };
@@ -102,18 +115,28 @@ template <> struct rows_row_ptr<true> { typedef const float* type; };
 // PIN (the iid multinomial only): the thread that holds column n - 1 takes the pinned weight into its registers before the
 // row's maximum is reduced, writes it back into the matrix and answers n - 1 for slot n - 1 whatever the search found; the
 // row's group writes the D pinned state words.  No barrier and no LDS of its own; without PIN nothing of it is compiled.
-template <int KIND, int W, bool PIN>
+// AS (the iid multinomial only, never with PIN): the row's group also holds the row's four-per-thread ancestor logits
+// (loaded with the weights: one wait), reduces their maximum, turns them into fixed point against their own reference and
+// scans them beside the weights — the same three barriers — and counts the columns whose inclusive sum is below the
+// threshold of as.keys[r] at counter 0, which is k_pick_row's answer for a row of one tile (K = k_b, nothing below the
+// tile); the thread that holds slot n - 1 stores that count, clamped, instead of its search.  64 bytes of LDS of its own;
+// without AS nothing of it is compiled.
+template <int KIND, int W, bool PIN, bool AS = false>
 __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ keys, typename rows_row_ptr<PIN>::type lw,
                                                 int64_t rows, int64_t n, int64_t ld, int64_t index_stride, float scale,
                                                 float* __restrict__ max_out, uint64_t* __restrict__ total_out,
                                                 int32_t* __restrict__ anc, unsigned long long* __restrict__ status,
-                                                const rows_pin& pin) {
+                                                const rows_pin& pin, const rows_as& as = rows_as{}) {
   static_assert(W == 1 || W == 2 || W == 4, "waves per row");
   static_assert(!PIN || KIND == GMX_RESAMPLE_MULTINOMIAL, "forcing a slot is a conditional draw under iid slots only");
+  static_assert(!AS || (KIND == GMX_RESAMPLE_MULTINOMIAL && !PIN), "re-drawing a slot: iid slots only; the pin is in the matrix");
   constexpr int RPW = 4 / W, GT = 64 * W;
   __shared__ float s_max[4];
   __shared__ uint64_t s_scan[4];
   __shared__ uint64_t s_cdf[GMX_PICK_TILE];
+  __shared__ float s_amax[AS ? 4 : 1];                   // (AS only: unused arrays take no LDS)
+  __shared__ uint64_t s_ascan[AS ? 4 : 1];
+  __shared__ uint32_t s_acnt[AS ? 4 : 1];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = tid / GT, gt = tid % GT;
   const int64_t r_ = (int64_t)blockIdx.x * RPW + grp;
@@ -129,6 +152,8 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
     if (live && gt < pin.D) px = pin.x[(int64_t)gt * rows + r];
   }
   pick_load4(row, base, n, x);
+  float a[4];
+  if (AS) pick_load4(as.lw + r * as.ld, base, n, a);     // (both matrices' loads are out before the first wait)
   if (PIN && live) {                                     // the D state words, by the row's thread group
     const int64_t at = r * pin.x_row_stride + n - 1;
     if (gt < pin.D) pin.x_out[(int64_t)gt * pin.x_ld + at] = px;
@@ -142,6 +167,10 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   }
   const float m = wave_max(gmx_rmax(gmx_rmax(x[0], x[1]), gmx_rmax(x[2], x[3])));
   if (lane == 0) s_max[wave] = m;
+  if (AS) {
+    const float ma = wave_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])));
+    if (lane == 0) s_amax[wave] = ma;
+  }
   __syncthreads();
   float M = s_max[grp * W];
 #pragma unroll
@@ -155,6 +184,20 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   }
   const uint64_t inc = wave_scan_u64(run);
   if (lane == 63) s_scan[wave] = inc;
+  uint64_t qa[4], run_a = 0, inc_a = 0;
+  if (AS) {                                              // the ancestor logits: one tile, their own reference
+    float MA = s_amax[grp * W];
+#pragma unroll
+    for (int w = 1; w < W; ++w) MA = gmx_rmax(MA, s_amax[grp * W + w]);
+    const float ref_a = gmx_tile_ref(gmx_tile_exp(MA));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      run_a += (base + c < n) ? weight_fixed(a[c], ref_a, scale) : 0ull;
+      qa[c] = run_a;
+    }
+    inc_a = wave_scan_u64(run_a);
+    if (lane == 63) s_ascan[wave] = inc_a;
+  }
   __syncthreads();
   uint64_t woff = 0, total = 0;
 #pragma unroll
@@ -167,6 +210,28 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   uint64_t* cdf = s_cdf + grp * (GT * 4);
 #pragma unroll
   for (int c = 0; c < 4; ++c) cdf[base + c] = loc + q[c];
+  uint64_t total_a = 0;
+  if (AS) {                                              // k_pick_row's count: #{ i : cdf_i < Thr }, Thr from as.keys[r]
+    uint64_t woff_a = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const uint64_t v = s_ascan[grp * W + w];
+      total_a += v;
+      woff_a += (grp * W + w < wave) ? v : 0ull;
+    }
+    const uint64_t loc_a = woff_a + (inc_a - run_a);
+    gmx_key ka; ka.k0 = as.keys[2 * r]; ka.k1 = as.keys[2 * r + 1];
+    const uint64_t u = (uint64_t)(gmx_bits32(ka, 0ull) >> 9);
+    const u128 P = mul64(total_a, (1ull << 23) - u);
+    const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
+    const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
+    const uint64_t Thr = (phi << 41) | (plo >> 23);                // ceil(P / 2^23), in [1, total_a] (0 without mass)
+    uint64_t lower = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) lower += (base + c < n && loc_a + qa[c] < Thr) ? 1ull : 0ull;
+    lower = wave_sum_u64(lower);
+    if (lane == 0) s_acnt[wave] = (uint32_t)lower;
+  }
   __syncthreads();
   if (!live) return;                                     // (no barrier follows)
   if (gt == 0) {
@@ -187,6 +252,16 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
       i = i < (int32_t)n ? i : (int32_t)n - 1;
     }
     if (PIN && base + c == n - 1) i = (int32_t)n - 1;    // slot n - 1 descends from slot n - 1 (its uniform is its own)
+    if (AS && base + c == n - 1) {                       // slot n - 1: the draw from the ancestor logits
+      uint32_t cnt = 0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) cnt += s_acnt[grp * W + w];
+      i = cnt < (uint32_t)n ? (int32_t)cnt : (int32_t)n - 1;
+      if (total_a == 0ull) {                             // no mass: the plain pin, and counted
+        i = (int32_t)n - 1;
+        atomicAdd(as.status, 1ull);
+      }
+    }
     out[c] = i + add;
   }
   rows_store4(anc + r * n, base, n, out);
@@ -210,15 +285,51 @@ k_rows_small_pinned(const uint32_t* __restrict__ keys, float* lw, int64_t rows, 
                                                      status, pin);
 }
 
-// n > 1024, pinned: the pins into the matrix and the state store before the row's statistics are taken.  blockIdx.x: 256
-// rows, blockIdx.y: the state word d < D, or (y = D) the weight.
+// (`lw` holds the pin already: only read)
+template <int W>
 __global__ void __launch_bounds__(GMX_ROWS_BLOCK)
-k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin pin) {
-  const int64_t r = (int64_t)blockIdx.x * GMX_ROWS_BLOCK + (int64_t)threadIdx.x;
-  if (r >= rows) return;
+k_rows_small_as(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld,
+                int64_t index_stride, float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out,
+                int32_t* __restrict__ anc, unsigned long long* __restrict__ status, rows_as as) {
+  rows_small_body<GMX_RESAMPLE_MULTINOMIAL, W, false, true>(keys, lw, rows, n, ld, index_stride, scale, max_out, total_out, anc,
+                                                            status, rows_pin{}, as);
+}
+
+// The pins into the matrix and the state store (gmx_rows_pin; gmx_resample_rows_pinned past one tile, before the row's
+// statistics are taken).  blockIdx.y: the state word d < D, or (y = D) the weight; the threads of a y stride over the rows.
+// next_x ([D, rows], may be null): state word d of row r also goes to every particle of the row in a second store,
+// next[d * next_ld + r * n + i], i < n — four consecutive particles per thread, one 16-byte store where the address allows.
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin pin, const float* __restrict__ next_x,
+           float* __restrict__ next, int64_t next_ld) {
+  const int64_t g = (int64_t)blockIdx.x * GMX_ROWS_BLOCK + (int64_t)threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * GMX_ROWS_BLOCK;
   const int32_t d = (int32_t)blockIdx.y;
-  if (d == pin.D) lw[r * ld + n - 1] = pin.lw[r];
-  else pin.x_out[(int64_t)d * pin.x_ld + r * pin.x_row_stride + n - 1] = pin.x[(int64_t)d * rows + r];
+  for (int64_t r = g; r < rows; r += step) {
+    if (d == pin.D) lw[r * ld + n - 1] = pin.lw[r];
+    else pin.x_out[(int64_t)d * pin.x_ld + r * pin.x_row_stride + n - 1] = pin.x[(int64_t)d * rows + r];
+  }
+  if (next_x == nullptr || d == pin.D) return;
+  const float* __restrict__ src = next_x + (int64_t)d * rows;
+  float* __restrict__ dst = next + (int64_t)d * next_ld;
+  const int64_t cols = rows * n, quads = (cols + 3) / 4;
+  for (int64_t qd = g; qd < quads; qd += step) {
+    const int64_t base = qd * 4;
+    int64_t r = base / n, k = base - r * n;              // particle `base` is column k of row r
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      v[c] = r < rows ? src[r] : 0.0f;
+      if (++k == n) { k = 0; ++r; }
+    }
+    if (base + 4 <= cols && (((uintptr_t)(dst + base)) & 15u) == 0u) {
+      *reinterpret_cast<float4*>(dst + base) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (base + c < cols) dst[base + c] = v[c];
+    }
+  }
 }
 
 // n > 1024: blockIdx.x the tile, blockIdx.y the row (row0 + y).  tmax / agg: k_pick_stats' [rows, n_tiles] statistics.
@@ -380,6 +491,51 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_pinned(const uint3
   if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
                         status_d, workspace_d, stream)) return 1;
   for (int64_t r = 0; r < rows; ++r) ancestors_d[r * n + n - 1] = (int32_t)(n - 1 + r * index_stride);
+  return 0;
+}
+
+// steps 1 and 2 of the above as a call of their own, and the broadcast of a second state over every particle of its row
+extern "C" __attribute__((used)) inline int gmx_rows_pin(float* lw_d, int64_t rows, int64_t n, int64_t ld, const float* pin_lw_d,
+                                   const float* pin_x_d, float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                                   const float* next_x_d, float* next_d, int64_t next_ld, gmx_stream stream) {
+  const char* who = "gmx_rows_pin";
+  (void)stream;
+  if (!lw_d || !pin_lw_d) return gmx_fail("%s: null argument", who, 0);
+  const gmx_refusal no = gmx_rows_pin_refusal_(rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr, next_ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (D > 0 && !pin_x_d) return gmx_fail("%s: null argument (pin_x_d with D > 0)", who, 0);
+  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
+  if (D > 0 && next_x_d && !next_d) return gmx_fail("%s: null argument (next_d with next_x_d)", who, 0);
+  for (int64_t r = 0; r < rows; ++r) {
+    lw_d[r * ld + n - 1] = pin_lw_d[r];
+    for (int64_t d = 0; d < D; ++d) x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r];
+    if (next_x_d)
+      for (int64_t d = 0; d < D; ++d)
+        for (int64_t i = 0; i < n; ++i) next_d[d * next_ld + r * n + i] = next_x_d[d * rows + r];
+  }
+  return 0;
+}
+
+extern "C" __attribute__((used)) inline size_t gmx_resample_rows_as_workspace(int64_t rows, int64_t n) {
+  return gmx_resample_rows_as_bytes_(rows, n);
+}
+
+// the definition, in order: the unconditional draw, one draw per row from the ancestor logits, that draw into slot n - 1
+extern "C" __attribute__((used)) inline int gmx_resample_rows_as(const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                                           int64_t index_stride, const uint32_t* as_keys_d, const float* as_lw_d, int64_t as_ld,
+                                           float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
+                                           void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_resample_rows_as";
+  if (!keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("%s: null argument", who, 0);
+  const gmx_refusal no = gmx_resample_rows_as_refusal_(rows, n, ld, index_stride, as_ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
+                        status_d, workspace_d, stream)) return 1;
+  std::vector<int32_t> tmp((size_t)rows);
+  std::vector<uint64_t> ws((gmx_resample_workspace(n) + 7) / 8 + 2);       // (what the per-row path may ask for)
+  if (gmx_pick_rows(as_keys_d, as_lw_d, rows, n, as_ld, tmp.data(), status_d + 1, ws.data(), stream)) return 1;
+  for (int64_t r = 0; r < rows; ++r) ancestors_d[r * n + n - 1] = tmp[(size_t)r] + (int32_t)(r * index_stride);
   return 0;
 }
 #endif

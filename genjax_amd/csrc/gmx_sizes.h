@@ -115,7 +115,7 @@ static inline const char* gmx_tile_form_refusal_(gmx_tile_form form, int kind, i
   return nullptr;
 }
 
-// ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned ----
+// ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned, gmx_rows_pin, gmx_resample_rows_as ----
 // gmx_pick_rows' workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
 static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n < 1) return 16;
@@ -161,6 +161,29 @@ static inline gmx_refusal gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n
       (rows > 1 && x_row_stride > (x_ld - n) / (rows - 1)))                   // x_ld >= (rows - 1) * x_row_stride + n
     return {"%s: x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)x_ld};
   return {nullptr, 0};
+}
+// gmx_rows_pin: the matrix's shape (gmx_resample_rows' rule for rows, n and ld), the pin's arguments as above, and — with a
+// broadcast — next_ld holding the rows * n particles of a row of the [D, next_ld] leaf
+static inline gmx_refusal gmx_rows_pin_refusal_(int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                                                bool has_next, int64_t next_ld) {
+  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, 0);
+  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return no;
+  if (has_next && D > 0 && (next_ld < rows * n || next_ld >= (1LL << 46)))
+    return {"%s: next_ld = %lld does not hold rows * n columns (or is 2^46 or more)", (long long)next_ld};
+  return {nullptr, 0};
+}
+// gmx_resample_rows_as: gmx_resample_rows' arguments (the iid multinomial) and the ancestor logits' row stride
+static inline gmx_refusal gmx_resample_rows_as_refusal_(int64_t rows, int64_t n, int64_t ld, int64_t index_stride, int64_t as_ld) {
+  const gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
+  if (no.fmt) return no;
+  if (as_ld < n) return {"%s: as_ld = %lld is smaller than n", (long long)as_ld};
+  return {nullptr, 0};
+}
+// gmx_resample_rows_as' workspace: gmx_resample_rows' (a multiple of 16 bytes), then gmx_pick_rows'; nothing for n <= 1024
+static inline size_t gmx_resample_rows_as_bytes_(int64_t rows, int64_t n) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
+  return gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n) + gmx_pick_rows_bytes_(rows, n);
 }
 
 // ---- sweep history ----

@@ -1414,6 +1414,61 @@ def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
     comp.run(flat.leaves, batch, None, out_buffers=bufs)
 
 
+def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, specialize=False, launch=True):
+    """out[i] = lw[i] + step.assess({sites[d]: x_next[d][i], obs_addr: y}, (x_prev[i], *extra))[0] in float32 over the
+    n = lw.shape[0] particles in ONE launch: the per-particle variant of _backward_logits (ancestor sampling:
+    ConditionalBank) — the constrained state is a per-particle leaf x_next[d] ([n] each: every chain's next retained state
+    on each of its particles), `extra` may hold per-particle leaves (the bank's parameters), `out` is [1, n].  The
+    program is cached on the model, the leaves' kinds and `specialize` (specialised once, when built); launch=False
+    builds it only."""
+    from .. import tracer as Tr
+    from ..engine import Compiled, Flat, Tracing, leaf_spec, unflatten
+    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
+    batch = (int(lw.shape[0]),)
+    flat = Flat()
+    atree = flat.add((x_prev,) + tuple(extra))
+    jy = len(flat.leaves)
+    flat.add(y)
+    jx = len(flat.leaves)
+    for v in x_next:
+        flat.add(v)
+    jl = len(flat.leaves)
+    flat.add(lw)
+    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
+    ck = (_gfkey(step), atree, specs, tuple(sites), obs_addr, "per-particle", bool(specialize))
+    ent = _BACKWARD_CACHE.get(ck)
+    if ent is None:
+        tr = Tracing(1)
+        ctx = _Ctx(tr)
+        ctx.store_sites = False
+        with Tr.tracing(tr.graph):
+            syms = [tr.sym_leaf(s_, j) for j, s_ in enumerate(specs)]
+            sargs = unflatten(atree, lambda j: syms[j].value)
+            con = ChoiceMap.empty().set(obs_addr, syms[jy])
+            for d, a in enumerate(sites):
+                con = con.set(a, syms[jx + d])
+            try:
+                _, _, _, sc = call_gen_fn(ctx, "assess", step, None, sargs, con, None, None, None, ())
+            except MissingAddress as e:
+                addr = tuple(a for a in e.args if a != ())
+                raise NotImplementedError(
+                    f"ConditionalBank(ancestor_sampling=True): the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
+                    f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
+                    "transition density would have to integrate it out") from None
+            o = tr.emit_output(syms[jl].value + Tr.as_float(sc))
+        comp = Compiled(tr)
+        if specialize:
+            comp.specialize()
+        ent = (comp, o)
+        _BACKWARD_CACHE[ck] = ent
+    if not launch:
+        return
+    comp, o = ent
+    bufs = [None] * len(comp.outputs)
+    bufs[o[1]] = out
+    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+
+
 class SweepHistory:
     """What BootstrapSweep(history=True) recorded: every step's particles, log-weights and ancestors.
 
@@ -2011,15 +2066,18 @@ class BootstrapBank(_Sweep):
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
 
-    def _key_tables(self, keys: Key):
-        """the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys (int32 words)"""
+    def _key_tables(self, keys: Key, third=False):
+        """the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys (int32 words);
+        third=True: also the [T, R, 2] table of the step key's third child (ConditionalBank's ancestor draws)"""
         from ..random import _derive_host
         R, T = self.R, self.T
         kh = np.asarray(keys.host(), dtype=np.uint32).reshape(R, 2)
-        prop, res = np.empty((T, R, 2), np.uint32), np.empty((T, R, 2), np.uint32)
+        prop, res, last = (np.empty((T, R, 2), np.uint32) for _ in range(3))
         for t in range(T):
             ks = _derive_host(_derive_host(kh, np.uint64(t))[:, None, :], np.arange(3, dtype=np.uint64))
-            prop[t], res[t] = ks[:, 0], ks[:, 1]
+            prop[t], res[t], last[t] = ks[:, 0], ks[:, 1], ks[:, 2]
+        if third:
+            return prop.view(np.int32), res.view(np.int32), last.view(np.int32)
         return prop.view(np.int32), res.view(np.int32)
 
     def prepare(self, keys: Key, ys: torch.Tensor):
@@ -2132,11 +2190,28 @@ class ConditionalBank(BootstrapBank):
     capture() fixes the form (conditional or not): going from "nothing retained" to "retained" drops the graph; rekey()
     and retain() on a captured conditional sweep only change buffer contents, which the graph reads when replayed.
 
-    Not here: ancestor sampling, rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations.
-    Memory: the history slabs take T * (D + 2) * R * n * 4 bytes."""
+    ancestor_sampling=True (particle Gibbs with ancestor sampling: Lindsten, Jordan & Schön 2014): at every step t < T - 1
+    the pinned slot does not record itself as its ancestor but ONE draw among the chain's n step-t particles, particle i
+    with probability proportional to exp(lw_t[i]) times the transition density from x_t[i] into the NEXT retained state
+    ref_x[t + 1] — where the lineages coalesce, the new trajectory then leaves the retained one instead of repeating it.
+    Only which ancestor the pinned slot records changes: particles, weights and every other ancestor are bit for bit those
+    of ancestor_sampling=False under the same keys.  Row r's draw at step t is under the THIRD child of its step key.
+    A conditional step t < T - 1 is then: the site program; gmx_rows_pin (the pins, and ref_x[t + 1] broadcast over each
+    chain's particles); one per-particle program, the model's own `assess`,
+
+        as_lw[i] = lw[i] + step.assess({state_sites[d]: next_x[d][i], obs_addr: y_{t+1}}, (x_t[i], *step_extra(t+1), *params[i]))[0]
+
+    in float32 (the observation's term is constant along a chain and kept so that the bits are defined, as in
+    SweepHistory.backward_sample); gmx_resample_rows_as (n <= 1024: one launch); gmx_history_record.  Step T - 1, and every
+    step while nothing is retained, are the launches of ancestor_sampling=False.  It needs state_sites= when the state has
+    more than one component, and a step model that samples nothing besides the state and the observation.  A chain whose
+    ancestor logits carry no mass at some step keeps the plain pin there and is counted: draw() raises FloatingPointError.
+
+    Not here: rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations.
+    Memory: the history slabs take T * (D + 2) * R * n * 4 bytes; ancestor sampling adds (D + 1) * R * n * 4."""
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
-                 specialize=True, state_addr="x", state_sites=None, resample="multinomial"):
+                 specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False):
         kind = _KINDS.get(resample, None) if isinstance(resample, str) else int(resample)
         if kind != MULTINOMIAL:
             name = resample if isinstance(resample, str) else next((k for k, v in _KINDS.items() if v == kind), resample)
@@ -2145,6 +2220,7 @@ class ConditionalBank(BootstrapBank):
         super().__init__(init, step, n_particles, n_chains, T, obs_addr=obs_addr, resample="multinomial",
                          step_extra=step_extra, params=params, specialize=specialize, state_addr=state_addr)
         self.state_sites = None if state_sites is None else tuple(state_sites)
+        self.ancestor_sampling = bool(ancestor_sampling)
         self.conditional = False
 
     def prepare(self, keys: Key, ys: torch.Tensor, retained=None):
@@ -2166,9 +2242,45 @@ class ConditionalBank(BootstrapBank):
         self.hist_status = torch.zeros((1,), dtype=torch.int64, device=dev)
         self.pick_ws = torch.zeros(((int(be.c.gmx_pick_rows_workspace(R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
         self._views = SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state)
+        if self.ancestor_sampling:
+            self._prepare_ancestors(keys)
         if retained is not None:
             self.set_retained(retained)
         return self
+
+    def _prepare_ancestors(self, keys):
+        """what ancestor sampling adds to prepare(): the third key table, the ancestor logits, the broadcast next state, two
+        status words, the wider workspace — and the logits program, built (and specialised) here"""
+        be = _lib.get()
+        dev = be.device
+        R, n, T, D = self.R, self.n, self.T, self.D
+        N = R * n
+        sites = self.state_sites
+        if sites is None:
+            if D > 1:
+                raise NotImplementedError("ConditionalBank(ancestor_sampling=True): a state of more than one component needs "
+                                          "state_sites= (the address of each component, in order)")
+            sites = (self.state_addr,)
+        if len(sites) != D:
+            raise ValueError(f"ConditionalBank(ancestor_sampling=True): state_sites names {len(sites)} addresses for a state "
+                             f"of {D} components")
+        self._as_sites = sites
+        self.keys_as = torch.from_numpy(self._key_tables(keys, third=True)[2]).to(dev)
+        self.as_lw = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.next_x = torch.zeros((D, N), dtype=torch.float32, device=dev)
+        self.status = torch.zeros((2,), dtype=torch.int64, device=dev)       # rows without mass; rows without ancestor mass
+        self.ws = torch.zeros(((max(int(be.c.gmx_resample_rows_as_workspace(R, n)),
+                                    int(be.c.gmx_resample_rows_workspace(self.kind, R, n))) + 7) // 8,), dtype=torch.int64,
+                              device=dev)
+        if T > 1:
+            self._ancestor_logits(0, launch=False)
+
+    def _ancestor_logits(self, t, launch=True):
+        """as_lw = lw + the transition (and observation) density of step t + 1 from every step-t particle into its chain's
+        next retained state (next_x: gmx_rows_pin's broadcast)"""
+        _ancestor_logits(self.step, self._as_sites, self.obs_addr, self.store.view(t % 2),
+                         tuple(self.step_extra(t + 1)) + self.tail, list(self.next_x), self.ys[t + 1], self.lw,
+                         self.as_lw.reshape(1, self.R * self.n), specialize=self.specialize, launch=launch)
 
     def _set_conditional(self, flag):
         if bool(flag) != self.conditional:
@@ -2178,13 +2290,33 @@ class ConditionalBank(BootstrapBank):
     def _resample(self, t):
         if not self.conditional:
             return super()._resample(t)
+        if self.ancestor_sampling and t < self.T - 1:
+            return self._resample_ancestors(t)
         resample_rows_pinned(self.step_keys[t][1], self.lw.reshape(self.R, self.n), self.ref_lw[t], self.ref_x[t],
                              self.store.rows[t % 2], index_stride=self.n, x_row_stride=self.n,
                              out=(self.anc, self.totals[t], self.maxs[t], self.status), workspace=self.ws)
 
+    def _resample_ancestors(self, t):
+        """a conditional step t < T - 1 under ancestor sampling: the pins and the next retained state over every particle
+        (gmx_rows_pin), the ancestor logits (one program), the multinomial with slot n - 1 drawn from them
+        (gmx_resample_rows_as)"""
+        be = _lib.get()
+        R, n, D = self.R, self.n, self.D
+        N = R * n
+        x = self.store.rows[t % 2]
+        be.check(be.c.gmx_rows_pin(be.ptr(self.lw), R, n, n, be.ptr(self.ref_lw[t]), be.ptr(self.ref_x[t]), be.ptr(x), D,
+                                   int(x.shape[1]), n, be.ptr(self.ref_x[t + 1]), be.ptr(self.next_x), N, be.stream()),
+                 "gmx_rows_pin")
+        self._ancestor_logits(t)
+        be.check(be.c.gmx_resample_rows_as(be.ptr(self.step_keys[t][1]), be.ptr(self.lw), R, n, n, n, be.ptr(self.keys_as[t]),
+                                           be.ptr(self.as_lw), n, be.ptr(self.maxs[t]), be.ptr(self.totals[t]),
+                                           be.ptr(self.anc), be.ptr(self.status), be.ptr(self.ws), be.stream()),
+                 "gmx_resample_rows_as")
+
     def enqueue(self):
         """every launch of the sweep on the current stream, per step: the site program over the R * n particles,
-        gmx_resample_rows_pinned (nothing retained: gmx_resample_rows), gmx_history_record — in this order, so that the
+        gmx_resample_rows_pinned (nothing retained: gmx_resample_rows; ancestor_sampling=True and t < T - 1: gmx_rows_pin,
+        the ancestor-logits program and gmx_resample_rows_as), gmx_history_record — in this order, so that the
         record holds the pins and the next step's gather extends every child of slot n - 1 from the retained state.  No
         syncs, no allocations, no host read of a device value."""
         be = _lib.get()
@@ -2200,13 +2332,16 @@ class ConditionalBank(BootstrapBank):
                                              be.ptr(self.hist_status), be.stream()), "gmx_history_record")
 
     def rekey(self, keys: Key):
-        """a new (R,) key batch: the proposal / resampling key tables are rewritten IN PLACE (BootstrapBank.prepare's
-        derivation), so a captured graph replays under the new keys"""
+        """a new (R,) key batch: the proposal / resampling key tables — and the ancestor-draw table of
+        ancestor_sampling=True — are rewritten IN PLACE (BootstrapBank.prepare's derivation), so a captured graph replays
+        under the new keys"""
         if tuple(keys.shape) != (self.R,):
             raise ValueError(f"ConditionalBank.rekey: {self.R} chains need keys of shape {(self.R,)}, got {tuple(keys.shape)}")
-        prop, res = self._key_tables(keys)
+        prop, res, last = self._key_tables(keys, third=True)
         self.keys_prop.copy_(torch.from_numpy(prop))
         self.keys_res.copy_(torch.from_numpy(res))
+        if self.ancestor_sampling:
+            self.keys_as.copy_(torch.from_numpy(last))
         self.keys = keys
         return self
 
@@ -2218,6 +2353,10 @@ class ConditionalBank(BootstrapBank):
         if tuple(key.shape) != ():
             raise ValueError("ConditionalBank.draw takes ONE key")
         be = _lib.get()
+        if self.ancestor_sampling and int(self.status[1].item()):
+            raise FloatingPointError(f"ConditionalBank.draw: {int(self.status[1].item())} ancestor draw(s) of the last sweep "
+                                     "found no particle with a positive transition density into the next retained state (a "
+                                     "row of -inf logits): those steps kept the plain pin")
         dev = self.hist_xs.device
         R, n, T, D = self.R, self.n, self.T, self.D
         k = torch.empty((R,), dtype=torch.int32, device=dev)

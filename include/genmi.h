@@ -679,6 +679,31 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
  *                   0 <= D <= 65533; with D > 0: x_row_stride >= 0, n <= x_ld < 2^46, x_ld >= (rows - 1) * x_row_stride + n,
  *                   pin_x_d and x_d not null (both are ignored when D = 0); every pointer aligned to its element;
  *                   workspace_d: gmx_resample_rows_workspace(GMX_RESAMPLE_MULTINOMIAL, rows, n) bytes.
+ *   gmx_rows_pin    (additive, ABI still v8.  Reference call site: none of its own.)  Steps 1 and 2 of
+ *                   gmx_resample_rows_pinned as a call of their own — lw_d[r * ld + n - 1] = pin_lw_d[r]; d < D:
+ *                   x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r] — and, when next_x_d ([D, rows]) is not
+ *                   null, a broadcast: next_d[d * next_ld + r * n + i] = next_x_d[d * rows + r] for every i < n, which puts
+ *                   a second per-row state (ancestor sampling: the chain's NEXT retained state) on every particle of the
+ *                   row as a per-particle leaf.  ONE launch (16-byte stores of the broadcast where the address allows);
+ *                   nothing else is written.  Limits: those of gmx_resample_rows_pinned for rows, n, ld, D, x_ld and
+ *                   x_row_stride; with a broadcast and D > 0: rows * n <= next_ld < 2^46 and next_d not null (next_x_d,
+ *                   next_d and next_ld are ignored when D = 0); every pointer aligned to its element.
+ *   gmx_resample_rows_as   (additive, ABI still v8.  Reference call site: none of its own — the resampling step of
+ *                   particle Gibbs with ancestor sampling, Lindsten, Jordan & Schön 2014.)  The iid multinomial of
+ *                   gmx_resample_rows with slot n - 1 of every row re-drawn from a second matrix of logits.  DEFINITION:
+ *                     1. gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d,
+ *                        total_d, ancestors_d, status_d, ...)  (lw_d is only read: a pin is already in it — gmx_rows_pin);
+ *                     2. gmx_pick_rows(as_keys_d, as_lw_d, rows, n, as_ld, tmp, status_d + 1, ...): one exact-integer draw
+ *                        per row from the ancestor logits, under as_keys_d[r] at counter 0;
+ *                     3. ancestors_d[r * n + n - 1] = tmp[r] + r * index_stride.
+ *                   status_d is [2] (the caller zeroes it): word 0 counts the rows whose weights carry no mass, word 1
+ *                   the rows whose ancestor logits carry none — such a row answers n - 1, the plain pin.  n <= 1024: ONE
+ *                   launch (the row's thread group holds both matrices' columns, scans both beside each other and counts
+ *                   the columns below the threshold as gmx_pick_rows does; no barrier added, 64 bytes of LDS);  n > 1024:
+ *                   gmx_resample_rows' three launches, then gmx_pick_rows' two, the last writing slot n - 1 of each row.
+ *                   Limits: those of gmx_resample_rows; as_ld >= n; every pointer aligned to its element; workspace_d:
+ *                   gmx_resample_rows_as_workspace(rows, n) bytes (gmx_resample_rows' plus gmx_pick_rows' past n = 1024),
+ *                   8-byte aligned, contents irrelevant on entry.
  * A null pointer or an out-of-range size returns non-zero before anything is launched.
  * ---------------------------------------------------------------------- */
 size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
@@ -696,6 +721,16 @@ int gmx_resample_rows_pinned(const uint32_t* keys_d /* [rows, 2] */, float* lw_d
                              int32_t D, int64_t x_ld, int64_t x_row_stride,
                              float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
                              void* workspace_d, gmx_stream stream);
+int gmx_rows_pin(float* lw_d, int64_t rows, int64_t n, int64_t ld, const float* pin_lw_d /* [rows] */,
+                 const float* pin_x_d /* [D, rows], null iff D = 0 */, float* x_d /* [D, x_ld], null iff D = 0 */, int32_t D,
+                 int64_t x_ld, int64_t x_row_stride, const float* next_x_d /* [D, rows] or null */,
+                 float* next_d /* [D, next_ld] */, int64_t next_ld, gmx_stream stream);
+size_t gmx_resample_rows_as_workspace(int64_t rows, int64_t n);
+int gmx_resample_rows_as(const uint32_t* keys_d /* [rows, 2] */, const float* lw_d, int64_t rows, int64_t n, int64_t ld,
+                         int64_t index_stride, const uint32_t* as_keys_d /* [rows, 2] */, const float* as_lw_d,
+                         int64_t as_ld /* elements between rows of as_lw_d, >= n */, float* max_d /* [rows] */,
+                         uint64_t* total_d /* [rows] */, int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [2] */,
+                         void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —

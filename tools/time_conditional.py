@@ -1,4 +1,4 @@
-"""What pinning a slot costs.  JSON lines, appended to --out:
+"""What pinning a slot costs, and what sampling its ancestor costs.  JSON lines, appended to --out:
 
   pinned_rows   (rows, n) in {(1024, 256), (256, 1024), (64, 4096)}, D in {1, 3}: gmx_resample_rows_pinned against
                 gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL) on the same weights, alternated: the median and the min / max
@@ -8,9 +8,15 @@
   sweep         ConditionalBank(R = 1024, n = 256, T = 100) on the LGSSM with a retained path, captured, against the
                 captured BootstrapBank(resample="multinomial") of the same shape (which records no history), and against
                 the ConditionalBank with nothing retained (which does)
+  ancestors     (R, n) in {(4096, 256), (64, 16384)}, T = 100, LGSSM with a retained path, three captured sweeps alternated
+                in one process: the plain conditional sweep; ConditionalBank(ancestor_sampling=True), whose resampling is
+                gmx_resample_rows_as; and the same sweep with that call COMPOSED from gmx_rows_pin + gmx_resample_rows +
+                gmx_pick_rows + an index copy (a subclass here).  The two ancestor forms are asserted equal, record for
+                record.  `spread_over_median`: (max - min) / median of each form's windows, the run-to-run spread the
+                fused / composed ratio is read against.
 
 Clocks as found; a host clock around work that ends in a device synchronise.  Environment: SHAPES ("rows:n,..."), BR, BN,
-BT.  Needs the MI355X: there is no CPU path."""
+BT, AS_SHAPES ("R:n,..."), AT.  Needs the MI355X: there is no CPU path."""
 import argparse
 import ctypes
 import json
@@ -32,6 +38,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--label", default="")
 ap.add_argument("--skip-sweep", action="store_true")
+ap.add_argument("--skip-kernel", action="store_true")
+ap.add_argument("--skip-ancestors", action="store_true")
 ap.add_argument("--parent-lib", default="", help="a build of the library without the pinned entry point")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_time_conditional.jsonl"))
 args = ap.parse_args()
@@ -71,6 +79,8 @@ def emit(rec):
 
 # ---- (a) the kernel -------------------------------------------------------------------------------------------------------
 shapes = [tuple(int(v) for v in s.split(":")) for s in os.environ.get("SHAPES", "1024:256,256:1024,64:4096").split(",")]
+if args.skip_kernel:
+    shapes = []
 kind = smc.MULTINOMIAL
 for rows, n in shapes:
     for D in (1, 3):
@@ -151,3 +161,70 @@ if not args.skip_sweep:
               conditional_over_nothing_retained=med["conditional"] / med["conditional_nothing_retained"],
               note="the bootstrap bank records no history; both conditional forms add one gmx_history_record per step",
               history_bytes=T * (cond.D + 2) * R * n * 4))
+
+# ---- (c) ancestor sampling: the fused entry point against its composition ---------------------------------------------------------
+
+
+class ComposedAncestorBank(smc.ConditionalBank):
+    """ancestor_sampling=True with gmx_resample_rows_as replaced by its definition, call for call"""
+
+    def prepare(self, keys, ys, retained=None):
+        super().prepare(keys, ys, retained)
+        self.as_tmp = torch.zeros((self.R,), dtype=torch.int32, device=self.lw.device)
+        self.as_offs = (torch.arange(self.R, dtype=torch.int32, device=self.lw.device) * self.n).contiguous()
+        self.as_status = torch.zeros((1,), dtype=torch.int64, device=self.lw.device)
+        return self
+
+    def _resample_ancestors(self, t):
+        R, n, D = self.R, self.n, self.D
+        x = self.store.rows[t % 2]
+        P, st = be.ptr, be.stream()
+        be.check(be.c.gmx_rows_pin(P(self.lw), R, n, n, P(self.ref_lw[t]), P(self.ref_x[t]), P(x), D, int(x.shape[1]), n,
+                                   P(self.ref_x[t + 1]), P(self.next_x), R * n, st), "gmx_rows_pin")
+        self._ancestor_logits(t)
+        be.check(be.c.gmx_resample_rows(smc.MULTINOMIAL, P(self.step_keys[t][1]), P(self.lw), R, n, n, n, P(self.maxs[t]),
+                                        P(self.totals[t]), P(self.anc), P(self.status), P(self.ws), st), "gmx_resample_rows")
+        be.check(be.c.gmx_pick_rows(P(self.keys_as[t]), P(self.as_lw), R, n, n, P(self.as_tmp), P(self.as_status),
+                                    P(self.pick_ws), st), "gmx_pick_rows")
+        torch.add(self.as_tmp, self.as_offs, out=self.anc[:, n - 1])
+
+
+if not args.skip_ancestors:
+    T = int(os.environ.get("AT", 100))
+    init, step = workloads.make_lgssm(G)
+    ys = torch.from_numpy(workloads.lgssm_data(T))
+    for R, n in [tuple(int(v) for v in s.split(":")) for s in os.environ.get("AS_SHAPES", "4096:256,64:16384").split(",")]:
+        keys = split(G.key(314159), R)
+        seed = smc.ConditionalBank(init, step, n, R, T).prepare(keys, ys)
+        seed.launch()
+        path = seed.draw(G.key(1)).clone()
+        del seed
+        banks = {"conditional": smc.ConditionalBank(init, step, n, R, T),
+                 "ancestors_fused": smc.ConditionalBank(init, step, n, R, T, ancestor_sampling=True),
+                 "ancestors_composed": ComposedAncestorBank(init, step, n, R, T, ancestor_sampling=True)}
+        for b in banks.values():
+            b.prepare(keys, ys, retained=path).capture()
+        forms = {name: b.launch for name, b in banks.items()}
+        for _ in range(3):                          # warm-up
+            for f in forms.values():
+                f()
+        torch.cuda.synchronize()
+        fu, co, pl = banks["ancestors_fused"], banks["ancestors_composed"], banks["conditional"]
+        assert torch.equal(fu.hist_ancs, co.hist_ancs) and torch.equal(fu.hist_xs, co.hist_xs), "fused and composed disagree"
+        assert torch.equal(fu.hist_xs, pl.hist_xs) and torch.equal(fu.hist_lws, pl.hist_lws), "ancestor sampling moved a particle"
+        moved = int((fu.hist_ancs != pl.hist_ancs).sum().item())
+        assert fu.status.tolist() == [0, 0]
+        ts = {name: [] for name in forms}
+        for _ in range(args.reps):                  # alternated: every form sees the same neighbours on the machine
+            for name, f in forms.items():
+                ts[name].append(timed(f, 3))
+        med = {name: statistics.median(v) for name, v in ts.items()}
+        emit(dict(common, tool="time_conditional", what="ancestors", R=R, n=n, T=T, ms={name: spread(v) for name, v in ts.items()},
+                  us_per_step={name: 1e6 * m / T for name, m in med.items()},
+                  spread_over_median={name: (max(v) - min(v)) / med[name] for name, v in ts.items()},
+                  fused_over_composed=med["ancestors_fused"] / med["ancestors_composed"],
+                  fused_over_conditional=med["ancestors_fused"] / med["conditional"],
+                  launches_per_ancestor_step={"conditional": 3 if n <= 1024 else 6, "ancestors_fused": 5 if n <= 1024 else 9,
+                                              "ancestors_composed": 8 if n <= 1024 else 10},
+                  pinned_ancestors_moved=moved, fused_equals_composed=True))
+        del banks, forms, fu, co, pl
