@@ -3695,6 +3695,46 @@ extern "C" int gmx_resample_rows_as(const uint32_t* keys_d, const float* lw_d, i
   return 0;
 }
 
+extern "C" size_t gmx_resample_rows_ess_workspace(int kind, int64_t rows, int64_t n) {
+  return gmx_resample_rows_ess_bytes_(kind, rows, n);
+}
+
+// gmx_resample_rows on lw + carry, each row resampled only when its integer ESS is below ess_q8 / 256 (adaptive
+// resampling): n <= 1024 only, ONE launch
+extern "C" int gmx_resample_rows_ess(int kind, const uint32_t* keys_d, float* lw_d, float* carry_d, int64_t rows, int64_t n,
+                                     int64_t ld, int64_t index_stride, uint32_t ess_q8, float* max_d, uint64_t* total_d,
+                                     int32_t* resampled_d, int32_t* ancestors_d, int64_t* status_d, void* workspace_d,
+                                     gmx_stream stream) {
+  if (!keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("gmx_resample_rows_ess: null argument%s");
+  const gmx_refusal no = gmx_resample_rows_ess_refusal_(kind, rows, n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_ess", no.v);
+  if (((uintptr_t)lw_d & 3) || ((uintptr_t)carry_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) ||
+      ((uintptr_t)resampled_d & 3) || ((uintptr_t)max_d & 3) || ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
+    return gmx_fail("gmx_resample_rows_ess: a pointer is not aligned to its element%s");
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  auto* status = (unsigned long long*)status_d;
+  rows_ess ess;
+  ess.carry = carry_d; ess.ess_q8 = ess_q8; ess.resampled = resampled_d;
+#define GMX_ROWS_ESS2(KIND, W_)                                                                                        \
+  hipLaunchKernelGGL((k_rows_small_ess<KIND, W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
+                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, ess)
+#define GMX_ROWS_ESS(KIND)                                                                                             \
+  do {                                                                                                                 \
+    if (n <= 256) GMX_ROWS_ESS2(KIND, 1);                                                                              \
+    else if (n <= 512) GMX_ROWS_ESS2(KIND, 2);                                                                         \
+    else GMX_ROWS_ESS2(KIND, 4);                                                                                       \
+  } while (0)
+  if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_ESS(GMX_RESAMPLE_SYSTEMATIC);
+  else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_ESS(GMX_RESAMPLE_STRATIFIED);
+  else GMX_ROWS_ESS(GMX_RESAMPLE_MULTINOMIAL);
+#undef GMX_ROWS_ESS
+#undef GMX_ROWS_ESS2
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------

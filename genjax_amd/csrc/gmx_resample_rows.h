@@ -24,6 +24,11 @@
 //               of logits as gmx_pick_rows draws it.  n <= 1024: k_rows_small_as<W>, the same body with that draw compiled
 //               in — still ONE launch, no barrier added; n > 1024: the chain above, then k_pick_stats and k_pick_row
 //               (gmx_backward.h) on the second matrix, k_pick_row writing slot n - 1 of the row.
+//   adaptive (gmx_resample_rows_ess, n <= 1024 only): a second matrix `carry` is added to the weights (one float32 add,
+//               written back), and the row is resampled only when the effective sample size of its fixed-point weights is
+//               below ess_q8 / 256 — an exact integer predicate; a row that is not keeps its accumulated weights in
+//               `carry` and gets identity ancestors.  k_rows_small_ess<kind, W>, the same body with the decision compiled in:
+//               still ONE launch, no barrier added.
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
 // host compiler: the ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
 // multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
@@ -106,7 +111,30 @@ struct rows_as {
   int64_t ld;
   unsigned long long* status;    // counts the rows whose ancestor logits carry no mass
 };
-// a row of the matrix as the kernel reads it: nothing else writes it — unless the kernel itself writes the pin back
+// What gmx_resample_rows_ess adds to a row (adaptive resampling: the row is resampled only when its ESS is low)
+struct rows_ess {
+  float* carry;                  // the log-weights carried since the row's last resampling: the matrix's layout, rows ld apart
+  uint32_t ess_q8;               // resample iff ESS < ess_q8 / 256
+  int32_t* resampled;            // [rows]: the decision
+};
+// sum of squares of the truncated weights as (hi, lo) += v^2 split at bit 32; V2 = (hi << 32) + lo, every part exact in u64
+__device__ __forceinline__ u128 rows_ess_v2(uint64_t hi, uint64_t lo) {
+  u128 r;
+  r.lo = (hi << 32) + lo;
+  r.hi = (hi >> 32) + (r.lo < lo ? 1ull : 0ull);
+  return r;
+}
+// Four floats of consecutive columns base .. base + 3 of a row: rows_store4's rule
+__device__ __forceinline__ void rows_store4f(float* row, int64_t base, int64_t n, const float v[4]) {
+  if (base + 4 <= n && (((uintptr_t)(row + base)) & 15u) == 0u) {
+    *reinterpret_cast<float4*>(row + base) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (base + c < n) row[base + c] = v[c];
+  }
+}
+// a row of the matrix as the kernel reads it: nothing else writes it — unless the kernel itself writes into it
 template <bool PIN> struct rows_row_ptr { typedef const float* __restrict__ type; };
 template <> struct rows_row_ptr<true> { typedef const float* type; };
 
@@ -121,15 +149,24 @@ template <> struct rows_row_ptr<true> { typedef const float* type; };
 // threshold of as.keys[r] at counter 0, which is k_pick_row's answer for a row of one tile (K = k_b, nothing below the
 // tile); the thread that holds slot n - 1 stores that count, clamped, instead of its search.  64 bytes of LDS of its own;
 // without AS nothing of it is compiled.
-template <int KIND, int W, bool PIN, bool AS = false>
-__device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ keys, typename rows_row_ptr<PIN>::type lw,
+// ESS (any kind, never with PIN or AS): the row's group also loads the row of `carry` (with the weights: one wait), adds it
+// — x = lw + carry, ONE float32 add, written back into the matrix — and everything above runs on x.  Each thread truncates
+// its four fixed-point weights to v = w >> (shift - 30) (at most 2^30) and sums v, and v^2 in two halves split at bit 32;
+// the three wave sums go to LDS packed in two words beside s_scan, before the barrier that follows it.  After that barrier
+// every thread of the group holds V1 = sum v and V2 = sum v^2 exactly and evaluates V1^2 * 256 < ess_q8 * V2 in 128 bits
+// (V1^2 <= 2^80, ess_q8 V2 < 2^102).  A resampled row: the searches as always, carry = 0.  Any other: no search, identity
+// ancestors, carry = x.  No barrier and 64 bytes of LDS of its own; without ESS nothing of it is compiled.
+template <int KIND, int W, bool PIN, bool AS = false, bool ESS = false>
+__device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ keys, typename rows_row_ptr<PIN || ESS>::type lw,
                                                 int64_t rows, int64_t n, int64_t ld, int64_t index_stride, float scale,
                                                 float* __restrict__ max_out, uint64_t* __restrict__ total_out,
                                                 int32_t* __restrict__ anc, unsigned long long* __restrict__ status,
-                                                const rows_pin& pin, const rows_as& as = rows_as{}) {
+                                                const rows_pin& pin, const rows_as& as = rows_as{},
+                                                const rows_ess& ess = rows_ess{}) {
   static_assert(W == 1 || W == 2 || W == 4, "waves per row");
   static_assert(!PIN || KIND == GMX_RESAMPLE_MULTINOMIAL, "forcing a slot is a conditional draw under iid slots only");
   static_assert(!AS || (KIND == GMX_RESAMPLE_MULTINOMIAL && !PIN), "re-drawing a slot: iid slots only; the pin is in the matrix");
+  static_assert(!ESS || (!PIN && !AS), "the adaptive form is the plain resampler's");
   constexpr int RPW = 4 / W, GT = 64 * W;
   __shared__ float s_max[4];
   __shared__ uint64_t s_scan[4];
@@ -137,12 +174,13 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   __shared__ float s_amax[AS ? 4 : 1];                   // (AS only: unused arrays take no LDS)
   __shared__ uint64_t s_ascan[AS ? 4 : 1];
   __shared__ uint32_t s_acnt[AS ? 4 : 1];
+  __shared__ uint64_t s_ess[ESS ? 8 : 1];                // (ESS only) per wave: V2's low word | V2's high byte + V1 << 8
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = tid / GT, gt = tid % GT;
   const int64_t r_ = (int64_t)blockIdx.x * RPW + grp;
   const bool live = r_ < rows;
   const int64_t r = live ? r_ : rows - 1;
-  typename rows_row_ptr<PIN>::type row = lw + r * ld;
+  typename rows_row_ptr<PIN || ESS>::type row = lw + r * ld;
   const int64_t base = (int64_t)gt * 4;
   float x[4];
   float p = 0.0f;
@@ -154,6 +192,13 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   pick_load4(row, base, n, x);
   float a[4];
   if (AS) pick_load4(as.lw + r * as.ld, base, n, a);     // (both matrices' loads are out before the first wait)
+  if (ESS) {                                             // (likewise) x = lw + carry, written back
+    float cy[4];
+    pick_load4(ess.carry + r * ld, base, n, cy);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = x[c] + cy[c];
+    if (live) rows_store4f(const_cast<float*>(lw) + r * ld, base, n, x);
+  }
   if (PIN && live) {                                     // the D state words, by the row's thread group
     const int64_t at = r * pin.x_row_stride + n - 1;
     if (gt < pin.D) pin.x_out[(int64_t)gt * pin.x_ld + at] = px;
@@ -184,6 +229,27 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   }
   const uint64_t inc = wave_scan_u64(run);
   if (lane == 63) s_scan[wave] = inc;
+  if (ESS) {                                             // v = w >> (shift - 30); sum v, sum v^2 (its halves apart), per wave
+    const int down = (int)(gmx_f2u(scale) >> 23) - 127 - 30;
+    uint64_t v1 = 0, lo2 = 0, hi2 = 0, prev = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const uint64_t v = (q[c] - prev) >> down;
+      prev = q[c];
+      const uint64_t sq = v * v;
+      v1 += v;
+      lo2 += sq & 0xffffffffull;
+      hi2 += sq >> 32;
+    }
+    v1 = wave_sum_u64(v1);
+    lo2 = wave_sum_u64(lo2);
+    hi2 = wave_sum_u64(hi2);
+    if (lane == 63) {
+      const u128 v2 = rows_ess_v2(hi2, lo2);             // below 2^72 per wave; V1 below 2^56
+      s_ess[2 * wave] = v2.lo;
+      s_ess[2 * wave + 1] = v2.hi | (v1 << 8);
+    }
+  }
   uint64_t qa[4], run_a = 0, inc_a = 0;
   if (AS) {                                              // the ancestor logits: one tile, their own reference
     float MA = s_amax[grp * W];
@@ -239,6 +305,32 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
     total_out[r] = total;
     if (total == 0ull) atomicAdd(status, 1ull);
   }
+  if (ESS) {                                             // the decision, by every thread of the row's group alike
+    u128 V2; V2.hi = 0ull; V2.lo = 0ull;
+    uint64_t V1 = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const uint64_t a0 = s_ess[2 * (grp * W + w)], a1 = s_ess[2 * (grp * W + w) + 1];
+      V2.lo += a0;
+      V2.hi += (a1 & 0xffull) + (V2.lo < a0 ? 1ull : 0ull);
+      V1 += a1 >> 8;
+    }
+    const u128 lhs = mul64(V1, V1 << 8);                 // V1^2 * 256 <= 2^88
+    const u128 m_lo = mul64(V2.lo, (uint64_t)ess.ess_q8);
+    u128 rhs; rhs.lo = m_lo.lo; rhs.hi = m_lo.hi + V2.hi * (uint64_t)ess.ess_q8;      // ess_q8 * V2 < 2^102
+    const bool go = total != 0ull && ((int64_t)ess.ess_q8 > 256 * n || gt128(rhs, lhs));
+    if (gt == 0) ess.resampled[r] = go ? 1 : 0;
+    float* crow = ess.carry + r * ld;
+    if (!go) {                                           // carried forward: identity ancestors, the weights kept
+      const int32_t first = (int32_t)(r * index_stride) + (int32_t)base;
+      const int32_t idn[4] = {first, first + 1, first + 2, first + 3};
+      rows_store4(anc + r * n, base, n, idn);
+      rows_store4f(crow, base, n, x);
+      return;
+    }
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    rows_store4f(crow, base, n, zero);
+  }
   gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
   const uint64_t u0 = KIND == GMX_RESAMPLE_SYSTEMATIC ? (uint64_t)(gmx_bits32(key, 0ull) >> 9) : 0ull;
   const uint64_t D = (uint64_t)n << 23;
@@ -293,6 +385,16 @@ k_rows_small_as(const uint32_t* __restrict__ keys, const float* __restrict__ lw,
                 int32_t* __restrict__ anc, unsigned long long* __restrict__ status, rows_as as) {
   rows_small_body<GMX_RESAMPLE_MULTINOMIAL, W, false, true>(keys, lw, rows, n, ld, index_stride, scale, max_out, total_out, anc,
                                                             status, rows_pin{}, as);
+}
+
+// (`lw` and `carry` are read and written: not __restrict__)
+template <int KIND, int W>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_small_ess(const uint32_t* __restrict__ keys, float* lw, int64_t rows, int64_t n, int64_t ld, int64_t index_stride,
+                 float scale, float* __restrict__ max_out, uint64_t* __restrict__ total_out, int32_t* __restrict__ anc,
+                 unsigned long long* __restrict__ status, rows_ess ess) {
+  rows_small_body<KIND, W, false, false, true>(keys, lw, rows, n, ld, index_stride, scale, max_out, total_out, anc, status,
+                                               rows_pin{}, rows_as{}, ess);
 }
 
 // The pins into the matrix and the state store (gmx_rows_pin; gmx_resample_rows_pinned past one tile, before the row's
@@ -536,6 +638,43 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_as(const uint32_t*
   std::vector<uint64_t> ws((gmx_resample_workspace(n) + 7) / 8 + 2);       // (what the per-row path may ask for)
   if (gmx_pick_rows(as_keys_d, as_lw_d, rows, n, as_ld, tmp.data(), status_d + 1, ws.data(), stream)) return 1;
   for (int64_t r = 0; r < rows; ++r) ancestors_d[r * n + n - 1] = tmp[(size_t)r] + (int32_t)(r * index_stride);
+  return 0;
+}
+
+extern "C" __attribute__((used)) inline size_t gmx_resample_rows_ess_workspace(int kind, int64_t rows, int64_t n) {
+  return gmx_resample_rows_ess_bytes_(kind, rows, n);
+}
+
+// the definition, in order: the sum into the matrix, the unconditional draw on it, the integer predicate, the gating
+extern "C" __attribute__((used)) inline int gmx_resample_rows_ess(int kind, const uint32_t* keys_d, float* lw_d, float* carry_d, int64_t rows,
+                                            int64_t n, int64_t ld, int64_t index_stride, uint32_t ess_q8, float* max_d,
+                                            uint64_t* total_d, int32_t* resampled_d, int32_t* ancestors_d, int64_t* status_d,
+                                            void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_resample_rows_ess";
+  if (!keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d)
+    return gmx_fail("%s: null argument", who, 0);
+  const gmx_refusal no = gmx_resample_rows_ess_refusal_(kind, rows, n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t i = 0; i < n; ++i) lw_d[r * ld + i] = lw_d[r * ld + i] + carry_d[r * ld + i];
+  if (gmx_resample_rows(kind, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d, status_d, workspace_d,
+                        stream)) return 1;
+  const int shift = gmx_pick_rows_shift_(n);
+  for (int64_t r = 0; r < rows; ++r) {
+    const float ref = gmx_tile_ref(gmx_tile_exp(max_d[r]));      // one tile: the row's reference is the tile's
+    unsigned __int128 V1 = 0, V2 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t v = gmx_exp_fixed(lw_d[r * ld + i] - ref, shift) >> (shift - 30);
+      V1 += v;
+      V2 += (unsigned __int128)v * v;
+    }
+    const bool go = total_d[r] != 0 && (ess_q8 > gmx_ess_always_(n) || V1 * V1 * 256 < (unsigned __int128)ess_q8 * V2);
+    resampled_d[r] = go ? 1 : 0;
+    for (int64_t i = 0; i < n; ++i) {
+      carry_d[r * ld + i] = go ? 0.0f : lw_d[r * ld + i];
+      if (!go) ancestors_d[r * n + i] = (int32_t)(i + r * index_stride);
+    }
+  }
   return 0;
 }
 #endif

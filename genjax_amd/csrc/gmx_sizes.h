@@ -115,7 +115,8 @@ static inline const char* gmx_tile_form_refusal_(gmx_tile_form form, int kind, i
   return nullptr;
 }
 
-// ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned, gmx_rows_pin, gmx_resample_rows_as ----
+// ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned, gmx_rows_pin, gmx_resample_rows_as,
+// gmx_resample_rows_ess ----
 // gmx_pick_rows' workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
 static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n < 1) return 16;
@@ -185,6 +186,23 @@ static inline size_t gmx_resample_rows_as_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
   return gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n) + gmx_pick_rows_bytes_(rows, n);
 }
+// gmx_resample_rows_ess: gmx_resample_rows' arguments, for rows of ONE tile — the decision is taken on the row's per-element
+// fixed-point weights, which past one tile are not the same integers (each tile has its own exponent), and it would have
+// to be known before any tile's ancestors are written: a launch boundary
+static inline gmx_refusal gmx_resample_rows_ess_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
+  if (n >= 1 && n <= GMX_TILE) return gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
+  const gmx_refusal no = gmx_resample_rows_refusal_(kind, 1, 1, 1, 0);                      // the kinds, in its words
+  if (no.fmt) return no;
+  return {"%s: n = %lld is outside [1, 1024]: the ESS decision is taken on the fixed-point weights of a row of one tile "
+          "(past one tile they are not the same integers, and the decision would need a launch of its own)", (long long)n};
+}
+// gmx_resample_rows_ess' workspace: nothing (one launch, a row is one tile)
+static inline size_t gmx_resample_rows_ess_bytes_(int kind, int64_t rows, int64_t n) {
+  (void)kind; (void)rows; (void)n;
+  return 16;
+}
+// an ess_q8 above this resamples every row with mass (the ESS of n weights is at most n)
+static inline uint32_t gmx_ess_always_(int64_t n) { return (uint32_t)(256 * n); }
 
 // ---- sweep history ----
 static inline gmx_refusal gmx_history_record_refusal_(int32_t D, int64_t n, uint32_t expect_tag, bool has_null, bool has_status) {

@@ -742,6 +742,7 @@ def resample(key: Key, collection: ParticleCollection, kind="systematic", n_out=
 
 ROW_KINDS = (SYSTEMATIC, STRATIFIED, MULTINOMIAL)      # what gmx_resample_rows takes
 ROWS_N_MAX = FUSED_RESAMPLE_MAX
+ROWS_ESS_N_MAX = 1024                  # gmx_resample_rows_ess: a row of one CDF tile
 
 
 def resample_rows(kind, keys: Key, lw: torch.Tensor, index_stride: int = 0, *, out=None, workspace=None):
@@ -2040,11 +2041,25 @@ class BootstrapBank(_Sweep):
     `params`: a tuple of float32 [R] tensors, one value per filter; the models are called as init(*params_r) and
     step(x_prev, *step_extra(t), *params_r).  Each is expanded ONCE, in prepare(), to a persistent [R * n] per-particle
     leaf (4 bytes per particle and parameter read by every step; nothing is launched for it inside the sweep) — the
-    engine's launch-uniform leaves have no per-row form.  ys: [T], shared by the filters."""
+    engine's launch-uniform leaves have no per-row form.  ys: [T], shared by the filters.
+
+    ess_threshold=tau (None: every row is resampled at every step, the sweep above launch for launch): ADAPTIVE
+    resampling, decided per filter and per step inside the row resampler's one launch (gmx_resample_rows_ess, n <= 1024).
+    Row r is resampled after step t only when the effective sample size of its accumulated weights is below tau * n — an
+    exact integer predicate on the fixed-point weights, ess_q8 = min(ceil(tau * n * 256), 256 n + 1) computed on the host:
+    tau = 0 never resamples, tau > 1 (or inf) always does, and is then bit for bit the sweep without the argument.  A row
+    that is not resampled keeps its particles (identity ancestors) and carries its log-weights into the next step, where
+    the new observation weights are added to them; state() returns these ACCUMULATED log-weights and resampled() the
+    [T, R] table of decisions.  log_ml()[r] sums the evidence terms of the steps after which row r was resampled, and of
+    step T - 1 always.  This is the unbiased estimate: between two resamplings a particle's weight is the unnormalised
+    PRODUCT of its incremental weights, so its mean over the row at the next resampling (or at the end) estimates the
+    ratio of normalisers across the whole stretch at once, and the product of those means over the stretches — each
+    started from an equally weighted population — is the usual product-form estimate of Z (Del Moral, Doucet & Jasra
+    2012, section 2); a skipped step's own term is already inside the next counted one."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
-                 noise_ahead=None, fuse_resample=None, comm=None):
+                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2065,6 +2080,17 @@ class BootstrapBank(_Sweep):
         self.step_extra = step_extra or (lambda t: ())
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
+        self.ess_threshold, self.ess_q8 = None, None
+        if ess_threshold is not None:
+            tau = float(ess_threshold)
+            if math.isnan(tau) or tau < 0.0:
+                raise ValueError(f"BootstrapBank(ess_threshold={ess_threshold!r}): a fraction of n, >= 0 (above 1, or inf: always)")
+            if self.n > ROWS_ESS_N_MAX:
+                raise NotImplementedError(f"BootstrapBank(ess_threshold=): n_particles = {self.n} > {ROWS_ESS_N_MAX} "
+                                          "(gmx_resample_rows_ess decides on the weights of a row of one tile)")
+            always = 256 * self.n + 1
+            self.ess_threshold = tau
+            self.ess_q8 = always if tau > 1.0 else min(int(math.ceil(tau * self.n * 256)), always)
 
     def _key_tables(self, keys: Key, third=False):
         """the key schedule of every row, on the host: [T, R, 2] proposal keys and [T, R, 2] resampling keys (int32 words);
@@ -2105,6 +2131,9 @@ class BootstrapBank(_Sweep):
         self.status = torch.zeros((1,), dtype=torch.int64, device=dev)         # rows without mass, over the last sweep
         self.shift = cdf_shift(n)
         self.ws = torch.zeros(((int(be.c.gmx_resample_rows_workspace(self.kind, R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
+        if self.ess_q8 is not None:
+            self.carry = torch.zeros((N,), dtype=torch.float32, device=dev)    # log-weights since the row's last resampling
+            self.flags = torch.zeros((T, R), dtype=torch.int32, device=dev)    # was row r resampled after step t
         self.params_full = []
         for p in self.params:
             p = torch.as_tensor(p)
@@ -2125,14 +2154,27 @@ class BootstrapBank(_Sweep):
         return self
 
     def _resample(self, t):
+        if self.ess_q8 is not None:
+            return self._resample_adaptive(t)
         resample_rows(self.kind, self.step_keys[t][1], self.lw.reshape(self.R, self.n), index_stride=self.n,
                       out=(self.anc, self.totals[t], self.maxs[t], self.status), workspace=self.ws)
 
+    def _resample_adaptive(self, t):
+        """lw += carry; every row whose integer ESS is below the threshold resampled, the others carried (one launch)"""
+        be = _lib.get()
+        R, n = self.R, self.n
+        be.check(be.c.gmx_resample_rows_ess(self.kind, be.ptr(self.step_keys[t][1]), be.ptr(self.lw), be.ptr(self.carry), R, n,
+                                            n, n, self.ess_q8, be.ptr(self.maxs[t]), be.ptr(self.totals[t]),
+                                            be.ptr(self.flags[t]), be.ptr(self.anc), be.ptr(self.status), be.ptr(self.ws),
+                                            be.stream()), "gmx_resample_rows_ess")
+
     def enqueue(self):
-        """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (no syncs, no
-        allocations, no host read of a device value)"""
+        """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
+        ess_threshold=: gmx_resample_rows_ess) — no syncs, no allocations, no host read of a device value"""
         N = self.R * self.n
         self.status.zero_()
+        if self.ess_q8 is not None:
+            self.carry.zero_()
         for t in range(self.T):
             _mh, prog, leaves, key, bufs = self._programs(t)
             bufs[prog.wo[1]] = self.lw.reshape(1, N)
@@ -2141,18 +2183,30 @@ class BootstrapBank(_Sweep):
 
     def log_ml(self) -> np.ndarray:
         """float64 [R]: row r is BootstrapSweep.log_ml() of that filter — sum_t [ ref(M_t) + log(total_t 2^-shift) - log n ]
-        from the [T, R] evidence terms, finished in float64 on the host (synchronises)."""
+        from the [T, R] evidence terms, finished in float64 on the host (synchronises).  With ess_threshold=: the terms of
+        the steps after which row r was resampled, and of step T - 1 always (the class docstring says why), in the same
+        order; with every row resampled at every step that is the same float."""
         terms = evidence_terms(self.maxs.cpu().numpy(), self.totals.cpu().numpy(), self.shift, self.n)      # [T, R]
+        counted = np.ones((self.T, self.R), dtype=bool)
+        if self.ess_q8 is not None:
+            counted = self.resampled().numpy().copy()
+            counted[self.T - 1] = True
         out = np.empty((self.R,), dtype=np.float64)
         for r in range(self.R):
-            tr = np.ascontiguousarray(terms[:, r])
+            tr = np.ascontiguousarray(terms[:, r][counted[:, r]])
             # (-inf: a step where no particle of the row carried any mass)
             out[r] = -math.inf if np.any(np.isneginf(tr)) else float(np.sum(tr))
         return out
 
+    def resampled(self) -> torch.Tensor:
+        """bool [T, R], on the host: was row r resampled after step t in the last sweep (ess_threshold= only; synchronises)"""
+        if self.ess_q8 is None:
+            raise ValueError("BootstrapBank.resampled: without ess_threshold= every row is resampled at every step")
+        return self.flags.cpu() != 0
+
     def state(self):
-        """(x_T before the last resampling: [R, n], [R, n, D] or a tuple of [R, n]; log-weights [R, n]; the last ancestors,
-        int32 [R, n], row-local)"""
+        """(x_T before the last resampling: [R, n], [R, n, D] or a tuple of [R, n]; log-weights [R, n] — with
+        ess_threshold=, accumulated since the row's last resampling; the last ancestors, int32 [R, n], row-local)"""
         R, n = self.R, self.n
         x = self.store.per_filter((self.T - 1) % 2, R, n)
         local = self.anc - (torch.arange(R, dtype=torch.int32, device=self.anc.device) * n).reshape(R, 1)
@@ -2207,11 +2261,15 @@ class ConditionalBank(BootstrapBank):
     more than one component, and a step model that samples nothing besides the state and the observation.  A chain whose
     ancestor logits carry no mass at some step keeps the plain pin there and is counted: draw() raises FloatingPointError.
 
-    Not here: rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations.
+    Not here: rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations, ess_threshold=.
     Memory: the history slabs take T * (D + 2) * R * n * 4 bytes; ancestor sampling adds (D + 1) * R * n * 4."""
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
-                 specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False):
+                 specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
+                 ess_threshold=None):
+        if ess_threshold is not None:
+            raise NotImplementedError("ConditionalBank: ess_threshold= is not supported (the pinned slot and the recorded "
+                                      "history assume a resampling after every step; BootstrapBank takes it)")
         kind = _KINDS.get(resample, None) if isinstance(resample, str) else int(resample)
         if kind != MULTINOMIAL:
             name = resample if isinstance(resample, str) else next((k for k, v in _KINDS.items() if v == kind), resample)

@@ -704,6 +704,32 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
  *                   Limits: those of gmx_resample_rows; as_ld >= n; every pointer aligned to its element; workspace_d:
  *                   gmx_resample_rows_as_workspace(rows, n) bytes (gmx_resample_rows' plus gmx_pick_rows' past n = 1024),
  *                   8-byte aligned, contents irrelevant on entry.
+ *   gmx_resample_rows_ess   (additive, ABI still v8.  Reference call site: none of its own — adaptive resampling, the
+ *                   ESS rule of Liu & Chen 1995 / Del Moral, Doucet & Jasra 2012, per row of a bank of filters.)
+ *                   gmx_resample_rows on the sum of two matrices, each row resampled only when the effective sample size of
+ *                   its weights is below ess_q8 / 256; a row that is not resampled carries its weights forward.  carry_d has
+ *                   the layout of lw_d (rows ld elements apart).  DEFINITION, in this order, for every row r:
+ *                     1. x_i = lw_d[r * ld + i] + carry_d[r * ld + i], ONE float32 add, WRITTEN BACK to lw_d[r * ld + i]:
+ *                        afterwards the matrix holds the accumulated log-weights;
+ *                     2. max_d[r], total_d[r], the CANDIDATE ancestors and the no-mass count in status_d[0] are exactly what
+ *                        gmx_resample_rows(kind, ...) gives on x — whatever the decision;
+ *                     3. with w_i the row's fixed-point weights (floor(exp(x_i - ref) 2^shift) against the row's reference
+ *                        ref = ceil(max / ln 2) ln 2, shift = 62 - ceil(log2 n): the terms of its integer CDF),
+ *                        v_i = w_i >> (shift - 30), V1 = sum v_i, V2 = sum v_i^2: the row is RESAMPLED iff
+ *                        V1^2 * 256 < ess_q8 * V2, that is ESS = V1^2 / V2 < ess_q8 / 256 on the truncated weights.
+ *                        V1^2 <= 2^80 and ess_q8 * V2 < 2^102: both sides are exact 128-bit integers, nothing is rounded.
+ *                        ess_q8 = 0: never; ess_q8 > 256 n: every row with mass; a row without mass (total = 0) is not
+ *                        resampled (and is counted in status_d[0] as always);
+ *                     4. a resampled row: ancestors_d[r, :] = the candidates, carry_d[r, :] = 0, resampled_d[r] = 1;
+ *                     5. any other row: ancestors_d[r * n + i] = i + r * index_stride, carry_d[r * ld + i] = x_i,
+ *                        resampled_d[r] = 0.
+ *                   The padding between rows of lw_d and carry_d is neither read as a weight nor written.  ONE launch (the
+ *                   row's thread group holds both matrices' columns; the three sums ride beside the scan of the weights:
+ *                   no barrier added, 64 bytes of LDS; a row that is not resampled skips its slot searches).
+ *                   Limits: kinds, rows, ld, index_stride and nulls as gmx_resample_rows; 1 <= n <= 1024 — past one tile
+ *                   the per-element weights at the row's scale are not the same integers and the decision would need a
+ *                   launch boundary before the ancestors: refused by name; every pointer aligned to its element;
+ *                   workspace_d: gmx_resample_rows_ess_workspace(kind, rows, n) bytes (16: nothing is kept in it), not null.
  * A null pointer or an out-of-range size returns non-zero before anything is launched.
  * ---------------------------------------------------------------------- */
 size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
@@ -731,6 +757,12 @@ int gmx_resample_rows_as(const uint32_t* keys_d /* [rows, 2] */, const float* lw
                          int64_t as_ld /* elements between rows of as_lw_d, >= n */, float* max_d /* [rows] */,
                          uint64_t* total_d /* [rows] */, int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [2] */,
                          void* workspace_d, gmx_stream stream);
+size_t gmx_resample_rows_ess_workspace(int kind, int64_t rows, int64_t n);
+int gmx_resample_rows_ess(int kind, const uint32_t* keys_d /* [rows, 2] */, float* lw_d, float* carry_d /* as lw_d */,
+                          int64_t rows, int64_t n, int64_t ld, int64_t index_stride, uint32_t ess_q8,
+                          float* max_d /* [rows] */, uint64_t* total_d /* [rows] */, int32_t* resampled_d /* [rows] */,
+                          int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [1] */, void* workspace_d,
+                          gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
