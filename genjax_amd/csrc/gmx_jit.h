@@ -66,6 +66,38 @@ struct gmx_jit_ctx {
   uint64_t* peer_land;      // gmx_run_args.peer: thread p < world (p != rank): rank p's landing block; else null
   uint32_t peer_tag;        // ... and this step's tag (loaded at the top of the kernel: the epilogue must not wait for it)
   bool first, last;         // this step handles the first / last of the thread's particles
+  // Tile-relative addressing of everything indexed by a particle's OWN row.  Row i = tile0 + p * 256 + tid of a leaf is
+  //   [base + 4 (tile0 + srow)]            workgroup-uniform: one 64-bit scalar address
+  //   + 4 tid                              one 32-bit VGPR per thread, whatever the leaf and the particle
+  //   + p * 1024                           the instruction's immediate offset
+  // which is the scalar-base form of a global load / store — no 64-bit vector address arithmetic per access.  That is
+  // what a STORE uses (inactive lanes are predicated off).  A LOAD may be a prefetch issued for every lane, so its
+  // offset is CLAMPED to the last particle of group p below n (one min against a uniform per particle, where the
+  // compare + select on the row used to be); a group wholly past n reads group 0 (the tile's first particle exists).
+  uint32_t tile0;           // first row of this workgroup's tile in every leaf (the row of a 2-D launch included)
+  uint32_t tid4;            // 4 * threadIdx.x
+  uint32_t grp[PPV];        // loads: p * 256 — 0 for a group wholly past n (uniform)
+  uint32_t off4[PPV], off1[PPV];   // loads: clamped offset inside the group, in bytes of a 32-bit / an 8-bit leaf
+  // (the zero-extension has to be made in the basic block of the access: instruction selection works block by block,
+  //  and a zero-extension shared with an access of an earlier block arrives as a 64-bit VGPR pair — a 64-bit vector
+  //  add per access again.  The empty asm gives every access its own copy of the offset; it emits nothing.)
+  static __device__ __forceinline__ uint64_t zext_here(uint32_t o) { asm volatile("" : "+v"(o)); return (uint64_t)o; }
+  template <class T>
+  __device__ __forceinline__ const T* own_in_of(const void* base, int p, int64_t srow = 0) const {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 1, "32-bit and 8-bit leaves");
+    const char* ub = (const char*)base + ((int64_t)(uint64_t)(tile0 + grp[p]) + srow) * (int64_t)sizeof(T);
+    return (const T*)(ub + zext_here(sizeof(T) == 4 ? off4[p] : off1[p]));
+  }
+  template <class T>
+  __device__ __forceinline__ T* own_out_of(void* base, int p, int64_t srow = 0) const {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 1, "32-bit and 8-bit leaves");
+    char* ub = (char*)base + ((int64_t)(uint64_t)tile0 + srow) * (int64_t)sizeof(T);
+    return (T*)(ub + zext_here(sizeof(T) == 4 ? tid4 : tid4 >> 2)) + p * GMX_BLOCK;
+  }
+  template <class T>
+  __device__ __forceinline__ const T* own_in(const void* base, int64_t srow) const { return own_in_of<T>(base, cur, srow); }
+  template <class T>
+  __device__ __forceinline__ T* own_out(void* base, int64_t srow) const { return own_out_of<T>(base, cur, srow); }
   __device__ __forceinline__ uint32_t pool(uint32_t i) const {
     return i < (uint32_t)NDYN ? A->uni[i] : consts[i - (uint32_t)NDYN];
   }
@@ -103,6 +135,9 @@ struct gmx_jit_ctx {
     gmx_red_lse(A->red_out_d, lds4, part, rows, x, active);
   }
 };
+
+template <int NDYN, int PPV>
+struct gmx_ctx_tiled<gmx_jit_ctx<NDYN, PPV> > { static constexpr bool value = true; };
 
 // PP particles per thread: particle p of a thread is row (blockIdx * PP + p) * 256 + threadIdx, so every
 // load / store stays a coalesced 256-particle group and the block partial rows are the ones the
@@ -176,8 +211,7 @@ struct gmx_jit_ctx {
        forms below are zero-extensions, so address arithmetic is a shift-add, not 64-bit compares / selects */  \
     const uint32_t n32 = (uint32_t)n;                                                            \
     int64_t idx[PP];                                                                             \
-    uint32_t cidx[PP];         /* idx clamped into [0, n): a valid row for prefetches of inactive lanes */ \
-    uint32_t arow[PP];         /* ancestors[cidx] */                                             \
+    uint32_t arow[PP];         /* ancestors[own row] */                                             \
     uint32_t pre[(NPRE) > 0 ? (NPRE) : 1][PP];                                                   \
     bool act[PP];                                                                                \
     uint32_t gmx_t = 0u;       /* iteration number of the innermost enclosing GMX_JIT_LOOP (0 outside) */ \
@@ -185,15 +219,25 @@ struct gmx_jit_ctx {
     /* a 2-D launch (gmx_program_run, GMX_KEY_ROWSPLIT background programs): n particles per ROW, blockIdx.y \
        is the row — row r's particles are rows r * n .. r * n + n - 1 of every leaf */           \
     const uint32_t row0 = blockIdx.y * n32;                                                      \
+    const uint32_t gmx_tb = GMX_JIT_BLK * (uint32_t)(PP * GMX_BLOCK);   /* the tile's first particle: < n (uniform) */ \
+    const uint32_t gmx_left = n32 - gmx_tb;                             /* particles from there to the row's end: >= 1 */ \
+    ctx.tile0 = row0 + gmx_tb; ctx.tid4 = threadIdx.x << 2;                                      \
     _Pragma("unroll") for (int p = 0; p < PP; ++p) {                                             \
       R[p].init();                                                                               \
-      const uint32_t i32 = (GMX_JIT_BLK * (uint32_t)PP + (uint32_t)p) * (uint32_t)GMX_BLOCK + threadIdx.x; \
+      const uint32_t i32 = gmx_tb + (uint32_t)(p * GMX_BLOCK) + threadIdx.x;                     \
       idx[p] = (int64_t)(row0 + i32);                                                            \
       act[p] = i32 < n32;                                                                        \
-      cidx[p] = row0 + (act[p] ? i32 : n32 - 1u);                                                \
+      /* (uniform) the group's last particle below n; a group wholly past n: group 0's */        \
+      const bool gmx_has = gmx_left > (uint32_t)(p * GMX_BLOCK);                                 \
+      const uint32_t gmx_g = gmx_has ? (uint32_t)(p * GMX_BLOCK) : 0u;                           \
+      const uint32_t gmx_rem = gmx_left - gmx_g;                                                 \
+      const uint32_t gmx_lastp = (gmx_rem < (uint32_t)GMX_BLOCK ? gmx_rem : (uint32_t)GMX_BLOCK) - 1u; \
+      ctx.grp[p] = gmx_g;                                                                        \
+      ctx.off1[p] = threadIdx.x < gmx_lastp ? threadIdx.x : gmx_lastp;                           \
+      ctx.off4[p] = ctx.off1[p] << 2;                                                            \
       arow[p] = 0u;                                                                              \
     }                                                                                            \
-    (void)cidx; (void)arow; (void)pre; (void)gmx_t; (void)gmx_t0; (void)gmx_tf;
+    (void)arow; (void)pre; (void)gmx_t; (void)gmx_t0; (void)gmx_tf;
 
 // the ancestors of the thread's particles: loaded — or, for a fused bootstrap step (gmx_run_args.rs), WRITTEN first
 // (this workgroup's tile of the previous step's resampling: gmx_offspring.h) and then polled until the words of this
@@ -205,7 +249,7 @@ struct gmx_jit_ctx {
       uint32_t gmx_av[PP];                                                                       \
       bool gmx_ok = true;                                                                        \
       _Pragma("unroll") for (int p = 0; p < PP; ++p) {                                           \
-        gmx_av[p] = __hip_atomic_load(gmx_aw + cidx[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+        gmx_av[p] = __hip_atomic_load(ctx.template own_in_of<uint32_t>(gmx_aw, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
         gmx_ok &= (gmx_av[p] >> GMX_ANC_TAG_SHIFT) == (TAG);                                     \
       }                                                                                          \
       if (!gmx_ok) {                                                                             \
@@ -214,7 +258,7 @@ struct gmx_jit_ctx {
           __builtin_amdgcn_s_sleep(1);                                                           \
           gmx_ok = true;                                                                         \
           _Pragma("unroll") for (int p = 0; p < PP; ++p) {                                       \
-            gmx_av[p] = __hip_atomic_load(gmx_aw + cidx[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+            gmx_av[p] = __hip_atomic_load(ctx.template own_in_of<uint32_t>(gmx_aw, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
             gmx_ok &= (gmx_av[p] >> GMX_ANC_TAG_SHIFT) == (TAG);                                 \
           }                                                                                      \
         } while (!gmx_ok && wall_clock64() - gmx_t0 < 200000000ull);                             \
@@ -243,14 +287,14 @@ struct gmx_jit_ctx {
       GMX_JIT_POLL_ANC(A.sh.tag, A.sh.status_d, gmx_lim)                                         \
       /* (no fence: a row in the tail was stored write-through BEFORE its word, the gather's load depends on the word) */ \
     } else {                                                                                     \
-      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)A.ancestors_d[cidx[p]]; \
+      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)*ctx.template own_in_of<int32_t>(A.ancestors_d, p); \
     }
 #elif defined(GMX_JIT_RS_LOOP)
 #define GMX_JIT_PRE_ANC                                                                          \
     if (PP == 4 && A.rs.lw_d) {                                                                  \
       GMX_JIT_POLL_ANC(A.rs.tag, A.rs.status_d, n32)                                             \
     } else {                                                                                     \
-      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)A.ancestors_d[cidx[p]]; \
+      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)*ctx.template own_in_of<int32_t>(A.ancestors_d, p); \
     }
 #elif defined(GMX_JIT_RS)
 #define GMX_JIT_PRE_ANC                                                                          \
@@ -260,18 +304,21 @@ struct gmx_jit_ctx {
           const_cast<int32_t*>(A.ancestors_d), nullptr, A.rs.tag);                                \
       GMX_JIT_POLL_ANC(A.rs.tag, A.rs.status_d, n32)                                             \
     } else {                                                                                     \
-      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)A.ancestors_d[cidx[p]]; \
+      _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)*ctx.template own_in_of<int32_t>(A.ancestors_d, p); \
     }
 #else
 #define GMX_JIT_PRE_ANC                                                                          \
-    _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)A.ancestors_d[cidx[p]];
+    _Pragma("unroll") for (int p = 0; p < PP; ++p) arow[p] = (uint32_t)*ctx.template own_in_of<int32_t>(A.ancestors_d, p);
 #endif
 
-#define GMX_JIT_PRE_LOAD(K, SLOT, U8, ROW)                                                       \
+// a prefetch of the particle's own row (tile-relative, clamped: gmx_jit_ctx) / of the row its ancestor names
+#define GMX_JIT_PRE(K, SLOT, U8)                                                                 \
     _Pragma("unroll") for (int p = 0; p < PP; ++p)                                               \
-      pre[K][p] = (U8) ? (uint32_t)((const uint8_t*)A.in_d[SLOT])[ROW[p]] : ((const uint32_t*)A.in_d[SLOT])[ROW[p]];
-#define GMX_JIT_PRE(K, SLOT, U8) GMX_JIT_PRE_LOAD(K, SLOT, U8, cidx)
-#define GMX_JIT_PRE_G(K, SLOT, U8) GMX_JIT_PRE_LOAD(K, SLOT, U8, arow)
+      pre[K][p] = (U8) ? (uint32_t)*ctx.template own_in_of<uint8_t>(A.in_d[SLOT], p)          \
+                       : *ctx.template own_in_of<uint32_t>(A.in_d[SLOT], p);
+#define GMX_JIT_PRE_G(K, SLOT, U8)                                                               \
+    _Pragma("unroll") for (int p = 0; p < PP; ++p)                                               \
+      pre[K][p] = (U8) ? (uint32_t)((const uint8_t*)A.in_d[SLOT])[arow[p]] : ((const uint32_t*)A.in_d[SLOT])[arow[p]];
 #define GMX_JIT_FENCE __builtin_amdgcn_sched_barrier(0);
 
 // OP_LDIN whose value was prefetched

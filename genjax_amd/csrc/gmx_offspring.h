@@ -104,7 +104,9 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   __shared__ uint64_t s_below[RS_WAVES], s_all[RS_WAVES], s_scan[RS_WAVES], s_g[RS_TPB];
   __shared__ float s_max[RS_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int grp = threadIdx.x >> 8, ltid = threadIdx.x & (GMX_BLOCK - 1);      // which of the block's tiles / thread within it
+  // which of the block's tiles / thread within it (one tile per block: the block is GMX_BLOCK threads, and tile_ok and
+  // full_tile below are WORKGROUP-uniform — said so that the compiler keeps them on the scalar unit)
+  const int grp = RS_TPB > 1 ? (int)(threadIdx.x >> 8) : 0, ltid = threadIdx.x & (GMX_BLOCK - 1);
   const int first_tile = blk * RS_TPB;
   const int my_tile = first_tile + grp;
   const bool tile_ok = my_tile < n_tiles;                                        // wave-uniform
@@ -184,9 +186,15 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   uint64_t q[CDF_VEC_OT];
   uint64_t run = 0;
 #pragma unroll
+  for (int c = 0; c < CDF_VEC_OT; ++c) q[c] = weight_fixed(x[c], ref_b, scale);
+  if (!(tile_ok && full_tile)) {          // wave-uniform: a full tile has no lane to mask, so no compares and selects
+    GMX_KEEP_BRANCH;
+#pragma unroll
+    for (int c = 0; c < CDF_VEC_OT; ++c) q[c] = (tile_ok && i0 + c < n) ? q[c] : 0ull;
+  }
+#pragma unroll
   for (int c = 0; c < CDF_VEC_OT; ++c) {
-    const uint64_t w = weight_fixed(x[c], ref_b, scale);
-    run += (tile_ok && i0 + c < n) ? w : 0ull;
+    run += q[c];
     q[c] = run;
   }
   const uint64_t inc = wave_scan_u64(run);
@@ -254,7 +262,12 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   uint64_t cv[CDF_VEC_OT + 1];
   cv[0] = prefix + gmx_tile_scale(loc, k_b, K);
 #pragma unroll
-  for (int c = 0; c < CDF_VEC_OT; ++c) cv[c + 1] = (i0 + c < n) ? prefix + gmx_tile_scale(loc + q[c], k_b, K) : total;
+  for (int c = 0; c < CDF_VEC_OT; ++c) cv[c + 1] = prefix + gmx_tile_scale(loc + q[c], k_b, K);
+  if (!full_tile) {                       // (wave-uniform, as above)
+    GMX_KEEP_BRANCH;
+#pragma unroll
+    for (int c = 0; c < CDF_VEC_OT; ++c) cv[c + 1] = (i0 + c < n) ? cv[c + 1] : total;
+  }
   int32_t e[CDF_VEC_OT + 1];
   bool near = false;
   uint32_t near_bits = 0;

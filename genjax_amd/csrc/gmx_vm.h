@@ -73,6 +73,14 @@ struct gmx_cword {
   static constexpr uint32_t w1() { return B0; }
 };
 
+// A Ctx that addresses the particle's OWN row relative to a workgroup-uniform tile (gmx_jit.h: gmx_jit_ctx) says so
+// here and provides
+//   const T* own_in<T>(base, srow)   &base[i + srow] as (uniform 64-bit base) + (32-bit offset inside the tile)
+//   T*       own_out<T>(base, srow)  the same for a store (active lanes only)
+// The interpreter and the CPU mirror keep the 64-bit form: the same addresses, computed per lane.
+template <class Ctx>
+struct gmx_ctx_tiled { static constexpr bool value = false; };
+
 // One instruction.  All of w0 / w1 are launch-uniform.
 template <class Regs, bool FULL, class W, class Ctx>
 GMX_HD void gmx_vm_step(Regs& R, const W w, int64_t i, bool active, const gmx_run_args& A, Ctx& ctx, uint32_t t = 0u,
@@ -95,6 +103,15 @@ GMX_HD void gmx_vm_step(Regs& R, const W w, int64_t i, bool active, const gmx_ru
           const void* p = ctx.in_ptr(a);
           r0 = (b & GMX_F_U8) ? (uint32_t)((const uint8_t*)p)[0] : ((const uint32_t*)p)[0];
         } else if (active) {
+          if constexpr (gmx_ctx_tiled<Ctx>::value) {
+            if (!(b & (GMX_F_GATHER | GMX_F_IDX))) {      // the particle's own row (of element t + imm of a [T, n] leaf)
+              const int64_t srow = (b & GMX_F_STEP) ? (int64_t)(((b & GMX_F_FLAT) ? tf : t) + w1) * A.step_stride : 0;
+              const void* p = ctx.in_ptr(a);
+              if (b & GMX_F_U8) r0 = (uint32_t)*ctx.template own_in<uint8_t>(p, srow);
+              else r0 = *ctx.template own_in<uint32_t>(p, srow);
+              break;
+            }
+          }
           int64_t row = i;
           if (b & GMX_F_GATHER) row = (int64_t)A.ancestors_d[i];
           if (b & GMX_F_BCAST) row = 0;
@@ -120,9 +137,15 @@ GMX_HD void gmx_vm_step(Regs& R, const W w, int64_t i, bool active, const gmx_ru
 #endif
         if (active) {
           void* p = ctx.out_ptr(a);
-          const int64_t orow = (dst & GMX_F_STEP) ? i + (int64_t)(((dst & GMX_F_FLAT) ? tf : t) + w1) * A.step_stride : i;
-          if (dst & GMX_F_U8) ((uint8_t*)p)[orow] = (uint8_t)(v != 0u);
-          else ((uint32_t*)p)[orow] = v;
+          const int64_t srow = (dst & GMX_F_STEP) ? (int64_t)(((dst & GMX_F_FLAT) ? tf : t) + w1) * A.step_stride : 0;
+          if constexpr (gmx_ctx_tiled<Ctx>::value) {
+            if (dst & GMX_F_U8) *ctx.template own_out<uint8_t>(p, srow) = (uint8_t)(v != 0u);
+            else *ctx.template own_out<uint32_t>(p, srow) = v;
+          } else {
+            const int64_t orow = i + srow;
+            if (dst & GMX_F_U8) ((uint8_t*)p)[orow] = (uint8_t)(v != 0u);
+            else ((uint32_t*)p)[orow] = v;
+          }
         }
         wr = 0;
       } break;

@@ -24,7 +24,7 @@ if variant == "nopoll":
     mark = "#if defined(GMX_JIT_SH)\n// a SHARDED sweep's step"
     assert mark in src
     src = src.replace(mark, "#undef GMX_JIT_POLL_ANC\n#define GMX_JIT_POLL_ANC(TAG, STATUS, LIMIT) "
-                            "_Pragma(\"unroll\") for (int p = 0; p < PP; ++p) arow[p] = cidx[p];\n" + mark, 1)
+                            "_Pragma(\"unroll\") for (int p = 0; p < PP; ++p) arow[p] = ctx.tile0 + ctx.grp[p] + ctx.off1[p];\n" + mark, 1)     # (the particle's own row, clamped below n)
 else:
     raise SystemExit("unknown variant")
 open(jit, "w").write(src)
