@@ -269,6 +269,11 @@ class Backend:
         c.gmx_resample_rows_ess_workspace.restype = c_size_t
         c.gmx_resample_rows_ess.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        c.gmx_pick_rows_take_workspace.argtypes = [c_int64, c_int64]
+        c.gmx_pick_rows_take_workspace.restype = c_size_t
+        c.gmx_pick_rows_take.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32,
+                                         c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                         c_void_p, c_void_p]
         c.gmx_capture_begin.argtypes = [c_void_p]
         c.gmx_capture_end.argtypes = [c_void_p, POINTER(c_void_p)]
         c.gmx_graph_launch.argtypes = [c_void_p, c_void_p]

@@ -3735,6 +3735,62 @@ extern "C" int gmx_resample_rows_ess(int kind, const uint32_t* keys_d, float* lw
   return 0;
 }
 
+extern "C" size_t gmx_pick_rows_take_workspace(int64_t rows, int64_t n) { return gmx_pick_rows_take_bytes_(rows, n); }
+
+// gmx_pick_rows, then what it picked taken and handed on (the step of backward simulation): n <= 1024 ONE launch; past it
+// gmx_pick_rows' two kernels writing the offset index, then the gather and the broadcast
+extern "C" int gmx_pick_rows_take(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
+                                  const float* lw_d, int64_t lw_ld, const float* x_d, int32_t D, int64_t x_ld,
+                                  int64_t x_row_stride, int64_t index_stride, int32_t* idx_out_d, float* lw_out_d,
+                                  float* x_out_d, float* next_d, int64_t next_ld, int64_t* status_d, void* workspace_d,
+                                  gmx_stream stream) {
+  if (!keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d)
+    return gmx_fail("gmx_pick_rows_take: null argument%s");
+  const gmx_refusal no = gmx_pick_rows_take_refusal_(rows, n, ld, lw_ld, D, x_ld, x_row_stride, index_stride, next_d != nullptr,
+                                                     next_ld);
+  if (no.fmt) return gmx_fail(no.fmt, "gmx_pick_rows_take", no.v);
+  if (D > 0 && !x_d) return gmx_fail("gmx_pick_rows_take: null argument (x_d with D > 0)%s");
+  if (D > 0 && !x_out_d) return gmx_fail("gmx_pick_rows_take: null argument (x_out_d with D > 0)%s");
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_pick_rows_take: workspace_d must be 8-byte aligned%s");
+  if (((uintptr_t)keys_d & 3) || ((uintptr_t)logits_d & 3) || ((uintptr_t)lw_d & 3) || ((uintptr_t)x_d & 3) ||
+      ((uintptr_t)idx_out_d & 3) || ((uintptr_t)lw_out_d & 3) || ((uintptr_t)x_out_d & 3) || ((uintptr_t)next_d & 3) ||
+      ((uintptr_t)status_d & 7))
+    return gmx_fail("gmx_pick_rows_take: a pointer is not aligned to its element%s");
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  hipStream_t st = (hipStream_t)stream;
+  auto* status = (unsigned long long*)status_d;
+  rows_take tk;
+  tk.lw = lw_d; tk.lw_ld = lw_ld; tk.x = D > 0 ? x_d : nullptr; tk.D = D; tk.x_ld = x_ld; tk.x_row_stride = x_row_stride;
+  tk.index_stride = index_stride; tk.idx_out = idx_out_d; tk.lw_out = lw_out_d; tk.x_out = x_out_d;
+  tk.next = D > 0 ? next_d : nullptr; tk.next_ld = next_ld;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+#define GMX_ROWS_TAKE(W_)                                                                                              \
+  hipLaunchKernelGGL((k_rows_small_take<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, st, \
+                     keys_d, logits_d, rows, n, ld, scale, status, tk)
+    if (n <= 256) GMX_ROWS_TAKE(1);
+    else if (n <= 512) GMX_ROWS_TAKE(2);
+    else GMX_ROWS_TAKE(4);
+#undef GMX_ROWS_TAKE
+    GMX_HIP(hipGetLastError());
+    return 0;
+  }
+  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
+  uint64_t* agg = (uint64_t*)workspace_d;
+  float* tmax = (float*)(agg + rows * tiles);
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
+    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
+    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, logits_d, n, ld,
+                       tiles, row0, scale, tmax, agg);
+  }
+  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
+                     (const float*)tmax, (const uint64_t*)agg, idx_out_d, (int64_t)1, (int64_t)0, index_stride, status);
+  const bool spread = tk.next != nullptr;
+  hipLaunchKernelGGL(k_rows_take, dim3(gmx_rows_pin_blocks_(rows, spread ? (rows * n + 3) / 4 : 0), (unsigned)(D + 1)),
+                     dim3(GMX_ROWS_BLOCK), 0, st, rows, n, tk);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------

@@ -29,6 +29,11 @@
 //               below ess_q8 / 256 — an exact integer predicate; a row that is not keeps its accumulated weights in
 //               `carry` and gets identity ancestors.  k_rows_small_ess<kind, W>, the same body with the decision compiled in:
 //               still ONE launch, no barrier added.
+//   pick and take (gmx_pick_rows_take, backward simulation): gmx_pick_rows' one draw per row, then the picked particle's
+//               weight and D state words taken, and the state broadcast over every particle of the row for the next step's
+//               densities.  n <= 1024: k_rows_small_take<W>, the packing above around the draw alone — ONE launch, three
+//               barriers, 64 bytes of LDS, no CDF tile; n > 1024: k_pick_stats and k_pick_row (gmx_backward.h) writing the
+//               offset index, then k_rows_take, the gather and the broadcast in k_rows_pin's shape.
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
 // host compiler: the ENTRY POINTS as a sequential loop over rows calling the per-row path (gmx_resample; for the iid
 // multinomial gmx_weight_cdf + gmx_ancestors, which is what gmx_resample does with that kind), as gmx_backward.h does
@@ -434,6 +439,146 @@ k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin
   }
 }
 
+// What gmx_pick_rows_take adds to a row's pick (backward simulation: what was picked, taken and handed on)
+struct rows_take {
+  const float* lw;      // the weights, rows lw_ld elements apart (may be the logits themselves): lw_out[r] = lw[r * lw_ld + k]
+  int64_t lw_ld;
+  const float* x;       // [D, x_ld]: x_out[d * rows + r] = x[d * x_ld + r * x_row_stride + k]
+  int32_t D;
+  int64_t x_ld, x_row_stride;
+  int64_t index_stride; // idx_out[r] = k + r * index_stride
+  int32_t* idx_out;     // [rows]
+  float* lw_out;        // [rows]
+  float* x_out;         // [D, rows]
+  float* next;          // [D, next_ld] or null: next[d * next_ld + r * n + i] = x_out[d * rows + r], i < n
+  int64_t next_ld;
+};
+
+// gmx_pick_rows_take, n <= 1024: k_rows_small's packing (W waves per row, 4 / W rows per workgroup, thread gt of a row's
+// group holds columns 4 gt .. 4 gt + 3) around the AS branch of rows_small_body on its own: the row's maximum, its
+// fixed-point weights against the row's reference and their scan, and the count of columns whose inclusive sum is below
+// the threshold of keys[r] at counter 0 — k_pick_row's answer for a row of one tile.  Three barriers, 64 bytes of LDS, no
+// CDF in LDS: nothing is searched.  After the third barrier every thread of the group knows k: thread 0 writes the three
+// outputs, every thread reads the one word x[.. + k] per state word (one address per group) and stores its four columns
+// of the broadcast.  Every thread reaches every barrier (a group past the last row works on the last row again and
+// writes nothing).
+template <int W>
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_small_take(const uint32_t* __restrict__ keys, const float* __restrict__ logits, int64_t rows, int64_t n, int64_t ld,
+                  float scale, unsigned long long* __restrict__ status, rows_take tk) {
+  static_assert(W == 1 || W == 2 || W == 4, "waves per row");
+  constexpr int RPW = 4 / W, GT = 64 * W;
+  __shared__ float s_max[4];
+  __shared__ uint64_t s_scan[4];
+  __shared__ uint32_t s_cnt[4];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int grp = tid / GT, gt = tid % GT;
+  const int64_t r_ = (int64_t)blockIdx.x * RPW + grp;
+  const bool live = r_ < rows;
+  const int64_t r = live ? r_ : rows - 1;
+  const int64_t base = (int64_t)gt * 4;
+  float a[4];
+  pick_load4(logits + r * ld, base, n, a);
+  const float m = wave_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])));
+  if (lane == 0) s_max[wave] = m;
+  __syncthreads();
+  float M = s_max[grp * W];
+#pragma unroll
+  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  const float ref = gmx_tile_ref(gmx_tile_exp(M));       // one tile: K = k_b, cdf_i = the tile-local inclusive sum
+  uint64_t q[4], run = 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    run += (base + c < n) ? weight_fixed(a[c], ref, scale) : 0ull;
+    q[c] = run;
+  }
+  const uint64_t inc = wave_scan_u64(run);
+  if (lane == 63) s_scan[wave] = inc;
+  __syncthreads();
+  uint64_t woff = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const uint64_t v = s_scan[grp * W + w];
+    total += v;
+    woff += (grp * W + w < wave) ? v : 0ull;
+  }
+  const uint64_t loc = woff + (inc - run);
+  gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
+  const uint64_t u = (uint64_t)(gmx_bits32(key, 0ull) >> 9);
+  const u128 P = mul64(total, (1ull << 23) - u);
+  const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
+  const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
+  const uint64_t Thr = (phi << 41) | (plo >> 23);                  // ceil(P / 2^23), in [1, total] (0 without mass)
+  uint64_t lower = 0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) lower += (base + c < n && loc + q[c] < Thr) ? 1ull : 0ull;
+  lower = wave_sum_u64(lower);
+  if (lane == 0) s_cnt[wave] = (uint32_t)lower;
+  __syncthreads();
+  if (!live) return;                                     // (no barrier follows)
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int w = 0; w < W; ++w) cnt += s_cnt[grp * W + w];
+  int64_t k = cnt < (uint32_t)n ? (int64_t)cnt : n - 1;
+  if (total == 0ull) k = n - 1;                          // no mass at all: the last column, as gmx_pick_rows answers, and counted
+  if (gt == 0) {
+    if (total == 0ull) atomicAdd(status, 1ull);
+    tk.idx_out[r] = (int32_t)k + (int32_t)(r * tk.index_stride);
+    tk.lw_out[r] = tk.lw[r * tk.lw_ld + k];
+  }
+  const float* __restrict__ src = tk.x + (r * tk.x_row_stride + k);
+  for (int32_t d = 0; d < tk.D; ++d) {
+    const float v = src[(int64_t)d * tk.x_ld];           // (one address per group)
+    if (gt == 0) tk.x_out[(int64_t)d * rows + r] = v;
+    if (tk.next != nullptr) {
+      const float v4[4] = {v, v, v, v};
+      rows_store4f(tk.next + ((int64_t)d * tk.next_ld + r * n), base, n, v4);
+    }
+  }
+}
+
+// gmx_pick_rows_take past one tile, after k_pick_row wrote idx_out: the gather and the broadcast, modelled on k_rows_pin.
+// blockIdx.y: the state word d < D, or (y = D) the weight; the threads of a y stride over the rows, then (d < D, with a
+// broadcast) over the quads of the rows * n particles.  Row r's pick is idx_out[r] - r * index_stride; the broadcast reads
+// the store through it, not x_out (which this launch writes).
+__global__ void __launch_bounds__(GMX_ROWS_BLOCK)
+k_rows_take(int64_t rows, int64_t n, rows_take tk) {
+  const int64_t g = (int64_t)blockIdx.x * GMX_ROWS_BLOCK + (int64_t)threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * GMX_ROWS_BLOCK;
+  const int32_t d = (int32_t)blockIdx.y;
+  const int32_t* __restrict__ idx = tk.idx_out;
+  for (int64_t r = g; r < rows; r += step) {
+    const int64_t k = (int64_t)(idx[r] - (int32_t)(r * tk.index_stride));
+    if (d == tk.D) tk.lw_out[r] = tk.lw[r * tk.lw_ld + k];
+    else tk.x_out[(int64_t)d * rows + r] = tk.x[(int64_t)d * tk.x_ld + r * tk.x_row_stride + k];
+  }
+  if (tk.next == nullptr || d == tk.D) return;
+  const float* __restrict__ src = tk.x + (int64_t)d * tk.x_ld;
+  float* __restrict__ dst = tk.next + (int64_t)d * tk.next_ld;
+  const int64_t cols = rows * n, quads = (cols + 3) / 4;
+  for (int64_t qd = g; qd < quads; qd += step) {
+    const int64_t base = qd * 4;
+    int64_t r = base / n, c_ = base - r * n;             // particle `base` is column c_ of row r
+    float cur = src[r * tk.x_row_stride + (int64_t)(idx[r] - (int32_t)(r * tk.index_stride))];      // (base < cols: r < rows)
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      v[c] = cur;
+      if (++c_ == n) {
+        c_ = 0; ++r;
+        if (r < rows) cur = src[r * tk.x_row_stride + (int64_t)(idx[r] - (int32_t)(r * tk.index_stride))];
+      }
+    }
+    if (base + 4 <= cols && (((uintptr_t)(dst + base)) & 15u) == 0u) {
+      *reinterpret_cast<float4*>(dst + base) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (base + c < cols) dst[base + c] = v[c];
+    }
+  }
+}
+
 // n > 1024: blockIdx.x the tile, blockIdx.y the row (row0 + y).  tmax / agg: k_pick_stats' [rows, n_tiles] statistics.
 // cdf_i = prefix_b + ((tile-local inclusive sum) >> (K - k_b)), as k_weight_cdf writes it.
 template <int KIND>
@@ -674,6 +819,39 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_ess(int kind, cons
       carry_d[r * ld + i] = go ? 0.0f : lw_d[r * ld + i];
       if (!go) ancestors_d[r * n + i] = (int32_t)(i + r * index_stride);
     }
+  }
+  return 0;
+}
+
+extern "C" __attribute__((used)) inline size_t gmx_pick_rows_take_workspace(int64_t rows, int64_t n) {
+  return gmx_pick_rows_take_bytes_(rows, n);
+}
+
+// the definition, in order: one draw per row from the logits, what it picked copied out, the picked state over the row
+extern "C" __attribute__((used)) inline int gmx_pick_rows_take(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
+                                         const float* lw_d, int64_t lw_ld, const float* x_d, int32_t D, int64_t x_ld,
+                                         int64_t x_row_stride, int64_t index_stride, int32_t* idx_out_d, float* lw_out_d,
+                                         float* x_out_d, float* next_d, int64_t next_ld, int64_t* status_d, void* workspace_d,
+                                         gmx_stream stream) {
+  const char* who = "gmx_pick_rows_take";
+  if (!keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d)
+    return gmx_fail("%s: null argument", who, 0);
+  const gmx_refusal no = gmx_pick_rows_take_refusal_(rows, n, ld, lw_ld, D, x_ld, x_row_stride, index_stride, next_d != nullptr,
+                                                     next_ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
+  if (D > 0 && !x_out_d) return gmx_fail("%s: null argument (x_out_d with D > 0)", who, 0);
+  std::vector<int32_t> k((size_t)rows);
+  std::vector<uint64_t> ws((gmx_resample_workspace(n) + 7) / 8 + 2);       // (what the per-row path may ask for)
+  if (gmx_pick_rows(keys_d, logits_d, rows, n, ld, k.data(), status_d, ws.data(), stream)) return 1;
+  for (int64_t r = 0; r < rows; ++r) {
+    const int64_t kr = k[(size_t)r];
+    idx_out_d[r] = (int32_t)(kr + r * index_stride);
+    lw_out_d[r] = lw_d[r * lw_ld + kr];
+    for (int64_t d = 0; d < D; ++d) x_out_d[d * rows + r] = x_d[d * x_ld + r * x_row_stride + kr];
+    if (next_d)
+      for (int64_t d = 0; d < D; ++d)
+        for (int64_t i = 0; i < n; ++i) next_d[d * next_ld + r * n + i] = x_out_d[d * rows + r];
   }
   return 0;
 }

@@ -116,7 +116,7 @@ static inline const char* gmx_tile_form_refusal_(gmx_tile_form form, int kind, i
 }
 
 // ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned, gmx_rows_pin, gmx_resample_rows_as,
-// gmx_resample_rows_ess ----
+// gmx_resample_rows_ess, gmx_pick_rows_take ----
 // gmx_pick_rows' workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
 static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n < 1) return 16;
@@ -129,6 +129,13 @@ static inline gmx_refusal gmx_pick_rows_refusal_(int64_t rows, int64_t n, int64_
   if (rows < 1 || rows > 0x7fffffffLL) return {"%s: rows = %lld is outside [1, 2^31)", (long long)rows};
   if (n < 1 || n > 0x7fffffffLL) return {"%s: n = %lld is outside [1, 2^31)", (long long)n};
   if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  return {nullptr, 0};
+}
+// row r's indices are offset by r * index_stride and stay int32: rows >= 1, n >= 1
+static inline gmx_refusal gmx_index_stride_refusal_(int64_t rows, int64_t n, int64_t index_stride) {
+  if (index_stride < 0 || (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
+                                                (rows - 1) * index_stride + n - 1 >= (1LL << 31))))
+    return {"%s: index_stride = %lld does not keep rows * index_stride below 2^31", (long long)index_stride};
   return {nullptr, 0};
 }
 // gmx_resample_rows' workspace: agg u64 [rows * tiles] | cdf u64 [rows * n] (iid multinomial only) | tmax f32 [rows * tiles];
@@ -147,10 +154,7 @@ static inline gmx_refusal gmx_resample_rows_refusal_(int kind, int64_t rows, int
   if (rows < 1 || rows > 0x7fffffffLL) return {"%s: rows = %lld is outside [1, 2^31)", (long long)rows};
   if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
   if (n < 1 || n > GMX_ROWS_MAX_N) return {"%s: n = %lld is outside [1, 2^21]", (long long)n};
-  if (index_stride < 0 || (index_stride > 0 && (index_stride >= (1LL << 31) || rows * index_stride >= (1LL << 31) ||
-                                                (rows - 1) * index_stride + n - 1 >= (1LL << 31))))
-    return {"%s: index_stride = %lld does not keep rows * index_stride below 2^31", (long long)index_stride};
-  return {nullptr, 0};
+  return gmx_index_stride_refusal_(rows, n, index_stride);
 }
 // gmx_resample_rows_pinned's own arguments (after the above): D, and x_ld / x_row_stride keeping column n - 1 of every
 // row inside a [D, x_ld] store
@@ -185,6 +189,26 @@ static inline gmx_refusal gmx_resample_rows_as_refusal_(int64_t rows, int64_t n,
 static inline size_t gmx_resample_rows_as_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
   return gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n) + gmx_pick_rows_bytes_(rows, n);
+}
+// gmx_pick_rows_take: gmx_pick_rows' matrix, the weights' row stride, the store gmx_rows_pin writes into (here: read), the
+// index_stride rule of gmx_resample_rows and — with a broadcast — gmx_rows_pin's next_ld
+static inline gmx_refusal gmx_pick_rows_take_refusal_(int64_t rows, int64_t n, int64_t ld, int64_t lw_ld, int32_t D, int64_t x_ld,
+                                                      int64_t x_row_stride, int64_t index_stride, bool has_next, int64_t next_ld) {
+  gmx_refusal no = gmx_pick_rows_refusal_(rows, n, ld);
+  if (no.fmt) return no;
+  if (lw_ld < n) return {"%s: lw_ld = %lld is smaller than n", (long long)lw_ld};
+  no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (!no.fmt) no = gmx_index_stride_refusal_(rows, n, index_stride);
+  if (no.fmt) return no;
+  if (has_next && D > 0 && (next_ld / rows < n || next_ld >= (1LL << 46)))             // (rows * n may pass 2^63)
+    return {"%s: next_ld = %lld does not hold rows * n columns (or is 2^46 or more)", (long long)next_ld};
+  return {nullptr, 0};
+}
+// gmx_pick_rows_take's workspace: nothing for n <= 1024 (one launch); past it gmx_pick_rows' (the gathering launch reads the
+// index k_pick_row wrote: nothing of its own)
+static inline size_t gmx_pick_rows_take_bytes_(int64_t rows, int64_t n) {
+  if (rows < 1 || n <= GMX_TILE) return 16;
+  return gmx_pick_rows_bytes_(rows, n);
 }
 // gmx_resample_rows_ess: gmx_resample_rows' arguments, for rows of ONE tile — the decision is taken on the row's per-element
 // fixed-point weights, which past one tile are not the same integers (each tile has its own exponent), and it would have

@@ -1415,13 +1415,15 @@ def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
     comp.run(flat.leaves, batch, None, out_buffers=bufs)
 
 
-def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, specialize=False, launch=True):
+def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, specialize=False, launch=True,
+                     who="ConditionalBank(ancestor_sampling=True)"):
     """out[i] = lw[i] + step.assess({sites[d]: x_next[d][i], obs_addr: y}, (x_prev[i], *extra))[0] in float32 over the
     n = lw.shape[0] particles in ONE launch: the per-particle variant of _backward_logits (ancestor sampling:
     ConditionalBank) — the constrained state is a per-particle leaf x_next[d] ([n] each: every chain's next retained state
     on each of its particles), `extra` may hold per-particle leaves (the bank's parameters), `out` is [1, n].  The
     program is cached on the model, the leaves' kinds and `specialize` (specialised once, when built); launch=False
-    builds it only."""
+    builds it only.  who: the caller a refusal names (ConditionalBank.draw(backward=True) runs the same program over the
+    recorded steps)."""
     from .. import tracer as Tr
     from ..engine import Compiled, Flat, Tracing, leaf_spec, unflatten
     from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
@@ -1453,7 +1455,7 @@ def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, s
             except MissingAddress as e:
                 addr = tuple(a for a in e.args if a != ())
                 raise NotImplementedError(
-                    f"ConditionalBank(ancestor_sampling=True): the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
+                    f"{who}: the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
                     f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
                     "transition density would have to integrate it out") from None
             o = tr.emit_output(syms[jl].value + Tr.as_float(sc))
@@ -2232,10 +2234,11 @@ class ConditionalBank(BootstrapBank):
       cb.prepare(keys, ys, retained=None)   keys (R,), ys [T]; every buffer is allocated here
       cb.launch()                           one sweep (the captured graph when there is one)
       traj = cb.draw(key)                   ONE key: one trajectory per chain from the last sweep
+      traj = cb.draw(key, backward=True)    ... by backward simulation over the recorded steps (below)
       cb.retain()                           the last draw becomes the retained path (device copies, in place)
       cb.rekey(keys)                        a new (R,) key batch into the existing key tables, in place
       cb.set_retained(x_ref)                a caller's own path(s), in draw()'s layout; weights from the model
-      cb.run(key, ys, iters, retained=None) the particle-Gibbs driver: [iters, R, T, ...]
+      cb.run(key, ys, iters, retained=None, backward=False)   the particle-Gibbs driver: [iters, R, T, ...]
 
     The recorded weight of a particle IS its observation weight under the same ys and params, so a retained path that came
     from a sweep needs no model evaluation.  log_ml() with a retained path is the CONDITIONAL sweep's normaliser estimate
@@ -2261,8 +2264,34 @@ class ConditionalBank(BootstrapBank):
     more than one component, and a step model that samples nothing besides the state and the observation.  A chain whose
     ancestor logits carry no mass at some step keeps the plain pin there and is counted: draw() raises FloatingPointError.
 
-    Not here: rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations, ess_threshold=.
-    Memory: the history slabs take T * (D + 2) * R * n * 4 bytes; ancestor sampling adds (D + 1) * R * n * 4."""
+    draw(key, backward=True) (particle Gibbs with backward simulation: Whiteley 2010; Lindsten & Schön 2013): the new
+    trajectory is drawn by backward simulation over the recorded particle system instead of walking the recorded
+    ancestors.  It is a choice made at draw time — any bank, ancestor_sampling or not, captured or not; the sweep keeps its
+    launches — and it applies to the unconditional first sweep too (one FFBS draw per chain).  For ONE key and R chains:
+
+        t = T-1:       row keys split(key, R)                 (draw()'s own: the last state equals draw(key)'s)
+                       logits = hist_lws[T-1]
+        t = T-2 .. 0:  row keys split(fold_in(key, t), R)
+                       logits[i] = hist_lws[t][i] + step.assess({state_sites[d]: next[d][i], obs_addr: y_{t+1}},
+                                                                (hist_x_t[i], *step_extra(t+1), *params[i]))[0]      (float32)
+        every t:       gmx_pick_rows_take(keys_t, logits, R, n, n, hist_lws[t], n, hist_xs[t], D, R*n, n, index_stride = n,
+                                          paths[t], lw_path[t], traj[t], next (null at t = 0), R*n, status[t], ...)
+
+    `next` is the per-particle leaf the call of step t + 1 broadcast: chain r's chosen state on each of its particles.  The
+    logits program is the ancestor-sampling one (same cache, same `specialize`); the observation's term is constant along
+    a row and kept so that the bits are defined, as in SweepHistory.backward_sample.  The pins are in the record, so the
+    retained particle is a candidate at every step.  Two launches per step for n <= 1024, nothing through the host between
+    steps, one synchronisation at the end; the buffers (next [D, R * n], logits [R * n], status [T], the [T, R, 2] key
+    table, the workspace) are allocated at the first backward draw and kept.  The recorded slabs, the ancestors, the
+    sweep's status and a captured graph are not touched.  retain() takes a backward draw as it takes any other.  It needs
+    state_sites= when the state has more than one component, and a step model that samples nothing besides the state and
+    the observation.  A chain whose logits carry no mass at a step t < T - 1 raises FloatingPointError naming the latest
+    such step and the count.
+
+    Not here: rejuvenate=, noise ahead, the fused one-launch step, sharding, per-chain observations, ess_threshold=, more
+    than one backward trajectory per chain.
+    Memory: the history slabs take T * (D + 2) * R * n * 4 bytes; ancestor sampling adds (D + 1) * R * n * 4, a backward
+    draw (D + 1) * R * n * 4."""
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
@@ -2403,11 +2432,12 @@ class ConditionalBank(BootstrapBank):
         self.keys = keys
         return self
 
-    def draw(self, key: Key):
+    def draw(self, key: Key, backward=False):
         """One trajectory per chain from the last sweep (synchronises): k[r] = gmx_pick_rows of chain r's final log-weights
         under split(key, R)[r]; one gmx_lineage walk from the flat indices k + r * n through the recorded ancestors.
         Returns SweepHistory.trajectories()' layout — [R, T], [R, T, D] or a tuple of [R, T] — and keeps the trajectories
-        and the recorded weights along them for retain()."""
+        and the recorded weights along them for retain().  backward=True: the same last state, then backward simulation
+        over the recorded steps instead of the walk (the class docstring has the definition)."""
         if tuple(key.shape) != ():
             raise ValueError("ConditionalBank.draw takes ONE key")
         be = _lib.get()
@@ -2415,6 +2445,8 @@ class ConditionalBank(BootstrapBank):
             raise FloatingPointError(f"ConditionalBank.draw: {int(self.status[1].item())} ancestor draw(s) of the last sweep "
                                      "found no particle with a positive transition density into the next retained state (a "
                                      "row of -inf logits): those steps kept the plain pin")
+        if backward:
+            return self._draw_backward(key)
         dev = self.hist_xs.device
         R, n, T, D = self.R, self.n, self.T, self.D
         k = torch.empty((R,), dtype=torch.int32, device=dev)
@@ -2434,6 +2466,86 @@ class ConditionalBank(BootstrapBank):
         if bad or int(self.hist_status.item()):
             raise IndexError(f"ConditionalBank.draw: {bad} index(es) outside [0, {R * n}) on the walk through the recorded "
                              "ancestors: they were clamped, nothing outside the history was read")
+        self._last = (traj, lw_path, paths, k)
+        return self._views._state_view(traj, 1)
+
+    def _backward_buffers(self):
+        """what the first backward draw allocates and every later one reuses: the state sites, the broadcast next state
+        [D, R * n], the logits [R * n], the status words [T], the [T, R, 2] key table and gmx_pick_rows_take's workspace"""
+        bw = getattr(self, "_bw", None)
+        if bw is not None and bw["of"] is self.hist_xs:
+            return bw
+        be = _lib.get()
+        dev = self.hist_xs.device
+        R, n, T, D = self.R, self.n, self.T, self.D
+        who = "ConditionalBank.draw(backward=True)"
+        sites = self.state_sites
+        if sites is None:
+            if D > 1:
+                raise NotImplementedError(f"{who}: a state of more than one component needs state_sites= (the address of "
+                                          "each component, in order)")
+            sites = (self.state_addr,)
+        if len(sites) != D:
+            raise ValueError(f"{who}: state_sites names {len(sites)} addresses for a state of {D} components")
+        bw = dict(of=self.hist_xs, sites=sites,
+                  next=torch.zeros((D, R * n), dtype=torch.float32, device=dev),
+                  logits=torch.zeros((R * n,), dtype=torch.float32, device=dev),
+                  status=torch.zeros((T,), dtype=torch.int64, device=dev),
+                  keys=torch.zeros((T, R, 2), dtype=torch.int32, device=dev),
+                  ws=torch.zeros(((int(be.c.gmx_pick_rows_take_workspace(R, n)) + 7) // 8,), dtype=torch.int64, device=dev))
+        self._bw = bw
+        return bw
+
+    def _backward_keys(self, key: Key):
+        """the row keys of a backward draw, on the host, int32 words [T, R, 2]: split(key, R) at t = T - 1 (draw()'s own),
+        split(fold_in(key, t), R) below it"""
+        from ..random import _derive_host
+        R, T = self.R, self.T
+        kh = np.asarray(key.host(), dtype=np.uint32).reshape(1, 2)
+        children = np.arange(R, dtype=np.uint64)
+        table = np.empty((T, R, 2), np.uint32)
+        if T > 1:
+            folds = _derive_host(kh, np.arange(T - 1, dtype=np.uint64)).reshape(T - 1, 1, 2)
+            table[:T - 1] = _derive_host(folds, children).reshape(T - 1, R, 2)
+        table[T - 1] = _derive_host(kh, children).reshape(R, 2)
+        return table.view(np.int32)
+
+    def _draw_backward(self, key: Key):
+        """draw(key, backward=True): per step the logits program (t < T - 1) and gmx_pick_rows_take, which hands the chosen
+        state to the next program — nothing passes through the host in between; one synchronisation at the end"""
+        be = _lib.get()
+        dev = self.hist_xs.device
+        R, n, T, D = self.R, self.n, self.T, self.D
+        N = R * n
+        bw = self._backward_buffers()
+        bw["keys"].copy_(torch.from_numpy(self._backward_keys(key)))           # (one upload)
+        status = bw["status"]
+        status.zero_()
+        paths = torch.empty((T, R), dtype=torch.int32, device=dev)
+        lw_path = torch.empty((T, R), dtype=torch.float32, device=dev)
+        traj = torch.empty((T, D, R), dtype=torch.float32, device=dev)
+        nxt, logits = bw["next"], bw["logits"]
+        for t in range(T - 1, -1, -1):
+            lw_t = self.hist_lws[t]
+            if t < T - 1:
+                x_t = self._views._state_view(self.hist_xs[t:t + 1], 0)
+                x_t = type(x_t)(v[0] for v in x_t) if self.tuple_state is not None else x_t[0]
+                _ancestor_logits(self.step, bw["sites"], self.obs_addr, x_t, tuple(self.step_extra(t + 1)) + self.tail,
+                                 list(nxt), self.ys[t + 1], lw_t, logits.reshape(1, N), specialize=self.specialize,
+                                 who="ConditionalBank.draw(backward=True)")
+            be.check(be.c.gmx_pick_rows_take(be.ptr(bw["keys"][t]), be.ptr(lw_t if t == T - 1 else logits), R, n, n,
+                                             be.ptr(lw_t), n, be.ptr(self.hist_xs[t]), D, N, n, n, be.ptr(paths[t]),
+                                             be.ptr(lw_path[t]), be.ptr(traj[t]), be.ptr(nxt) if t > 0 else None, N,
+                                             be.ptr(status[t:]), be.ptr(bw["ws"]), be.stream()), "gmx_pick_rows_take")
+        counts = status.tolist()
+        if counts[T - 1]:
+            raise FloatingPointError(f"ConditionalBank.draw: the final weights of {counts[T - 1]} of the {R} chains carry no mass")
+        bad = [t for t in range(T - 1) if counts[t]]
+        if bad:
+            raise FloatingPointError(f"ConditionalBank.draw(backward=True): step {bad[-1]}: {counts[bad[-1]]} of the {R} chains "
+                                     "found no step-t particle with a positive transition density into their next state (a "
+                                     "row of -inf logits)")
+        k = paths[T - 1] - torch.arange(R, dtype=torch.int32, device=dev) * n
         self._last = (traj, lw_path, paths, k)
         return self._views._state_view(traj, 1)
 
@@ -2519,12 +2631,12 @@ class ConditionalBank(BootstrapBank):
         self.ref_lw.copy_(ref_lw)
         return self
 
-    def run(self, key: Key, ys=None, iters: int = 1, retained=None):
+    def run(self, key: Key, ys=None, iters: int = 1, retained=None, backward=False):
         """The particle-Gibbs driver: `iters` conditional sweeps, each followed by a draw that becomes the next sweep's
         retained path.  Schedule (build-defined, as the sweeps' key schedules are): for k = 0 .. iters - 1
 
             (k_sweep, k_draw) = split(fold_in(key, k), 2)
-            rekey(split(k_sweep, R)); launch(); draw(k_draw); retain()
+            rekey(split(k_sweep, R)); launch(); draw(k_draw, backward); retain()
 
         With nothing retained (no `retained`, no earlier retain() / set_retained()) iteration 0 is an unconditional sweep.
         ys given: the bank is prepared for it first (prepare(split(key, R), ys, retained)); ys = None keeps a prepared bank
@@ -2541,7 +2653,7 @@ class ConditionalBank(BootstrapBank):
             ks = split(fold_in(key, k), 2)
             self.rekey(split(ks[0], self.R))
             self.launch()
-            x = self.draw(ks[1])
+            x = self.draw(ks[1], backward=backward)
             self.retain()
             out.append(x)                  # (views of this draw's own buffer)
         if self.tuple_state is not None:

@@ -730,6 +730,30 @@ int gmx_lineage(const int32_t* anc_d /* [T, n] */, const float* xs_d /* [T, D, n
  *                   the per-element weights at the row's scale are not the same integers and the decision would need a
  *                   launch boundary before the ancestors: refused by name; every pointer aligned to its element;
  *                   workspace_d: gmx_resample_rows_ess_workspace(kind, rows, n) bytes (16: nothing is kept in it), not null.
+ *   gmx_pick_rows_take   (additive, ABI still v8.  Reference call site: none of its own — the step of backward simulation
+ *                   (particle Gibbs with backward simulation: Whiteley 2010; Lindsten & Schön 2013), vmapped over chains:
+ *                   one particle per chain drawn with probability proportional to weight x transition density, then that
+ *                   particle's state and weight taken and the state handed to the next step's densities.)  gmx_pick_rows,
+ *                   plus what was picked.  DEFINITION, for every row r, in this order:
+ *                     1. k[r] = what gmx_pick_rows(keys_d, logits_d, rows, n, ld, ...) gives, its count in *status_d included:
+ *                        a row without mass answers n - 1 and adds 1 to *status_d; its neighbours are unaffected;
+ *                     2. idx_out_d[r] = k[r] + r * index_stride;  lw_out_d[r] = lw_d[r * lw_ld + k[r]];  d < D:
+ *                        x_out_d[d * rows + r] = x_d[d * x_ld + r * x_row_stride + k[r]]  (x_d: a struct-of-arrays [D, x_ld]
+ *                        store whose row r starts x_row_stride columns after row r - 1; lw_d may be logits_d itself);
+ *                     3. when next_d is not null, d < D, i < n: next_d[d * next_ld + r * n + i] = x_out_d[d * rows + r] —
+ *                        gmx_rows_pin's broadcast of x_out_d: the picked state on every particle of its row, a
+ *                        per-particle leaf of the next step's density program.
+ *                   Nothing else is written (the padding between rows included); the outputs never alias an input.
+ *                   n <= 1024: ONE launch with gmx_resample_rows' packing (a thread holds four consecutive logits, a row
+ *                   takes 1, 2 or 4 waves, a workgroup four, two or one rows): the row's maximum, its fixed-point scan and
+ *                   the count of columns below the threshold — gmx_pick_rows' answer for a row of one tile — over three
+ *                   barriers, 64 bytes of LDS, then the copies and 16-byte stores of the broadcast where the address
+ *                   allows.  n > 1024: gmx_pick_rows' two launches writing idx_out_d, then one that gathers and broadcasts.
+ *                   Limits: rows, n and ld as gmx_pick_rows; lw_ld >= n; D, x_ld and x_row_stride as gmx_rows_pin (x_d and
+ *                   x_out_d not null when D > 0, ignored when D = 0); the index_stride rule of gmx_resample_rows; with a
+ *                   broadcast and D > 0: rows * n <= next_ld < 2^46; every pointer aligned to its element; rows may start at
+ *                   any 4-byte boundary; workspace_d: gmx_pick_rows_take_workspace(rows, n) bytes (gmx_pick_rows' past
+ *                   n = 1024, else 16), 8-byte aligned, not null, contents irrelevant on entry.
  * A null pointer or an out-of-range size returns non-zero before anything is launched.
  * ---------------------------------------------------------------------- */
 size_t gmx_pick_rows_workspace(int64_t rows, int64_t n);
@@ -763,6 +787,13 @@ int gmx_resample_rows_ess(int kind, const uint32_t* keys_d /* [rows, 2] */, floa
                           float* max_d /* [rows] */, uint64_t* total_d /* [rows] */, int32_t* resampled_d /* [rows] */,
                           int32_t* ancestors_d /* [rows, n] */, int64_t* status_d /* [1] */, void* workspace_d,
                           gmx_stream stream);
+size_t gmx_pick_rows_take_workspace(int64_t rows, int64_t n);
+int gmx_pick_rows_take(const uint32_t* keys_d /* [rows, 2] */, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
+                       const float* lw_d, int64_t lw_ld /* elements between rows of lw_d, >= n */,
+                       const float* x_d /* [D, x_ld], null iff D = 0 */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                       int64_t index_stride, int32_t* idx_out_d /* [rows] */, float* lw_out_d /* [rows] */,
+                       float* x_out_d /* [D, rows], null iff D = 0 */, float* next_d /* [D, next_ld] or null */,
+                       int64_t next_ld, int64_t* status_d /* [1] */, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —

@@ -15,8 +15,15 @@
                 record.  `spread_over_median`: (max - min) / median of each form's windows, the run-to-run spread the
                 fused / composed ratio is read against.
 
+  backward      (--backward: this section alone) (R, n, T) in {(2048, 8, 32), (64, 1024, 32), (16, 4096, 32)}, LGSSM, a
+                conditional sweep with a retained path, then three forms of ONE draw alternated: draw(key), the walk through
+                the recorded ancestors; draw(key, backward=True), per step the logits program and gmx_pick_rows_take; and the
+                backward draw COMPOSED from the entry points the library had before — gmx_rows_pin's broadcast, the program,
+                gmx_pick_rows, an index add and two index-selects per step.  The two backward forms are asserted equal in
+                paths, states and weights.  Each figure is per draw, its final synchronisation included.
+
 Clocks as found; a host clock around work that ends in a device synchronise.  Environment: SHAPES ("rows:n,..."), BR, BN,
-BT, AS_SHAPES ("R:n,..."), AT.  Needs the MI355X: there is no CPU path."""
+BT, AS_SHAPES ("R:n,..."), AT, BW_SHAPES ("R:n:T,...").  Needs the MI355X: there is no CPU path."""
 import argparse
 import ctypes
 import json
@@ -40,9 +47,12 @@ ap.add_argument("--label", default="")
 ap.add_argument("--skip-sweep", action="store_true")
 ap.add_argument("--skip-kernel", action="store_true")
 ap.add_argument("--skip-ancestors", action="store_true")
+ap.add_argument("--backward", action="store_true", help="time draw(key, backward=True) and nothing else")
 ap.add_argument("--parent-lib", default="", help="a build of the library without the pinned entry point")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_time_conditional.jsonl"))
 args = ap.parse_args()
+if args.backward:
+    args.skip_kernel = args.skip_sweep = args.skip_ancestors = True
 assert torch.cuda.is_available(), "tools/time_conditional.py measures on the GPU only"
 be = _lib.get()
 dev = be.device
@@ -228,3 +238,87 @@ if not args.skip_ancestors:
                                               "ancestors_composed": 8 if n <= 1024 else 10},
                   pinned_ancestors_moved=moved, fused_equals_composed=True))
         del banks, forms, fu, co, pl
+
+# ---- (d) backward simulation: the fused pick against its composition ---------------------------------------------------------------
+
+
+def composed_backward_draw(cb, key, bufs):
+    """draw(key, backward=True) without gmx_pick_rows_take: per step gmx_rows_pin's broadcast of the chosen state (its
+    pins go to scratch), the logits program, gmx_pick_rows, an index add and two index-selects"""
+    R, n, T, D = cb.R, cb.n, cb.T, cb.D
+    N = R * n
+    P, st = be.ptr, be.stream()
+    bufs["keys"].copy_(torch.from_numpy(cb._backward_keys(key)))
+    status = bufs["status"]
+    status.zero_()
+    paths = torch.empty((T, R), dtype=torch.int32, device=dev)
+    lw_path = torch.empty((T, R), dtype=torch.float32, device=dev)
+    traj = torch.empty((T, D, R), dtype=torch.float32, device=dev)
+    for t in range(T - 1, -1, -1):
+        lw_t = cb.hist_lws[t]
+        logits = lw_t
+        if t < T - 1:
+            be.check(be.c.gmx_rows_pin(P(bufs["pin_lw"]), R, n, n, P(bufs["zeros"]), P(traj[t + 1]), P(bufs["pin_x"]), D, N, n,
+                                       P(traj[t + 1]), P(bufs["next"]), N, st), "gmx_rows_pin")
+            x_t = cb._views._state_view(cb.hist_xs[t:t + 1], 0)
+            x_t = type(x_t)(v[0] for v in x_t) if cb.tuple_state is not None else x_t[0]
+            smc._ancestor_logits(cb.step, bufs["sites"], cb.obs_addr, x_t, tuple(cb.step_extra(t + 1)) + cb.tail,
+                                 list(bufs["next"]), cb.ys[t + 1], lw_t, bufs["logits"].reshape(1, N), specialize=cb.specialize)
+            logits = bufs["logits"]
+        be.check(be.c.gmx_pick_rows(P(bufs["keys"][t]), P(logits), R, n, n, P(bufs["k"]), P(status[t:]), P(cb.pick_ws), st),
+                 "gmx_pick_rows")
+        torch.add(bufs["k"], bufs["offs"], out=paths[t])
+        flat = paths[t].long()
+        torch.index_select(cb.hist_xs[t], 1, flat, out=traj[t])
+        torch.index_select(lw_t, 0, flat, out=lw_path[t])
+    assert not any(status.tolist())
+    return traj, lw_path, paths
+
+
+if args.backward:
+    import hashlib
+    with open(_lib.LIB_PATH, "rb") as fh:
+        lib_hash = hashlib.sha256(fh.read()).hexdigest()
+    init, step = workloads.make_lgssm(G)
+    for R, n, T in [tuple(int(v) for v in s.split(":")) for s in
+                    os.environ.get("BW_SHAPES", "2048:8:32,64:1024:32,16:4096:32").split(",")]:
+        ys = torch.from_numpy(workloads.lgssm_data(T))
+        cb = smc.ConditionalBank(init, step, n, R, T).prepare(split(G.key(314159), R), ys)
+        cb.launch()
+        cb.draw(G.key(1))
+        cb.retain()
+        cb.launch()
+        D, N = cb.D, R * n
+        bufs = dict(sites=(cb.state_addr,), keys=torch.zeros((T, R, 2), dtype=torch.int32, device=dev),
+                    status=torch.zeros((T,), dtype=torch.int64, device=dev), k=torch.zeros((R,), dtype=torch.int32, device=dev),
+                    offs=(torch.arange(R, dtype=torch.int32, device=dev) * n).contiguous(),
+                    next=torch.zeros((D, N), dtype=torch.float32, device=dev), logits=torch.zeros((N,), dtype=torch.float32, device=dev),
+                    pin_lw=torch.zeros((N,), dtype=torch.float32, device=dev), pin_x=torch.zeros((D, N), dtype=torch.float32, device=dev),
+                    zeros=torch.zeros((R,), dtype=torch.float32, device=dev))
+        key = G.key(2)
+        forms = {"lineage": lambda: cb.draw(key), "backward_fused": lambda: cb.draw(key, backward=True),
+                 "backward_composed": lambda: composed_backward_draw(cb, key, bufs)}
+        for _ in range(3):                          # warm-up (the logits program is built and specialised here)
+            for f in forms.values():
+                f()
+        cb.draw(key, backward=True)
+        fused = [v.clone() for v in cb._last[:3]]
+        comp = composed_backward_draw(cb, key, bufs)
+        assert all(torch.equal(a, b) for a, b in zip(fused, comp)), "fused and composed backward draws disagree"
+        cb.draw(key)
+        moved = int((cb._last[2] != fused[2]).sum().item())
+        per_window = max(3, min(400, int(0.2 / max(timed(forms["backward_fused"], 3), 1e-7))))      # ~0.2 s of draws per window
+        ts = {name: [] for name in forms}
+        for _ in range(args.reps):                  # alternated: every form sees the same neighbours on the machine
+            for name, f in forms.items():
+                ts[name].append(timed(f, per_window))
+        med = {name: statistics.median(v) for name, v in ts.items()}
+        emit(dict(common, tool="time_conditional", what="backward", library_sha256=lib_hash, R=R, n=n, T=T,
+                  draws_per_window=per_window, ms_per_draw={name: spread(v) for name, v in ts.items()},
+                  us_per_step={name: 1e6 * m / T for name, m in med.items()},
+                  spread_over_median={name: (max(v) - min(v)) / med[name] for name, v in ts.items()},
+                  fused_over_composed=med["backward_fused"] / med["backward_composed"],
+                  fused_over_lineage=med["backward_fused"] / med["lineage"],
+                  launches_per_backward_step={"backward_fused": 2 if n <= 1024 else 4, "backward_composed": 8},
+                  picks_off_the_lineage=moved, fused_equals_composed=True))
+        del cb, bufs, forms
