@@ -50,6 +50,11 @@ __device__ __forceinline__ uint32_t gmx_dpp(uint32_t identity, uint32_t v) {
   OP("row_shr:1 row_mask:0xf bank_mask:0xf") OP("row_shr:2 row_mask:0xf bank_mask:0xf") \
   OP("row_shr:4 row_mask:0xf bank_mask:0xf") OP("row_shr:8 row_mask:0xf bank_mask:0xf") \
   OP("row_bcast:15 row_mask:0xa bank_mask:0xf") OP("row_bcast:31 row_mask:0xc bank_mask:0xf")
+// ... without the last step: an inclusive scan of each half-wave on its own (lanes 31 and 63 hold the halves' totals)
+#define GMX_DPP_ASM_HALF_STEPS(OP) \
+  OP("row_shr:1 row_mask:0xf bank_mask:0xf") OP("row_shr:2 row_mask:0xf bank_mask:0xf") \
+  OP("row_shr:4 row_mask:0xf bank_mask:0xf") OP("row_shr:8 row_mask:0xf bank_mask:0xf") \
+  OP("row_bcast:15 row_mask:0xa bank_mask:0xf")
 
 // inclusive max-scan; lane 63 holds the wave maximum.  v_max_f32 (IEEE mode) returns the other operand when one is
 // NaN and +0 for max(-0, +0): gmx_rmax below is the same function on the host.
@@ -120,6 +125,21 @@ __device__ __forceinline__ uint64_t wave_last_u64(uint64_t v) {      // lane 63'
   return ((uint64_t)hi << 32) | lo;
 }
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) { return wave_last_u64(wave_scan_u64(v)); }
+// the wave sums of TWO u64 in one DPP tree.  v_permlane32_swap (gfx950) exchanges lanes 32 .. 63 of `a` with lanes 0 .. 31 of
+// `b`: one 64-bit add then leaves a[l] + a[l + 32] in lane l < 32 and b[l - 32] + b[l] in lane l >= 32, and the five steps
+// that stay inside a half-wave (row_shr:1/2/4/8, row_bcast:15) put a's sum into lane 31 and b's into lane 63 —
+// 2 swaps + 2 + 10 vector instructions where two scans of six steps are 24 (integer sums: any order, same bits).
+__device__ __forceinline__ void wave_sum2_u64(uint64_t& a, uint64_t& b) {
+  const auto slo = __builtin_amdgcn_permlane32_swap((uint32_t)a, (uint32_t)b, false, false);
+  const auto shi = __builtin_amdgcn_permlane32_swap((uint32_t)(a >> 32), (uint32_t)(b >> 32), false, false);
+  const uint64_t v = (((uint64_t)(uint32_t)shi[0] << 32) | (uint32_t)slo[0]) + (((uint64_t)(uint32_t)shi[1] << 32) | (uint32_t)slo[1]);
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#define GMX_OP(CTRL) "s_nop 1\n\tv_add_co_u32_dpp %0, vcc, %0, %0 " CTRL "\n\tv_addc_co_u32_dpp %1, vcc, %1, %1, vcc " CTRL "\n\t"
+  asm(GMX_DPP_ASM_ENTER GMX_DPP_ASM_HALF_STEPS(GMX_OP) : "+v"(lo), "+v"(hi) : : "vcc");
+#undef GMX_OP
+  a = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, 31) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lo, 31);
+  b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
+}
 // lane l receives lane l-1's value (wave_shr:1); lane 0 receives `first`
 __device__ __forceinline__ uint32_t wave_shr1_u32(uint32_t v, uint32_t first) { return gmx_dpp<0x138, 0xf>(first, v); }
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {

@@ -453,9 +453,9 @@ extern "C" int gmx_program_set_background(gmx_program* p, uint32_t lds_pad) {
 
 // ---- on-disk cache of specialised code objects -----------------------------
 // hiprtc needs 0.5-2 s per program; the code object depends only on the generated translation unit,
-// the embedded device headers and the compiler, so it is kept under
+// its compile options, the embedded device headers and the compiler, so it is kept under
 //   $GENMI_JIT_CACHE  (default $XDG_CACHE_HOME/genjax_amd/jit or $HOME/.cache/genjax_amd/jit; "0" disables)
-// as <fnv1a-64 of all three>.co, written to a temporary name and renamed (concurrent ranks are safe).
+// as <fnv1a-64 of all four>.co, written to a temporary name and renamed (concurrent ranks are safe).
 static uint64_t fnv1a(uint64_t h, const char* s, size_t n) {
   for (size_t i = 0; i < n; ++i) { h ^= (unsigned char)s[i]; h *= 0x100000001b3ull; }
   return h;
@@ -477,10 +477,32 @@ static void mkdirs(const std::string& d) {
     if (i == d.size() || d[i] == '/') (void)mkdir(d.substr(0, i).c_str(), 0755);
 }
 
-static std::string jit_cache_path(const std::string& src) {
+// The hiprtc options of a specialised program, stated ONCE: gmx_program_specialize and the dry run compile with the same
+// list, and its text enters the cache key.  A chain program (everything but a background one) is compiled WITHOUT the SLP
+// vectoriser: left on, it pairs the f32 arithmetic of two of a thread's four particles into v_pk_fma_f32 / v_pk_mul_f32 /
+// v_pk_add_f32, which take a whole issue slot for two operations, where the two unpacked ones ride beside the kernel's
+// integer instructions for nothing (third accounting).  A background program keeps the vectoriser: its
+// static count rises without it.  The results are the same bits either way (-ffp-contract=off: no operation is fused).
+struct jit_options {
+  const char* v[5];
+  int n;
+  std::string text() const {
+    std::string s;
+    for (int k = 0; k < n; ++k) { s += v[k]; s += ' '; }
+    return s;
+  }
+};
+static jit_options jit_options_of(bool background, const char* level) {
+  jit_options o = {{"--offload-arch=gfx950", level, "-std=c++17", "-ffp-contract=off", nullptr}, 4};
+  if (!background) o.v[o.n++] = "-fno-slp-vectorize";
+  return o;
+}
+
+static std::string jit_cache_path(const std::string& src, const std::string& opts) {
   std::string dir = jit_cache_dir();
   if (dir.empty()) return "";
   uint64_t h = fnv1a(0xcbf29ce484222325ull, src.data(), src.size());
+  h = fnv1a(h, opts.data(), opts.size());
   for (int k = 0; k < GMX_EMBED_COUNT; ++k) h = fnv1a(h, gmx_embed_src[k], strlen(gmx_embed_src[k]));
   int major = 0, minor = 0;
   (void)hiprtcVersion(&major, &minor);
@@ -538,15 +560,14 @@ static void jit_cache_write(const std::string& path, const std::vector<char>& co
   if (!ok || rename(t.c_str(), path.c_str()) != 0) (void)remove(t.c_str());
 }
 
-static int jit_compile(const std::string& src, std::vector<char>& code) {
+static int jit_compile(const std::string& src, const jit_options& opts, std::vector<char>& code) {
   hiprtcProgram prog;
   const char* hdr_src[GMX_EMBED_COUNT];
   const char* hdr_name[GMX_EMBED_COUNT];
   for (int k = 0; k < GMX_EMBED_COUNT; ++k) { hdr_src[k] = gmx_embed_src[k]; hdr_name[k] = gmx_embed_name[k]; }
   hiprtcResult rc = hiprtcCreateProgram(&prog, src.c_str(), "gmx_jit_program.hip", GMX_EMBED_COUNT, hdr_src, hdr_name);
   if (rc != HIPRTC_SUCCESS) return gmx_fail("hiprtcCreateProgram: %s", hiprtcGetErrorString(rc));
-  const char* opts[4] = {"--offload-arch=gfx950", jit_opt_level(), "-std=c++17", "-ffp-contract=off"};
-  rc = hiprtcCompileProgram(prog, 4, opts);
+  rc = hiprtcCompileProgram(prog, opts.n, const_cast<const char**>(opts.v));
   if (rc != HIPRTC_SUCCESS) {
     size_t ls = 0;
     hiprtcGetProgramLogSize(prog, &ls);
@@ -598,16 +619,31 @@ extern "C" int gmx_program_specialize(gmx_program* p) {
   if (!jit_enabled()) return gmx_fail("gmx_program_specialize: disabled by GENMI_JIT=0%s");
   if (p->n_instr == 0 || p->n_instr > 8192) return gmx_fail("gmx_program_specialize: program size out of range%s");
   const std::string src = jit_source(p, &p->jit_gathers_pre);
-  const std::string path = jit_cache_path(src);
+  const jit_options opts = jit_options_of(p->background, jit_opt_level());
+  const std::string path = jit_cache_path(src, opts.text());
   std::vector<char> code;
   if (jit_cache_read(path, code)) {
     if (jit_load(p, code) == 0) return 0;
     (void)hipGetLastError();                 // a damaged entry just recompiles (and leaves no sticky error behind)
   }
-  if (jit_compile(src, code)) return 1;
+  if (jit_compile(src, opts, code)) return 1;
   if (jit_load(p, code)) return 1;
   jit_cache_write(path, code);
   return 0;
+}
+
+// offline: the cache file a translation unit compiled with an option string would be kept under (no compile, no GPU; an
+// empty string when the cache is disabled) — what the tests hold the cache key to.  Returns the path's length.
+extern "C" size_t gmx_jit_cache_path_of(const char* src, const char* opts, char* out, size_t cap) {
+  const std::string path = jit_cache_path(src ? src : "", opts ? opts : "");
+  if (out && cap) snprintf(out, cap, "%s", path.c_str());
+  return path.size();
+}
+// ... and the option string a program kind is compiled with at the cached level (flags as below)
+extern "C" size_t gmx_jit_options_of(int flags, char* out, size_t cap) {
+  const std::string t = jit_options_of((flags & 2) != 0, "-O3").text();
+  if (out && cap) snprintf(out, cap, "%s", t.c_str());
+  return t.size();
 }
 
 // offline entry point used by tests / tools on machines without a GPU: compile
@@ -635,8 +671,8 @@ extern "C" size_t gmx_specialize_dryrun2(const uint32_t* blob, size_t n_words, i
   for (int k = 0; k < GMX_EMBED_COUNT; ++k) { hdr_src[k] = gmx_embed_src[k]; hdr_name[k] = gmx_embed_name[k]; }
   if (hiprtcCreateProgram(&prog, src.c_str(), "gmx_jit_program.hip", GMX_EMBED_COUNT, hdr_src, hdr_name) != HIPRTC_SUCCESS)
     return 0;
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-  hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
+  const jit_options opts = jit_options_of(P.background, "-O3");
+  hiprtcResult rc = hiprtcCompileProgram(prog, opts.n, const_cast<const char**>(opts.v));
   size_t ls = 0;
   hiprtcGetProgramLogSize(prog, &ls);
   if (log_out && log_cap) {

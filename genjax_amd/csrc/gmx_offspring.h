@@ -27,6 +27,13 @@ __device__ __forceinline__ void gmx_store_u32x4_sc1(uint32_t* p, uint32_t a, uin
   v4 v; v.x = a; v.y = b; v.z = c; v.w = d;
   asm volatile("s_nop 1\n\tglobal_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
 }
+// eight consecutive words at [uniform base + 32-bit byte offset]: the scalar-base form, the second half in the offset field
+__device__ __forceinline__ void gmx_store_u32x8_sc1(uint32_t* base_uniform, uint32_t off, uint4 a, uint4 b) {
+  typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+  v4 va, vb; va.x = a.x; va.y = a.y; va.z = a.z; va.w = a.w; vb.x = b.x; vb.y = b.y; vb.z = b.z; vb.w = b.w;
+  asm volatile("s_nop 1\n\tglobal_store_dwordx4 %0, %1, %3 sc1\n\tglobal_store_dwordx4 %0, %2, %3 offset:16 sc1\n\ts_nop 1"
+               :: "v"(off), "v"(va), "v"(vb), "s"(base_uniform) : "memory");
+}
 __device__ __forceinline__ void gmx_store_u32_sc1(uint32_t* p, uint32_t a) {
   __hip_atomic_store(p, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -78,6 +85,9 @@ __device__ __forceinline__ int64_t sorted_below_exact(const sorted_ctx& X, uint6
 // selects on the scalar condition (every lane issues both sides — measured: MORE vector instructions than the per-lane
 // compare it replaced); an empty volatile asm in the body cannot be speculated, so the scalar branch stays a branch
 #define GMX_KEEP_BRANCH asm volatile("")
+// a 32-bit byte offset widened in the basic block of its access, so that the access takes the [scalar base + offset] form
+// (gmx_jit.h, gmx_jit_ctx::zext_here, says why the copy is needed; it emits nothing)
+__device__ __forceinline__ uint64_t rs_zext_here(uint32_t o) { asm volatile("" : "+v"(o)); return (uint64_t)o; }
 #define RS_BLOCK (GMX_BLOCK * RS_TPB)
 #define RS_WAVES (RS_BLOCK / GMX_WAVE)
 static_assert(RS_MAX_TILES % RS_BLOCK == 0, "tile table shape");
@@ -134,6 +144,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   static_assert(!PREF || RS_TPB == 1, "the prefix form works on one tile per block");
   uint64_t ta[PERN];
   float tm[PERN];
+  const uint32_t tid4 = threadIdx.x * 4u;
   uint64_t pf_prefix = 0, pf_total = 0, pf_mk = 0;
   if (PREF) {
     if (agg) { pf_prefix = agg[tile_c]; pf_total = agg[n_tiles]; pf_mk = agg[n_tiles + 1]; }
@@ -143,10 +154,18 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     for (int r = 0; r < PERN; ++r) {              // loads only (clamped rows): nothing here waits
       ta[r] = 0ull; tm[r] = -gmx_inf();
       if (r * RS_BLOCK < n_tiles) {                // uniform: rows of the table that exist
-        const int t = r * RS_BLOCK + (int)threadIdx.x;
-        const int tc = t < n_tiles ? t : n_tiles - 1;
-        ta[r] = agg[tc];
-        tm[r] = tmax[tc];
+        if ((r + 1) * RS_BLOCK <= n_tiles) {       // uniform: a whole row — [scalar base of the row] + 8 tid / 4 tid, no
+          GMX_KEEP_BRANCH;                         // 64-bit vector add, compare or select per row (gmx_jit.h, gmx_jit_ctx)
+          uint32_t r0 = (uint32_t)(r * RS_BLOCK);     // (opaque, in a scalar register: the row's base is a scalar add — left
+          asm volatile("" : "+s"(r0));                //  to itself hipcc adds an offset past the immediate field per lane)
+          ta[r] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(agg + r0) + rs_zext_here(tid4 * 2u));
+          tm[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(tmax + r0) + rs_zext_here(tid4));
+        } else {                                   // the table's last row: clamped
+          const int t = r * RS_BLOCK + (int)threadIdx.x;
+          const int tc = t < n_tiles ? t : n_tiles - 1;
+          ta[r] = agg[tc];
+          tm[r] = tmax[tc];
+        }
       }
     }
   }
@@ -232,8 +251,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
           if (t >= first_tile && t < first_tile + RS_TPB) s_g[t - first_tile] = G;      // t >= n_tiles: G = 0
       }
     }
-    below = wave_sum_u64(below);
-    all = wave_sum_u64(all);
+    wave_sum2_u64(below, all);
     if (lane == 0) { s_below[wave] = below; s_all[wave] = all; }
     __syncthreads();
 #pragma unroll
@@ -387,7 +405,9 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   if (lane == 63) s_edge[wave] = e[CDF_VEC_OT];      // the (settled) upper edge of this wave, for lane 0 of the next
   // Sources past n have e[c] = n = e of the last real source, so they own no slot.
   const int32_t e4 = e[4];
-  const int32_t src0 = (int32_t)i0;
+  // the marks carry the step's tag already: (src0 + c) | tagw == src0t + c (the index field cannot carry into bit 24), every
+  // compared mark has the same tag and an empty one is 0, so the max-scan gives the tagged maxima and no store ORs anything
+  const uint32_t src0t = (uint32_t)(int32_t)i0 | tagw;
   static_assert(RS_TPB == 1, "the LDS fill works on one tile per block");
   __shared__ __attribute__((aligned(16))) uint32_t s_mark[RS_FILL_SLOTS];
   __shared__ int32_t s_rng[2];
@@ -409,7 +429,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
 #pragma unroll
     for (int c = 0; c < CDF_VEC_OT; ++c) {
       const int32_t lo = e[c] > base ? e[c] : base;
-      if (e[c + 1] > lo && lo - base < RS_FILL_SLOTS) s_mark[lo - base] = (uint32_t)(src0 + c);
+      if (e[c + 1] > lo && lo - base < RS_FILL_SLOTS) s_mark[lo - base] = src0t + (uint32_t)c;
     }
     __syncthreads();
     uint4 a = reinterpret_cast<const uint4*>(s_mark)[2 * threadIdx.x];
@@ -429,21 +449,20 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
       rs_u32x4_a4 va, vb;
       va.x = a.x; va.y = a.y; va.z = a.z; va.w = a.w; vb.x = b.x; vb.y = b.y; vb.z = b.z; vb.w = b.w;
       if (TAGGED) {
-        gmx_store_u32x4_sc1(reinterpret_cast<uint32_t*>(anc) + j, va.x | tagw, va.y | tagw, va.z | tagw, va.w | tagw);
-        gmx_store_u32x4_sc1(reinterpret_cast<uint32_t*>(anc) + j + 4, vb.x | tagw, vb.y | tagw, vb.z | tagw, vb.w | tagw);
+        gmx_store_u32x8_sc1(reinterpret_cast<uint32_t*>(anc) + base, 32u * threadIdx.x, a, b);      // (`base`: block-uniform)
       } else {
         *reinterpret_cast<rs_u32x4_a4*>(anc + j) = va;
         *reinterpret_cast<rs_u32x4_a4*>(anc + j + 4) = vb;
       }
     } else {
-      if (j + 0 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 0, a.x | tagw); else anc[j + 0] = (int32_t)a.x; }
-      if (j + 1 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 1, a.y | tagw); else anc[j + 1] = (int32_t)a.y; }
-      if (j + 2 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 2, a.z | tagw); else anc[j + 2] = (int32_t)a.z; }
-      if (j + 3 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 3, a.w | tagw); else anc[j + 3] = (int32_t)a.w; }
-      if (j + 4 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 4, b.x | tagw); else anc[j + 4] = (int32_t)b.x; }
-      if (j + 5 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 5, b.y | tagw); else anc[j + 5] = (int32_t)b.y; }
-      if (j + 6 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 6, b.z | tagw); else anc[j + 6] = (int32_t)b.z; }
-      if (j + 7 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 7, b.w | tagw); else anc[j + 7] = (int32_t)b.w; }
+      if (j + 0 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 0, a.x); else anc[j + 0] = (int32_t)a.x; }
+      if (j + 1 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 1, a.y); else anc[j + 1] = (int32_t)a.y; }
+      if (j + 2 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 2, a.z); else anc[j + 2] = (int32_t)a.z; }
+      if (j + 3 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 3, a.w); else anc[j + 3] = (int32_t)a.w; }
+      if (j + 4 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 4, b.x); else anc[j + 4] = (int32_t)b.x; }
+      if (j + 5 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 5, b.y); else anc[j + 5] = (int32_t)b.y; }
+      if (j + 6 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 6, b.z); else anc[j + 6] = (int32_t)b.z; }
+      if (j + 7 < T1) { if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + j + 7, b.w); else anc[j + 7] = (int32_t)b.w; }
     }
   }
 }
@@ -485,8 +504,7 @@ gmx_tile_table_pass(const float* __restrict__ tmax, const uint64_t* __restrict__
         else if (tb < mine) { GMX_KEEP_BRANCH; part += (t < mine) ? g_ : 0ull; }
       }
     }
-    tot = wave_sum_u64(tot);
-    part = wave_sum_u64(part);
+    wave_sum2_u64(tot, part);
     if (lane == 0) { s_acc[wave][0] = tot; s_acc[wave][1] = part; }
     __syncthreads();
     uint64_t T_ = 0, P_ = 0;

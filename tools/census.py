@@ -3,14 +3,17 @@
 resampling prologue (gmx_jit_kernel) and its NoiseProgram as a background kernel (gmx_jit_background_kernel) — specialised
 for gfx950 like tools/dump_isa.py does, and their F / I / X / T histogram (tools/valu_model.py).
 
-    python tools/census.py [label]      -> profiles/tile_addressing_census_<label>.json   (default label: tree)
-                                           /tmp/census_<label>_{chain,background}.s
+    python tools/census.py [label [stem]]  -> profiles/<stem>_<label>.json   (defaults: tree, tile_addressing_census)
+                                              /tmp/census_<label>_{chain,background}.s
+    GENMI_LIB=<a parent's libgenmi_hip.so> python tools/census.py parent <stem>: the parent's kernels (the library carries
+    its own device headers and compile options)
 
 `xi2t` = X + I + 2 T is the number that pays when it falls (an F rides free beside an X).  STATIC
 counts over every key mode the kernel carries; what a wave executes is SQ_INSTS_VALU (tools/prof.sh).
 """
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +53,10 @@ def census(label="tree"):
         sym, lines = valu_model.kernel_listing(s)
         m = valu_model.model(lines)
         m["xi2t"] = m["X"] + m["I"] + 2 * m["T"]
+        m["v_pk"] = sum(1 for ln in lines if re.match(r"\s*v_pk_", str(ln)))
+        for key in ("vgpr_count", "sgpr_count", "private_segment_fixed_size"):      # (one kernel per code object)
+            f = re.search(r"\." + key + r":\s*(\d+)", meta)
+            m[key] = int(f.group(1)) if f else None
         out[sym] = m
     out["xi2t_sum"] = sum(v["xi2t"] for v in out.values())
     return out
@@ -57,8 +64,9 @@ def census(label="tree"):
 
 if __name__ == "__main__":
     label = sys.argv[1] if len(sys.argv) > 1 else "tree"
+    stem = sys.argv[2] if len(sys.argv) > 2 else "tile_addressing_census"
     res = census(label)
-    path = os.path.join(ROOT, "profiles", f"tile_addressing_census_{label}.json")
+    path = os.path.join(ROOT, "profiles", f"{stem}_{label}.json")
     json.dump(res, open(path, "w"), indent=1)
     print(json.dumps(res, indent=1))
     print("wrote", path)

@@ -40,7 +40,7 @@ def step_blob(which="step"):
 
 
 def compile_blob(blob, out_prefix):
-    so = os.path.join(ROOT, "genjax_amd", "lib", "libgenmi_hip.so")
+    so = os.environ.get("GENMI_LIB") or os.path.join(ROOT, "genjax_amd", "lib", "libgenmi_hip.so")   # (a parent's build)
     lib = ctypes.CDLL(so)
     lib.gmx_specialize_dryrun2.restype = ctypes.c_size_t
     lib.gmx_specialize_dryrun2.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
