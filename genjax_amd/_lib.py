@@ -144,6 +144,7 @@ class Backend:
         c.gmx_split_rows.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_void_p]
         c.gmx_fold_in.argtypes = [c_void_p, c_uint32, c_int64, c_void_p, c_void_p]
         c.gmx_random_bits.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_void_p]
+        c.gmx_std_normal_from_bits.argtypes = [c_void_p, c_int64, c_void_p, c_void_p]
         c.gmx_program_create.argtypes = [POINTER(c_uint32), c_size_t, POINTER(c_void_p)]
         c.gmx_program_destroy.argtypes = [c_void_p]
         c.gmx_program_specialize.argtypes = [c_void_p]

@@ -930,6 +930,22 @@ extern "C" int gmx_random_bits(const uint32_t* keys_d, int64_t n, int64_t m, uin
   return 0;
 }
 
+// the normal draw's tail on chosen bits (grid-stride, elementwise): what every sampler applies to a Threefry word
+__global__ void __launch_bounds__(GMX_BLOCK)
+k_std_normal_from_bits(const uint32_t* __restrict__ bits, int64_t n, float* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * GMX_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * GMX_BLOCK + threadIdx.x; i < n; i += stride) out[i] = gmx_std_normal_from_bits(bits[i]);
+}
+extern "C" int gmx_std_normal_from_bits(const uint32_t* bits_d, int64_t n, float* out_d, gmx_stream stream) {
+  if (n <= 0) return 0;
+  if (!bits_d || !out_d) return gmx_fail("gmx_std_normal_from_bits: null argument%s");
+  const int64_t blocks = (n + GMX_BLOCK - 1) / GMX_BLOCK;
+  hipLaunchKernelGGL(k_std_normal_from_bits, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(GMX_BLOCK), 0,
+                     (hipStream_t)stream, bits_d, n, out_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // log-sum-exp
 // ---------------------------------------------------------------------------

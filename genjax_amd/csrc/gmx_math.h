@@ -179,6 +179,17 @@ GMX_HD uint32_t gmx_exp_fixed_packed(float d, int shift) {
 GMX_HD uint64_t gmx_fixed_unpack(uint32_t pk) { return ((uint64_t)(pk & 0x00ffffffu) << 39) >> (pk >> 24); }
 GMX_HD uint64_t gmx_exp_fixed(float d, int shift) { return gmx_fixed_unpack(gmx_exp_fixed_packed(d, shift)); }
 
+// The cephes split of a positive normal float with bits `us`, x = m * 2^e, m in [0.5, 1), "if m < sqrt(1/2) then e - 1,
+// f = 2m - 1 else f = m - 1", without the compare and the two selects: adding (bits of 1) - (bits of sqrt(1/2)) carries
+// into the exponent field exactly when the mantissa is at or above sqrt(1/2)'s (the same f32 threshold 0x3f3504f3), and
+// the low 23 bits put back on sqrt(1/2)'s bits are 2m below the threshold and m from it on (m + m was exact): the same
+// e and f, bit for bit.  Bits outside the positive normals give values the callers' special-case selects override.
+GMX_HD void gmx_log_split(uint32_t us, int* e, float* f) {
+  const uint32_t ix = us + (0x3f800000u - 0x3f3504f3u);
+  *e = (int)(ix >> 23) - 127;
+  *f = gmx_u2f((ix & 0x007fffffu) + 0x3f3504f3u) - 1.0f;
+}
+
 // log(x), natural.  cephes logf polynomial on [sqrt(1/2), sqrt(2)).
 // Straight-line like gmx_expf: special cases are selects over the main path's result.
 GMX_HD float gmx_logf(float x) {
@@ -186,12 +197,10 @@ GMX_HD float gmx_logf(float x) {
   const int den = ux < 0x00800000u;          // denormal (or +0: overridden below): scale up by 2^23 (exact)
   const float xs = den ? x * 8388608.0f : x;
   const uint32_t us = gmx_f2u(xs);
-  // frexp: x = m * 2^e with m in [0.5, 1)
-  int e = (den ? -23 : 0) + (int)(us >> 23) - 126;
-  const float m = gmx_u2f((us & 0x007fffffu) | 0x3f000000u);
-  const int low = m < 0.707106781186547524f;
-  e -= low;
-  const float f = low ? (m + m) - 1.0f : m - 1.0f;
+  // x = (1 + f) * 2^e with 1 + f in [sqrt(1/2), sqrt(2)), see gmx_log_split
+  int e; float f;
+  gmx_log_split(us, &e, &f);
+  e += den ? -23 : 0;
   float z = f * f;
   float p = 7.0376836292e-2f;
   p = gmx_fma(p, f, -1.1514610310e-1f);
@@ -254,6 +263,25 @@ GMX_HD float gmx_tanhf(float x) {
   return (gmx_f2u(x) >> 31) ? -t : t;
 }
 
+// t / d for t, d in [-1, -2^-24] with t / d in [1/2, 2] (gmx_neg_log1m_sq: d = fl(1 + t) - 1), and anything at all for
+// d == 0 (overridden there).  On the device the IEEE division is v_rcp_f32, two Newton steps and the scale / fix-up
+// instructions around them; in this range neither scale fires and the fix-up passes its input through, so the same
+// operations without them give the same bits (tests/test_normal_tail_gpu.py: all 2^23 draws).  The host keeps t / d.
+#if defined(__HIP_DEVICE_COMPILE__)
+GMX_HD float gmx_div_near(float t, float d) {
+  float rc = __builtin_amdgcn_rcpf(d);
+  const float er = gmx_fma(-d, rc, 1.0f);
+  rc = gmx_fma(er, rc, rc);
+  float q = t * rc;
+  float rem = gmx_fma(-d, q, t);
+  q = gmx_fma(rem, rc, q);
+  rem = gmx_fma(-d, q, t);
+  return gmx_fma(rem, rc, q);
+}
+#else
+GMX_HD float gmx_div_near(float t, float d) { return t / d; }
+#endif
+
 // -log1p(-x*x) for |x| <= 1, i.e. gmx_log1pf(-(x*x)) negated, with only the cases that argument can reach:
 // u = 1 - x*x lies in [0, 1] (never NaN / negative / infinite, and never denormal: it is 0 or >= 2^-24), so of
 // gmx_logf's and gmx_log1pf's special handling only "u == 1" (return the argument) and "u == 0" (log = -inf) are
@@ -263,11 +291,8 @@ GMX_HD float gmx_neg_log1m_sq(float x) {
   const float t = -(x * x);
   const float u = 1.0f + t;
   const uint32_t us = gmx_f2u(u);
-  int e = (int)(us >> 23) - 126;
-  const float m = gmx_u2f((us & 0x007fffffu) | 0x3f000000u);
-  const int low = m < 0.707106781186547524f;
-  e -= low;
-  const float f = low ? (m + m) - 1.0f : m - 1.0f;
+  int e; float f;
+  gmx_log_split(us, &e, &f);
   float z = f * f;
   float p = 7.0376836292e-2f;
   p = gmx_fma(p, f, -1.1514610310e-1f);
@@ -286,7 +311,7 @@ GMX_HD float gmx_neg_log1m_sq(float x) {
   l = gmx_fma(ef, 0.693359375f, l);
   l = (us == 0u) ? -gmx_inf() : l;          // log(0)
   const float d = u - 1.0f;
-  float r = l * (t / d);                     // d == 0 only when u == 1: overridden
+  float r = l * gmx_div_near(t, d);          // d == 0 only when u == 1: overridden
   r = (u == 1.0f) ? t : r;
   return -r;
 }

@@ -114,6 +114,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   __shared__ uint64_t s_below[RS_WAVES], s_all[RS_WAVES], s_scan[RS_WAVES], s_g[RS_TPB];
   __shared__ float s_max[RS_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);      // the same number in a scalar register: selects on it are scalar
   // which of the block's tiles / thread within it (one tile per block: the block is GMX_BLOCK threads, and tile_ok and
   // full_tile below are WORKGROUP-uniform — said so that the compiler keeps them on the scalar unit)
   const int grp = RS_TPB > 1 ? (int)(threadIdx.x >> 8) : 0, ltid = threadIdx.x & (GMX_BLOCK - 1);
@@ -227,7 +228,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   }
   uint64_t wave_off = 0;
 #pragma unroll
-  for (int w = 0; w < 4; ++w) wave_off += (w < (wave & 3)) ? s_scan[4 * grp + w] : 0ull;     // the tile's own four waves
+  for (int w = 0; w < 4; ++w) wave_off += (w < (wave_s & 3)) ? s_scan[4 * grp + w] : 0ull;   // the tile's own four waves
   const uint64_t loc = wave_off + (inc - run);          // tile-local mass before this thread's sources
   // phase 2: G_t = A_t * 2^(k_t - K) for every tile -> the mass before this block's first tile, the block's own
   // four G, and the total
@@ -441,7 +442,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     if (lane == 63) s_carry[wave] = incl;
     __syncthreads();
 #pragma unroll
-    for (int w = 0; w < RS_WAVES - 1; ++w) { const uint32_t v = s_carry[w]; carry = (w < wave && v > carry) ? v : carry; }
+    for (int w = 0; w < RS_WAVES - 1; ++w) { const uint32_t v = s_carry[w]; carry = (w < wave_s && v > carry) ? v : carry; }
     a.x = a.x > carry ? a.x : carry; a.y = a.y > carry ? a.y : carry; a.z = a.z > carry ? a.z : carry; a.w = a.w > carry ? a.w : carry;
     b.x = b.x > carry ? b.x : carry; b.y = b.y > carry ? b.y : carry; b.z = b.z > carry ? b.z : carry; b.w = b.w > carry ? b.w : carry;
     const int32_t j = base + 8 * (int32_t)threadIdx.x;

@@ -73,7 +73,10 @@ GMX_HD float gmx_uniform_from_bits(uint32_t bits, float lo, float hi) {
 // jax.random.normal: sqrt(2) * erf_inv(uniform(nextafter(-1, 0), 1)).
 GMX_HD float gmx_std_normal_from_bits(uint32_t bits) {
   const float lo = -0.99999994f;   // nextafter(-1, 0) in f32
-  float u = gmx_uniform_from_bits(bits, lo, 1.0f);
+  // gmx_uniform_from_bits(bits, lo, 1) with its clamp as one max: v is never NaN here, so max(v, lo) is `v > lo ? v : lo`
+  float v = gmx_bits_to_unit(bits) * (1.0f - lo);
+  v = v + lo;
+  const float u = __builtin_fmaxf(v, lo);
   return 1.41421354f * gmx_erfinvf_unit(u);     // |u| < 1 by construction
 }
 // jax.random.gumbel: -log(-log(uniform(tiny, 1))).

@@ -75,6 +75,10 @@ int gmx_fold_in(const uint32_t* keys_d /* [n,2] */, uint32_t data, int64_t n,
 /* raw 32-bit draws: out_d[i*m + j] = random_bits(keys_d[i], 32, (m,))[j]. */
 int gmx_random_bits(const uint32_t* keys_d /* [n,2] */, int64_t n, int64_t m,
                     uint32_t* out_d /* [n*m] */, gmx_stream stream);
+/* the standard normal every sampler makes of one 32-bit draw (jax.random.normal's uniform on (-1, 1) through
+ * sqrt(2) * erf_inv): out_d[i] = normal(bits_d[i]), so the draw's tail can be driven with chosen bits. */
+int gmx_std_normal_from_bits(const uint32_t* bits_d /* [n] */, int64_t n, float* out_d /* [n] */,
+                             gmx_stream stream);
 
 /* ------------------------------------------------------------------------
  * Site programs: one fused kernel per generative-function-interface call.
