@@ -3517,97 +3517,120 @@ extern "C" int gmx_lineage(const int32_t* anc_d, const float* xs_d, int32_t T, i
 }
 
 // ---------------------------------------------------------------------------
-// row-wise exact-integer draws: one multinomial index per row of logits (gmx_backward.h)
+// row-wise exact-integer draws: one multinomial index per row of logits (gmx_backward.h), and many independent rows,
+// each resampled as gmx_resample resamples it alone (gmx_resample_rows.h).  Every entry point: its refusal (gmx_sizes.h:
+// nulls, shapes, conditional nulls), the HIP build's alignment check, then launches through the helpers below.
 // ---------------------------------------------------------------------------
+#include <initializer_list>
+#include <type_traits>
 #include "gmx_backward.h"
+#include "gmx_resample_rows.h"
 static_assert(GMX_PICK_TILE == RS_TILE, "gmx_pick_rows draws from the resamplers' two-level CDF: the same definition tile");
+static_assert(GMX_ROWS_MAX_N == (int64_t)RS_MAX_TILES * RS_TILE && GMX_TP_MAX_TILES == RS_MAX_TILES,
+              "gmx_resample_rows takes the rows the per-row fused path takes");
+
+// the workspace to 8 bytes, then every (pointer, mask) pair: 1 with the message left, 0 when all are aligned
+struct rows_ptr { const void* p; uintptr_t mask; };
+static int rows_misaligned_(const char* who, const void* workspace_d, std::initializer_list<rows_ptr> ptrs,
+                            const char* fmt = "%s: a pointer is not aligned to its element") {
+  if ((uintptr_t)workspace_d & 7) return gmx_fail("%s: workspace_d must be 8-byte aligned", who);
+  for (const rows_ptr& a : ptrs)
+    if ((uintptr_t)a.p & a.mask) return gmx_fail(fmt, who);
+  return 0;
+}
+
+// a grid's y extent holds 65535 rows: launch(row0, count) for each chunk of the rows
+template <class F>
+static void rows_for_chunks_(int64_t rows, F launch) {
+  for (int64_t row0 = 0; row0 < rows; row0 += 65535) launch(row0, (unsigned)(rows - row0 < 65535 ? rows - row0 : 65535));
+}
+// n <= 1024, the packing of k_rows_small: launch(W as a constant, the grid) with W = 1, 2 or 4 waves per row, 4 / W rows per
+// workgroup
+template <class F>
+static void rows_for_packing_(int64_t rows, int64_t n, F launch) {
+  auto go = [&](auto w) { launch(w, dim3((unsigned)((rows + (4 / w.value) - 1) / (4 / w.value)))); };
+  if (n <= 256) go(std::integral_constant<int, 1>{});
+  else if (n <= 512) go(std::integral_constant<int, 2>{});
+  else go(std::integral_constant<int, 4>{});
+}
+// f(kind as a constant), kind one of the three row forms (checked by the refusal)
+template <class F>
+static void rows_for_kind_(int kind, F f) {
+  if (kind == GMX_RESAMPLE_SYSTEMATIC) f(std::integral_constant<int, GMX_RESAMPLE_SYSTEMATIC>{});
+  else if (kind == GMX_RESAMPLE_STRATIFIED) f(std::integral_constant<int, GMX_RESAMPLE_STRATIFIED>{});
+  else f(std::integral_constant<int, GMX_RESAMPLE_MULTINOMIAL>{});
+}
+
+// k_pick_stats over every (row, tile), then k_pick_row: row r's draw plus r * index_stride into out[r * out_stride + out_offset]
+static void launch_pick_(hipStream_t st, const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
+                         float scale, gmx_rows_ws w, int32_t* out_d, int64_t out_stride, int64_t out_offset,
+                         int64_t index_stride, unsigned long long* status) {
+  const int64_t tiles = gmx_tiles_(n);
+  rows_for_chunks_(rows, [&](int64_t row0, unsigned cnt) {
+    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, cnt), dim3(GMX_PICK_BLOCK), 0, st, logits_d, n, ld, tiles, row0,
+                       scale, w.tmax, w.agg);
+  });
+  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
+                     (const float*)w.tmax, (const uint64_t*)w.agg, out_d, out_stride, out_offset, index_stride, status);
+}
+
+// n > 1024, per chunk of rows: k_pick_stats, k_rows_tile<kind> and — the iid multinomial — k_rows_mn<PIN> on the CDF it wrote
+template <bool PIN>
+static void launch_rows_tiled_(int kind, hipStream_t st, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n,
+                               int64_t ld, int64_t index_stride, float scale, gmx_rows_ws w, float* max_d, uint64_t* total_d,
+                               int32_t* ancestors_d, unsigned long long* status) {
+  const int64_t tiles = gmx_tiles_(n);
+  rows_for_chunks_(rows, [&](int64_t row0, unsigned cnt) {
+    const dim3 grid((unsigned)tiles, cnt), block(GMX_ROWS_BLOCK);
+    hipLaunchKernelGGL(k_pick_stats, grid, block, 0, st, lw_d, n, ld, tiles, row0, scale, w.tmax, w.agg);
+    rows_for_kind_(kind, [&](auto k) {
+      hipLaunchKernelGGL((k_rows_tile<decltype(k)::value>), grid, block, 0, st, keys_d, lw_d, n, ld, (int)tiles, row0,
+                         index_stride, scale, (const float*)w.tmax, (const uint64_t*)w.agg, max_d, total_d, ancestors_d, w.cdf,
+                         status);
+    });
+    if (kind == GMX_RESAMPLE_MULTINOMIAL)
+      hipLaunchKernelGGL(k_rows_mn<PIN>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), cnt), block, 0, st, keys_d,
+                         (const uint64_t*)w.cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
+  });
+}
 
 extern "C" size_t gmx_pick_rows_workspace(int64_t rows, int64_t n) { return gmx_pick_rows_bytes_(rows, n); }
 
 extern "C" int gmx_pick_rows(const uint32_t* keys_d, const float* logits_d, int64_t rows, int64_t n, int64_t ld,
                              int32_t* out_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !logits_d || !out_d || !status_d || !workspace_d) return gmx_fail("gmx_pick_rows: null argument%s");
-  const gmx_refusal no = gmx_pick_rows_refusal_(rows, n, ld);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_pick_rows", no.v);
-  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_pick_rows: workspace_d must be 8-byte aligned%s");
-  if (((uintptr_t)logits_d & 3) || ((uintptr_t)keys_d & 3)) return gmx_fail("gmx_pick_rows: keys_d and logits_d must be 4-byte aligned%s");
-  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
-  uint64_t* agg = (uint64_t*)workspace_d;
-  float* tmax = (float*)(agg + rows * tiles);
-  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
-  hipStream_t st = (hipStream_t)stream;
-  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
-    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
-    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, logits_d, n, ld,
-                       tiles, row0, scale, tmax, agg);
-  }
-  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
-                     (const float*)tmax, (const uint64_t*)agg, out_d, (int64_t)1, (int64_t)0, (int64_t)0,
-                     (unsigned long long*)status_d);
+  const char* who = "gmx_pick_rows";
+  const gmx_refusal no = gmx_pick_rows_refusal_(!keys_d || !logits_d || !out_d || !status_d || !workspace_d, rows, n, ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{logits_d, 3}, {keys_d, 3}}, "%s: keys_d and logits_d must be 4-byte aligned")) return 1;
+  launch_pick_((hipStream_t)stream, keys_d, logits_d, rows, n, ld, gmx_pow2i(gmx_pick_rows_shift_(n)),
+               gmx_pick_rows_carve_(workspace_d, rows, n), out_d, 1, 0, 0, (unsigned long long*)status_d);
   GMX_HIP(hipGetLastError());
   return 0;
 }
-
-// ---------------------------------------------------------------------------
-// row-wise resampling: many independent rows, each resampled as gmx_resample resamples it alone (gmx_resample_rows.h)
-// ---------------------------------------------------------------------------
-#include "gmx_resample_rows.h"
-static_assert(GMX_ROWS_MAX_N == (int64_t)RS_MAX_TILES * RS_TILE && GMX_TP_MAX_TILES == RS_MAX_TILES,
-              "gmx_resample_rows takes the rows the per-row fused path takes");
 
 extern "C" size_t gmx_resample_rows_workspace(int kind, int64_t rows, int64_t n) { return gmx_resample_rows_bytes_(kind, rows, n); }
 
 extern "C" int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n, int64_t ld,
                                  int64_t index_stride, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
                                  int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("gmx_resample_rows: null argument%s");
-  const gmx_refusal no = gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows", no.v);
-  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows: workspace_d must be 8-byte aligned%s");
-  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) ||
-      ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
-    return gmx_fail("gmx_resample_rows: a pointer is not aligned to its element%s");
+  const char* who = "gmx_resample_rows";
+  const gmx_refusal no = gmx_resample_rows_refusal_(!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d,
+                                                    kind, rows, n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {keys_d, 3}, {ancestors_d, 3}, {max_d, 3}, {total_d, 7}, {status_d, 7}})) return 1;
   const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
   hipStream_t st = (hipStream_t)stream;
   auto* status = (unsigned long long*)status_d;
   if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
-#define GMX_ROWS_SMALL2(KIND, W_)                                                                                      \
-  hipLaunchKernelGGL((k_rows_small<KIND, W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
-                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status)
-#define GMX_ROWS_SMALL(KIND)                                                                                           \
-  do {                                                                                                                 \
-    if (n <= 256) GMX_ROWS_SMALL2(KIND, 1);                                                                            \
-    else if (n <= 512) GMX_ROWS_SMALL2(KIND, 2);                                                                       \
-    else GMX_ROWS_SMALL2(KIND, 4);                                                                                     \
-  } while (0)
-    if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_SMALL(GMX_RESAMPLE_SYSTEMATIC);
-    else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_SMALL(GMX_RESAMPLE_STRATIFIED);
-    else GMX_ROWS_SMALL(GMX_RESAMPLE_MULTINOMIAL);
-#undef GMX_ROWS_SMALL
-#undef GMX_ROWS_SMALL2
-    GMX_HIP(hipGetLastError());
-    return 0;
-  }
-  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
-  uint64_t* agg = (uint64_t*)workspace_d;
-  uint64_t* cdf = agg + rows * tiles;
-  float* tmax = (float*)(cdf + (kind == GMX_RESAMPLE_MULTINOMIAL ? rows * n : 0));
-  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
-    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
-    const dim3 grid((unsigned)tiles, (unsigned)cnt), block(GMX_ROWS_BLOCK);
-    hipLaunchKernelGGL(k_pick_stats, grid, block, 0, st, lw_d, n, ld, tiles, row0, scale, tmax, agg);
-#define GMX_ROWS_TILE(KIND)                                                                                            \
-  hipLaunchKernelGGL((k_rows_tile<KIND>), grid, block, 0, st, keys_d, lw_d, n, ld, (int)tiles, row0, index_stride, scale, \
-                     (const float*)tmax, (const uint64_t*)agg, max_d, total_d, ancestors_d, cdf, status)
-    if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_TILE(GMX_RESAMPLE_SYSTEMATIC);
-    else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_TILE(GMX_RESAMPLE_STRATIFIED);
-    else {
-      GMX_ROWS_TILE(GMX_RESAMPLE_MULTINOMIAL);
-      hipLaunchKernelGGL(k_rows_mn<false>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0, st,
-                         keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
-    }
-#undef GMX_ROWS_TILE
+    rows_for_kind_(kind, [&](auto k) {
+      rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+        hipLaunchKernelGGL((k_rows_small<decltype(k)::value, decltype(w)::value>), grid, dim3(GMX_ROWS_BLOCK), 0, st, keys_d, lw_d,
+                           rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status);
+      });
+    });
+  } else {
+    launch_rows_tiled_<false>(kind, st, keys_d, lw_d, rows, n, ld, index_stride, scale,
+                              gmx_resample_rows_carve_(workspace_d, kind, rows, n), max_d, total_d, ancestors_d, status);
   }
   GMX_HIP(hipGetLastError());
   return 0;
@@ -3620,6 +3643,11 @@ static unsigned gmx_rows_pin_blocks_(int64_t rows, int64_t quads) {
   const int64_t blocks = (items + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK;
   return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));
 }
+static rows_pin rows_pin_of_(const float* pin_lw_d, const float* pin_x_d, float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride) {
+  rows_pin pin;
+  pin.lw = pin_lw_d; pin.x = pin_x_d; pin.x_out = x_d; pin.D = D; pin.x_ld = x_ld; pin.x_row_stride = x_row_stride;
+  return pin;
+}
 
 // the iid multinomial with slot n - 1 of every row pinned (conditional SMC): n <= 1024 ONE launch; past it the pins, then
 // the unpinned chain with the last slot forced in k_rows_mn
@@ -3627,49 +3655,28 @@ extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int
                                         int64_t index_stride, const float* pin_lw_d, const float* pin_x_d, float* x_d,
                                         int32_t D, int64_t x_ld, int64_t x_row_stride, float* max_d, uint64_t* total_d,
                                         int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("gmx_resample_rows_pinned: null argument%s");
-  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
-  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_pinned", no.v);
-  if (D > 0 && !pin_x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (pin_x_d with D > 0)%s");
-  if (D > 0 && !x_d) return gmx_fail("gmx_resample_rows_pinned: null argument (x_d with D > 0)%s");
-  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows_pinned: workspace_d must be 8-byte aligned%s");
-  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) ||
-      ((uintptr_t)pin_lw_d & 3) || ((uintptr_t)pin_x_d & 3) || ((uintptr_t)x_d & 3) || ((uintptr_t)total_d & 7) ||
-      ((uintptr_t)status_d & 7))
-    return gmx_fail("gmx_resample_rows_pinned: a pointer is not aligned to its element%s");
+  const char* who = "gmx_resample_rows_pinned";
+  const gmx_refusal no = gmx_resample_rows_pinned_refusal_(
+      !keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d, rows, n, ld, index_stride,
+      D, x_ld, x_row_stride, !pin_x_d, !x_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {keys_d, 3}, {ancestors_d, 3}, {max_d, 3}, {pin_lw_d, 3}, {pin_x_d, 3}, {x_d, 3},
+                                          {total_d, 7}, {status_d, 7}})) return 1;
   const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
   hipStream_t st = (hipStream_t)stream;
   auto* status = (unsigned long long*)status_d;
-  rows_pin pin;
-  pin.lw = pin_lw_d; pin.x = pin_x_d; pin.x_out = x_d; pin.D = D; pin.x_ld = x_ld; pin.x_row_stride = x_row_stride;
+  const rows_pin pin = rows_pin_of_(pin_lw_d, pin_x_d, x_d, D, x_ld, x_row_stride);
   if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
-#define GMX_ROWS_PINNED(W_)                                                                                            \
-  hipLaunchKernelGGL((k_rows_small_pinned<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
-                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, pin)
-    if (n <= 256) GMX_ROWS_PINNED(1);
-    else if (n <= 512) GMX_ROWS_PINNED(2);
-    else GMX_ROWS_PINNED(4);
-#undef GMX_ROWS_PINNED
-    GMX_HIP(hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(k_rows_pin, dim3(gmx_rows_pin_blocks_(rows, 0), (unsigned)(D + 1)), dim3(GMX_ROWS_BLOCK), 0, st, lw_d,
-                     rows, n, ld, pin, (const float*)nullptr, (float*)nullptr, (int64_t)0);
-  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
-  uint64_t* agg = (uint64_t*)workspace_d;
-  uint64_t* cdf = agg + rows * tiles;
-  float* tmax = (float*)(cdf + rows * n);
-  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
-    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
-    const dim3 grid((unsigned)tiles, (unsigned)cnt), block(GMX_ROWS_BLOCK);
-    hipLaunchKernelGGL(k_pick_stats, grid, block, 0, st, (const float*)lw_d, n, ld, tiles, row0, scale, tmax, agg);
-    hipLaunchKernelGGL((k_rows_tile<GMX_RESAMPLE_MULTINOMIAL>), grid, block, 0, st, keys_d, (const float*)lw_d, n, ld,
-                       (int)tiles, row0, index_stride, scale, (const float*)tmax, (const uint64_t*)agg, max_d, total_d,
-                       ancestors_d, cdf, status);
-    hipLaunchKernelGGL(k_rows_mn<true>, dim3((unsigned)((n + GMX_ROWS_BLOCK - 1) / GMX_ROWS_BLOCK), (unsigned)cnt), block, 0,
-                       st, keys_d, (const uint64_t*)cdf, n, row0, index_stride, (const uint64_t*)total_d, ancestors_d);
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_small_pinned<decltype(w)::value>), grid, dim3(GMX_ROWS_BLOCK), 0, st, keys_d, lw_d, rows, n, ld,
+                         index_stride, scale, max_d, total_d, ancestors_d, status, pin);
+    });
+  } else {
+    hipLaunchKernelGGL(k_rows_pin, dim3(gmx_rows_pin_blocks_(rows, 0), (unsigned)(D + 1)), dim3(GMX_ROWS_BLOCK), 0, st, lw_d,
+                       rows, n, ld, pin, (const float*)nullptr, (float*)nullptr, (int64_t)0);
+    launch_rows_tiled_<true>(GMX_RESAMPLE_MULTINOMIAL, st, keys_d, lw_d, rows, n, ld, index_stride, scale,
+                             gmx_resample_rows_carve_(workspace_d, GMX_RESAMPLE_MULTINOMIAL, rows, n), max_d, total_d,
+                             ancestors_d, status);
   }
   GMX_HIP(hipGetLastError());
   return 0;
@@ -3680,21 +3687,15 @@ extern "C" int gmx_resample_rows_pinned(const uint32_t* keys_d, float* lw_d, int
 extern "C" int gmx_rows_pin(float* lw_d, int64_t rows, int64_t n, int64_t ld, const float* pin_lw_d, const float* pin_x_d,
                             float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride, const float* next_x_d, float* next_d,
                             int64_t next_ld, gmx_stream stream) {
-  if (!lw_d || !pin_lw_d) return gmx_fail("gmx_rows_pin: null argument%s");
-  const gmx_refusal no = gmx_rows_pin_refusal_(rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr, next_ld);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_rows_pin", no.v);
-  if (D > 0 && !pin_x_d) return gmx_fail("gmx_rows_pin: null argument (pin_x_d with D > 0)%s");
-  if (D > 0 && !x_d) return gmx_fail("gmx_rows_pin: null argument (x_d with D > 0)%s");
-  if (D > 0 && next_x_d && !next_d) return gmx_fail("gmx_rows_pin: null argument (next_d with next_x_d)%s");
-  if (((uintptr_t)lw_d & 3) || ((uintptr_t)pin_lw_d & 3) || ((uintptr_t)pin_x_d & 3) || ((uintptr_t)x_d & 3) ||
-      ((uintptr_t)next_x_d & 3) || ((uintptr_t)next_d & 3))
-    return gmx_fail("gmx_rows_pin: a pointer is not aligned to its element%s");
-  rows_pin pin;
-  pin.lw = pin_lw_d; pin.x = pin_x_d; pin.x_out = x_d; pin.D = D; pin.x_ld = x_ld; pin.x_row_stride = x_row_stride;
+  const char* who = "gmx_rows_pin";
+  const gmx_refusal no = gmx_rows_pin_refusal_(!lw_d || !pin_lw_d, rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr,
+                                               next_ld, !pin_x_d, !x_d, !next_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{lw_d, 3}, {pin_lw_d, 3}, {pin_x_d, 3}, {x_d, 3}, {next_x_d, 3}, {next_d, 3}})) return 1;
   const bool spread = D > 0 && next_x_d != nullptr;
   hipLaunchKernelGGL(k_rows_pin, dim3(gmx_rows_pin_blocks_(rows, spread ? (rows * n + 3) / 4 : 0), (unsigned)(D + 1)),
-                     dim3(GMX_ROWS_BLOCK), 0, (hipStream_t)stream, lw_d, rows, n, ld, pin, spread ? next_x_d : nullptr,
-                     next_d, next_ld);
+                     dim3(GMX_ROWS_BLOCK), 0, (hipStream_t)stream, lw_d, rows, n, ld,
+                     rows_pin_of_(pin_lw_d, pin_x_d, x_d, D, x_ld, x_row_stride), spread ? next_x_d : nullptr, next_d, next_ld);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -3707,42 +3708,30 @@ extern "C" int gmx_resample_rows_as(const uint32_t* keys_d, const float* lw_d, i
                                     int64_t index_stride, const uint32_t* as_keys_d, const float* as_lw_d, int64_t as_ld,
                                     float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
                                     void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("gmx_resample_rows_as: null argument%s");
-  const gmx_refusal no = gmx_resample_rows_as_refusal_(rows, n, ld, index_stride, as_ld);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_as", no.v);
-  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_resample_rows_as: workspace_d must be 8-byte aligned%s");
-  if (((uintptr_t)lw_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)as_lw_d & 3) || ((uintptr_t)as_keys_d & 3) ||
-      ((uintptr_t)ancestors_d & 3) || ((uintptr_t)max_d & 3) || ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
-    return gmx_fail("gmx_resample_rows_as: a pointer is not aligned to its element%s");
+  const char* who = "gmx_resample_rows_as";
+  const gmx_refusal no = gmx_resample_rows_as_refusal_(
+      !keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d, rows, n, ld,
+      index_stride, as_ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {keys_d, 3}, {as_lw_d, 3}, {as_keys_d, 3}, {ancestors_d, 3}, {max_d, 3},
+                                          {total_d, 7}, {status_d, 7}})) return 1;
   const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
   hipStream_t st = (hipStream_t)stream;
   auto* status = (unsigned long long*)status_d;
   if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
     rows_as as;
     as.keys = as_keys_d; as.lw = as_lw_d; as.ld = as_ld; as.status = status + 1;
-#define GMX_ROWS_AS(W_)                                                                                                \
-  hipLaunchKernelGGL((k_rows_small_as<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, st, \
-                     keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, as)
-    if (n <= 256) GMX_ROWS_AS(1);
-    else if (n <= 512) GMX_ROWS_AS(2);
-    else GMX_ROWS_AS(4);
-#undef GMX_ROWS_AS
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_small_as<decltype(w)::value>), grid, dim3(GMX_ROWS_BLOCK), 0, st, keys_d, lw_d, rows, n, ld,
+                         index_stride, scale, max_d, total_d, ancestors_d, status, as);
+    });
     GMX_HIP(hipGetLastError());
     return 0;
   }
   if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
                         status_d, workspace_d, stream)) return 1;
-  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
-  uint64_t* agg = (uint64_t*)((uint8_t*)workspace_d + gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n));
-  float* tmax = (float*)(agg + rows * tiles);
-  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
-    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
-    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, as_lw_d, n, as_ld,
-                       tiles, row0, scale, tmax, agg);
-  }
-  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, as_keys_d, as_lw_d, n, as_ld, tiles, scale,
-                     (const float*)tmax, (const uint64_t*)agg, ancestors_d, n, n - 1, index_stride, status + 1);
+  launch_pick_(st, as_keys_d, as_lw_d, rows, n, as_ld, scale, gmx_resample_rows_as_carve_(workspace_d, rows, n), ancestors_d, n,
+               n - 1, index_stride, status + 1);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -3757,37 +3746,39 @@ extern "C" int gmx_resample_rows_ess(int kind, const uint32_t* keys_d, float* lw
                                      int64_t ld, int64_t index_stride, uint32_t ess_q8, float* max_d, uint64_t* total_d,
                                      int32_t* resampled_d, int32_t* ancestors_d, int64_t* status_d, void* workspace_d,
                                      gmx_stream stream) {
-  if (!keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("gmx_resample_rows_ess: null argument%s");
-  const gmx_refusal no = gmx_resample_rows_ess_refusal_(kind, rows, n, ld, index_stride);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows_ess", no.v);
-  if (((uintptr_t)lw_d & 3) || ((uintptr_t)carry_d & 3) || ((uintptr_t)keys_d & 3) || ((uintptr_t)ancestors_d & 3) ||
-      ((uintptr_t)resampled_d & 3) || ((uintptr_t)max_d & 3) || ((uintptr_t)total_d & 7) || ((uintptr_t)status_d & 7))
-    return gmx_fail("gmx_resample_rows_ess: a pointer is not aligned to its element%s");
+  const char* who = "gmx_resample_rows_ess";
+  const gmx_refusal no = gmx_resample_rows_ess_refusal_(
+      !keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d, kind, rows,
+      n, ld, index_stride);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{lw_d, 3}, {carry_d, 3}, {keys_d, 3}, {ancestors_d, 3}, {resampled_d, 3}, {max_d, 3},
+                                      {total_d, 7}, {status_d, 7}})) return 1;
   const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
   hipStream_t st = (hipStream_t)stream;
   auto* status = (unsigned long long*)status_d;
   rows_ess ess;
   ess.carry = carry_d; ess.ess_q8 = ess_q8; ess.resampled = resampled_d;
-#define GMX_ROWS_ESS2(KIND, W_)                                                                                        \
-  hipLaunchKernelGGL((k_rows_small_ess<KIND, W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, \
-                     st, keys_d, lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, ess)
-#define GMX_ROWS_ESS(KIND)                                                                                             \
-  do {                                                                                                                 \
-    if (n <= 256) GMX_ROWS_ESS2(KIND, 1);                                                                              \
-    else if (n <= 512) GMX_ROWS_ESS2(KIND, 2);                                                                         \
-    else GMX_ROWS_ESS2(KIND, 4);                                                                                       \
-  } while (0)
-  if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_ROWS_ESS(GMX_RESAMPLE_SYSTEMATIC);
-  else if (kind == GMX_RESAMPLE_STRATIFIED) GMX_ROWS_ESS(GMX_RESAMPLE_STRATIFIED);
-  else GMX_ROWS_ESS(GMX_RESAMPLE_MULTINOMIAL);
-#undef GMX_ROWS_ESS
-#undef GMX_ROWS_ESS2
+  rows_for_kind_(kind, [&](auto k) {
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_small_ess<decltype(k)::value, decltype(w)::value>), grid, dim3(GMX_ROWS_BLOCK), 0, st, keys_d,
+                         lw_d, rows, n, ld, index_stride, scale, max_d, total_d, ancestors_d, status, ess);
+    });
+  });
   GMX_HIP(hipGetLastError());
   return 0;
 }
 
 extern "C" size_t gmx_pick_rows_take_workspace(int64_t rows, int64_t n) { return gmx_pick_rows_take_bytes_(rows, n); }
+
+static rows_take rows_take_of_(const float* lw_d, int64_t lw_ld, const float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                               int64_t index_stride, int32_t* idx_out_d, float* lw_out_d, float* x_out_d, float* next_d,
+                               int64_t next_ld) {
+  rows_take tk;
+  tk.lw = lw_d; tk.lw_ld = lw_ld; tk.x = D > 0 ? x_d : nullptr; tk.D = D; tk.x_ld = x_ld; tk.x_row_stride = x_row_stride;
+  tk.index_stride = index_stride; tk.idx_out = idx_out_d; tk.lw_out = lw_out_d; tk.x_out = x_out_d;
+  tk.next = D > 0 ? next_d : nullptr; tk.next_ld = next_ld;
+  return tk;
+}
 
 // gmx_pick_rows, then what it picked taken and handed on (the step of backward simulation): n <= 1024 ONE launch; past it
 // gmx_pick_rows' two kernels writing the offset index, then the gather and the broadcast
@@ -3796,49 +3787,30 @@ extern "C" int gmx_pick_rows_take(const uint32_t* keys_d, const float* logits_d,
                                   int64_t x_row_stride, int64_t index_stride, int32_t* idx_out_d, float* lw_out_d,
                                   float* x_out_d, float* next_d, int64_t next_ld, int64_t* status_d, void* workspace_d,
                                   gmx_stream stream) {
-  if (!keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d)
-    return gmx_fail("gmx_pick_rows_take: null argument%s");
-  const gmx_refusal no = gmx_pick_rows_take_refusal_(rows, n, ld, lw_ld, D, x_ld, x_row_stride, index_stride, next_d != nullptr,
-                                                     next_ld);
-  if (no.fmt) return gmx_fail(no.fmt, "gmx_pick_rows_take", no.v);
-  if (D > 0 && !x_d) return gmx_fail("gmx_pick_rows_take: null argument (x_d with D > 0)%s");
-  if (D > 0 && !x_out_d) return gmx_fail("gmx_pick_rows_take: null argument (x_out_d with D > 0)%s");
-  if ((uintptr_t)workspace_d & 7) return gmx_fail("gmx_pick_rows_take: workspace_d must be 8-byte aligned%s");
-  if (((uintptr_t)keys_d & 3) || ((uintptr_t)logits_d & 3) || ((uintptr_t)lw_d & 3) || ((uintptr_t)x_d & 3) ||
-      ((uintptr_t)idx_out_d & 3) || ((uintptr_t)lw_out_d & 3) || ((uintptr_t)x_out_d & 3) || ((uintptr_t)next_d & 3) ||
-      ((uintptr_t)status_d & 7))
-    return gmx_fail("gmx_pick_rows_take: a pointer is not aligned to its element%s");
+  const char* who = "gmx_pick_rows_take";
+  const gmx_refusal no = gmx_pick_rows_take_refusal_(
+      !keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d, rows, n, ld, lw_ld, D, x_ld,
+      x_row_stride, index_stride, next_d != nullptr, next_ld, !x_d, !x_out_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{keys_d, 3}, {logits_d, 3}, {lw_d, 3}, {x_d, 3}, {idx_out_d, 3}, {lw_out_d, 3},
+                                          {x_out_d, 3}, {next_d, 3}, {status_d, 7}})) return 1;
   const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
   hipStream_t st = (hipStream_t)stream;
   auto* status = (unsigned long long*)status_d;
-  rows_take tk;
-  tk.lw = lw_d; tk.lw_ld = lw_ld; tk.x = D > 0 ? x_d : nullptr; tk.D = D; tk.x_ld = x_ld; tk.x_row_stride = x_row_stride;
-  tk.index_stride = index_stride; tk.idx_out = idx_out_d; tk.lw_out = lw_out_d; tk.x_out = x_out_d;
-  tk.next = D > 0 ? next_d : nullptr; tk.next_ld = next_ld;
+  const rows_take tk = rows_take_of_(lw_d, lw_ld, x_d, D, x_ld, x_row_stride, index_stride, idx_out_d, lw_out_d, x_out_d, next_d,
+                                     next_ld);
   if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
-#define GMX_ROWS_TAKE(W_)                                                                                              \
-  hipLaunchKernelGGL((k_rows_small_take<W_>), dim3((unsigned)((rows + (4 / W_) - 1) / (4 / W_))), dim3(GMX_ROWS_BLOCK), 0, st, \
-                     keys_d, logits_d, rows, n, ld, scale, status, tk)
-    if (n <= 256) GMX_ROWS_TAKE(1);
-    else if (n <= 512) GMX_ROWS_TAKE(2);
-    else GMX_ROWS_TAKE(4);
-#undef GMX_ROWS_TAKE
-    GMX_HIP(hipGetLastError());
-    return 0;
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_small_take<decltype(w)::value>), grid, dim3(GMX_ROWS_BLOCK), 0, st, keys_d, logits_d, rows, n,
+                         ld, scale, status, tk);
+    });
+  } else {
+    launch_pick_(st, keys_d, logits_d, rows, n, ld, scale, gmx_pick_rows_take_carve_(workspace_d, rows, n), idx_out_d, 1, 0,
+                 index_stride, status);
+    const bool spread = tk.next != nullptr;
+    hipLaunchKernelGGL(k_rows_take, dim3(gmx_rows_pin_blocks_(rows, spread ? (rows * n + 3) / 4 : 0), (unsigned)(D + 1)),
+                       dim3(GMX_ROWS_BLOCK), 0, st, rows, n, tk);
   }
-  const int64_t tiles = (n + GMX_PICK_TILE - 1) / GMX_PICK_TILE;
-  uint64_t* agg = (uint64_t*)workspace_d;
-  float* tmax = (float*)(agg + rows * tiles);
-  for (int64_t row0 = 0; row0 < rows; row0 += 65535) {           // (the grid's y extent)
-    const int64_t cnt = rows - row0 < 65535 ? rows - row0 : 65535;
-    hipLaunchKernelGGL(k_pick_stats, dim3((unsigned)tiles, (unsigned)cnt), dim3(GMX_PICK_BLOCK), 0, st, logits_d, n, ld,
-                       tiles, row0, scale, tmax, agg);
-  }
-  hipLaunchKernelGGL(k_pick_row, dim3((unsigned)rows), dim3(GMX_PICK_BLOCK), 0, st, keys_d, logits_d, n, ld, tiles, scale,
-                     (const float*)tmax, (const uint64_t*)agg, idx_out_d, (int64_t)1, (int64_t)0, index_stride, status);
-  const bool spread = tk.next != nullptr;
-  hipLaunchKernelGGL(k_rows_take, dim3(gmx_rows_pin_blocks_(rows, spread ? (rows * n + 3) / 4 : 0), (unsigned)(D + 1)),
-                     dim3(GMX_ROWS_BLOCK), 0, st, rows, n, tk);
   GMX_HIP(hipGetLastError());
   return 0;
 }

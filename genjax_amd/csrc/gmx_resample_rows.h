@@ -53,17 +53,13 @@
 
 // Slot j's ancestor inside ONE ascending run of CDF values cdf[0 .. cnt): the first i whose value passes the slot's
 // threshold, cnt when none does.  systematic / stratified: cdf_i D > P_j = (j 2^23 + u_j) total, D = n 2^23 (k_offspring's
-// predicate); multinomial: cdf_i >= ceil(total (2^23 - u_j) / 2^23) (k_ancestors_mn's integer form).  total >= 1.
+// predicate); multinomial: cdf_i >= pick_threshold(total, u_j) (gmx_backward.h).  total >= 1.
 template <int KIND>
 __device__ __forceinline__ int32_t rows_slot_search(const uint64_t* cdf, int32_t cnt, gmx_key key, uint64_t u0, int64_t j,
                                                     uint64_t total, uint64_t D) {
   int32_t lo = 0, hi = cnt;
   if (KIND == GMX_RESAMPLE_MULTINOMIAL) {
-    const uint64_t u = (uint64_t)(gmx_bits32(key, (uint64_t)j) >> 9);
-    const u128 P = mul64(total, (1ull << 23) - u);                 // >= 1
-    const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
-    const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
-    const uint64_t Thr = (phi << 41) | (plo >> 23);                // ceil(P / 2^23), in [1, total]
+    const uint64_t Thr = pick_threshold(total, (uint64_t)(gmx_bits32(key, (uint64_t)j) >> 9));
     while (lo < hi) {
       const int32_t mid = lo + ((hi - lo) >> 1);
       if (cdf[mid] >= Thr) hi = mid; else lo = mid + 1;
@@ -90,16 +86,7 @@ __device__ __forceinline__ int64_t rows_slots_below(gmx_key key, uint64_t u0, ui
   return lo;
 }
 
-// Four ancestors of consecutive slots base .. base + 3 of a row: one 16-byte store where the address allows
-__device__ __forceinline__ void rows_store4(int32_t* __restrict__ row, int64_t base, int64_t n, const int32_t v[4]) {
-  if (base + 4 <= n && (((uintptr_t)(row + base)) & 15u) == 0u) {
-    *reinterpret_cast<int4*>(row + base) = make_int4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (base + c < n) row[base + c] = v[c];
-  }
-}
+// (four ancestors or four floats of consecutive slots of a row: rows_store4, gmx_backward.h)
 
 // What gmx_resample_rows_pinned adds to a row (conditional SMC: slot n - 1 of every row is the retained particle)
 struct rows_pin {
@@ -129,16 +116,6 @@ __device__ __forceinline__ u128 rows_ess_v2(uint64_t hi, uint64_t lo) {
   r.hi = (hi >> 32) + (r.lo < lo ? 1ull : 0ull);
   return r;
 }
-// Four floats of consecutive columns base .. base + 3 of a row: rows_store4's rule
-__device__ __forceinline__ void rows_store4f(float* row, int64_t base, int64_t n, const float v[4]) {
-  if (base + 4 <= n && (((uintptr_t)(row + base)) & 15u) == 0u) {
-    *reinterpret_cast<float4*>(row + base) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (base + c < n) row[base + c] = v[c];
-  }
-}
 // a row of the matrix as the kernel reads it: nothing else writes it — unless the kernel itself writes into it
 template <bool PIN> struct rows_row_ptr { typedef const float* __restrict__ type; };
 template <> struct rows_row_ptr<true> { typedef const float* type; };
@@ -149,11 +126,9 @@ template <> struct rows_row_ptr<true> { typedef const float* type; };
 // row's maximum is reduced, writes it back into the matrix and answers n - 1 for slot n - 1 whatever the search found; the
 // row's group writes the D pinned state words.  No barrier and no LDS of its own; without PIN nothing of it is compiled.
 // AS (the iid multinomial only, never with PIN): the row's group also holds the row's four-per-thread ancestor logits
-// (loaded with the weights: one wait), reduces their maximum, turns them into fixed point against their own reference and
-// scans them beside the weights — the same three barriers — and counts the columns whose inclusive sum is below the
-// threshold of as.keys[r] at counter 0, which is k_pick_row's answer for a row of one tile (K = k_b, nothing below the
-// tile); the thread that holds slot n - 1 stores that count, clamped, instead of its search.  64 bytes of LDS of its own;
-// without AS nothing of it is compiled.
+// (loaded with the weights: one wait) and runs the three phases of the one-tile pick (pick1_*, gmx_backward.h) on them
+// beside the weights' — the same three barriers; the thread that holds slot n - 1 stores that pick instead of its search.
+// 64 bytes of LDS of its own; without AS nothing of it is compiled.
 // ESS (any kind, never with PIN or AS): the row's group also loads the row of `carry` (with the weights: one wait), adds it
 // — x = lw + carry, ONE float32 add, written back into the matrix — and everything above runs on x.  Each thread truncates
 // its four fixed-point weights to v = w >> (shift - 30) (at most 2^30) and sums v, and v^2 in two halves split at bit 32;
@@ -202,7 +177,7 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
     pick_load4(ess.carry + r * ld, base, n, cy);
 #pragma unroll
     for (int c = 0; c < 4; ++c) x[c] = x[c] + cy[c];
-    if (live) rows_store4f(const_cast<float*>(lw) + r * ld, base, n, x);
+    if (live) rows_store4(const_cast<float*>(lw) + r * ld, base, n, x);
   }
   if (PIN && live) {                                     // the D state words, by the row's thread group
     const int64_t at = r * pin.x_row_stride + n - 1;
@@ -215,25 +190,12 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
       if (base + c == n - 1) x[c] = p;
     if (live) const_cast<float*>(lw)[r * ld + n - 1] = p;
   }
-  const float m = wave_max(gmx_rmax(gmx_rmax(x[0], x[1]), gmx_rmax(x[2], x[3])));
-  if (lane == 0) s_max[wave] = m;
-  if (AS) {
-    const float ma = wave_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])));
-    if (lane == 0) s_amax[wave] = ma;
-  }
+  pick1_put_max(x, s_max, lane, wave);
+  if (AS) pick1_put_max(a, s_amax, lane, wave);
   __syncthreads();
-  float M = s_max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
-  const float ref = gmx_tile_ref(gmx_tile_exp(M));       // one tile: K = k_b, cdf_i = the tile-local inclusive sum
-  uint64_t q[4], run = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    run += (base + c < n) ? weight_fixed(x[c], ref, scale) : 0ull;
-    q[c] = run;
-  }
-  const uint64_t inc = wave_scan_u64(run);
-  if (lane == 63) s_scan[wave] = inc;
+  float M;
+  uint64_t q[4], run;
+  const uint64_t inc = pick1_put_scan<W>(x, base, n, scale, s_max, s_scan, grp, lane, wave, M, q, run);
   if (ESS) {                                             // v = w >> (shift - 30); sum v, sum v^2 (its halves apart), per wave
     const int down = (int)(gmx_f2u(scale) >> 23) - 127 - 30;
     uint64_t v1 = 0, lo2 = 0, hi2 = 0, prev = 0;
@@ -257,52 +219,18 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
   }
   uint64_t qa[4], run_a = 0, inc_a = 0;
   if (AS) {                                              // the ancestor logits: one tile, their own reference
-    float MA = s_amax[grp * W];
-#pragma unroll
-    for (int w = 1; w < W; ++w) MA = gmx_rmax(MA, s_amax[grp * W + w]);
-    const float ref_a = gmx_tile_ref(gmx_tile_exp(MA));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      run_a += (base + c < n) ? weight_fixed(a[c], ref_a, scale) : 0ull;
-      qa[c] = run_a;
-    }
-    inc_a = wave_scan_u64(run_a);
-    if (lane == 63) s_ascan[wave] = inc_a;
+    float MA;
+    inc_a = pick1_put_scan<W>(a, base, n, scale, s_amax, s_ascan, grp, lane, wave, MA, qa, run_a);
   }
   __syncthreads();
-  uint64_t woff = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < W; ++w) {
-    const uint64_t v = s_scan[grp * W + w];
-    total += v;
-    woff += (grp * W + w < wave) ? v : 0ull;
-  }
+  uint64_t woff, total;
+  pick_group_offsets<W>(s_scan, grp, wave, woff, total);
   const uint64_t loc = woff + (inc - run);
   uint64_t* cdf = s_cdf + grp * (GT * 4);
 #pragma unroll
   for (int c = 0; c < 4; ++c) cdf[base + c] = loc + q[c];
   uint64_t total_a = 0;
-  if (AS) {                                              // k_pick_row's count: #{ i : cdf_i < Thr }, Thr from as.keys[r]
-    uint64_t woff_a = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      const uint64_t v = s_ascan[grp * W + w];
-      total_a += v;
-      woff_a += (grp * W + w < wave) ? v : 0ull;
-    }
-    const uint64_t loc_a = woff_a + (inc_a - run_a);
-    gmx_key ka; ka.k0 = as.keys[2 * r]; ka.k1 = as.keys[2 * r + 1];
-    const uint64_t u = (uint64_t)(gmx_bits32(ka, 0ull) >> 9);
-    const u128 P = mul64(total_a, (1ull << 23) - u);
-    const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
-    const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
-    const uint64_t Thr = (phi << 41) | (plo >> 23);                // ceil(P / 2^23), in [1, total_a] (0 without mass)
-    uint64_t lower = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) lower += (base + c < n && loc_a + qa[c] < Thr) ? 1ull : 0ull;
-    lower = wave_sum_u64(lower);
-    if (lane == 0) s_acnt[wave] = (uint32_t)lower;
-  }
+  if (AS) total_a = pick1_put_count<W>(as.keys, r, base, n, qa, run_a, inc_a, s_ascan, s_acnt, grp, lane, wave);
   __syncthreads();
   if (!live) return;                                     // (no barrier follows)
   if (gt == 0) {
@@ -330,11 +258,11 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
       const int32_t first = (int32_t)(r * index_stride) + (int32_t)base;
       const int32_t idn[4] = {first, first + 1, first + 2, first + 3};
       rows_store4(anc + r * n, base, n, idn);
-      rows_store4f(crow, base, n, x);
+      rows_store4(crow, base, n, x);
       return;
     }
     const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    rows_store4f(crow, base, n, zero);
+    rows_store4(crow, base, n, zero);
   }
   gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
   const uint64_t u0 = KIND == GMX_RESAMPLE_SYSTEMATIC ? (uint64_t)(gmx_bits32(key, 0ull) >> 9) : 0ull;
@@ -350,10 +278,7 @@ __device__ __forceinline__ void rows_small_body(const uint32_t* __restrict__ key
     }
     if (PIN && base + c == n - 1) i = (int32_t)n - 1;    // slot n - 1 descends from slot n - 1 (its uniform is its own)
     if (AS && base + c == n - 1) {                       // slot n - 1: the draw from the ancestor logits
-      uint32_t cnt = 0;
-#pragma unroll
-      for (int w = 0; w < W; ++w) cnt += s_acnt[grp * W + w];
-      i = cnt < (uint32_t)n ? (int32_t)cnt : (int32_t)n - 1;
+      i = (int32_t)pick1_index<W>(s_acnt, grp, n);
       if (total_a == 0ull) {                             // no mass: the plain pin, and counted
         i = (int32_t)n - 1;
         atomicAdd(as.status, 1ull);
@@ -402,10 +327,33 @@ k_rows_small_ess(const uint32_t* __restrict__ keys, float* lw, int64_t rows, int
                                                rows_pin{}, rows_as{}, ess);
 }
 
+// One value per row, value_of(r), over every particle of the row in dst[r * n + i], i < n: the threads (g of `step`) stride
+// over the quads of the rows * n particles — four consecutive particles per thread, one store (rows_store4); a quad may
+// span rows (n is arbitrary), the value is read again only where the row changes.
+template <class F>
+__device__ __forceinline__ void rows_spread(float* __restrict__ dst, int64_t rows, int64_t n, int64_t g, int64_t step, F value_of) {
+  const int64_t cols = rows * n, quads = (cols + 3) / 4;
+  for (int64_t qd = g; qd < quads; qd += step) {
+    const int64_t base = qd * 4;
+    int64_t r = base / n, k = base - r * n;              // particle `base` is column k of row r
+    float cur = value_of(r);                             // (base < cols: r < rows)
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      v[c] = cur;
+      if (++k == n) {
+        k = 0; ++r;
+        if (r < rows) cur = value_of(r);
+      }
+    }
+    rows_store4(dst, base, cols, v);
+  }
+}
+
 // The pins into the matrix and the state store (gmx_rows_pin; gmx_resample_rows_pinned past one tile, before the row's
 // statistics are taken).  blockIdx.y: the state word d < D, or (y = D) the weight; the threads of a y stride over the rows.
 // next_x ([D, rows], may be null): state word d of row r also goes to every particle of the row in a second store,
-// next[d * next_ld + r * n + i], i < n — four consecutive particles per thread, one 16-byte store where the address allows.
+// next[d * next_ld + r * n + i], i < n (rows_spread).
 __global__ void __launch_bounds__(GMX_ROWS_BLOCK)
 k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin pin, const float* __restrict__ next_x,
            float* __restrict__ next, int64_t next_ld) {
@@ -418,25 +366,7 @@ k_rows_pin(float* __restrict__ lw, int64_t rows, int64_t n, int64_t ld, rows_pin
   }
   if (next_x == nullptr || d == pin.D) return;
   const float* __restrict__ src = next_x + (int64_t)d * rows;
-  float* __restrict__ dst = next + (int64_t)d * next_ld;
-  const int64_t cols = rows * n, quads = (cols + 3) / 4;
-  for (int64_t qd = g; qd < quads; qd += step) {
-    const int64_t base = qd * 4;
-    int64_t r = base / n, k = base - r * n;              // particle `base` is column k of row r
-    float v[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      v[c] = r < rows ? src[r] : 0.0f;
-      if (++k == n) { k = 0; ++r; }
-    }
-    if (base + 4 <= cols && (((uintptr_t)(dst + base)) & 15u) == 0u) {
-      *reinterpret_cast<float4*>(dst + base) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (base + c < cols) dst[base + c] = v[c];
-    }
-  }
+  rows_spread(next + (int64_t)d * next_ld, rows, n, g, step, [&](int64_t r) { return src[r]; });
 }
 
 // What gmx_pick_rows_take adds to a row's pick (backward simulation: what was picked, taken and handed on)
@@ -455,13 +385,11 @@ struct rows_take {
 };
 
 // gmx_pick_rows_take, n <= 1024: k_rows_small's packing (W waves per row, 4 / W rows per workgroup, thread gt of a row's
-// group holds columns 4 gt .. 4 gt + 3) around the AS branch of rows_small_body on its own: the row's maximum, its
-// fixed-point weights against the row's reference and their scan, and the count of columns whose inclusive sum is below
-// the threshold of keys[r] at counter 0 — k_pick_row's answer for a row of one tile.  Three barriers, 64 bytes of LDS, no
-// CDF in LDS: nothing is searched.  After the third barrier every thread of the group knows k: thread 0 writes the three
-// outputs, every thread reads the one word x[.. + k] per state word (one address per group) and stores its four columns
-// of the broadcast.  Every thread reaches every barrier (a group past the last row works on the last row again and
-// writes nothing).
+// group holds columns 4 gt .. 4 gt + 3) around the one-tile pick (pick1_*, gmx_backward.h) on its own.  Three barriers, 64
+// bytes of LDS, no CDF in LDS: nothing is searched.  After the third barrier every thread of the group knows k: thread 0
+// writes the three outputs, every thread reads the one word x[.. + k] per state word (one address per group) and stores
+// its four columns of the broadcast.  Every thread reaches every barrier (a group past the last row works on the last
+// row again and writes nothing).
 template <int W>
 __global__ void __launch_bounds__(GMX_ROWS_BLOCK)
 k_rows_small_take(const uint32_t* __restrict__ keys, const float* __restrict__ logits, int64_t rows, int64_t n, int64_t ld,
@@ -479,47 +407,16 @@ k_rows_small_take(const uint32_t* __restrict__ keys, const float* __restrict__ l
   const int64_t base = (int64_t)gt * 4;
   float a[4];
   pick_load4(logits + r * ld, base, n, a);
-  const float m = wave_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])));
-  if (lane == 0) s_max[wave] = m;
+  pick1_put_max(a, s_max, lane, wave);
   __syncthreads();
-  float M = s_max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
-  const float ref = gmx_tile_ref(gmx_tile_exp(M));       // one tile: K = k_b, cdf_i = the tile-local inclusive sum
-  uint64_t q[4], run = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    run += (base + c < n) ? weight_fixed(a[c], ref, scale) : 0ull;
-    q[c] = run;
-  }
-  const uint64_t inc = wave_scan_u64(run);
-  if (lane == 63) s_scan[wave] = inc;
+  float M;
+  uint64_t q[4], run;
+  const uint64_t inc = pick1_put_scan<W>(a, base, n, scale, s_max, s_scan, grp, lane, wave, M, q, run);
   __syncthreads();
-  uint64_t woff = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < W; ++w) {
-    const uint64_t v = s_scan[grp * W + w];
-    total += v;
-    woff += (grp * W + w < wave) ? v : 0ull;
-  }
-  const uint64_t loc = woff + (inc - run);
-  gmx_key key; key.k0 = keys[2 * r]; key.k1 = keys[2 * r + 1];
-  const uint64_t u = (uint64_t)(gmx_bits32(key, 0ull) >> 9);
-  const u128 P = mul64(total, (1ull << 23) - u);
-  const uint64_t plo = P.lo + ((1ull << 23) - 1ull);
-  const uint64_t phi = P.hi + (plo < P.lo ? 1ull : 0ull);
-  const uint64_t Thr = (phi << 41) | (plo >> 23);                  // ceil(P / 2^23), in [1, total] (0 without mass)
-  uint64_t lower = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) lower += (base + c < n && loc + q[c] < Thr) ? 1ull : 0ull;
-  lower = wave_sum_u64(lower);
-  if (lane == 0) s_cnt[wave] = (uint32_t)lower;
+  const uint64_t total = pick1_put_count<W>(keys, r, base, n, q, run, inc, s_scan, s_cnt, grp, lane, wave);
   __syncthreads();
   if (!live) return;                                     // (no barrier follows)
-  uint32_t cnt = 0;
-#pragma unroll
-  for (int w = 0; w < W; ++w) cnt += s_cnt[grp * W + w];
-  int64_t k = cnt < (uint32_t)n ? (int64_t)cnt : n - 1;
+  int64_t k = (int64_t)pick1_index<W>(s_cnt, grp, n);
   if (total == 0ull) k = n - 1;                          // no mass at all: the last column, as gmx_pick_rows answers, and counted
   if (gt == 0) {
     if (total == 0ull) atomicAdd(status, 1ull);
@@ -532,7 +429,7 @@ k_rows_small_take(const uint32_t* __restrict__ keys, const float* __restrict__ l
     if (gt == 0) tk.x_out[(int64_t)d * rows + r] = v;
     if (tk.next != nullptr) {
       const float v4[4] = {v, v, v, v};
-      rows_store4f(tk.next + ((int64_t)d * tk.next_ld + r * n), base, n, v4);
+      rows_store4(tk.next + ((int64_t)d * tk.next_ld + r * n), base, n, v4);
     }
   }
 }
@@ -554,29 +451,9 @@ k_rows_take(int64_t rows, int64_t n, rows_take tk) {
   }
   if (tk.next == nullptr || d == tk.D) return;
   const float* __restrict__ src = tk.x + (int64_t)d * tk.x_ld;
-  float* __restrict__ dst = tk.next + (int64_t)d * tk.next_ld;
-  const int64_t cols = rows * n, quads = (cols + 3) / 4;
-  for (int64_t qd = g; qd < quads; qd += step) {
-    const int64_t base = qd * 4;
-    int64_t r = base / n, c_ = base - r * n;             // particle `base` is column c_ of row r
-    float cur = src[r * tk.x_row_stride + (int64_t)(idx[r] - (int32_t)(r * tk.index_stride))];      // (base < cols: r < rows)
-    float v[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      v[c] = cur;
-      if (++c_ == n) {
-        c_ = 0; ++r;
-        if (r < rows) cur = src[r * tk.x_row_stride + (int64_t)(idx[r] - (int32_t)(r * tk.index_stride))];
-      }
-    }
-    if (base + 4 <= cols && (((uintptr_t)(dst + base)) & 15u) == 0u) {
-      *reinterpret_cast<float4*>(dst + base) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (base + c < cols) dst[base + c] = v[c];
-    }
-  }
+  rows_spread(tk.next + (int64_t)d * tk.next_ld, rows, n, g, step, [&](int64_t r) {
+    return src[r * tk.x_row_stride + (int64_t)(idx[r] - (int32_t)(r * tk.index_stride))];
+  });
 }
 
 // n > 1024: blockIdx.x the tile, blockIdx.y the row (row0 + y).  tmax / agg: k_pick_stats' [rows, n_tiles] statistics.
@@ -602,19 +479,13 @@ k_rows_tile(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int
   gmx_tile_prefix_block(tm, agg + r * n_tiles, n_tiles, s_pref, lds4, lds8);
   const int32_t k_b = gmx_tile_exp(tmax_mine);
   const float ref_b = gmx_tile_ref(k_b);
-  uint64_t q[4], run = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    run += (base + c < n) ? weight_fixed(x[c], ref_b, scale) : 0ull;
-    q[c] = run;
-  }
-  const uint64_t inc = wave_scan_u64(run);
+  uint64_t q[4], run;
+  const uint64_t inc = pick_fixed_scan(x, base, n, ref_b, scale, q, run);
   __syncthreads();                                       // s_pref is written; lds8 has been read
   if (lane == 63) lds8[wave] = inc;
   __syncthreads();
-  uint64_t woff = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) woff += (w < wave) ? lds8[w] : 0ull;
+  uint64_t woff, tile_sum;
+  pick_group_offsets<4>(lds8, 0, wave, woff, tile_sum);
   const uint64_t loc = woff + (inc - run);
   const uint64_t prefix = s_pref[b], total = s_pref[n_tiles], mk = s_pref[n_tiles + 1];
   const int32_t K = (int32_t)(uint32_t)(mk >> 32);
@@ -689,9 +560,8 @@ extern "C" __attribute__((used)) inline size_t gmx_resample_rows_workspace(int k
 extern "C" __attribute__((used)) inline int gmx_resample_rows(int kind, const uint32_t* keys_d, const float* lw_d, int64_t rows, int64_t n,
                                         int64_t ld, int64_t index_stride, float* max_d, uint64_t* total_d, int32_t* ancestors_d,
                                         int64_t* status_d, void* workspace_d, gmx_stream stream) {
-  if (!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("%s: null argument", "gmx_resample_rows", 0);
-  const gmx_refusal no = gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
+  const gmx_refusal no = gmx_resample_rows_refusal_(!keys_d || !lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d,
+                                                    kind, rows, n, ld, index_stride);
   if (no.fmt) return gmx_fail(no.fmt, "gmx_resample_rows", no.v);
   const int shift = gmx_pick_rows_shift_(n);
   std::vector<float> row((size_t)n);                             // (the per-row path asks for an aligned row)
@@ -724,13 +594,10 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_pinned(const uint3
                                                int32_t D, int64_t x_ld, int64_t x_row_stride, float* max_d, uint64_t* total_d,
                                                int32_t* ancestors_d, int64_t* status_d, void* workspace_d, gmx_stream stream) {
   const char* who = "gmx_resample_rows_pinned";
-  if (!keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("%s: null argument", who, 0);
-  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
-  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  const gmx_refusal no = gmx_resample_rows_pinned_refusal_(
+      !keys_d || !lw_d || !pin_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d, rows, n, ld, index_stride,
+      D, x_ld, x_row_stride, !pin_x_d, !x_d);
   if (no.fmt) return gmx_fail(no.fmt, who, no.v);
-  if (D > 0 && !pin_x_d) return gmx_fail("%s: null argument (pin_x_d with D > 0)", who, 0);
-  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
   for (int64_t r = 0; r < rows; ++r) {
     lw_d[r * ld + n - 1] = pin_lw_d[r];
     for (int64_t d = 0; d < D; ++d) x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r];
@@ -747,12 +614,9 @@ extern "C" __attribute__((used)) inline int gmx_rows_pin(float* lw_d, int64_t ro
                                    const float* next_x_d, float* next_d, int64_t next_ld, gmx_stream stream) {
   const char* who = "gmx_rows_pin";
   (void)stream;
-  if (!lw_d || !pin_lw_d) return gmx_fail("%s: null argument", who, 0);
-  const gmx_refusal no = gmx_rows_pin_refusal_(rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr, next_ld);
+  const gmx_refusal no = gmx_rows_pin_refusal_(!lw_d || !pin_lw_d, rows, n, ld, D, x_ld, x_row_stride, next_x_d != nullptr,
+                                               next_ld, !pin_x_d, !x_d, !next_d);
   if (no.fmt) return gmx_fail(no.fmt, who, no.v);
-  if (D > 0 && !pin_x_d) return gmx_fail("%s: null argument (pin_x_d with D > 0)", who, 0);
-  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
-  if (D > 0 && next_x_d && !next_d) return gmx_fail("%s: null argument (next_d with next_x_d)", who, 0);
   for (int64_t r = 0; r < rows; ++r) {
     lw_d[r * ld + n - 1] = pin_lw_d[r];
     for (int64_t d = 0; d < D; ++d) x_d[d * x_ld + r * x_row_stride + n - 1] = pin_x_d[d * rows + r];
@@ -773,9 +637,9 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_as(const uint32_t*
                                            float* max_d, uint64_t* total_d, int32_t* ancestors_d, int64_t* status_d,
                                            void* workspace_d, gmx_stream stream) {
   const char* who = "gmx_resample_rows_as";
-  if (!keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("%s: null argument", who, 0);
-  const gmx_refusal no = gmx_resample_rows_as_refusal_(rows, n, ld, index_stride, as_ld);
+  const gmx_refusal no = gmx_resample_rows_as_refusal_(
+      !keys_d || !lw_d || !as_keys_d || !as_lw_d || !max_d || !total_d || !ancestors_d || !status_d || !workspace_d, rows, n, ld,
+      index_stride, as_ld);
   if (no.fmt) return gmx_fail(no.fmt, who, no.v);
   if (gmx_resample_rows(GMX_RESAMPLE_MULTINOMIAL, keys_d, lw_d, rows, n, ld, index_stride, max_d, total_d, ancestors_d,
                         status_d, workspace_d, stream)) return 1;
@@ -796,9 +660,9 @@ extern "C" __attribute__((used)) inline int gmx_resample_rows_ess(int kind, cons
                                             uint64_t* total_d, int32_t* resampled_d, int32_t* ancestors_d, int64_t* status_d,
                                             void* workspace_d, gmx_stream stream) {
   const char* who = "gmx_resample_rows_ess";
-  if (!keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d)
-    return gmx_fail("%s: null argument", who, 0);
-  const gmx_refusal no = gmx_resample_rows_ess_refusal_(kind, rows, n, ld, index_stride);
+  const gmx_refusal no = gmx_resample_rows_ess_refusal_(
+      !keys_d || !lw_d || !carry_d || !max_d || !total_d || !resampled_d || !ancestors_d || !status_d || !workspace_d, kind, rows,
+      n, ld, index_stride);
   if (no.fmt) return gmx_fail(no.fmt, who, no.v);
   for (int64_t r = 0; r < rows; ++r)
     for (int64_t i = 0; i < n; ++i) lw_d[r * ld + i] = lw_d[r * ld + i] + carry_d[r * ld + i];
@@ -834,13 +698,10 @@ extern "C" __attribute__((used)) inline int gmx_pick_rows_take(const uint32_t* k
                                          float* x_out_d, float* next_d, int64_t next_ld, int64_t* status_d, void* workspace_d,
                                          gmx_stream stream) {
   const char* who = "gmx_pick_rows_take";
-  if (!keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d)
-    return gmx_fail("%s: null argument", who, 0);
-  const gmx_refusal no = gmx_pick_rows_take_refusal_(rows, n, ld, lw_ld, D, x_ld, x_row_stride, index_stride, next_d != nullptr,
-                                                     next_ld);
+  const gmx_refusal no = gmx_pick_rows_take_refusal_(
+      !keys_d || !logits_d || !lw_d || !idx_out_d || !lw_out_d || !status_d || !workspace_d, rows, n, ld, lw_ld, D, x_ld,
+      x_row_stride, index_stride, next_d != nullptr, next_ld, !x_d, !x_out_d);
   if (no.fmt) return gmx_fail(no.fmt, who, no.v);
-  if (D > 0 && !x_d) return gmx_fail("%s: null argument (x_d with D > 0)", who, 0);
-  if (D > 0 && !x_out_d) return gmx_fail("%s: null argument (x_out_d with D > 0)", who, 0);
   std::vector<int32_t> k((size_t)rows);
   std::vector<uint64_t> ws((gmx_resample_workspace(n) + 7) / 8 + 2);       // (what the per-row path may ask for)
   if (gmx_pick_rows(keys_d, logits_d, rows, n, ld, k.data(), status_d, ws.data(), stream)) return 1;

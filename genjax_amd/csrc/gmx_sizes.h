@@ -117,15 +117,38 @@ static inline const char* gmx_tile_form_refusal_(gmx_tile_form form, int kind, i
 
 // ---- row-wise draws: gmx_pick_rows, gmx_resample_rows, gmx_resample_rows_pinned, gmx_rows_pin, gmx_resample_rows_as,
 // gmx_resample_rows_ess, gmx_pick_rows_take ----
-// gmx_pick_rows' workspace: agg u64 [rows * tiles], then tmax f32 [rows * tiles]
+// Every refusal below is the entry point's whole argument check but alignment (the HIP build's own): has_null — one of its
+// always-required pointers is null — first, then the shapes, then the pointers a shape makes required (no_*: that pointer
+// is null).
+// The family's workspace: agg u64 [rows * tiles] | cdf u64 [cdf_words] | tmax f32 [rows * tiles], rounded up to 16 bytes.
+// A size and the pointers into it are written from the same two terms.
+struct gmx_rows_ws { uint64_t* agg; uint64_t* cdf; float* tmax; };
+static inline uint64_t gmx_rows_cells_(int64_t rows, int64_t n) { return (uint64_t)rows * (uint64_t)gmx_tiles_(n); }
+static inline uint64_t gmx_rows_cdf_words_(int kind, int64_t rows, int64_t n) {      // the iid multinomial's [rows, n] CDF
+  return kind == GMX_RESAMPLE_MULTINOMIAL ? (uint64_t)rows * (uint64_t)n : 0u;
+}
+static inline size_t gmx_rows_ws_bytes_(uint64_t cells, uint64_t cdf_words) {
+  return (size_t)((cells * 12u + cdf_words * 8u + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_rows_ws gmx_rows_ws_carve_(void* workspace, uint64_t cells, uint64_t cdf_words) {
+  gmx_rows_ws w;
+  w.agg = (uint64_t*)workspace;
+  w.cdf = w.agg + cells;
+  w.tmax = (float*)(w.cdf + cdf_words);
+  return w;
+}
+// gmx_pick_rows' workspace: no cdf
 static inline size_t gmx_pick_rows_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n < 1) return 16;
-  const uint64_t cells = (uint64_t)rows * (uint64_t)gmx_tiles_(n);
-  return (size_t)((cells * 12u + 15u) & ~(uint64_t)15u);
+  return gmx_rows_ws_bytes_(gmx_rows_cells_(rows, n), 0);
+}
+static inline gmx_rows_ws gmx_pick_rows_carve_(void* workspace, int64_t rows, int64_t n) {
+  return gmx_rows_ws_carve_(workspace, gmx_rows_cells_(rows, n), 0);
 }
 // shift = 62 - ceil(log2 n): a sum of n terms <= 2^shift stays below 2^62 (smc.cdf_shift)
 static inline int gmx_pick_rows_shift_(int64_t n) { return 62 - gmx_ceil_log2_(n); }
-static inline gmx_refusal gmx_pick_rows_refusal_(int64_t rows, int64_t n, int64_t ld) {
+static inline gmx_refusal gmx_pick_rows_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld) {
+  if (has_null) return {"%s: null argument", 0};
   if (rows < 1 || rows > 0x7fffffffLL) return {"%s: rows = %lld is outside [1, 2^31)", (long long)rows};
   if (n < 1 || n > 0x7fffffffLL) return {"%s: n = %lld is outside [1, 2^31)", (long long)n};
   if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
@@ -138,15 +161,17 @@ static inline gmx_refusal gmx_index_stride_refusal_(int64_t rows, int64_t n, int
     return {"%s: index_stride = %lld does not keep rows * index_stride below 2^31", (long long)index_stride};
   return {nullptr, 0};
 }
-// gmx_resample_rows' workspace: agg u64 [rows * tiles] | cdf u64 [rows * n] (iid multinomial only) | tmax f32 [rows * tiles];
-// nothing for n <= 1024
+// gmx_resample_rows' workspace: the cdf for the iid multinomial only; nothing for n <= 1024
 static inline size_t gmx_resample_rows_bytes_(int kind, int64_t rows, int64_t n) {
   if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
-  const uint64_t cells = (uint64_t)rows * (uint64_t)gmx_tiles_(n);
-  const uint64_t cdf = kind == GMX_RESAMPLE_MULTINOMIAL ? (uint64_t)rows * (uint64_t)n * 8u : 0u;
-  return (size_t)((cells * 12u + cdf + 15u) & ~(uint64_t)15u);
+  return gmx_rows_ws_bytes_(gmx_rows_cells_(rows, n), gmx_rows_cdf_words_(kind, rows, n));
 }
-static inline gmx_refusal gmx_resample_rows_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
+static inline gmx_rows_ws gmx_resample_rows_carve_(void* workspace, int kind, int64_t rows, int64_t n) {
+  return gmx_rows_ws_carve_(workspace, gmx_rows_cells_(rows, n), gmx_rows_cdf_words_(kind, rows, n));
+}
+static inline gmx_refusal gmx_resample_rows_refusal_(bool has_null, int kind, int64_t rows, int64_t n, int64_t ld,
+                                                     int64_t index_stride) {
+  if (has_null) return {"%s: null argument", 0};
   if (kind == GMX_RESAMPLE_MULTINOMIAL_TILED || kind == GMX_RESAMPLE_MULTINOMIAL_SORTED)
     return {"%s: GMX_RESAMPLE_MULTINOMIAL_TILED and GMX_RESAMPLE_MULTINOMIAL_SORTED have no row form (systematic, stratified "
             "or multinomial)", 0};
@@ -156,8 +181,7 @@ static inline gmx_refusal gmx_resample_rows_refusal_(int kind, int64_t rows, int
   if (n < 1 || n > GMX_ROWS_MAX_N) return {"%s: n = %lld is outside [1, 2^21]", (long long)n};
   return gmx_index_stride_refusal_(rows, n, index_stride);
 }
-// gmx_resample_rows_pinned's own arguments (after the above): D, and x_ld / x_row_stride keeping column n - 1 of every
-// row inside a [D, x_ld] store
+// a pin's own arguments: D, and x_ld / x_row_stride keeping column n - 1 of every row inside a [D, x_ld] store
 static inline gmx_refusal gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n, int32_t D, int64_t x_ld, int64_t x_row_stride) {
   if (D < 0 || D > GMX_ROWS_PIN_MAX_D) return {"%s: D = %lld is outside [0, 65533]", (long long)D};
   if (D == 0) return {nullptr, 0};
@@ -167,20 +191,36 @@ static inline gmx_refusal gmx_resample_rows_pin_refusal_(int64_t rows, int64_t n
     return {"%s: x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)x_ld};
   return {nullptr, 0};
 }
-// gmx_rows_pin: the matrix's shape (gmx_resample_rows' rule for rows, n and ld), the pin's arguments as above, and — with a
-// broadcast — next_ld holding the rows * n particles of a row of the [D, next_ld] leaf
-static inline gmx_refusal gmx_rows_pin_refusal_(int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld, int64_t x_row_stride,
-                                                bool has_next, int64_t next_ld) {
-  gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, 0);
+// gmx_resample_rows_pinned: gmx_resample_rows' arguments (the iid multinomial), the pin's, and the pin's two stores with D > 0
+static inline gmx_refusal gmx_resample_rows_pinned_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int64_t index_stride,
+                                                            int32_t D, int64_t x_ld, int64_t x_row_stride, bool no_pin_x,
+                                                            bool no_x) {
+  gmx_refusal no = gmx_resample_rows_refusal_(has_null, GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
+  if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return no;
+  if (D > 0 && no_pin_x) return {"%s: null argument (pin_x_d with D > 0)", 0};
+  if (D > 0 && no_x) return {"%s: null argument (x_d with D > 0)", 0};
+  return {nullptr, 0};
+}
+// gmx_rows_pin: the above without an index_stride, and — with a broadcast — next_ld holding the rows * n particles of a row
+// of the [D, next_ld] leaf
+static inline gmx_refusal gmx_rows_pin_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                int64_t x_row_stride, bool has_next, int64_t next_ld, bool no_pin_x, bool no_x,
+                                                bool no_next) {
+  gmx_refusal no = gmx_resample_rows_refusal_(has_null, GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, 0);
   if (!no.fmt) no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
   if (no.fmt) return no;
   if (has_next && D > 0 && (next_ld < rows * n || next_ld >= (1LL << 46)))
     return {"%s: next_ld = %lld does not hold rows * n columns (or is 2^46 or more)", (long long)next_ld};
+  if (D > 0 && no_pin_x) return {"%s: null argument (pin_x_d with D > 0)", 0};
+  if (D > 0 && no_x) return {"%s: null argument (x_d with D > 0)", 0};
+  if (D > 0 && has_next && no_next) return {"%s: null argument (next_d with next_x_d)", 0};
   return {nullptr, 0};
 }
 // gmx_resample_rows_as: gmx_resample_rows' arguments (the iid multinomial) and the ancestor logits' row stride
-static inline gmx_refusal gmx_resample_rows_as_refusal_(int64_t rows, int64_t n, int64_t ld, int64_t index_stride, int64_t as_ld) {
-  const gmx_refusal no = gmx_resample_rows_refusal_(GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
+static inline gmx_refusal gmx_resample_rows_as_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int64_t index_stride,
+                                                        int64_t as_ld) {
+  const gmx_refusal no = gmx_resample_rows_refusal_(has_null, GMX_RESAMPLE_MULTINOMIAL, rows, n, ld, index_stride);
   if (no.fmt) return no;
   if (as_ld < n) return {"%s: as_ld = %lld is smaller than n", (long long)as_ld};
   return {nullptr, 0};
@@ -190,11 +230,16 @@ static inline size_t gmx_resample_rows_as_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N) return 16;
   return gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n) + gmx_pick_rows_bytes_(rows, n);
 }
+// (its second part: the first is gmx_resample_rows_carve_'s)
+static inline gmx_rows_ws gmx_resample_rows_as_carve_(void* workspace, int64_t rows, int64_t n) {
+  return gmx_pick_rows_carve_((uint8_t*)workspace + gmx_resample_rows_bytes_(GMX_RESAMPLE_MULTINOMIAL, rows, n), rows, n);
+}
 // gmx_pick_rows_take: gmx_pick_rows' matrix, the weights' row stride, the store gmx_rows_pin writes into (here: read), the
-// index_stride rule of gmx_resample_rows and — with a broadcast — gmx_rows_pin's next_ld
-static inline gmx_refusal gmx_pick_rows_take_refusal_(int64_t rows, int64_t n, int64_t ld, int64_t lw_ld, int32_t D, int64_t x_ld,
-                                                      int64_t x_row_stride, int64_t index_stride, bool has_next, int64_t next_ld) {
-  gmx_refusal no = gmx_pick_rows_refusal_(rows, n, ld);
+// index_stride rule of gmx_resample_rows, — with a broadcast — gmx_rows_pin's next_ld, and the two stores with D > 0
+static inline gmx_refusal gmx_pick_rows_take_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int64_t lw_ld, int32_t D,
+                                                      int64_t x_ld, int64_t x_row_stride, int64_t index_stride, bool has_next,
+                                                      int64_t next_ld, bool no_x, bool no_x_out) {
+  gmx_refusal no = gmx_pick_rows_refusal_(has_null, rows, n, ld);
   if (no.fmt) return no;
   if (lw_ld < n) return {"%s: lw_ld = %lld is smaller than n", (long long)lw_ld};
   no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
@@ -202,6 +247,8 @@ static inline gmx_refusal gmx_pick_rows_take_refusal_(int64_t rows, int64_t n, i
   if (no.fmt) return no;
   if (has_next && D > 0 && (next_ld / rows < n || next_ld >= (1LL << 46)))             // (rows * n may pass 2^63)
     return {"%s: next_ld = %lld does not hold rows * n columns (or is 2^46 or more)", (long long)next_ld};
+  if (D > 0 && no_x) return {"%s: null argument (x_d with D > 0)", 0};
+  if (D > 0 && no_x_out) return {"%s: null argument (x_out_d with D > 0)", 0};
   return {nullptr, 0};
 }
 // gmx_pick_rows_take's workspace: nothing for n <= 1024 (one launch); past it gmx_pick_rows' (the gathering launch reads the
@@ -210,12 +257,16 @@ static inline size_t gmx_pick_rows_take_bytes_(int64_t rows, int64_t n) {
   if (rows < 1 || n <= GMX_TILE) return 16;
   return gmx_pick_rows_bytes_(rows, n);
 }
+static inline gmx_rows_ws gmx_pick_rows_take_carve_(void* workspace, int64_t rows, int64_t n) {
+  return gmx_pick_rows_carve_(workspace, rows, n);
+}
 // gmx_resample_rows_ess: gmx_resample_rows' arguments, for rows of ONE tile — the decision is taken on the row's per-element
 // fixed-point weights, which past one tile are not the same integers (each tile has its own exponent), and it would have
 // to be known before any tile's ancestors are written: a launch boundary
-static inline gmx_refusal gmx_resample_rows_ess_refusal_(int kind, int64_t rows, int64_t n, int64_t ld, int64_t index_stride) {
-  if (n >= 1 && n <= GMX_TILE) return gmx_resample_rows_refusal_(kind, rows, n, ld, index_stride);
-  const gmx_refusal no = gmx_resample_rows_refusal_(kind, 1, 1, 1, 0);                      // the kinds, in its words
+static inline gmx_refusal gmx_resample_rows_ess_refusal_(bool has_null, int kind, int64_t rows, int64_t n, int64_t ld,
+                                                         int64_t index_stride) {
+  if (has_null || (n >= 1 && n <= GMX_TILE)) return gmx_resample_rows_refusal_(has_null, kind, rows, n, ld, index_stride);
+  const gmx_refusal no = gmx_resample_rows_refusal_(false, kind, 1, 1, 1, 0);               // the kinds, in its words
   if (no.fmt) return no;
   return {"%s: n = %lld is outside [1, 1024]: the ESS decision is taken on the fixed-point weights of a row of one tile "
           "(past one tile they are not the same integers, and the decision would need a launch of its own)", (long long)n};

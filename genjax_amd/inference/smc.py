@@ -745,6 +745,19 @@ ROWS_N_MAX = FUSED_RESAMPLE_MAX
 ROWS_ESS_N_MAX = 1024                  # gmx_resample_rows_ess: a row of one CDF tile
 
 
+def _rows_buffers(be, kind, lw, out, workspace):
+    """the out= / workspace= defaults of resample_rows and resample_rows_pinned: fresh (anc, total, max, status) with
+    status zeroed, and a fresh workspace of gmx_resample_rows_workspace(kind) bytes"""
+    R, n = lw.shape
+    if out is None:
+        out = (torch.empty((R, n), dtype=torch.int32, device=lw.device), torch.empty((R,), dtype=torch.int64, device=lw.device),
+               torch.empty((R,), dtype=torch.float32, device=lw.device), torch.zeros((1,), dtype=torch.int64, device=lw.device))
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(int(kind), R, n)) + 7) // 8,), dtype=torch.int64,
+                                device=lw.device)
+    return out, workspace
+
+
 def resample_rows(kind, keys: Key, lw: torch.Tensor, index_stride: int = 0, *, out=None, workspace=None):
     """gmx_resample_rows: R independent rows in one call.  lw [R, n] float32 (contiguous), keys of shape (R,) ->
     (ancestors int32 [R, n] — row-local, or into the flat [R * n] store with index_stride = n —, total [R], max [R],
@@ -753,16 +766,7 @@ def resample_rows(kind, keys: Key, lw: torch.Tensor, index_stride: int = 0, *, o
     be = _lib.get()
     R, n = lw.shape
     kd = keys if isinstance(keys, torch.Tensor) else keys.data()
-    if out is None:
-        anc = torch.empty((R, n), dtype=torch.int32, device=lw.device)
-        total = torch.empty((R,), dtype=torch.int64, device=lw.device)
-        mx = torch.empty((R,), dtype=torch.float32, device=lw.device)
-        status = torch.zeros((1,), dtype=torch.int64, device=lw.device)
-    else:
-        anc, total, mx, status = out
-    if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(int(kind), R, n)) + 7) // 8,), dtype=torch.int64,
-                                device=lw.device)
+    (anc, total, mx, status), workspace = _rows_buffers(be, kind, lw, out, workspace)
     be.check(be.c.gmx_resample_rows(int(kind), be.ptr(kd), be.ptr(lw), R, n, n, int(index_stride), be.ptr(mx), be.ptr(total),
                                     be.ptr(anc), be.ptr(status), be.ptr(workspace), be.stream()), "gmx_resample_rows")
     return anc, total, mx, cdf_shift(n), status
@@ -785,16 +789,7 @@ def resample_rows_pinned(keys: Key, lw: torch.Tensor, pin_lw: torch.Tensor, pin_
         raise ValueError(f"resample_rows_pinned: pin_x is [D, R] = {(D, R)} for a store of {D} rows; got {tuple(pin_x.shape)}")
     if tuple(pin_lw.shape) != (R,):
         raise ValueError(f"resample_rows_pinned: pin_lw is [R] = {(R,)}; got {tuple(pin_lw.shape)}")
-    if out is None:
-        anc = torch.empty((R, n), dtype=torch.int32, device=lw.device)
-        total = torch.empty((R,), dtype=torch.int64, device=lw.device)
-        mx = torch.empty((R,), dtype=torch.float32, device=lw.device)
-        status = torch.zeros((1,), dtype=torch.int64, device=lw.device)
-    else:
-        anc, total, mx, status = out
-    if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(MULTINOMIAL, R, n)) + 7) // 8,), dtype=torch.int64,
-                                device=lw.device)
+    (anc, total, mx, status), workspace = _rows_buffers(be, MULTINOMIAL, lw, out, workspace)
     be.check(be.c.gmx_resample_rows_pinned(be.ptr(kd), be.ptr(lw), R, n, n, int(index_stride), be.ptr(pin_lw), be.ptr(pin_x),
                                            be.ptr(x), D, x_ld, n if x_row_stride is None else int(x_row_stride), be.ptr(mx),
                                            be.ptr(total), be.ptr(anc), be.ptr(status), be.ptr(workspace), be.stream()),

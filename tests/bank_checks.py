@@ -128,6 +128,42 @@ def rows_refusal_calls():
     return calls, buf
 
 
+# --- more rows than one launch's grid holds ---------------------------------------------------------------------------------
+CHUNK_ROWS, CHUNK_N = 65537, 1025       # the smallest that reach a second chunk (65535 rows each) on the tiled path
+CHUNK_CALLS = ["systematic", "multinomial", "pick"]
+
+
+def check_rows_chunks(be, which):
+    """row r is row r % 3 of row_case("normal1025") under key r % 3, built on the device by indexing: rows 0, 1 and 2 are
+    the oracle's per-row answer bit for bit, and every row r equals row r % 3 (compared on the device)"""
+    R, n = CHUNK_ROWS, CHUNK_N
+    dev = be.device
+    rows, keys = row_case("normal%d" % n)[:3], row_keys(4)[:3]
+    of = torch.arange(R, device=dev) % 3
+    lw = torch.from_numpy(np.array(rows)).to(dev)[of].contiguous()
+    k_d = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint32).view(np.int32).reshape(3, 2)).to(dev)[of].contiguous()
+    status = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if which == "pick":
+        out = torch.full((R,), -7, dtype=torch.int32, device=dev)
+        ws = torch.empty(((be.c.gmx_pick_rows_workspace(R, n) + 7) // 8,), dtype=torch.int64, device=dev)
+        rc = be.c.gmx_pick_rows(be.ptr(k_d), be.ptr(lw), R, n, n, be.ptr(out), be.ptr(status), be.ptr(ws), be.stream())
+        assert rc == 0, be.c.gmx_last_error()
+        assert out[:3].cpu().tolist() == [B.oracle_pick(rows[r], keys[r]) for r in range(3)]
+    else:
+        kind = ROW_KINDS[which]
+        out = torch.full((R, n), -7, dtype=torch.int32, device=dev)
+        mx = torch.full((R,), 7.0, dtype=torch.float32, device=dev)
+        total = torch.full((R,), -7, dtype=torch.int64, device=dev)
+        ws = torch.empty(((be.c.gmx_resample_rows_workspace(kind, R, n) + 7) // 8,), dtype=torch.int64, device=dev)
+        rc = be.c.gmx_resample_rows(kind, be.ptr(k_d), be.ptr(lw), R, n, n, 0, be.ptr(mx), be.ptr(total), be.ptr(out),
+                                    be.ptr(status), be.ptr(ws), be.stream())
+        assert rc == 0, be.c.gmx_last_error()
+        got = (out[:3].cpu().numpy(), mx[:3].cpu().numpy(), [int(v) & 0xFFFFFFFFFFFFFFFF for v in total[:3].cpu().tolist()], 0)
+        assert_rows_equal(got, oracle_rows(which, "normal%d" % n)[:3], 0, n, (which, "chunks"))
+    assert int(status.item()) == 0
+    assert torch.equal(out, out[:3][of]), (which, "a row differs from row r % 3")
+
+
 # --- smc.resample on a batched collection -----------------------------------------------------------------------------------
 BATCH_R, BATCH_N = 3, 1500
 

@@ -76,6 +76,12 @@ def test_resample_rows_offsets_past_two_to_the_31(gpu):
     K.assert_rows_equal(got, K.oracle_rows("systematic", "normal1025")[:rows], 0, n, "past 2^31")
 
 
+@pytest.mark.parametrize("which", K.CHUNK_CALLS)
+def test_rows_past_one_grid_of_65535_rows(gpu, which):
+    """rows = 65537, n = 1025: the launches over (tile, row) go out in two chunks of rows; every row is one of three"""
+    K.check_rows_chunks(gpu, which)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_resample_batched_equals_the_one_dimensional_calls(gpu, kind):
     K.check_resample_batched(gpu, kind)
