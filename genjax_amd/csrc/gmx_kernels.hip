@@ -55,6 +55,11 @@ extern "C" void gmx_threefry2x32_host(uint32_t k0, uint32_t k1, uint32_t c0, uin
                                       uint32_t out[2]) {
   gmx_threefry2x32(k0, k1, c0, c1, &out[0], &out[1]);
 }
+// bits32(key, 0) >> 9 on the host, a kernel argument: the one uniform of a systematic resampling (slot 0's of a stratified)
+static uint32_t host_u0_(uint32_t k0, uint32_t k1) {
+  gmx_key k; k.k0 = k0; k.k1 = k1;
+  return gmx_bits32(k, 0) >> 9;
+}
 
 // ---------------------------------------------------------------------------
 // site-program interpreter
@@ -698,7 +703,6 @@ extern "C" int64_t gmx_program_grid(const gmx_program* p, int64_t n) {
   return (n + per - 1) / per;
 }
 
-static int peer_check(const char* who, const gmx_peer& P, int64_t n_per_rank);
 extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_args* args,
                                gmx_stream stream) {
   if (!p || !args) return gmx_fail("gmx_program_run: null argument%s");
@@ -750,7 +754,7 @@ extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_ar
       return gmx_fail("gmx_program_run: sh has a null pointer%s");
     if (((uintptr_t)q.lw_d & 15) || ((uintptr_t)q.stats_own_d & 7))
       return gmx_fail("gmx_program_run: sh.lw_d must be 16-byte and sh.stats_own_d 8-byte aligned%s");
-    if (peer_check("gmx_program_run (sh)", q.peer, n)) return 1;
+    if (const char* m = gmx_peer_check_(q.peer, n)) return gmx_fail(m, "gmx_program_run (sh)");
     if (q.peer.world > 8 || (int64_t)q.peer.world * q.peer.tiles > 4 * GMX_BLOCK)
       return gmx_fail("gmx_program_run: sh: world <= 8 and world * tiles <= 1024%s");
     if (n + (int64_t)q.peer.world * q.peer.capacity > (int64_t)GMX_ANC_INDEX_MASK + 1)
@@ -792,16 +796,8 @@ extern "C" int gmx_program_run(const gmx_program* p, int64_t n, const gmx_run_ar
   if (p->n_const || fused_rs || fused_sh) {
     patched = *args;
     for (uint32_t k = 0; k < p->n_const; ++k) patched.uni[p->n_dyn + k] = p->consts[k];
-    if (fused_rs) {
-      uint32_t b0, b1;
-      gmx_threefry2x32(patched.rs.key0, patched.rs.key1, 0u, 0u, &b0, &b1);     // bits32(key, 0) on the host
-      patched.rs.u0 = (b0 ^ b1) >> 9;
-    }
-    if (fused_sh) {
-      uint32_t b0, b1;
-      gmx_threefry2x32(patched.sh.key0, patched.sh.key1, 0u, 0u, &b0, &b1);
-      patched.sh.u0 = (b0 ^ b1) >> 9;
-    }
+    if (fused_rs) patched.rs.u0 = host_u0_(patched.rs.key0, patched.rs.key1);
+    if (fused_sh) patched.sh.u0 = host_u0_(patched.sh.key0, patched.sh.key1);
     args = &patched;
   }
   if (p->jit_fn) {
@@ -1756,34 +1752,38 @@ k_offspring_tile(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __rest
   gmx_offspring_tile_body<kind, PER, false>(k0, k1, u0_host, lw, tmax, agg, n, n_tiles, scale, max_out, total_out, anc, uslot, 0u);
 }
 
+// f(PER as a constant): the rows of the <= 2048-row tile table a thread of a `block`-thread workgroup holds — 1, 2, 4 or 8
+// by tile count
+template <class F>
+static void tiles_for_per_(int64_t tiles, int block, F f) {
+  if (tiles <= 1 * block) f(std::integral_constant<int, 1>{});
+  else if (tiles <= 2 * block) f(std::integral_constant<int, 2>{});
+  else if (tiles <= 4 * block) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
+}
+// f(kind as a constant), kind one of k_offspring_tile's three (checked by the refusals; anything else: stratified)
+template <class F>
+static void offspring_for_kind_(int kind, F f) {
+  if (kind == GMX_RESAMPLE_SYSTEMATIC) f(std::integral_constant<int, GMX_RESAMPLE_SYSTEMATIC>{});
+  else if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED) f(std::integral_constant<int, GMX_RESAMPLE_MULTINOMIAL_SORTED>{});
+  else f(std::integral_constant<int, GMX_RESAMPLE_STRATIFIED>{});
+}
+
 static int launch_offspring_tile(int kind, const uint32_t key[2], const float* lw_d, int64_t n, int shift,
                                  const float* tile_max_d, const uint64_t* tile_agg_d, float* max_d, uint64_t* total_d,
                                  int32_t* ancestors_d, gmx_stream stream, bool pref = false, const uint32_t* u_d = nullptr) {
-  uint32_t b0, b1;
-  gmx_threefry2x32(key[0], key[1], 0u, 0u, &b0, &b1);           // bits32(key, 0) on the host
-  const uint32_t u0 = (b0 ^ b1) >> 9;
+  const uint32_t u0 = host_u0_(key[0], key[1]);
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
   const dim3 grid((unsigned)((tiles + RS_TPB - 1) / RS_TPB)), block(RS_BLOCK);
-  hipStream_t st = (hipStream_t)stream;
   const float scale = gmx_pow2i(shift);
-#define GMX_LAUNCH_OT2(KIND, PER_)                                                                                   \
-  hipLaunchKernelGGL((k_offspring_tile<KIND, PER_>), grid, block, 0, st, key[0], key[1], u0, lw_d, tile_max_d,        \
-                     tile_agg_d, n, (int)tiles, scale, max_d, total_d, ancestors_d, u_d)
-#define GMX_LAUNCH_OT(KIND)                                                                                         \
-  do {                                                                                                              \
-    if (pref) GMX_LAUNCH_OT2(KIND, 0);          /* `tile_agg_d` is the prefix block gmx_tile_prefix wrote */         \
-    else if (tiles <= 1 * RS_BLOCK) GMX_LAUNCH_OT2(KIND, 1);                                                        \
-    else if (tiles <= 2 * RS_BLOCK) GMX_LAUNCH_OT2(KIND, 2);                                                        \
-    else if (tiles <= 4 * RS_BLOCK) GMX_LAUNCH_OT2(KIND, 4);                                                        \
-    else GMX_LAUNCH_OT2(KIND, 8);                                                                                   \
-  } while (0)
-  if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_LAUNCH_OT(GMX_RESAMPLE_SYSTEMATIC);
-  else if (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED) {        // from the log-weights, the 977-fold statistics pass
-    GMX_LAUNCH_OT(GMX_RESAMPLE_MULTINOMIAL_SORTED);
-  }
-  else GMX_LAUNCH_OT(GMX_RESAMPLE_STRATIFIED);
-#undef GMX_LAUNCH_OT
-#undef GMX_LAUNCH_OT2
+  auto launch = [&](auto k, auto per) {
+    hipLaunchKernelGGL((k_offspring_tile<decltype(k)::value, decltype(per)::value>), grid, block, 0, (hipStream_t)stream, key[0],
+                       key[1], u0, lw_d, tile_max_d, tile_agg_d, n, (int)tiles, scale, max_d, total_d, ancestors_d, u_d);
+  };
+  offspring_for_kind_(kind, [&](auto k) {
+    if (pref) launch(k, std::integral_constant<int, 0>{});      // PER = 0: `tile_agg_d` is the prefix block gmx_tile_prefix wrote
+    else tiles_for_per_(tiles, RS_BLOCK, [&](auto per) { launch(k, per); });
+  });
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -2149,14 +2149,10 @@ extern "C" int gmx_multinomial_tiled(const uint32_t key[2], const float* lw_d, i
   hipLaunchKernelGGL(k_mn_hist, dim3(hb), dim3(GMX_BLOCK), 0, st, k1[0], k1[1], tile_max_d, tile_agg_d, n, (int)tiles, u_d,
                      max_d, total_d, counts);
   const float scale = gmx_pow2i(shift);
-#define GMX_LAUNCH_MT(PER_)                                                                                          \
-  hipLaunchKernelGGL((k_mn_tile<PER_>), dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, st, k2[0], k2[1], lw_d, tile_max_d,  \
-                     tile_agg_d, n, (int)tiles, scale, (const uint32_t*)counts, other, ancestors_d)
-  if (tiles <= 1 * GMX_BLOCK) GMX_LAUNCH_MT(1);
-  else if (tiles <= 2 * GMX_BLOCK) GMX_LAUNCH_MT(2);
-  else if (tiles <= 4 * GMX_BLOCK) GMX_LAUNCH_MT(4);
-  else GMX_LAUNCH_MT(8);
-#undef GMX_LAUNCH_MT
+  tiles_for_per_(tiles, GMX_BLOCK, [&](auto per) {
+    hipLaunchKernelGGL((k_mn_tile<decltype(per)::value>), dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, st, k2[0], k2[1], lw_d,
+                       tile_max_d, tile_agg_d, n, (int)tiles, scale, (const uint32_t*)counts, other, ancestors_d);
+  });
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -2493,14 +2489,9 @@ extern "C" int gmx_tile_prefix(const float* tile_max_d, const uint64_t* tile_agg
                                gmx_stream stream) {
   if (n <= 0 || n > 0x7fffffffLL) return gmx_fail("gmx_tile_prefix: n out of range%s");
   if (!tile_max_d || !tile_agg_d || !tile_pref_d) return gmx_fail("gmx_tile_prefix: null argument%s");
-  if ((n + RS_TILE - 1) / RS_TILE > RS_MAX_TILES) {
-    hipLaunchKernelGGL(k_tile_prefix_big, dim3(1), dim3(GMX_BLOCK), 0, (hipStream_t)stream, tile_max_d, tile_agg_d,
-                       (int)((n + RS_TILE - 1) / RS_TILE), tile_pref_d);
-    GMX_HIP(hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(GMX_BLOCK), 0, (hipStream_t)stream, tile_max_d, tile_agg_d,
-                     (int)((n + RS_TILE - 1) / RS_TILE), tile_pref_d);
+  const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
+  hipLaunchKernelGGL(tiles > RS_MAX_TILES ? k_tile_prefix_big : k_tile_prefix, dim3(1), dim3(GMX_BLOCK), 0, (hipStream_t)stream,
+                     tile_max_d, tile_agg_d, (int)tiles, tile_pref_d);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -2822,38 +2813,40 @@ k_shard_step(int kind, uint32_t k0, uint32_t k1, const uint64_t* __restrict__ to
 
 extern "C" size_t gmx_shard_plan_words(int world) { return gmx_shard_plan_words_(world); }
 
-static int shard_check(const char* who, int kind, const void* key, int rank, int world, int64_t n) {
-  if (!key) return gmx_fail("%s: null key", who);
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED)
-    return gmx_fail("%s: systematic / stratified only (ordered slot thresholds)", who);
-  if (world < 1 || world > 1024 || rank < 0 || rank >= world) return gmx_fail("%s: rank / world out of range", who);
-  if (n <= 0 || n > 0x7fffffffLL || n * world >= (1LL << 40)) return gmx_fail("%s: n_per_rank out of range", who);
+static_assert(SHARD_MAX_WORLD == GMX_SHARD_MAX_WORLD, "the one-launch forms refuse (gmx_sizes.h) the worlds their LDS tables cannot hold");
+
+// k_shard_plan (with totals_d), then k_shard_route against the plan (with cdf_d); sorted_tab: the order-statistics table
+// of the sorted multinomial (the key is unused then), or nullptr
+static int launch_shard_plan_route_(hipStream_t st, int kind, uint32_t k0, uint32_t k1, const uint64_t* totals_d, int64_t* plan_d,
+                                    uint64_t* total_out_d, const uint64_t* cdf_d, int rank, int world, int64_t n_per_rank,
+                                    int64_t capacity, const void* state_d, void* send_d, int32_t* next_idx_d,
+                                    const uint32_t* sorted_tab) {
+  if (totals_d)
+    hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(64), 0, st, kind, k0, k1, totals_d, rank, world, n_per_rank, plan_d,
+                       total_out_d, sorted_tab);
+  if (cdf_d)
+    hipLaunchKernelGGL(k_shard_route, grid_for(n_per_rank), dim3(GMX_BLOCK), 0, st, kind, k0, k1, plan_d, cdf_d, rank, world,
+                       n_per_rank, capacity, (const uint32_t*)state_d, (uint32_t*)send_d, next_idx_d, sorted_tab);
+  GMX_HIP(hipGetLastError());
   return 0;
 }
 
 extern "C" int gmx_shard_plan(int kind, const uint32_t key[2], const uint64_t* totals_d, int rank, int world,
                               int64_t n_per_rank, int64_t* plan_d, uint64_t* total_out_d, gmx_stream stream) {
-  if (shard_check("gmx_shard_plan", kind, key, rank, world, n_per_rank)) return 1;
-  if (!totals_d || !plan_d) return gmx_fail("gmx_shard_plan: null argument%s");
-  hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(64), 0, (hipStream_t)stream, kind, key[0], key[1], totals_d, rank,
-                     world, n_per_rank, plan_d, total_out_d, (const uint32_t*)nullptr);
-  GMX_HIP(hipGetLastError());
-  return 0;
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_PLAN, !key, kind, rank, world, n_per_rank, !totals_d || !plan_d))
+    return gmx_fail(m, "gmx_shard_plan");
+  return launch_shard_plan_route_((hipStream_t)stream, kind, key[0], key[1], totals_d, plan_d, total_out_d, nullptr, rank, world,
+                                  n_per_rank, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" int gmx_shard_route(int kind, const uint32_t key[2], int64_t* plan_d, const uint64_t* cdf_d, int rank,
                                int world, int64_t n_per_rank, int64_t capacity, const void* state_d, void* send_d,
                                int32_t* next_idx_d, gmx_stream stream) {
-  if (shard_check("gmx_shard_route", kind, key, rank, world, n_per_rank)) return 1;
-  if (!plan_d || !cdf_d || !state_d || !send_d || !next_idx_d) return gmx_fail("gmx_shard_route: null argument%s");
-  if (capacity < 1 || capacity > n_per_rank) return gmx_fail("gmx_shard_route: capacity must be in [1, n_per_rank]%s");
-  if (n_per_rank + (int64_t)world * capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_route: extended state index exceeds int32%s");
-  hipLaunchKernelGGL(k_shard_route, grid_for(n_per_rank), dim3(GMX_BLOCK), 0, (hipStream_t)stream, kind, key[0],
-                     key[1], plan_d, cdf_d, rank, world, n_per_rank, capacity, (const uint32_t*)state_d,
-                     (uint32_t*)send_d, next_idx_d, (const uint32_t*)nullptr);
-  GMX_HIP(hipGetLastError());
-  return 0;
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_ROUTE, !key, kind, rank, world, n_per_rank,
+                                              !plan_d || !cdf_d || !state_d || !send_d || !next_idx_d, capacity))
+    return gmx_fail(m, "gmx_shard_route");
+  return launch_shard_plan_route_((hipStream_t)stream, kind, key[0], key[1], nullptr, plan_d, nullptr, cdf_d, rank, world,
+                                  n_per_rank, capacity, state_d, send_d, next_idx_d, nullptr);
 }
 
 // gmx_shard_step for GMX_RESAMPLE_MULTINOMIAL_SORTED (include/genmi.h): plan + route against the order-statistics table
@@ -2862,41 +2855,26 @@ extern "C" int gmx_shard_step_sorted(const uint32_t* table_d, const uint64_t* to
                                      uint64_t* total_out_d, const uint64_t* cdf_d, int rank, int world,
                                      int64_t n_per_rank, int64_t capacity, const void* state_d, void* send_d,
                                      int32_t* next_idx_d, gmx_stream stream) {
-  if (!table_d || !totals_d || !plan_d || !cdf_d || !state_d || !send_d || !next_idx_d)
-    return gmx_fail("gmx_shard_step_sorted: null argument%s");
-  if (world < 1 || world > 1024 || rank < 0 || rank >= world) return gmx_fail("gmx_shard_step_sorted: rank / world out of range%s");
-  if (n_per_rank <= 0 || n_per_rank * world > 0x7fffffffLL) return gmx_fail("gmx_shard_step_sorted: n_per_rank * world out of range (< 2^31)%s");
-  if (capacity < 1 || capacity > n_per_rank) return gmx_fail("gmx_shard_step_sorted: capacity must be in [1, n_per_rank]%s");
-  if (n_per_rank + (int64_t)world * capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_step_sorted: extended state index exceeds int32%s");
-  if ((uintptr_t)table_d & 15) return gmx_fail("gmx_shard_step_sorted: table_d must be 16-byte aligned%s");
-  const int kind = GMX_RESAMPLE_MULTINOMIAL_SORTED;
-  hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(64), 0, (hipStream_t)stream, kind, 0u, 0u, totals_d, rank, world,
-                     n_per_rank, plan_d, total_out_d, table_d);
-  GMX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_shard_route, grid_for(n_per_rank), dim3(GMX_BLOCK), 0, (hipStream_t)stream, kind, 0u, 0u, plan_d,
-                     cdf_d, rank, world, n_per_rank, capacity, (const uint32_t*)state_d, (uint32_t*)send_d, next_idx_d,
-                     table_d);
-  GMX_HIP(hipGetLastError());
-  return 0;
+  if (const char* m = gmx_shard_step_sorted_refusal_(!table_d || !totals_d || !plan_d || !cdf_d || !state_d || !send_d || !next_idx_d,
+                                                     rank, world, n_per_rank, capacity, table_d))
+    return gmx_fail(m, "gmx_shard_step_sorted");
+  return launch_shard_plan_route_((hipStream_t)stream, GMX_RESAMPLE_MULTINOMIAL_SORTED, 0u, 0u, totals_d, plan_d, total_out_d, cdf_d,
+                                  rank, world, n_per_rank, capacity, state_d, send_d, next_idx_d, table_d);
 }
 
 extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* totals_d, int64_t* plan_d,
                               uint64_t* total_out_d, const uint64_t* cdf_d, int rank, int world, int64_t n_per_rank,
                               int64_t capacity, const void* state_d, void* send_d, int32_t* next_idx_d,
                               gmx_stream stream) {
-  if (shard_check("gmx_shard_step", kind, key, rank, world, n_per_rank)) return 1;
-  if (!totals_d || !plan_d || !cdf_d || !state_d || !send_d || !next_idx_d)
-    return gmx_fail("gmx_shard_step: null argument%s");
-  if (capacity < 1 || capacity > n_per_rank) return gmx_fail("gmx_shard_step: capacity must be in [1, n_per_rank]%s");
-  if (n_per_rank + (int64_t)world * capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_step: extended state index exceeds int32%s");
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP, !key, kind, rank, world, n_per_rank,
+                                              !totals_d || !plan_d || !cdf_d || !state_d || !send_d || !next_idx_d, capacity, 1,
+                                              cdf_d))
+    return gmx_fail(m, "gmx_shard_step");
   if (world > SHARD_MAX_WORLD) {          // large worlds: the two-launch form
     if (gmx_shard_plan(kind, key, totals_d, rank, world, n_per_rank, plan_d, total_out_d, stream)) return 1;
     return gmx_shard_route(kind, key, plan_d, cdf_d, rank, world, n_per_rank, capacity, state_d, send_d, next_idx_d,
                            stream);
   }
-  if ((uintptr_t)cdf_d & 15) return gmx_fail("gmx_shard_step: cdf_d must be 16-byte aligned%s");
   shard_tiles none = {nullptr, nullptr, nullptr, nullptr, 0.0f, 0};
   hipLaunchKernelGGL((k_shard_step<false>), grid_for((n_per_rank + 3) / 4), dim3(GMX_BLOCK), 0, (hipStream_t)stream,
                      kind, key[0], key[1], totals_d, plan_d, total_out_d, cdf_d, none, rank, world, n_per_rank,
@@ -2906,8 +2884,8 @@ extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* t
 }
 
 // ---- the same step from tile statistics: no local CDF array, no all-reduce of the max ----
-// Every rank all-gathers its tile statistics (gmx_shard_stats_bytes per rank: agg[tiles_pad] u64 then
-// tmax[tiles_pad] f32, tiles_pad = tiles rounded up to even) — ONE collective carries what the max all-reduce
+// Every rank all-gathers its tile statistics (gmx_shard_stats_bytes per rank; the block's layout and gmx_stats_block_at,
+// which reads it: csrc/gmx_peer.h) — ONE collective carries what the max all-reduce
 // and the totals all-gather carried.  k_shard_totals (one block) turns the gathered table into the global max
 // and every rank's integer total; k_shard_step<true> rebuilds this rank's CDF per tile in registers.
 extern "C" size_t gmx_shard_stats_bytes(int64_t n_per_rank) { return gmx_shard_stats_bytes_(n_per_rank); }
@@ -2918,20 +2896,18 @@ k_shard_totals(const uint8_t* __restrict__ stats_all, int world, int n_tiles, si
   __shared__ float lds4[4];
   __shared__ uint64_t s_sum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tiles_pad = n_tiles + (n_tiles & 1);
   float m = -gmx_inf();
   for (int r = 0; r < world; ++r) {
-    const float* tmax = reinterpret_cast<const float*>(stats_all + (size_t)r * stride + (size_t)tiles_pad * 8);
+    const float* tmax = gmx_stats_block_at(stats_all + (size_t)r * stride, n_tiles).tmax;
     for (int t = (int)threadIdx.x; t < n_tiles; t += GMX_BLOCK) m = gmx_rmax(m, tmax[t]);
   }
   const float M = block_max(m, lds4);
   const int32_t K = gmx_tile_exp(M);
   if (threadIdx.x == 0) *max_out = M;
   for (int r = 0; r < world; ++r) {
-    const uint64_t* agg = reinterpret_cast<const uint64_t*>(stats_all + (size_t)r * stride);
-    const float* tmax = reinterpret_cast<const float*>(stats_all + (size_t)r * stride + (size_t)tiles_pad * 8);
+    const gmx_stats_block blk = gmx_stats_block_at(stats_all + (size_t)r * stride, n_tiles);
     uint64_t sum = 0;
-    for (int t = (int)threadIdx.x; t < n_tiles; t += GMX_BLOCK) sum += gmx_tile_scale(agg[t], gmx_tile_exp(tmax[t]), K);
+    for (int t = (int)threadIdx.x; t < n_tiles; t += GMX_BLOCK) sum += gmx_tile_scale(blk.agg[t], gmx_tile_exp(blk.tmax[t]), K);
     sum = wave_sum_u64(sum);
     __syncthreads();
     if (lane == 0) s_sum[wave] = sum;
@@ -2942,14 +2918,10 @@ k_shard_totals(const uint8_t* __restrict__ stats_all, int world, int n_tiles, si
 
 extern "C" int gmx_shard_totals(const void* stats_all_d, int world, int64_t n_per_rank, uint64_t* totals_d,
                                 float* max_d, gmx_stream stream) {
-  if (!stats_all_d || !totals_d || !max_d) return gmx_fail("gmx_shard_totals: null argument%s");
-  if (world < 1 || world > 1024) return gmx_fail("gmx_shard_totals: world out of range%s");
-  const int64_t tiles = (n_per_rank + RS_TILE - 1) / RS_TILE;
-  // (one workgroup strides over the whole gathered table: any number of tiles — config 4's 1e7 particles on ONE rank are 9766)
-  if (n_per_rank <= 0 || n_per_rank > 0x7fffffffLL) return gmx_fail("gmx_shard_totals: n_per_rank out of range (< 2^31)%s");
-  if ((uintptr_t)stats_all_d & 7) return gmx_fail("gmx_shard_totals: stats_all_d must be 8-byte aligned%s");
+  if (const char* m = gmx_shard_totals_refusal_(!stats_all_d || !totals_d || !max_d, world, n_per_rank, stats_all_d))
+    return gmx_fail(m, "gmx_shard_totals");
   hipLaunchKernelGGL(k_shard_totals, dim3(1), dim3(GMX_BLOCK), 0, (hipStream_t)stream, (const uint8_t*)stats_all_d,
-                     world, (int)tiles, gmx_shard_stats_bytes(n_per_rank), totals_d, max_d);
+                     world, (int)gmx_tiles_(n_per_rank), gmx_shard_stats_bytes(n_per_rank), totals_d, max_d);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -2959,26 +2931,13 @@ extern "C" int gmx_shard_step_tiles(int kind, const uint32_t key[2], const uint6
                                     const float* max_d, int shift, int rank, int world, int64_t n_per_rank,
                                     int64_t capacity, const void* state_d, void* send_d, int32_t* next_idx_d,
                                     gmx_stream stream) {
-  if (shard_check("gmx_shard_step_tiles", kind, key, rank, world, n_per_rank)) return 1;
-  if (!totals_d || !plan_d || !lw_d || !stats_own_d || !max_d || !state_d || !send_d || !next_idx_d)
-    return gmx_fail("gmx_shard_step_tiles: null argument%s");
-  if (capacity < 1 || capacity > n_per_rank)
-    return gmx_fail("gmx_shard_step_tiles: capacity must be in [1, n_per_rank]%s");
-  if (n_per_rank + (int64_t)world * capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_step_tiles: extended state index exceeds int32%s");
-  if (world > SHARD_MAX_WORLD) return gmx_fail("gmx_shard_step_tiles: world <= 64 (use gmx_weight_cdf + gmx_shard_step)%s");
-  if (shift < 1 || shift > 62) return gmx_fail("gmx_shard_step_tiles: shift out of range%s");
-  const int64_t tiles = (n_per_rank + RS_TILE - 1) / RS_TILE;
-  // (k_shard_step<true> sums the mass of its rank's EARLIER tiles by striding over them — no table in registers or LDS —
-  //  so the per-rank size is not bounded by RS_MAX_TILES; the fused / peer forms below hold the table and are)
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)stats_own_d & 7))
-    return gmx_fail("gmx_shard_step_tiles: lw_d must be 16-byte and stats_own_d 8-byte aligned%s");
-  const int64_t tiles_pad = tiles + (tiles & 1);
-  shard_tiles ts;
-  ts.lw = lw_d;
-  ts.agg = (const uint64_t*)stats_own_d;
-  ts.tmax = (const float*)((const uint8_t*)stats_own_d + (size_t)tiles_pad * 8);
-  ts.max_g = max_d; ts.scale = gmx_pow2i(shift); ts.n_tiles = (int)tiles;
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP_TILES, !key, kind, rank, world, n_per_rank,
+                                              !totals_d || !plan_d || !lw_d || !stats_own_d || !max_d || !state_d || !send_d || !next_idx_d,
+                                              capacity, shift, lw_d, stats_own_d))
+    return gmx_fail(m, "gmx_shard_step_tiles");
+  const int64_t tiles = gmx_tiles_(n_per_rank);
+  const gmx_stats_block own = gmx_stats_block_at(stats_own_d, (int)tiles);
+  const shard_tiles ts = {lw_d, own.tmax, own.agg, max_d, gmx_pow2i(shift), (int)tiles};
   hipLaunchKernelGGL((k_shard_step<true>), dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, (hipStream_t)stream, kind, key[0],
                      key[1], totals_d, plan_d, total_out_d, (const uint64_t*)nullptr, ts, rank, world, n_per_rank,
                      capacity, (const uint32_t*)state_d, (uint32_t*)send_d, next_idx_d);
@@ -3013,11 +2972,35 @@ k_shard_step_fill(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __res
                   float* __restrict__ max_out, const uint32_t* __restrict__ state, uint32_t* __restrict__ send,
                   int32_t* __restrict__ next_idx, const shard_peer_args Pa) {
   GMX_SETPRIO
-  shard_peer P;
-  P.land = Pa.land; P.tag_base = Pa.tag_base; P.status = Pa.status; P.step = Pa.step; P.leaves = Pa.leaves;
-  P.state = Pa.state; P.tail = Pa.tail;
   gmx_shard_fill_body<kind, SMALL, PEER, false>(k0, k1, u0_host, lw, stats_all, stride, n_tiles, scale, rank, world, n, cap, plan,
-                                                total_out, max_out, state, send, next_idx, P, 0u);
+                                                total_out, max_out, state, send, next_idx, shard_peer_of(Pa), 0u);
+}
+
+// k_shard_step_fill<kind, SMALL, PEER>, one workgroup per tile of this rank's shard.  SMALL (the comment above the kernel):
+// world <= 8 and the gathered table has <= 1024 rows.  n_per_rank <= 2^21 and world <= 64: slots are 32-bit integers.
+// PEER: `stats` is this rank's own block (stride 0), state / send are the peer block's leaves; else the gathered table.
+template <bool PEER>
+static int launch_shard_fill_(int kind, const uint32_t key[2], const void* stats, size_t stride, int64_t* plan_d,
+                              uint64_t* total_out_d, const float* lw_d, float* max_out_d, int shift, int rank, int world,
+                              int64_t n_per_rank, int64_t capacity, const void* state_d, void* send_d, int32_t* next_idx_d,
+                              const shard_peer_args& peer, gmx_stream stream) {
+  const int64_t tiles = gmx_tiles_(n_per_rank);
+  const uint32_t u0 = host_u0_(key[0], key[1]);
+  const float scale = gmx_pow2i(shift);
+  auto launch = [&](auto k, auto small) {
+    hipLaunchKernelGGL((k_shard_step_fill<decltype(k)::value, decltype(small)::value, PEER>), dim3((unsigned)tiles),
+                       dim3(GMX_BLOCK), 0, (hipStream_t)stream, key[0], key[1], u0, lw_d, (const uint8_t*)stats, stride,
+                       (int)tiles, scale, rank, world, (int32_t)n_per_rank, (int32_t)capacity, plan_d, total_out_d, max_out_d,
+                       (const uint32_t*)state_d, (uint32_t*)send_d, next_idx_d, peer);
+  };
+  auto for_kind = [&](auto small) {
+    if (kind == GMX_RESAMPLE_SYSTEMATIC) launch(std::integral_constant<int, GMX_RESAMPLE_SYSTEMATIC>{}, small);
+    else launch(std::integral_constant<int, GMX_RESAMPLE_STRATIFIED>{}, small);
+  };
+  if (world <= 8 && (int64_t)world * tiles <= 4 * GMX_BLOCK) for_kind(std::true_type{});
+  else for_kind(std::false_type{});
+  GMX_HIP(hipGetLastError());
+  return 0;
 }
 
 // gmx_shard_totals + gmx_shard_step_tiles as ONE launch: straight from the all-gathered statistics table.
@@ -3025,37 +3008,12 @@ extern "C" int gmx_shard_step_fused(int kind, const uint32_t key[2], const void*
                                     uint64_t* total_out_d, const float* lw_d, float* max_out_d, int shift, int rank,
                                     int world, int64_t n_per_rank, int64_t capacity, const void* state_d, void* send_d,
                                     int32_t* next_idx_d, gmx_stream stream) {
-  if (shard_check("gmx_shard_step_fused", kind, key, rank, world, n_per_rank)) return 1;
-  if (!stats_all_d || !plan_d || !lw_d || !max_out_d || !state_d || !send_d || !next_idx_d)
-    return gmx_fail("gmx_shard_step_fused: null argument%s");
-  if (capacity < 1 || capacity > n_per_rank)
-    return gmx_fail("gmx_shard_step_fused: capacity must be in [1, n_per_rank]%s");
-  if (n_per_rank + (int64_t)world * capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_step_fused: extended state index exceeds int32%s");
-  if (world > SHARD_MAX_WORLD) return gmx_fail("gmx_shard_step_fused: world <= 64%s");
-  if (shift < 1 || shift > 62) return gmx_fail("gmx_shard_step_fused: shift out of range%s");
-  const int64_t tiles = (n_per_rank + RS_TILE - 1) / RS_TILE;
-  if (tiles > RS_MAX_TILES) return gmx_fail("gmx_shard_step_fused: n_per_rank too large (<= 2^21)%s");
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)stats_all_d & 7))
-    return gmx_fail("gmx_shard_step_fused: lw_d must be 16-byte and stats_all_d 8-byte aligned%s");
-  const size_t stride = gmx_shard_stats_bytes(n_per_rank);
-  const float scale = gmx_pow2i(shift);
-  // n_per_rank <= 2^21 and world <= 64: slots are 32-bit integers
-  uint32_t b0, b1;
-  gmx_threefry2x32(key[0], key[1], 0u, 0u, &b0, &b1);           // bits32(key, 0) on the host
-  const uint32_t u0 = (b0 ^ b1) >> 9;
-  const bool small = world <= 8 && (int64_t)world * tiles <= 4 * GMX_BLOCK;
-#define GMX_LAUNCH_SF2(KIND, SM)                                                                                      \
-  hipLaunchKernelGGL((k_shard_step_fill<KIND, SM, false>), dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, (hipStream_t)stream, key[0],  \
-                     key[1], u0, lw_d, (const uint8_t*)stats_all_d, stride, (int)tiles, scale, rank, world,           \
-                     (int32_t)n_per_rank, (int32_t)capacity, plan_d, total_out_d, max_out_d, (const uint32_t*)state_d,   \
-                     (uint32_t*)send_d, next_idx_d, shard_peer_args())
-#define GMX_LAUNCH_SF(KIND) do { if (small) GMX_LAUNCH_SF2(KIND, true); else GMX_LAUNCH_SF2(KIND, false); } while (0)
-  if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_LAUNCH_SF(GMX_RESAMPLE_SYSTEMATIC); else GMX_LAUNCH_SF(GMX_RESAMPLE_STRATIFIED);
-#undef GMX_LAUNCH_SF
-#undef GMX_LAUNCH_SF2
-  GMX_HIP(hipGetLastError());
-  return 0;
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP_FUSED, !key, kind, rank, world, n_per_rank,
+                                              !stats_all_d || !plan_d || !lw_d || !max_out_d || !state_d || !send_d || !next_idx_d,
+                                              capacity, shift, lw_d, stats_all_d))
+    return gmx_fail(m, "gmx_shard_step_fused");
+  return launch_shard_fill_<false>(kind, key, stats_all_d, gmx_shard_stats_bytes(n_per_rank), plan_d, total_out_d, lw_d, max_out_d,
+                                   shift, rank, world, n_per_rank, capacity, state_d, send_d, next_idx_d, shard_peer_args(), stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -3069,7 +3027,7 @@ __global__ void k_peer_bump(uint32_t* tag_base, uint32_t T) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *tag_base += T;
 }
 extern "C" int gmx_peer_bump(uint32_t* tag_base_d, int32_t T, gmx_stream stream) {
-  if (!tag_base_d || T < 1) return gmx_fail("gmx_peer_bump: bad argument%s");
+  if (const char* m = gmx_peer_bump_refusal_(tag_base_d, T)) return gmx_fail(m, "gmx_peer_bump");
   hipLaunchKernelGGL(k_peer_bump, dim3(1), dim3(64), 0, (hipStream_t)stream, tag_base_d, (uint32_t)T);
   GMX_HIP(hipGetLastError());
   return 0;
@@ -3084,8 +3042,7 @@ __global__ void k_sweep_verdict(const int64_t* overflow, const uint64_t* w0, con
 }
 extern "C" int gmx_sweep_verdict(const int64_t* overflow_d, const uint64_t* const* status_h, int32_t n_status,
                                  int64_t* verdict_d, gmx_stream stream) {
-  if (!overflow_d || !verdict_d || n_status < 0 || n_status > 4 || (n_status && !status_h))
-    return gmx_fail("gmx_sweep_verdict: bad argument (at most 4 status words)%s");
+  if (const char* m = gmx_sweep_verdict_refusal_(overflow_d, status_h, n_status, verdict_d)) return gmx_fail(m, "gmx_sweep_verdict");
   const uint64_t* w[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int k = 0; k < n_status; ++k) w[k] = status_h[k];
   hipLaunchKernelGGL(k_sweep_verdict, dim3(1), dim3(64), 0, (hipStream_t)stream, overflow_d, w[0], w[1], w[2], w[3], verdict_d);
@@ -3093,38 +3050,26 @@ extern "C" int gmx_sweep_verdict(const int64_t* overflow_d, const uint64_t* cons
   return 0;
 }
 
-static int peer_check(const char* who, const gmx_peer& P, int64_t n_per_rank) {
-  if (!P.land_d || !P.tag_base_d || !P.status_d) return gmx_fail("%s: peer has a null pointer", who);
-  if (P.world < 1 || P.world > SHARD_MAX_WORLD || P.rank < 0 || P.rank >= P.world) return gmx_fail("%s: peer rank / world out of range (world <= 64)", who);
-  if (P.step < 0) return gmx_fail("%s: peer.step is negative", who);
-  const int64_t tiles = (n_per_rank + RS_TILE - 1) / RS_TILE;
-  if (n_per_rank <= 0 || tiles > RS_MAX_TILES || P.tiles != (int32_t)tiles) return gmx_fail("%s: peer.tiles must be ceil(n_per_rank / 1024) <= 2048", who);
-  if (P.capacity < 1 || P.capacity > n_per_rank) return gmx_fail("%s: peer.capacity must be in [1, n_per_rank]", who);
-  if (P.leaves < 1 || P.leaves > GMX_PEER_MAX_LEAVES) return gmx_fail("%s: peer.leaves must be in [1, GMX_PEER_MAX_LEAVES = 32]", who);
-  return 0;
-}
-
 // the statistics block of a launch that has no epilogue put (gmx_tile_stats, an interpreted site program): thread b
 // puts tile b's row to every other rank
 __global__ void __launch_bounds__(GMX_BLOCK)
-k_peer_put_stats(const uint8_t* __restrict__ own, int tiles, int tiles_pad, uint64_t* const* __restrict__ land,
+k_peer_put_stats(const uint8_t* __restrict__ own, int tiles, uint64_t* const* __restrict__ land,
                  const uint32_t* __restrict__ tag_base, int step, int rank, int world) {
   const int b = (int)(blockIdx.x * GMX_BLOCK + threadIdx.x);
   if (b >= tiles) return;
   const uint32_t tag = *tag_base + (uint32_t)step;
-  const uint64_t a = reinterpret_cast<const uint64_t*>(own)[b];
-  const float m = reinterpret_cast<const float*>(own + (size_t)tiles_pad * 8)[b];
+  const gmx_stats_block blk = gmx_stats_block_at(own, tiles);
+  const uint64_t a = blk.agg[b];
+  const float m = blk.tmax[b];
   for (int d = 0; d < world; ++d)
     if (d != rank) gmx_peer_put_tile(land[d], tag, world, tiles, rank, b, a, m);
 }
 extern "C" int gmx_peer_put_stats(const void* stats_own_d, gmx_peer P, int64_t n_per_rank, gmx_stream stream) {
-  if (!stats_own_d) return gmx_fail("gmx_peer_put_stats: null argument%s");
-  if (peer_check("gmx_peer_put_stats", P, n_per_rank)) return 1;
+  if (const char* m = gmx_peer_put_stats_refusal_(!stats_own_d, P, n_per_rank)) return gmx_fail(m, "gmx_peer_put_stats");
   if (P.world == 1) return 0;
-  const int tiles = P.tiles, tiles_pad = tiles + (tiles & 1);
-  hipLaunchKernelGGL(k_peer_put_stats, dim3((unsigned)((tiles + GMX_BLOCK - 1) / GMX_BLOCK)), dim3(GMX_BLOCK), 0,
-                     (hipStream_t)stream, (const uint8_t*)stats_own_d, tiles, tiles_pad, (uint64_t* const*)P.land_d,
-                     P.tag_base_d, P.step, P.rank, P.world);
+  hipLaunchKernelGGL(k_peer_put_stats, dim3((unsigned)((P.tiles + GMX_BLOCK - 1) / GMX_BLOCK)), dim3(GMX_BLOCK), 0,
+                     (hipStream_t)stream, (const uint8_t*)stats_own_d, P.tiles, (uint64_t* const*)P.land_d, P.tag_base_d,
+                     P.step, P.rank, P.world);
   GMX_HIP(hipGetLastError());
   return 0;
 }
@@ -3133,41 +3078,20 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
                                    uint64_t* total_out_d, const float* lw_d, float* max_out_d, int shift,
                                    int64_t n_per_rank, const void* const* state_rows_h, void* const* tail_rows_h,
                                    int32_t* next_idx_d, gmx_stream stream) {
-  if (shard_check("gmx_shard_step_peer", kind, key, Pe.rank, Pe.world, n_per_rank)) return 1;
-  if (peer_check("gmx_shard_step_peer", Pe, n_per_rank)) return 1;
-  if (!stats_own_d || !plan_d || !lw_d || !max_out_d || !state_rows_h || !tail_rows_h || !next_idx_d)
-    return gmx_fail("gmx_shard_step_peer: null argument%s");
-  if (n_per_rank + (int64_t)Pe.world * Pe.capacity > 0x7fffffffLL)
-    return gmx_fail("gmx_shard_step_peer: extended state index exceeds int32%s");
-  if (shift < 1 || shift > 62) return gmx_fail("gmx_shard_step_peer: shift out of range%s");
-  if (((uintptr_t)lw_d & 15) || ((uintptr_t)stats_own_d & 7))
-    return gmx_fail("gmx_shard_step_peer: lw_d must be 16-byte and stats_own_d 8-byte aligned%s");
+  if (const char* m = gmx_shard_step_peer_refusal_(!key, kind, Pe, n_per_rank,
+                                                   !stats_own_d || !plan_d || !lw_d || !max_out_d || !state_rows_h || !tail_rows_h || !next_idx_d,
+                                                   shift, lw_d, stats_own_d, state_rows_h, tail_rows_h))
+    return gmx_fail(m, "gmx_shard_step_peer");
   shard_peer_args P;
   memset(&P, 0, sizeof(P));
   P.land = (uint64_t* const*)Pe.land_d;
   P.tag_base = Pe.tag_base_d; P.status = Pe.status_d; P.step = Pe.step; P.leaves = Pe.leaves;
   for (int l = 0; l < Pe.leaves; ++l) {
-    if (!state_rows_h[l] || !tail_rows_h[l]) return gmx_fail("gmx_shard_step_peer: a leaf pointer is null%s");
     P.state[l] = (const uint32_t*)state_rows_h[l];
     P.tail[l] = (uint32_t*)tail_rows_h[l];
   }
-  const int64_t tiles = Pe.tiles;
-  const float scale = gmx_pow2i(shift);
-  uint32_t b0, b1;
-  gmx_threefry2x32(key[0], key[1], 0u, 0u, &b0, &b1);           // bits32(key, 0) on the host
-  const uint32_t u0 = (b0 ^ b1) >> 9;
-  const bool small = Pe.world <= 8 && (int64_t)Pe.world * tiles <= 4 * GMX_BLOCK;
-#define GMX_LAUNCH_SP2(KIND, SM)                                                                                      \
-  hipLaunchKernelGGL((k_shard_step_fill<KIND, SM, true>), dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, (hipStream_t)stream, key[0],  \
-                     key[1], u0, lw_d, (const uint8_t*)stats_own_d, (size_t)0, (int)tiles, scale, Pe.rank, Pe.world,  \
-                     (int32_t)n_per_rank, (int32_t)Pe.capacity, plan_d, total_out_d, max_out_d, (const uint32_t*)nullptr, \
-                     (uint32_t*)nullptr, next_idx_d, P)
-#define GMX_LAUNCH_SP(KIND) do { if (small) GMX_LAUNCH_SP2(KIND, true); else GMX_LAUNCH_SP2(KIND, false); } while (0)
-  if (kind == GMX_RESAMPLE_SYSTEMATIC) GMX_LAUNCH_SP(GMX_RESAMPLE_SYSTEMATIC); else GMX_LAUNCH_SP(GMX_RESAMPLE_STRATIFIED);
-#undef GMX_LAUNCH_SP
-#undef GMX_LAUNCH_SP2
-  GMX_HIP(hipGetLastError());
-  return 0;
+  return launch_shard_fill_<true>(kind, key, stats_own_d, 0, plan_d, total_out_d, lw_d, max_out_d, shift, Pe.rank, Pe.world,
+                                  n_per_rank, Pe.capacity, nullptr, nullptr, next_idx_d, P, stream);
 }
 
 // ---------------------------------------------------------------------------

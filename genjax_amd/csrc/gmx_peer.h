@@ -14,6 +14,19 @@
                                                peer that never arrives must not hang the GPU; ranks are microseconds
                                                apart inside a sweep and a host barrier apart before its first launch */
 
+// ---- a rank's tile-statistics block (gmx_shard_stats_bytes): agg[tiles_pad] u64, then tmax[tiles_pad] f32, tiles_pad =
+// the tile count rounded up to even (a block is a multiple of 8 bytes).  A gathered table holds rank r's block at
+// base + r * gmx_stats_block_bytes(tiles).  THE statement of this layout: sizes and pointers are written from it ----
+template <class T> GMX_HD T gmx_stats_tiles_pad(T tiles) { return tiles + (tiles & 1); }
+GMX_HD size_t gmx_stats_block_bytes(int64_t tiles) { return (size_t)gmx_stats_tiles_pad(tiles) * 12u; }
+struct gmx_stats_block { const uint64_t* agg; const float* tmax; };
+GMX_HD gmx_stats_block gmx_stats_block_at(const void* base, int tiles) {
+  gmx_stats_block b;
+  b.agg = (const uint64_t*)base;
+  b.tmax = (const float*)((const uint8_t*)base + (size_t)gmx_stats_tiles_pad(tiles) * 8u);
+  return b;
+}
+
 // ---- layout of a rank's landing block, in u64 words ----
 GMX_HD size_t gmx_peer_stats_words(int world, int tiles) { return (size_t)2 * (size_t)world * (size_t)tiles * 3u; }
 GMX_HD size_t gmx_peer_state_words(int world, int64_t cap, int leaves) {

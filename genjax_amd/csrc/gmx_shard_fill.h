@@ -70,6 +70,12 @@ struct shard_peer_args {                         // the AOT kernel's by-value pa
   const uint32_t* state[GMX_PEER_MAX_LEAVES];
   uint32_t* tail[GMX_PEER_MAX_LEAVES];
 };
+__device__ __forceinline__ shard_peer shard_peer_of(const shard_peer_args& a) {      // (the arrays stay where `a` lives)
+  shard_peer P;
+  P.land = a.land; P.tag_base = a.tag_base; P.status = a.status; P.step = a.step; P.leaves = a.leaves;
+  P.state = a.state; P.tail = a.tail;
+  return P;
+}
 // one row of another rank's statistics: spin (bounded) until all three granules carry `tag`
 __device__ __forceinline__ bool shard_peer_row(const uint64_t* row, uint32_t tag, uint64_t& agg, float& tmax) {
   uint64_t g0 = gmx_granule_peek(row), g1 = gmx_granule_peek(row + 1), g2 = gmx_granule_peek(row + 2);
@@ -119,7 +125,6 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   const int my_tile = (int)blockIdx.x;
   const int32_t i0 = my_tile * RS_TILE + tid * CDF_VEC;
   const int32_t N = n * world, base = rank * n;
-  const int tiles_pad = n_tiles + (n_tiles & 1);
   gmx_key key; key.k0 = k0; key.k1 = k1;
   // ---- loads first: this tile's log-weights ----
   float x[CDF_VEC];
@@ -136,7 +141,7 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   }
   // PEER: `stats_all` is this rank's own block; the other ranks' rows are granules in the landing block
   const uint8_t* own = PEER ? stats_all : stats_all + (size_t)rank * stride;
-  const float tmax_mine = reinterpret_cast<const float*>(own + (size_t)tiles_pad * 8)[my_tile];
+  const float tmax_mine = gmx_stats_block_at(own, n_tiles).tmax[my_tile];
   uint32_t tag = 0u;
   const uint64_t* land_own = nullptr;            // this rank's own landing block (entry `rank` of the table)
   bool timed_out = false;     // (PEER) a wait gave up — or the sweep had lost a peer before this launch: no wait at all then
@@ -169,9 +174,9 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
         else if (rho < rows) { ta[k] = 0ull; tm[k] = -gmx_inf(); }
         else { ta[k] = 0ull; tm[k] = -gmx_inf(); }
       } else {
-        const uint8_t* blk = PEER ? own : stats_all + (size_t)r * stride;
-        ta[k] = reinterpret_cast<const uint64_t*>(blk)[t];
-        tm[k] = reinterpret_cast<const float*>(blk + (size_t)tiles_pad * 8)[t];
+        const gmx_stats_block blk = gmx_stats_block_at(PEER ? own : stats_all + (size_t)r * stride, n_tiles);
+        ta[k] = blk.agg[t];
+        tm[k] = blk.tmax[t];
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -186,7 +191,7 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
           m = gmx_rmax(m, m_);
         }
       } else {
-        const float* tmax = reinterpret_cast<const float*>((PEER ? own : stats_all + (size_t)r * stride) + (size_t)tiles_pad * 8);
+        const float* tmax = gmx_stats_block_at(PEER ? own : stats_all + (size_t)r * stride, n_tiles).tmax;
         for (int t = tid; t < n_tiles; t += GMX_BLOCK) m = gmx_rmax(m, tmax[t]);
       }
     }
@@ -232,14 +237,12 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
     }
   } else {
     for (int r = 0; r < world; ++r) {
-      const uint8_t* blk = PEER ? own : stats_all + (size_t)r * stride;
-      const uint64_t* agg = reinterpret_cast<const uint64_t*>(blk);
-      const float* tmax = reinterpret_cast<const float*>(blk + (size_t)tiles_pad * 8);
+      const gmx_stats_block blk = gmx_stats_block_at(PEER ? own : stats_all + (size_t)r * stride, n_tiles);
       uint64_t sum = 0;
       for (int t = tid; t < n_tiles; t += GMX_BLOCK) {
         uint64_t a_; float m_;
         if (PEER && r != rank) (void)shard_peer_row(land_own + gmx_peer_stats_at(tag, world, n_tiles, r, t), tag, a_, m_);   // (complete: pass 1 waited)
-        else { a_ = agg[t]; m_ = tmax[t]; }
+        else { a_ = blk.agg[t]; m_ = blk.tmax[t]; }
         const uint64_t G = gmx_tile_scale(a_, gmx_tile_exp(m_), K);
         sum += G;
         below += (r == rank && t < my_tile) ? G : 0ull;

@@ -3,7 +3,8 @@
 //   the tile constants        the definition tile of the two-level integer CDF and the tile tables built on it
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
-//                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string
+//                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
+//                             the tile-form resamplers, the row-wise draws, the sharded / peer family, the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
 // Plain host C++ (static inline): no HIP, no kernel, no algorithm.  hiprtc never sees this file (it is not among the
@@ -57,12 +58,8 @@ static inline size_t gmx_tile_prefix_words_(int64_t n) { return (size_t)((gmx_ti
 static inline size_t gmx_sorted_uniforms_words_(int64_t n) { return n > 0 ? gmx_sorted_layout_of(n).words : 0; }
 
 // ---- sharded resampling ----
-// a rank's tile statistics: agg[tiles_pad] u64 then tmax[tiles_pad] f32, tiles_pad = tiles rounded up to even
-static inline size_t gmx_shard_stats_bytes_(int64_t n_per_rank) {
-  int64_t tiles = gmx_tiles_(n_per_rank);
-  tiles += tiles & 1;
-  return (size_t)tiles * 12;
-}
+// a rank's tile statistics: the block gmx_peer.h lays out (gmx_stats_block_at reads it)
+static inline size_t gmx_shard_stats_bytes_(int64_t n_per_rank) { return gmx_stats_block_bytes(gmx_tiles_(n_per_rank)); }
 static inline size_t gmx_shard_plan_words_(int world) { return (size_t)(GMX_PLAN_BOUNDS + world + 1); }
 static inline size_t gmx_peer_landing_bytes_(int world, int64_t n_per_rank, int64_t capacity, int leaves) {
   if (world < 1 || n_per_rank < 1 || capacity < 1 || leaves < 1) return 0;
@@ -278,6 +275,103 @@ static inline size_t gmx_resample_rows_ess_bytes_(int kind, int64_t rows, int64_
 }
 // an ess_q8 above this resamples every row with mass (the ESS of n weights is at most n)
 static inline uint32_t gmx_ess_always_(int64_t n) { return (uint32_t)(256 * n); }
+
+// ---- sharded resampling and the fused peer exchange: gmx_shard_plan, _route, _step, _step_sorted, _totals, _step_tiles,
+// _step_fused, gmx_peer_put_stats, gmx_shard_step_peer, gmx_peer_bump, gmx_sweep_verdict ----
+// Each refusal is the entry point's whole argument check, in its order; none quotes a value, so it returns the format
+// alone.  has_null: one of the entry point's required pointers other than the key is null.
+#define GMX_SHARD_MAX_WORLD 64         /* ranks of the one-launch forms: a wave's lanes hold one total each (SHARD_MAX_WORLD) */
+static inline const char* gmx_shard_check_(bool no_key, int kind, int rank, int world, int64_t n) {
+  if (no_key) return "%s: null key";
+  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED) return "%s: systematic / stratified only (ordered slot thresholds)";
+  if (world < 1 || world > 1024 || rank < 0 || rank >= world) return "%s: rank / world out of range";
+  if (n <= 0 || n > 0x7fffffffLL || n * world >= (1LL << 40)) return "%s: n_per_rank out of range";
+  return nullptr;
+}
+// capacity, then the extended index: a slot's ancestor indexes [ n_per_rank local | world * capacity received ]
+static inline const char* gmx_shard_capacity_refusal_(int64_t n_per_rank, int64_t capacity) {
+  return capacity < 1 || capacity > n_per_rank ? "%s: capacity must be in [1, n_per_rank]" : nullptr;
+}
+static inline const char* gmx_shard_extended_refusal_(int64_t n_per_rank, int world, int64_t capacity) {
+  return n_per_rank + (int64_t)world * capacity > 0x7fffffffLL ? "%s: extended state index exceeds int32" : nullptr;
+}
+static inline const char* gmx_shard_shift_refusal_(int shift) { return shift < 1 || shift > 62 ? "%s: shift out of range" : nullptr; }
+// array_form: the form has a CDF-array counterpart, which takes any world
+static inline const char* gmx_shard_world_refusal_(int world, bool array_form) {
+  if (world <= GMX_SHARD_MAX_WORLD) return nullptr;
+  return array_form ? "%s: world <= 64 (use gmx_weight_cdf + gmx_shard_step)" : "%s: world <= 64";
+}
+// the keyed forms: gmx_shard_check_, null arguments, then what the form adds — capacity and the extended index (all but
+// the plan); world <= 64 and the shift (the forms on tile statistics); n_per_rank <= 2^21 (the fused form holds the table:
+// the step on this rank's own block strides over its earlier tiles and takes any size); alignment last.  a16: the form's
+// 16-byte pointer (lw_d; cdf_d, which only the one-launch step, world <= 64, reads 16 bytes at a time); a8: its statistics
+enum gmx_shard_form { GMX_SHARD_PLAN, GMX_SHARD_ROUTE, GMX_SHARD_STEP, GMX_SHARD_STEP_TILES, GMX_SHARD_STEP_FUSED };
+static inline const char* gmx_shard_form_refusal_(gmx_shard_form form, bool no_key, int kind, int rank, int world,
+                                                  int64_t n_per_rank, bool has_null, int64_t capacity = 1, int shift = 1,
+                                                  const void* a16 = nullptr, const void* a8 = nullptr) {
+  const char* m = gmx_shard_check_(no_key, kind, rank, world, n_per_rank);
+  if (!m && has_null) m = "%s: null argument";
+  if (m || form == GMX_SHARD_PLAN) return m;
+  if (!m) m = gmx_shard_capacity_refusal_(n_per_rank, capacity);
+  if (!m) m = gmx_shard_extended_refusal_(n_per_rank, world, capacity);
+  if (m || form == GMX_SHARD_ROUTE) return m;
+  if (form == GMX_SHARD_STEP) return world <= GMX_SHARD_MAX_WORLD && ((uintptr_t)a16 & 15) ? "%s: cdf_d must be 16-byte aligned" : nullptr;
+  if (!m) m = gmx_shard_world_refusal_(world, form == GMX_SHARD_STEP_TILES);
+  if (!m) m = gmx_shard_shift_refusal_(shift);
+  if (!m && form == GMX_SHARD_STEP_FUSED && gmx_tiles_(n_per_rank) > GMX_MAX_TILES) m = "%s: n_per_rank too large (<= 2^21)";
+  if (!m && (((uintptr_t)a16 & 15) || ((uintptr_t)a8 & 7)))
+    m = form == GMX_SHARD_STEP_TILES ? "%s: lw_d must be 16-byte and stats_own_d 8-byte aligned"
+                                     : "%s: lw_d must be 16-byte and stats_all_d 8-byte aligned";
+  return m;
+}
+// the unkeyed sorted-multinomial step: the n_per_rank * world global slots index ONE order-statistics table
+static inline const char* gmx_shard_step_sorted_refusal_(bool has_null, int rank, int world, int64_t n_per_rank, int64_t capacity,
+                                                         const void* table_d) {
+  if (has_null) return "%s: null argument";
+  if (world < 1 || world > 1024 || rank < 0 || rank >= world) return "%s: rank / world out of range";
+  if (n_per_rank <= 0 || n_per_rank * world > 0x7fffffffLL) return "%s: n_per_rank * world out of range (< 2^31)";
+  const char* m = gmx_shard_capacity_refusal_(n_per_rank, capacity);
+  if (!m) m = gmx_shard_extended_refusal_(n_per_rank, world, capacity);
+  return m || !((uintptr_t)table_d & 15) ? m : "%s: table_d must be 16-byte aligned";
+}
+// (one workgroup strides over the whole gathered table: any number of tiles)
+static inline const char* gmx_shard_totals_refusal_(bool has_null, int world, int64_t n_per_rank, const void* stats_all_d) {
+  if (has_null) return "%s: null argument";
+  if (world < 1 || world > 1024) return "%s: world out of range";
+  if (n_per_rank <= 0 || n_per_rank > 0x7fffffffLL) return "%s: n_per_rank out of range (< 2^31)";
+  return (uintptr_t)stats_all_d & 7 ? "%s: stats_all_d must be 8-byte aligned" : nullptr;
+}
+static inline const char* gmx_peer_check_(const gmx_peer& P, int64_t n_per_rank) {
+  if (!P.land_d || !P.tag_base_d || !P.status_d) return "%s: peer has a null pointer";
+  if (P.world < 1 || P.world > GMX_SHARD_MAX_WORLD || P.rank < 0 || P.rank >= P.world) return "%s: peer rank / world out of range (world <= 64)";
+  if (P.step < 0) return "%s: peer.step is negative";
+  const int64_t tiles = gmx_tiles_(n_per_rank);
+  if (n_per_rank <= 0 || tiles > GMX_MAX_TILES || P.tiles != (int32_t)tiles) return "%s: peer.tiles must be ceil(n_per_rank / 1024) <= 2048";
+  if (P.capacity < 1 || P.capacity > n_per_rank) return "%s: peer.capacity must be in [1, n_per_rank]";
+  if (P.leaves < 1 || P.leaves > GMX_PEER_MAX_LEAVES) return "%s: peer.leaves must be in [1, GMX_PEER_MAX_LEAVES = 32]";
+  return nullptr;
+}
+static inline const char* gmx_peer_put_stats_refusal_(bool has_null, const gmx_peer& P, int64_t n_per_rank) {
+  return has_null ? "%s: null argument" : gmx_peer_check_(P, n_per_rank);
+}
+// rank, world and capacity are the peer's; the leaves' HOST arrays are read last, once they are known to be there
+static inline const char* gmx_shard_step_peer_refusal_(bool no_key, int kind, const gmx_peer& P, int64_t n_per_rank, bool has_null,
+                                                       int shift, const void* lw_d, const void* stats_own_d,
+                                                       const void* const* state_rows_h, void* const* tail_rows_h) {
+  const char* m = gmx_shard_check_(no_key, kind, P.rank, P.world, n_per_rank);
+  if (!m) m = gmx_peer_check_(P, n_per_rank);
+  if (!m && has_null) m = "%s: null argument";
+  if (!m) m = gmx_shard_extended_refusal_(n_per_rank, P.world, P.capacity);
+  if (!m) m = gmx_shard_shift_refusal_(shift);
+  if (!m && (((uintptr_t)lw_d & 15) || ((uintptr_t)stats_own_d & 7))) m = "%s: lw_d must be 16-byte and stats_own_d 8-byte aligned";
+  for (int l = 0; !m && l < P.leaves; ++l)
+    if (!state_rows_h[l] || !tail_rows_h[l]) m = "%s: a leaf pointer is null";
+  return m;
+}
+static inline const char* gmx_peer_bump_refusal_(const void* tag_base_d, int32_t T) { return !tag_base_d || T < 1 ? "%s: bad argument" : nullptr; }
+static inline const char* gmx_sweep_verdict_refusal_(const void* overflow_d, const void* status_h, int32_t n_status, const void* verdict_d) {
+  return !overflow_d || !verdict_d || n_status < 0 || n_status > 4 || (n_status && !status_h) ? "%s: bad argument (at most 4 status words)" : nullptr;
+}
 
 // ---- sweep history ----
 static inline gmx_refusal gmx_history_record_refusal_(int32_t D, int64_t n, uint32_t expect_tag, bool has_null, bool has_status) {

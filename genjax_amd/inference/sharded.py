@@ -67,6 +67,15 @@ def systematic_slot_bounds(offsets, total: int, n_total: int, u0: int):
 CDF_TILE = 1024
 
 
+def stats_views(block, n_per_rank: int):
+    """(agg, tmax) of one rank's tile-statistics block — `block`: its gmx_shard_stats_bytes(n_per_rank) bytes — as views:
+    agg[tiles_pad] int64, then tmax[tiles_pad] float32, tiles_pad = the tile count rounded up to even (the layout
+    csrc/gmx_peer.h states: gmx_stats_block_at)"""
+    tiles = (n_per_rank + CDF_TILE - 1) // CDF_TILE
+    pad = tiles + (tiles & 1)
+    return block[:pad * 8].view(torch.int64), block[pad * 8:].view(torch.float32)
+
+
 def _check_shard_alignment(n_per_rank: int, world: int):
     """The integer CDF is defined on tiles of 1024 consecutive GLOBAL particle indices (include/genmi.h,
     "Resampling"): a shard must start on a tile boundary or the result would depend on the rank count."""
@@ -131,11 +140,9 @@ class _ShardRouter:
                 self.sorted_tab = zeros((int(be.c.gmx_sorted_uniforms_words(self.n * W)),), torch.int32)
             return
         sb = int(be.c.gmx_shard_stats_bytes(self.n))
-        pad = self.tiles + (self.tiles & 1)
         self.stats_own = [zeros((sb,), torch.uint8) for _ in range(sets)]
         self.stats_all = shared((W * sb,), torch.uint8)
-        self.tile_agg = [b_[:pad * 8].view(torch.int64) for b_ in self.stats_own]
-        self.tile_max = [b_[pad * 8:].view(torch.float32) for b_ in self.stats_own]
+        self.tile_agg, self.tile_max = zip(*(stats_views(b_, self.n) for b_ in self.stats_own))
         if form == "peer":
             self.tag, self.status = cx.step_words()
 

@@ -172,7 +172,7 @@ typedef struct gmx_peer {
  * here must not be the ones this launch writes (two sets, alternating). */
 typedef struct gmx_shard_in {
   const float* lw_d;              /* [n] log-weights of step t - 1 (16-byte aligned); NULL = not fused                  */
-  const void* stats_own_d;        /* this rank's statistics block of step t - 1 (gmx_shard_stats_bytes: A_b, then m_b)  */
+  const void* stats_own_d;        /* this rank's statistics block of step t - 1 (gmx_stats_block_at: A_b, then m_b)     */
   int64_t* plan_d;                /* gmx_shard_plan_words(world): as gmx_shard_step_peer                                */
   uint64_t* total_out_d;          /* [1]: the global integer total of step t - 1                                         */
   float* max_out_d;               /* [1]: the global max log-weight of step t - 1                                        */
@@ -519,7 +519,8 @@ int gmx_shard_step_sorted(const uint32_t* table_d, const uint64_t* totals_d /* [
                           int64_t capacity, const void* state_d, void* send_d, int32_t* next_idx_d, gmx_stream stream);
 /* The same step from TILE STATISTICS — two collectives per step instead of three, no local CDF array.
  * Each rank's statistics block (gmx_shard_stats_bytes(n_per_rank) bytes: agg[tiles_pad] u64, then
- * tmax[tiles_pad] f32, tiles_pad = ceil(n_per_rank / 1024) rounded up to even; written by gmx_tile_stats or by
+ * tmax[tiles_pad] f32, tiles_pad = ceil(n_per_rank / 1024) rounded up to even — the layout csrc/gmx_peer.h states and
+ * gmx_stats_block_at reads; written by gmx_tile_stats or by
  * the site program itself, gmx_run_args.tile_agg_d / red_out_d) is all-gathered — that one collective carries what
  * the max all-reduce and the totals all-gather carried.  gmx_shard_totals (one block) turns the gathered
  * table into the global max (*max_d) and every rank's integer total (totals_d[world]);

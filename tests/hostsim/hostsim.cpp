@@ -602,7 +602,7 @@ static int64_t hs_slots_below(int kind, gmx_key k, uint64_t c, uint64_t total, i
 extern "C" size_t gmx_shard_plan_words(int world) { return gmx_shard_plan_words_(world); }
 extern "C" int gmx_shard_plan(int kind, const uint32_t key[2], const uint64_t* totals, int rank, int world, int64_t n,
                               int64_t* plan, uint64_t* total_out, gmx_stream) {
-  if (kind != GMX_RESAMPLE_SYSTEMATIC && kind != GMX_RESAMPLE_STRATIFIED) return gmx_fail("shard_plan: kind");
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_PLAN, !key, kind, rank, world, n, !totals || !plan)) return gmx_fail(m, "gmx_shard_plan");
   gmx_key k; k.k0 = key[0]; k.k1 = key[1];
   int64_t N = n * world;
   uint64_t total = 0, off = 0;
@@ -632,7 +632,8 @@ static void hs_remote_slots(int64_t* plan, int rank, int world, int64_t n, int64
 }
 extern "C" int gmx_shard_route(int kind, const uint32_t key[2], int64_t* plan, const uint64_t* cdf, int rank, int world,
                                int64_t n, int64_t cap, const void* state_v, void* send_v, int32_t* next_idx, gmx_stream st) {
-  if (cap < 1 || cap > n) return gmx_fail("shard_route: capacity");
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_ROUTE, !key, kind, rank, world, n, !plan || !cdf || !state_v || !send_v || !next_idx, cap))
+    return gmx_fail(m, "gmx_shard_route");
   const uint32_t* state = (const uint32_t*)state_v; uint32_t* send = (uint32_t*)send_v;
   const int64_t* bounds = plan + GMX_PLAN_BOUNDS;
   const int64_t N = n * world, base = (int64_t)rank * n, S = bounds[rank], E = bounds[rank + 1];
@@ -654,6 +655,9 @@ extern "C" int gmx_shard_route(int kind, const uint32_t key[2], int64_t* plan, c
 extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* totals, int64_t* plan, uint64_t* total_out,
                               const uint64_t* cdf, int rank, int world, int64_t n, int64_t cap, const void* state,
                               void* send, int32_t* next_idx, gmx_stream st) {
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP, !key, kind, rank, world, n,
+                                              !totals || !plan || !cdf || !state || !send || !next_idx, cap, 1, cdf))
+    return gmx_fail(m, "gmx_shard_step");
   int64_t flag = plan[GMX_PLAN_OVERFLOW];
   if (gmx_shard_plan(kind, key, totals, rank, world, n, plan, total_out, st)) return 1;
   plan[GMX_PLAN_OVERFLOW] = flag;
@@ -664,7 +668,9 @@ extern "C" int gmx_shard_step(int kind, const uint32_t key[2], const uint64_t* t
 extern "C" int gmx_shard_step_sorted(const uint32_t* table, const uint64_t* totals, int64_t* plan, uint64_t* total_out,
                                      const uint64_t* cdf, int rank, int world, int64_t n, int64_t cap,
                                      const void* state_v, void* send_v, int32_t* next_idx, gmx_stream) {
-  if (cap < 1 || cap > n) return gmx_fail("shard_step_sorted: capacity");
+  if (const char* m = gmx_shard_step_sorted_refusal_(!table || !totals || !plan || !cdf || !state_v || !send_v || !next_idx, rank, world, n,
+                                                     cap, table))
+    return gmx_fail(m, "gmx_shard_step_sorted");
   const int64_t N = n * world, base = (int64_t)rank * n;
   const gmx_sorted_layout L = gmx_sorted_layout_of(N);
   const uint64_t* toff = (const uint64_t*)(table + L.off_toff);
@@ -701,20 +707,19 @@ extern "C" int gmx_shard_step_sorted(const uint32_t* table, const uint64_t* tota
 }
 extern "C" size_t gmx_shard_stats_bytes(int64_t n) { return gmx_shard_stats_bytes_(n); }
 extern "C" int gmx_shard_totals(const void* stats_all, int world, int64_t n, uint64_t* totals, float* max_d, gmx_stream) {
-  if (!stats_all || !totals || !max_d) return gmx_fail("shard_totals: null argument");
-  const int64_t tiles = gmx_tiles_(n), pad = tiles + (tiles & 1);
+  if (const char* m = gmx_shard_totals_refusal_(!stats_all || !totals || !max_d, world, n, stats_all)) return gmx_fail(m, "gmx_shard_totals");
+  const int tiles = (int)gmx_tiles_(n);
   const size_t stride = gmx_shard_stats_bytes(n);
   float M = -gmx_inf();
   for (int r = 0; r < world; ++r) {
-    const float* tm = (const float*)((const uint8_t*)stats_all + r * stride + pad * 8);
-    for (int64_t t = 0; t < tiles; ++t) M = gmx_rmax(M, tm[t]);
+    const float* tm = gmx_stats_block_at((const uint8_t*)stats_all + r * stride, tiles).tmax;
+    for (int t = 0; t < tiles; ++t) M = gmx_rmax(M, tm[t]);
   }
   const int32_t K = gmx_tile_exp(M);
   for (int r = 0; r < world; ++r) {
-    const uint64_t* ag = (const uint64_t*)((const uint8_t*)stats_all + r * stride);
-    const float* tm = (const float*)((const uint8_t*)stats_all + r * stride + pad * 8);
+    const gmx_stats_block blk = gmx_stats_block_at((const uint8_t*)stats_all + r * stride, tiles);
     uint64_t sum = 0;
-    for (int64_t t = 0; t < tiles; ++t) sum += gmx_tile_scale(ag[t], gmx_tile_exp(tm[t]), K);
+    for (int t = 0; t < tiles; ++t) sum += gmx_tile_scale(blk.agg[t], gmx_tile_exp(blk.tmax[t]), K);
     totals[r] = sum;
   }
   *max_d = M;
@@ -724,19 +729,23 @@ extern "C" int gmx_shard_totals(const void* stats_all, int world, int64_t n, uin
 extern "C" int gmx_shard_step_tiles(int kind, const uint32_t key[2], const uint64_t* totals, int64_t* plan, uint64_t* total_out,
                                     const float* lw, const void* stats_own, const float* max_d, int shift, int rank, int world,
                                     int64_t n, int64_t cap, const void* state, void* send, int32_t* next_idx, gmx_stream st) {
-  if (!lw || !stats_own || !max_d) return gmx_fail("shard_step_tiles: null argument");
-  const int64_t tiles = gmx_tiles_(n), pad = tiles + (tiles & 1);
-  const uint64_t* ag = (const uint64_t*)stats_own;
-  const float* tm = (const float*)((const uint8_t*)stats_own + pad * 8);
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP_TILES, !key, kind, rank, world, n,
+                                              !totals || !plan || !lw || !stats_own || !max_d || !state || !send || !next_idx, cap, shift,
+                                              lw, stats_own))
+    return gmx_fail(m, "gmx_shard_step_tiles");
+  const gmx_stats_block own = gmx_stats_block_at(stats_own, (int)gmx_tiles_(n));
   std::vector<uint64_t> cdf((size_t)n);
-  hs_cdf(lw, n, shift, tm, gmx_tile_exp(*max_d), ag, nullptr, cdf.data());
+  hs_cdf(lw, n, shift, own.tmax, gmx_tile_exp(*max_d), own.agg, nullptr, cdf.data());
   return gmx_shard_step(kind, key, totals, plan, total_out, cdf.data(), rank, world, n, cap, state, send, next_idx, st);
 }
 // the one-launch form: the totals from the gathered table, then the step with this rank's own block of it
 extern "C" int gmx_shard_step_fused(int kind, const uint32_t key[2], const void* stats_all, int64_t* plan, uint64_t* total_out,
                                     const float* lw, float* max_out, int shift, int rank, int world, int64_t n, int64_t cap,
                                     const void* state, void* send, int32_t* next_idx, gmx_stream st) {
-  if (!stats_all || !max_out || world < 1 || world > 64) return gmx_fail("shard_step_fused: bad argument");
+  if (const char* m = gmx_shard_form_refusal_(GMX_SHARD_STEP_FUSED, !key, kind, rank, world, n,
+                                              !stats_all || !plan || !lw || !max_out || !state || !send || !next_idx, cap, shift, lw,
+                                              stats_all))
+    return gmx_fail(m, "gmx_shard_step_fused");
   std::vector<uint64_t> totals((size_t)world);
   if (gmx_shard_totals(stats_all, world, n, totals.data(), max_out, st)) return 1;
   const void* own = (const uint8_t*)stats_all + (size_t)rank * gmx_shard_stats_bytes(n);
@@ -750,35 +759,25 @@ extern "C" size_t gmx_peer_landing_bytes(int world, int64_t n, int64_t cap, int 
   return gmx_peer_landing_bytes_(world, n, cap, leaves);
 }
 extern "C" int gmx_peer_bump(uint32_t* tag_base, int32_t T, gmx_stream) {
-  if (!tag_base || T < 1) return gmx_fail("peer_bump: bad argument");
+  if (const char* m = gmx_peer_bump_refusal_(tag_base, T)) return gmx_fail(m, "gmx_peer_bump");
   *tag_base += (uint32_t)T;
   return 0;
 }
 extern "C" int gmx_sweep_verdict(const int64_t* overflow, const uint64_t* const* status, int32_t n_status, int64_t* verdict,
                                  gmx_stream) {
-  if (!overflow || !verdict || n_status < 0 || n_status > 4 || (n_status && !status)) return gmx_fail("sweep_verdict: bad argument");
+  if (const char* m = gmx_sweep_verdict_refusal_(overflow, status, n_status, verdict)) return gmx_fail(m, "gmx_sweep_verdict");
   bool bad = false;
   for (int k = 0; k < n_status; ++k) bad = bad || (status[k] && *status[k] != 0);
   *verdict = bad ? 2 : *overflow;
   return 0;
 }
-static int hs_peer_check(const gmx_peer& P, int64_t n) {
-  if (!P.land_d || !P.tag_base_d || !P.status_d) return gmx_fail("peer: null pointer");
-  if (P.world < 1 || P.world > 64 || P.rank < 0 || P.rank >= P.world || P.step < 0) return gmx_fail("peer: rank / world / step out of range");
-  if (n <= 0 || P.tiles != (int32_t)(gmx_tiles_(n))) return gmx_fail("peer: tiles must be ceil(n / 1024)");
-  if (P.capacity < 1 || P.capacity > n || P.leaves < 1 || P.leaves > GMX_PEER_MAX_LEAVES) return gmx_fail("peer: capacity / leaves out of range");
-  return 0;
-}
 extern "C" int gmx_peer_put_stats(const void* stats_own, gmx_peer P, int64_t n, gmx_stream) {
-  if (!stats_own) return gmx_fail("peer_put_stats: null argument");
-  if (hs_peer_check(P, n)) return 1;
-  const int pad = P.tiles + (P.tiles & 1);
-  const uint64_t* ag = (const uint64_t*)stats_own;
-  const float* tm = (const float*)((const uint8_t*)stats_own + (size_t)pad * 8);
+  if (const char* m = gmx_peer_put_stats_refusal_(!stats_own, P, n)) return gmx_fail(m, "gmx_peer_put_stats");
+  const gmx_stats_block own = gmx_stats_block_at(stats_own, P.tiles);
   const uint32_t tag = *P.tag_base_d + (uint32_t)P.step;
   for (int d = 0; d < P.world; ++d)
     if (d != P.rank)
-      for (int b = 0; b < P.tiles; ++b) hs_peer_put_tile((uint64_t*)P.land_d[d], tag, P.world, P.tiles, P.rank, b, ag[b], tm[b]);
+      for (int b = 0; b < P.tiles; ++b) hs_peer_put_tile((uint64_t*)P.land_d[d], tag, P.world, P.tiles, P.rank, b, own.agg[b], own.tmax[b]);
   return 0;
 }
 // wait (bounded) until granule *g carries `tag`; its data
@@ -794,9 +793,10 @@ static bool hs_peer_wait(const uint64_t* g, uint32_t tag, uint32_t* data, const 
 extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* stats_own, gmx_peer P, int64_t* plan,
                                    uint64_t* total_out, const float* lw, float* max_out, int shift, int64_t n,
                                    const void* const* state_rows, void* const* tail_rows, int32_t* next_idx, gmx_stream st) {
-  if (!stats_own || !plan || !lw || !max_out || !state_rows || !tail_rows || !next_idx) return gmx_fail("shard_step_peer: null argument");
-  if (hs_peer_check(P, n)) return 1;
-  const int W = P.world, me = P.rank, tiles = P.tiles, pad = tiles + (tiles & 1);
+  if (const char* m = gmx_shard_step_peer_refusal_(!key, kind, P, n, !stats_own || !plan || !lw || !max_out || !state_rows || !tail_rows || !next_idx,
+                                                   shift, lw, stats_own, state_rows, tail_rows))
+    return gmx_fail(m, "gmx_shard_step_peer");
+  const int W = P.world, me = P.rank, tiles = P.tiles;
   const int64_t cap = P.capacity;
   const uint32_t tag = *P.tag_base_d + (uint32_t)P.step;
   const size_t stride = gmx_shard_stats_bytes(n);
@@ -807,8 +807,9 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
   const uint64_t* land_own = (const uint64_t*)P.land_d[me];
   for (int r = 0; r < W; ++r) {
     if (r == me) continue;
-    uint64_t* ag = (uint64_t*)(all.data() + (size_t)r * stride);
-    float* tm = (float*)(all.data() + (size_t)r * stride + (size_t)pad * 8);
+    const gmx_stats_block blk = gmx_stats_block_at(all.data() + (size_t)r * stride, tiles);      // (`all` is ours to write)
+    uint64_t* ag = const_cast<uint64_t*>(blk.agg);
+    float* tm = const_cast<float*>(blk.tmax);
     for (int b = 0; b < tiles; ++b) {
       const uint64_t* row = land_own + gmx_peer_stats_at(tag, W, tiles, r, b);
       uint32_t lo, hi, mb;
@@ -824,7 +825,6 @@ extern "C" int gmx_shard_step_peer(int kind, const uint32_t key[2], const void* 
   if (gmx_shard_totals(all.data(), W, n, totals.data(), max_out, st)) return 1;
   std::vector<uint32_t> send((size_t)W * (size_t)cap);
   for (int l = 0; l < P.leaves; ++l) {
-    if (!state_rows[l] || !tail_rows[l]) return gmx_fail("shard_step_peer: a leaf pointer is null");
     if (gmx_shard_step_tiles(kind, key, totals.data(), plan, total_out, lw, stats_own, max_out, shift, me, W, n, cap,
                              state_rows[l], send.data(), next_idx, st)) return 1;
     // what this rank ships to d: the slots of d's shard whose ancestor lives here, [max(bounds[me], d n), min(bounds[me+1], (d+1) n))

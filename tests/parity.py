@@ -256,6 +256,7 @@ def check_plates(n=257, seed=4):
 def check_shard_route(n=1000, world=4, capacity=None, kind=None, seed=0, skew=0.0, dead=False, fused=False, spike=0.0):
     from ctypes import c_uint32
     from genjax_amd import _lib
+    from genjax_amd.inference.sharded import stats_views
     be = _lib.get()
     dev = be.device
     kind = O.SYSTEMATIC if kind is None else kind
@@ -287,13 +288,10 @@ def check_shard_route(n=1000, world=4, capacity=None, kind=None, seed=0, skew=0.
     lws = [T(lw[r * n:(r + 1) * n]) for r in range(world)]
     if fused in ("tiles", "stats"):        # the two-collective form: tile statistics -> totals + global max, no CDF array
         sb = int(be.c.gmx_shard_stats_bytes(n))
-        pad = (n + 1023) // 1024
-        pad += pad & 1
         stats_all = torch.zeros((world * sb,), dtype=torch.uint8, device=dev)
         for r in range(world):
-            blk = stats_all[r * sb:(r + 1) * sb]
-            be.check(be.c.gmx_tile_stats(be.ptr(lws[r]), n, shift, be.ptr(blk[pad * 8:]), be.ptr(blk), be.stream()),
-                     "gmx_tile_stats")
+            agg, tmax = stats_views(stats_all[r * sb:(r + 1) * sb], n)
+            be.check(be.c.gmx_tile_stats(be.ptr(lws[r]), n, shift, be.ptr(tmax), be.ptr(agg), be.stream()), "gmx_tile_stats")
         max_d = torch.zeros((1,), dtype=torch.float32, device=dev)
         be.check(be.c.gmx_shard_totals(be.ptr(stats_all), world, n, be.ptr(totals), be.ptr(max_d), be.stream()),
                  "gmx_shard_totals")

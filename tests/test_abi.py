@@ -133,6 +133,7 @@ def test_specialisation_compiles_offline():
 def test_entry_points_reject_null_arguments_before_any_launch():
     """Host-side validation comes first: with null pointers every entry point returns non-zero and leaves
     a message in gmx_last_error() — nothing reaches the GPU (runs on a box without one)."""
+    from genjax_amd import _lib
     so = os.path.join(ROOT, "genjax_amd", "lib", "libgenmi_hip.so")
     lib = ctypes.CDLL(so)
     lib.gmx_last_error.restype = ctypes.c_char_p
@@ -168,6 +169,11 @@ def test_entry_points_reject_null_arguments_before_any_launch():
         "gmx_shard_plan": (i32(0), N, N, i32(0), i32(4), i64(10), N, N),
         "gmx_shard_route": (i32(0), N, N, N, i32(0), i32(4), i64(10), i64(4), N, N, N, N),
         "gmx_shard_step": (i32(0), N, N, N, N, N, i32(0), i32(4), i64(10), i64(4), N, N, N, N),
+        "gmx_shard_step_sorted": (N, N, N, N, N, i32(0), i32(4), i64(10), i64(4), N, N, N, N),
+        "gmx_peer_put_stats": (N, _lib.Peer(), i64(1024), N),
+        "gmx_shard_step_peer": (i32(0), N, N, _lib.Peer(), N, N, N, N, i32(40), i64(1024), N, N, N, N),
+        "gmx_peer_bump": (N, ctypes.c_int32(1), N),
+        "gmx_sweep_verdict": (N, N, ctypes.c_int32(0), N, N),
         "gmx_graph_launch": (N, N),
         "gmx_capture_end": (N, N),
         "gmx_timer_start": (N, N),
@@ -227,6 +233,120 @@ def test_mirror_and_hip_library_state_the_same_sizes():
     assert hip.gmx_weight_cdf_workspace(1) == 24 and hip.gmx_resample_workspace(1) == 10240      # (the layouts did not move)
 
 
+def _shard_refusal_cases(B, B4, key):
+    """the sharded / peer family (csrc/gmx_sizes.h "sharded resampling and the fused peer exchange"): every distinct refusal
+    of each entry point, as (entry point, arguments, the phrase its message carries).  B: a zeroed 16-byte aligned
+    buffer (as a host array of leaf pointers: null leaves); B4: B + 4."""
+    from genjax_amd import _lib
+    N, i64, i32 = ctypes.c_void_p(0), ctypes.c_int64, ctypes.c_int
+    ok = dict(kind=0, key=key, rank=0, world=2, n=1024, cap=4, shift=40, p=B, lw=B, stats=B, cdf=B)
+
+    def peer(**kw):
+        P = _lib.Peer()
+        P.land_d, P.tag_base_d, P.status_d = B.value, B.value, B.value
+        P.rank, P.world, P.step, P.tiles, P.capacity, P.leaves = 0, 2, 0, 1, 4, 1
+        for f, v in kw.items():
+            setattr(P, f, v)
+        return P
+
+    def call(name, **kw):
+        a = dict(ok, **kw)
+        k, K, p, n, c = i32(a["kind"]), a["key"], a["p"], i64(a["n"]), i64(a["cap"])
+        r, w, sh, lw, st, cdf = i32(a["rank"]), i32(a["world"]), i32(a["shift"]), a["lw"], a["stats"], a["cdf"]
+        P = a.get("peer") or peer()
+        return {
+            "gmx_shard_plan": (k, K, p, r, w, n, p, p, N),
+            "gmx_shard_route": (k, K, p, cdf, r, w, n, c, p, p, p, N),
+            "gmx_shard_step": (k, K, p, p, p, cdf, r, w, n, c, p, p, p, N),
+            "gmx_shard_step_sorted": (cdf, p, p, p, p, r, w, n, c, p, p, p, N),         # (cdf: the table's place)
+            "gmx_shard_totals": (st, w, n, p, p, N),
+            "gmx_shard_step_tiles": (k, K, p, p, p, lw, st, p, sh, r, w, n, c, p, p, p, N),
+            "gmx_shard_step_fused": (k, K, st, p, p, lw, p, sh, r, w, n, c, p, p, p, N),
+            "gmx_peer_put_stats": (st, P, n, N),
+            "gmx_shard_step_peer": (k, K, st, P, p, p, lw, p, sh, n, a.get("rows", p), a.get("rows", p), p, N),
+        }[name]
+
+    cases = []
+
+    def refuse(name, why, **kw):
+        cases.append((name, call(name, **kw), why))
+
+    keyed = ("gmx_shard_plan", "gmx_shard_route", "gmx_shard_step", "gmx_shard_step_tiles", "gmx_shard_step_fused")
+    for name in keyed:
+        refuse(name, b"null key", key=None)
+        refuse(name, b"systematic / stratified only", kind=2)
+        refuse(name, b"rank / world out of range", world=0)
+        refuse(name, b"rank / world out of range", rank=2)
+        refuse(name, b"rank / world out of range", world=1025)
+        refuse(name, b"n_per_rank out of range", n=0)
+        refuse(name, b"n_per_rank out of range", n=2 ** 31)
+        refuse(name, b"null argument", p=N)
+    for name in keyed[1:] + ("gmx_shard_step_sorted",):
+        refuse(name, b"capacity must be in [1, n_per_rank]", cap=0)
+        refuse(name, b"capacity must be in [1, n_per_rank]", cap=1025)
+    for name in keyed[1:]:
+        refuse(name, b"extended state index exceeds int32", n=2 ** 30, cap=2 ** 30)
+    refuse("gmx_shard_step", b"cdf_d must be 16-byte aligned", cdf=B4)
+    for name in keyed[3:]:
+        refuse(name, b"world <= 64", world=65)
+        refuse(name, b"shift out of range", shift=0)
+        refuse(name, b"shift out of range", shift=63)
+        refuse(name, b"lw_d must be 16-byte and stats_", lw=B4)
+        refuse(name, b"8-byte aligned", stats=B4)
+    refuse("gmx_shard_step_tiles", b"(use gmx_weight_cdf + gmx_shard_step)", world=65)
+    refuse("gmx_shard_step_fused", b"n_per_rank too large (<= 2^21)", n=2 ** 21 + 1)
+    refuse("gmx_shard_step_sorted", b"null argument", p=N)
+    refuse("gmx_shard_step_sorted", b"rank / world out of range", world=0)
+    refuse("gmx_shard_step_sorted", b"rank / world out of range", rank=2)
+    refuse("gmx_shard_step_sorted", b"n_per_rank * world out of range (< 2^31)", n=2 ** 30, cap=1)
+    refuse("gmx_shard_step_sorted", b"n_per_rank * world out of range (< 2^31)", n=0)
+    refuse("gmx_shard_step_sorted", b"extended state index exceeds int32", n=2 ** 29, world=3, cap=2 ** 29)
+    refuse("gmx_shard_step_sorted", b"table_d must be 16-byte aligned", cdf=B4)
+    refuse("gmx_shard_totals", b"null argument", p=N)
+    refuse("gmx_shard_totals", b"world out of range", world=0)
+    refuse("gmx_shard_totals", b"world out of range", world=1025)
+    refuse("gmx_shard_totals", b"n_per_rank out of range (< 2^31)", n=0)
+    refuse("gmx_shard_totals", b"n_per_rank out of range (< 2^31)", n=2 ** 31)
+    refuse("gmx_shard_totals", b"stats_all_d must be 8-byte aligned", stats=B4)
+    # gmx_peer, by value: each condition of the peer check, through both entry points that take one
+    refuse("gmx_peer_put_stats", b"null argument", stats=N)
+    for name in ("gmx_peer_put_stats", "gmx_shard_step_peer"):
+        for field in ("land_d", "tag_base_d", "status_d"):
+            refuse(name, b"peer has a null pointer", peer=peer(**{field: None}))
+        refuse(name, b"peer rank / world out of range (world <= 64)", peer=peer(world=65))
+        refuse(name, b"peer.step is negative", peer=peer(step=-1))
+        refuse(name, b"peer.tiles must be ceil(n_per_rank / 1024) <= 2048", peer=peer(tiles=2))
+        refuse(name, b"peer.tiles must be ceil(n_per_rank / 1024) <= 2048", peer=peer(tiles=2049), n=2 ** 21 + 1)
+        refuse(name, b"peer.capacity must be in [1, n_per_rank]", peer=peer(capacity=0))
+        refuse(name, b"peer.capacity must be in [1, n_per_rank]", peer=peer(capacity=1025))
+        refuse(name, b"peer.leaves must be in [1, GMX_PEER_MAX_LEAVES = 32]", peer=peer(leaves=0))
+        refuse(name, b"peer.leaves must be in [1, GMX_PEER_MAX_LEAVES = 32]", peer=peer(leaves=33))
+    refuse("gmx_peer_put_stats", b"peer rank / world out of range (world <= 64)", peer=peer(rank=2))
+    refuse("gmx_peer_put_stats", b"peer rank / world out of range (world <= 64)", peer=peer(world=0))
+    # (the step's own rank / world check comes first and names them without "peer"; its extended-index check cannot
+    #  fire behind the peer check: n_per_rank <= 2^21, world <= 64, capacity <= n_per_rank)
+    name = "gmx_shard_step_peer"
+    refuse(name, b"null key", key=None)
+    refuse(name, b"systematic / stratified only", kind=2)
+    refuse(name, b": rank / world out of range", peer=peer(world=0))
+    refuse(name, b": rank / world out of range", peer=peer(rank=2))
+    refuse(name, b"n_per_rank out of range", n=0)
+    refuse(name, b"null argument", p=N)
+    refuse(name, b"shift out of range", shift=0)
+    refuse(name, b"shift out of range", shift=63)
+    refuse(name, b"lw_d must be 16-byte and stats_own_d 8-byte aligned", lw=B4)
+    refuse(name, b"lw_d must be 16-byte and stats_own_d 8-byte aligned", stats=B4)
+    refuse(name, b"a leaf pointer is null")                                  # (B as the leaves' host arrays: zeros)
+    cases += [("gmx_peer_bump", (N, i32(1), N), b"bad argument"),
+              ("gmx_peer_bump", (B, i32(0), N), b"bad argument"),
+              ("gmx_sweep_verdict", (N, B, i32(1), B, N), b"bad argument (at most 4 status words)"),
+              ("gmx_sweep_verdict", (B, B, i32(1), N, N), b"bad argument (at most 4 status words)"),
+              ("gmx_sweep_verdict", (B, B, i32(5), B, N), b"bad argument (at most 4 status words)"),
+              ("gmx_sweep_verdict", (B, B, i32(-1), B, N), b"bad argument (at most 4 status words)"),
+              ("gmx_sweep_verdict", (B, N, i32(1), B, N), b"bad argument (at most 4 status words)")]
+    return cases
+
+
 def _refusal_cases():
     """(entry point, argument tuple, what the message has to name) for the refusals csrc/gmx_sizes.h states: every one is
     decided before a pointer is read, so one small aligned buffer stands for all of them"""
@@ -277,6 +397,7 @@ def _refusal_cases():
     cases += [("gmx_pick_rows", (Bp, Bp, i64(2), i64(10), i64(9), Bp, Bp, Bp, N), b"ld = 9"),
               ("gmx_pick_rows", (Bp, Bp, i64(0), i64(10), i64(10), Bp, Bp, Bp, N), b"rows = 0"),
               ("gmx_lineage", hist[-2][1], b"must be positive")]
+    cases += _shard_refusal_cases(B, B4, key)
     return cases, (buf, keep1, keep2, keep3)
 
 
@@ -286,7 +407,7 @@ def test_mirror_refusals_carry_the_entry_points_message():
     sees a call the mirror refused (nothing here may reach a launch)."""
     hip, mirror = _hip_and_mirror()
     cases, _keep = _refusal_cases()
-    assert len(cases) >= 100
+    assert len(cases) >= 223
     for name, args, why in cases:
         assert getattr(mirror, name)(*args) != 0, (name, why)
         said = mirror.gmx_last_error()

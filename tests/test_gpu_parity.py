@@ -430,6 +430,8 @@ def test_plates_match_oracle(gpu, n):
     (100_352, 8, {"seed": 6, "capacity": 12_500}), (250_880, 2, {"seed": 7, "skew": 0.5}),
     (101_376, 5, {"seed": 8}), (2048, 4, {"seed": 9, "kind": 1}),
     (2048, 4, {"seed": 12, "spike": 14.0}), (4096, 3, {"seed": 13, "spike": 30.0, "kind": 1}),   # wave-cooperative long runs
+    # the two sides of the fill kernel's SMALL edge (world <= 8 and world * tiles <= 1024): 1024 table rows, then 1032
+    (131_072, 8, {"seed": 31}), (132_096, 8, {"seed": 32}),
 ])
 @pytest.mark.parametrize("fused", [False, True, "tiles", "stats"])
 def test_global_resampling_routes_match_oracle(gpu, n, world, kw, fused):
