@@ -8,9 +8,9 @@
 // No n-entry CDF array.  Everything after the per-element exp is integer arithmetic, so the index is the one
 // gmx_weight_cdf + gmx_ancestors give for the row, whatever the grid.
 // Under hipcc: the two kernels and the device pieces the whole row-wise family is put together from (gmx_resample_rows.h
-// includes this file): pick_threshold, pick_fixed4 / pick_fixed_scan, pick_group_offsets, rows_store4 and the three phases
-// of the pick of a row of one tile (pick1_*), each stated once, at its definition.  Included by gmx_kernels.hip only (not
-// among the headers embedded for hiprtc).  Under a
+// includes this file): pick_threshold, pick_group_offsets, rows_store4 and the three phases of the pick of a row of one tile
+// (pick1_*), each stated once, at its definition; the four fixed-point weights of a thread are gmx_block.h's
+// gmx_tile_fixed4.  Included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a
 // plain host compiler: the two ENTRY POINTS, the draw as a sequential loop over rows calling gmx_weight_cdf and
 // gmx_ancestors (both declared in genmi.h and exported by a CPU build of the C-ABI; gmx_vm.h includes this file there).
 // That loop validates its arguments as the HIP entry point does and leaves its message (gmx_sizes.h: the checks, gmx_fail).
@@ -65,24 +65,6 @@ __device__ __forceinline__ uint64_t pick_threshold(const uint32_t* __restrict__ 
   return pick_threshold(total, (uint64_t)(gmx_bits32(key, j) >> 9));
 }
 
-// A thread's four fixed-point weights (columns base .. base + 3 against the tile's reference; columns >= n weigh 0) as
-// running sums q[0 .. 3]; returns their sum q[3]
-__device__ __forceinline__ uint64_t pick_fixed4(const float x[4], int64_t base, int64_t n, float ref, float scale, uint64_t q[4]) {
-  uint64_t run = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    run += (base + c < n) ? weight_fixed(x[c], ref, scale) : 0ull;
-    q[c] = run;
-  }
-  return run;
-}
-// ... and the wave-inclusive scan of that sum (`run`): column base + c's CDF value inside the wave is (scan - run) + q[c]
-__device__ __forceinline__ uint64_t pick_fixed_scan(const float x[4], int64_t base, int64_t n, float ref, float scale,
-                                                    uint64_t q[4], uint64_t& run) {
-  run = pick_fixed4(x, base, n, ref, scale, q);
-  return wave_scan_u64(run);
-}
-
 // A row held by waves grp * W .. grp * W + W - 1 of the workgroup, each wave's inclusive sum in s[wave]: the sum of the
 // group's waves before `wave`, and the row's total
 template <int W>
@@ -131,7 +113,8 @@ __device__ __forceinline__ uint64_t pick1_put_scan(const float x[4], int64_t bas
 #pragma unroll
   for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
   const float ref = gmx_tile_ref(gmx_tile_exp(M));       // one tile: K = k_b, cdf_i = the tile-local inclusive sum
-  const uint64_t inc = pick_fixed_scan(x, base, n, ref, scale, q, run);
+  run = gmx_tile_fixed4(x, base, n, false, ref, scale, q);
+  const uint64_t inc = wave_scan_u64(run);
   if (lane == 63) s_scan[wave] = inc;
   return inc;
 }
@@ -173,7 +156,7 @@ k_pick_stats(const float* __restrict__ logits, int64_t n, int64_t ld, int64_t n_
   float m = gmx_rmax(gmx_rmax(x[0], x[1]), gmx_rmax(x[2], x[3]));
   m = block_max(m, lds4);
   uint64_t q[4];
-  const uint64_t run = pick_block_sum(pick_fixed4(x, base, n, gmx_tile_ref(gmx_tile_exp(m)), scale, q), lds8);
+  const uint64_t run = pick_block_sum(gmx_tile_fixed4(x, base, n, false, gmx_tile_ref(gmx_tile_exp(m)), scale, q), lds8);
   if (threadIdx.x == 0) {
     tmax[r * n_tiles + blockIdx.x] = m;
     agg[r * n_tiles + blockIdx.x] = run;
@@ -232,8 +215,9 @@ k_pick_row(const uint32_t* __restrict__ keys, const float* __restrict__ logits, 
   const int64_t base = b * GMX_PICK_TILE + (int64_t)tid * 4;
   float x[4];
   pick_load4(logits + r * ld, base, n, x);
-  uint64_t q[4], run;
-  const uint64_t inc = pick_fixed_scan(x, base, n, gmx_tile_ref(k_b), scale, q, run);
+  uint64_t q[4];
+  const uint64_t run = gmx_tile_fixed4(x, base, n, false, gmx_tile_ref(k_b), scale, q);
+  const uint64_t inc = wave_scan_u64(run);
   __syncthreads();
   if (lane == 63) lds8[wave] = inc;
   __syncthreads();

@@ -155,6 +155,60 @@ __device__ __forceinline__ uint64_t weight_fixed(float lw, float ref, float scal
   return gmx_exp_fixed(lw - ref, (int)(gmx_f2u(scale) >> 23) - 127);
 }
 
+// ---- the local CDF of one 1024-column tile held by a workgroup of 256 threads, four consecutive columns to the thread:
+// the pieces gmx_shard_fill.h, k_tile_stats, k_mn_tile, k_shard_step<true> and the row-wise draws (gmx_backward.h) are put
+// together from (gmx_offspring.h writes the same phases out and says why).  None of them holds a barrier. ----
+#define CDF_VEC 4                      /* consecutive columns per thread (one float4) */
+// a branch on a workgroup-uniform condition whose body is a few vector instructions: left alone, hipcc turns it into
+// selects on the scalar condition (every lane issues both sides — measured: MORE vector instructions than the per-lane
+// compare it replaced); an empty volatile asm in the body cannot be speculated, so the scalar branch stays a branch
+#define GMX_KEEP_BRANCH asm volatile("")
+// The log-weights of columns i0 .. i0 + 3 of n.  `whole` (workgroup-uniform): every column of the tile exists — one 16-byte
+// load; otherwise four loads at clamped addresses (unconditional: nothing waits), and a column at or past n reads as -inf.
+template <typename I>
+__device__ __forceinline__ void gmx_tile_load4(const float* __restrict__ lw, I i0, I n, bool whole, float x[CDF_VEC]) {
+  if (whole) {
+    const float4 v = *reinterpret_cast<const float4*>(lw + i0);
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+  } else {
+#pragma unroll
+    for (int c = 0; c < CDF_VEC; ++c) {
+      const I ic = i0 + c < n ? i0 + c : n - 1;
+      const float xv = lw[ic];
+      x[c] = (i0 + c < n) ? xv : -gmx_inf();
+    }
+  }
+}
+// Their fixed-point weights against the tile's reference as running sums q[0 .. 3]; returns the sum q[3].  A column at or
+// past n weighs 0: its weight is evaluated under the column's condition; with `whole` (as above) there is no condition.
+template <typename I>
+__device__ __forceinline__ uint64_t gmx_tile_fixed4(const float x[CDF_VEC], I i0, I n, bool whole, float ref, float scale,
+                                                    uint64_t q[CDF_VEC]) {
+  uint64_t run = 0;
+  if (whole) {
+#pragma unroll
+    for (int c = 0; c < CDF_VEC; ++c) {
+      run += weight_fixed(x[c], ref, scale);
+      q[c] = run;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < CDF_VEC; ++c) {
+      run += (i0 + c < n) ? weight_fixed(x[c], ref, scale) : 0ull;
+      q[c] = run;
+    }
+  }
+  return run;
+}
+// The tile-local mass before the thread's columns: `inc` the wave-inclusive scan of its sum `run`, s_scan[w] lane 63's `inc`
+// of wave w (LDS, behind the caller's barrier).  `wave_s`: the wave's index in a scalar register — the selects are scalar.
+__device__ __forceinline__ uint64_t gmx_tile_local_pos(const uint64_t* s_scan, int wave_s, uint64_t inc, uint64_t run) {
+  uint64_t wave_off = 0;
+#pragma unroll
+  for (int w = 0; w < GMX_BLOCK / GMX_WAVE; ++w) wave_off += (w < wave_s) ? s_scan[w] : 0ull;
+  return wave_off + (inc - run);
+}
+
 // ---- tile statistics -> tile prefixes, ONCE per resampling (include/genmi.h: gmx_tile_prefix) ----
 // One workgroup of 256 threads turns the <= 2048 (m_b, A_b) into M, K = ceil(M / ln 2), the exclusive prefixes
 // P_b = sum_{b' < b} A_b' >> (K - k_b'), and the total.  Thread t owns the `per` consecutive tiles [t per, (t+1) per)

@@ -1190,9 +1190,6 @@ extern "C" int gmx_sum_rows(const float* x_d, int64_t rows, int64_t cols, float*
 #define CDF_THREADS 1024               /* 16 waves: 4 per SIMD, enough to hide the load + look-back latency */
 #endif
 #define CDF_WAVES (CDF_THREADS / GMX_WAVE)
-#ifndef CDF_VEC
-#define CDF_VEC 4                      /* consecutive items per thread (one float4) */
-#endif
 #define CDF_TILE (CDF_THREADS * CDF_VEC)
 static_assert(CDF_THREADS % 256 == 0 && CDF_VEC * 256 == GMX_TILE, "a definition tile of the CDF is 1024 items = 256 threads");
 static_assert(CDF_TILE == GMX_SCAN_TILE, "gmx_weight_cdf's workspace (gmx_sizes.h) holds one descriptor per scan tile");
@@ -1708,29 +1705,22 @@ struct rs_ws {                 // layout of the gmx_resample workspace
 };
 
 
-__global__ void __launch_bounds__(RS_THREADS)
+__global__ void __launch_bounds__(GMX_BLOCK)
 k_tile_stats(const float* __restrict__ lw, int64_t n, float scale, float* __restrict__ tmax, uint64_t* __restrict__ agg) {
   __shared__ float lds4[4];
-  __shared__ uint64_t s_sum[RS_THREADS / GMX_WAVE];
+  __shared__ uint64_t s_sum[GMX_BLOCK / GMX_WAVE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)threadIdx.x * CDF_VEC;
+  const bool whole = (int64_t)(blockIdx.x + 1) * RS_TILE <= n;
   float x[CDF_VEC];
-  if (base + CDF_VEC <= n) {
-    float4 v = *reinterpret_cast<const float4*>(lw + base);
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < CDF_VEC; ++c) x[c] = (base + c < n) ? lw[base + c] : -gmx_inf();
-  }
+  gmx_tile_load4(lw, base, n, whole, x);
   float m = -gmx_inf();
 #pragma unroll
   for (int c = 0; c < CDF_VEC; ++c) m = gmx_rmax(m, x[c]);
   m = block_max(m, lds4);
   const float ref = gmx_tile_ref(gmx_tile_exp(m));
-  uint64_t run = 0;
-#pragma unroll
-  for (int c = 0; c < CDF_VEC; ++c) run += (base + c < n) ? weight_fixed(x[c], ref, scale) : 0ull;
-  run = wave_sum_u64(run);
+  uint64_t q[CDF_VEC];
+  const uint64_t run = wave_sum_u64(gmx_tile_fixed4(x, base, n, false, ref, scale, q));      // (masked also for a whole tile: 6 VGPRs less)
   if (lane == 0) s_sum[wave] = run;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1743,7 +1733,7 @@ k_tile_stats(const float* __restrict__ lw, int64_t n, float scale, float* __rest
 
 // (k_offspring_tile's body: csrc/gmx_offspring.h — shared with the specialised site programs that resample first)
 template <int kind, int PER>
-__global__ void __launch_bounds__(RS_BLOCK)
+__global__ void __launch_bounds__(GMX_BLOCK)
 k_offspring_tile(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __restrict__ lw,
                  const float* __restrict__ tmax, const uint64_t* __restrict__ agg, int64_t n, int n_tiles, float scale,
                  float* __restrict__ max_out, uint64_t* __restrict__ total_out, int32_t* __restrict__ anc,
@@ -1774,7 +1764,7 @@ static int launch_offspring_tile(int kind, const uint32_t key[2], const float* l
                                  int32_t* ancestors_d, gmx_stream stream, bool pref = false, const uint32_t* u_d = nullptr) {
   const uint32_t u0 = host_u0_(key[0], key[1]);
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
-  const dim3 grid((unsigned)((tiles + RS_TPB - 1) / RS_TPB)), block(RS_BLOCK);
+  const dim3 grid((unsigned)tiles), block(GMX_BLOCK);
   const float scale = gmx_pow2i(shift);
   auto launch = [&](auto k, auto per) {
     hipLaunchKernelGGL((k_offspring_tile<decltype(k)::value, decltype(per)::value>), grid, block, 0, (hipStream_t)stream, key[0],
@@ -1782,7 +1772,7 @@ static int launch_offspring_tile(int kind, const uint32_t key[2], const float* l
   };
   offspring_for_kind_(kind, [&](auto k) {
     if (pref) launch(k, std::integral_constant<int, 0>{});      // PER = 0: `tile_agg_d` is the prefix block gmx_tile_prefix wrote
-    else tiles_for_per_(tiles, RS_BLOCK, [&](auto per) { launch(k, per); });
+    else tiles_for_per_(tiles, GMX_BLOCK, [&](auto per) { launch(k, per); });
   });
   GMX_HIP(hipGetLastError());
   return 0;
@@ -1793,7 +1783,7 @@ extern "C" int gmx_tile_stats(const float* lw_d, int64_t n, int shift, float* ti
   if (const char* m = gmx_tile_form_refusal_(GMX_FORM_STATS, 0, n, shift, !lw_d || !tile_max_d || !tile_agg_d, lw_d))
     return gmx_fail(m, "gmx_tile_stats");
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
-  hipLaunchKernelGGL(k_tile_stats, dim3((unsigned)tiles), dim3(RS_THREADS), 0, (hipStream_t)stream, lw_d, n,
+  hipLaunchKernelGGL(k_tile_stats, dim3((unsigned)tiles), dim3(GMX_BLOCK), 0, (hipStream_t)stream, lw_d, n,
                      gmx_pow2i(shift), tile_max_d, tile_agg_d);
   GMX_HIP(hipGetLastError());
   return 0;
@@ -1961,18 +1951,9 @@ k_mn_tile(uint32_t k0, uint32_t k1, const float* __restrict__ lw, const float* _
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int my_tile = (int)blockIdx.x;
   const int64_t i0 = (int64_t)my_tile * RS_TILE + (int64_t)tid * CDF_VEC;
+  const bool whole = (int64_t)(my_tile + 1) * RS_TILE <= n;
   float x[CDF_VEC];
-  if ((int64_t)(my_tile + 1) * RS_TILE <= n) {
-    const float4 v = *reinterpret_cast<const float4*>(lw + i0);
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < CDF_VEC; ++c) {
-      const int64_t ic = i0 + c < n ? i0 + c : n - 1;
-      const float xv = lw[ic];
-      x[c] = (i0 + c < n) ? xv : -gmx_inf();
-    }
-  }
+  gmx_tile_load4(lw, i0, n, whole, x);
   // the table: global max (-> K), the total (zero: no mass), and the slots of the tiles before mine
   float tm[PER];
   uint64_t ta[PER];
@@ -1998,12 +1979,9 @@ k_mn_tile(uint32_t k0, uint32_t k1, const float* __restrict__ lw, const float* _
   before = (uint32_t)wave_sum_u64((uint64_t)before);
   const int32_t k_b = gmx_tile_exp(tmax_mine);
   const float ref_b = gmx_tile_ref(k_b);
-  uint64_t q[CDF_VEC], run = 0;
-#pragma unroll
-  for (int c = 0; c < CDF_VEC; ++c) {
-    run += (i0 + c < n) ? weight_fixed(x[c], ref_b, scale) : 0ull;
-    q[c] = run;
-  }
+  uint64_t q[CDF_VEC];
+  // (the masked form also for a whole tile: four weights side by side cost this kernel 4 VGPRs)
+  const uint64_t run = gmx_tile_fixed4(x, i0, n, false, ref_b, scale, q);
   const uint64_t inc = wave_scan_u64(run);
   if (lane == 0) { s_max[wave] = m; s_cb[wave] = before; }
   if (lane == 63) s_scan[wave] = inc;
@@ -2017,10 +1995,7 @@ k_mn_tile(uint32_t k0, uint32_t k1, const float* __restrict__ lw, const float* _
     all += (r * GMX_BLOCK + tid < n_tiles) ? gmx_tile_scale(ta[r], gmx_tile_exp(tm[r]), K) : 0ull;
   all = wave_sum_u64(all);
   if (lane == 0) s_all[wave] = all;
-  uint64_t wave_off = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) wave_off += (w < wave) ? s_scan[w] : 0ull;
-  const uint64_t loc = wave_off + (inc - run);
+  const uint64_t loc = gmx_tile_local_pos(s_scan, wave, inc, run);      // (the vector index: a scalar copy costs PER = 8 a VGPR)
   uint64_t edge[CDF_VEC + 1];                      // scaled local CDF at the lower edge of my first source and after each
   edge[0] = gmx_tile_scale(loc, k_b, K);
 #pragma unroll
@@ -2042,7 +2017,7 @@ k_mn_tile(uint32_t k0, uint32_t k1, const float* __restrict__ lw, const float* _
   gmx_key k2; k2.k0 = k0; k2.k1 = k1;
   const gmx_key kb = gmx_fold_in(k2, (uint32_t)my_tile);
   const int32_t base_i = my_tile * RS_TILE;
-  const int cnt_i = (int64_t)(my_tile + 1) * RS_TILE <= n ? RS_TILE : (int)(n - (int64_t)my_tile * RS_TILE);
+  const int cnt_i = whole ? RS_TILE : (int)(n - (int64_t)my_tile * RS_TILE);
   // a GUIDE over the local CDF instead of a search per slot: bucket g of 1024 covers the positions [g, g + 1) * G_b / 1024;
   // every particle with mass marks the first bucket that starts inside its interval, a max-scan fills the rest, and a
   // slot starts at guide[v >> 13] (its bucket: Q = v * G_b >> 23) and WALKS to the exact answer — the marks come from a
@@ -2291,11 +2266,10 @@ k_sorted_offsets(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, 
   }
 }
 
-#define SORTED_FILL 2048               /* guide entries filled per pass (8 per thread): a tile owns ~1024 */
 __global__ void __launch_bounds__(GMX_BLOCK)
 k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, int64_t n, size_t words, uint32_t* __restrict__ out) {
   __shared__ uint32_t s_last[GMX_BLOCK];
-  __shared__ __attribute__((aligned(16))) uint32_t s_mark[SORTED_FILL];
+  __shared__ __attribute__((aligned(16))) uint32_t s_mark[RS_FILL_SLOTS];
   __shared__ uint32_t s_carry[GMX_BLOCK / GMX_WAVE];
   gmx_key key; key.k0 = hk0; key.k1 = hk1;
   if (keys) {
@@ -2307,7 +2281,6 @@ k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, in
   uint32_t* guide = row + L.off_guide;
   const uint64_t* tsum = reinterpret_cast<const uint64_t*>(row + L.off_tsum);
   const uint64_t* toff = reinterpret_cast<const uint64_t*>(row + L.off_toff);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tile = (int)blockIdx.x, tiles = (int)L.tiles;
   const int64_t j0 = (int64_t)tile * GMX_SORTED_TILE + (int64_t)threadIdx.x * 4;
   const uint4 loc = *reinterpret_cast<const uint4*>(row + j0);
@@ -2315,14 +2288,15 @@ k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, in
   const uint64_t below = toff[tile], stot = toff[tiles];        // k_sorted_offsets wrote them
   const uint32_t sh = row[L.off_sh];
   s_last[threadIdx.x] = loc.w;
-  __syncthreads();
+  gmx_fill_zero(s_mark);
+  __syncthreads();                       // s_last, and the first fill pass's zeroes
   // the tile's slots as low words of the global sums; slot j owns the guide entries (bucket(S_{j-1}), bucket(S_j)]
   const uint32_t lv[4] = {loc.x, loc.y, loc.z, loc.w};
   const int32_t gA = tile == 0 ? 0 : (int32_t)(below >> sh) + 1;             // the tile's first guide entry ...
   const int32_t gB = (int32_t)((below + own) >> sh);                         // ... and its last (buckets < NG < 2^22)
   uint64_t prev = below + (threadIdx.x ? s_last[threadIdx.x - 1] : 0u);      // S_{j0 - 1}
   uint32_t lowv[4];
-  int32_t st[4], en[4];                                                      // entries [st, en] get the value j
+  int32_t st[4], en[4], end[4];                                              // entries [st, en] = [st, end) get the value j
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int64_t j = j0 + c;
@@ -2334,33 +2308,16 @@ k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, in
       const int32_t top = (int32_t)(stot >> sh) + 1;
       for (int32_t g = en[c] + 1; g <= top; ++g) guide[g] = (uint32_t)n;
     }
+    end[c] = en[c] + 1;
     prev = S;
   }
   *reinterpret_cast<uint4*>(row + j0) = make_uint4(lowv[0], lowv[1], lowv[2], lowv[3]);
-  // through LDS (k_offspring_tile's fill): a slot marks the first of its entries with j + 1, a max-scan fills the rest
-  // (j increases with the entry), the workgroup stores 8 consecutive entries per thread
-  for (int32_t base = gA; base <= gB; base += SORTED_FILL) {                 // block-uniform trip count (1, rarely 2)
-    reinterpret_cast<uint4*>(s_mark)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    reinterpret_cast<uint4*>(s_mark)[threadIdx.x + GMX_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int32_t lo = st[c] > base ? st[c] : base;
-      if (en[c] >= lo && lo - base < SORTED_FILL) s_mark[lo - base] = (uint32_t)(j0 + c) + 1u;
-    }
-    __syncthreads();
-    uint4 a = reinterpret_cast<const uint4*>(s_mark)[2 * threadIdx.x];
-    uint4 b = reinterpret_cast<const uint4*>(s_mark)[2 * threadIdx.x + 1];
-    a.y = a.y > a.x ? a.y : a.x; a.z = a.z > a.y ? a.z : a.y; a.w = a.w > a.z ? a.w : a.z;
-    b.x = b.x > a.w ? b.x : a.w; b.y = b.y > b.x ? b.y : b.x; b.z = b.z > b.y ? b.z : b.y; b.w = b.w > b.z ? b.w : b.z;
-    const uint32_t incl = gmx_wave_umax_scan(b.w);
-    uint32_t carry = wave_shr1_u32(incl, 0u);
-    if (lane == 63) s_carry[wave] = incl;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < GMX_BLOCK / GMX_WAVE - 1; ++w) { const uint32_t v = s_carry[w]; carry = (w < wave && v > carry) ? v : carry; }
-    a.x = a.x > carry ? a.x : carry; a.y = a.y > carry ? a.y : carry; a.z = a.z > carry ? a.z : carry; a.w = a.w > carry ? a.w : carry;
-    b.x = b.x > carry ? b.x : carry; b.y = b.y > carry ? b.y : carry; b.z = b.z > carry ? b.z : carry; b.w = b.w > carry ? b.w : carry;
+  // through LDS (gmx_fill_pass): slot j marks the first of its entries with j + 1, the workgroup stores 8 consecutive
+  // entries per thread
+#pragma clang loop unroll(disable)      // (not peeled either: one copy of the pass)
+  for (int32_t base = gA; base <= gB; base += RS_FILL_SLOTS) {               // block-uniform trip count (1, rarely 2)
+    uint4 a, b;
+    gmx_fill_pass(base, base != gA, st, end, (uint32_t)j0 + 1u, s_mark, s_carry, a, b);
     const int32_t g = base + 8 * (int32_t)threadIdx.x;
     if (g + 7 <= gB) {
       rs_u32x4_a4 va, vb;
@@ -2378,7 +2335,6 @@ k_sorted_guide(const uint32_t* __restrict__ keys, uint32_t hk0, uint32_t hk1, in
       if (g + 6 <= gB) guide[g + 6] = b.z - 1u;
       if (g + 7 <= gB) guide[g + 7] = b.w - 1u;
     }
-    __syncthreads();
   }
 }
 
@@ -2746,23 +2702,14 @@ k_shard_step(int kind, uint32_t k0, uint32_t k1, const uint64_t* __restrict__ to
       const int32_t K = gmx_tile_exp(*TS.max_g);
       const int32_t k_b = gmx_tile_exp(TS.tmax[my_tile]);
       const float ref_b = gmx_tile_ref(k_b);
-      float x[4];
-      if (i0 + 4 <= n) {
-        float4 v = *reinterpret_cast<const float4*>(TS.lw + i0);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = (i0 + c < n) ? TS.lw[i0 + c] : -gmx_inf();
-      }
+      const bool whole = (int64_t)(my_tile + 1) * RS_TILE <= n;
+      float x[CDF_VEC];
+      gmx_tile_load4(TS.lw, i0, n, whole, x);
       uint64_t below = 0;
       for (int t = (int)threadIdx.x; t < my_tile; t += GMX_BLOCK)
         below += gmx_tile_scale(TS.agg[t], gmx_tile_exp(TS.tmax[t]), K);
-      uint64_t q[4], run = 0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        run += (i0 + c < n) ? weight_fixed(x[c], ref_b, TS.scale) : 0ull;
-        q[c] = run;
-      }
+      uint64_t q[CDF_VEC];
+      const uint64_t run = gmx_tile_fixed4(x, i0, n, whole, ref_b, TS.scale, q);
       const uint64_t inc = wave_scan_u64(run);
       below = wave_sum_u64(below);
       if (lane == 0) s_below[wave] = below;

@@ -7,13 +7,9 @@
 #include "gmx_resample.h"
 #include "gmx_sorted.h"
 
-#define CDF_VEC_OT 4
-#ifndef RS_THREADS
-#define RS_THREADS 256                 /* 4 waves per tile                         */
-#endif
-#define RS_TILE (RS_THREADS * CDF_VEC_OT) /* 1024 log-weights per tile = one definition tile of the CDF */
+#define RS_TILE (GMX_BLOCK * CDF_VEC)   /* 1024 log-weights per tile = one definition tile of the CDF */
 #define RS_MAX_TILES GMX_MAX_TILES     /* n <= 2^21                                */
-static_assert(RS_TILE == GMX_TILE && RS_THREADS == GMX_BLOCK, "resampling tiles are the CDF's definition tiles");
+static_assert(RS_TILE == GMX_TILE, "resampling tiles are the CDF's definition tiles");
 static_assert(RS_MAX_TILES % GMX_BLOCK == 0, "tile table shape");
 
 // TAGGED (a site program's prologue): every ancestor is stored as {tag: bits 24..31 | index: bits 0..23} with a
@@ -70,35 +66,28 @@ __device__ __forceinline__ int64_t sorted_below_exact(const sorted_ctx& X, uint6
   return j;
 }
 
-// One thread owns 4 consecutive sources (one float4 of log-weights); 256 threads are one tile; a block is RS_TPB
-// consecutive tiles.  RS_TPB = 1.  Every block has to turn ALL tile statistics into its prefix and the total, and
-// with RS_TPB = 4 (1024 threads) that pass is shared by four tiles — measured on MI355X (config 2): the kernel
-// itself 7.8 -> 7.3 us per launch, but the site program that follows went 13.1 -> 14.9 us: with one tile per
-// 256-thread block, tile j of BOTH kernels runs as block j, i.e. on XCD j mod 8 (blocks are dealt round-robin), so
-// the log-weights, ancestors and states one kernel leaves are found in that XCD's L2 by the other; four consecutive
-// tiles per block put three of them on another XCD.  (An interleaved assignment — tiles b mod 8 + 8 k — would keep the
-// affinity; it needs four separate prefixes per block and gives most of the saving back.)
+// One thread owns 4 consecutive sources (one float4 of log-weights); a workgroup of 256 threads is ONE tile.  Every
+// workgroup has to turn ALL tile statistics into its prefix and the total; four consecutive tiles to a workgroup of 1024
+// threads would share that pass — measured on MI355X (config 2): the kernel itself 7.8 -> 7.3 us per launch, but the
+// site program that follows went 13.1 -> 14.9 us: with one tile per 256-thread block, tile j of BOTH kernels runs as
+// block j, i.e. on XCD j mod 8 (blocks are dealt round-robin), so the log-weights, ancestors and states one kernel
+// leaves are found in that XCD's L2 by the other; four consecutive tiles per block put three of them on another XCD.
 // Every load is issued before anything waits (unconditional, clamped addresses), wave-level reductions and scans are
 // DPP (gmx_block.h), the slot ranges are straight-line f64 code with one cold exact path.
-#define RS_TPB 1
-// a branch on a workgroup-uniform condition whose body is a few vector instructions: left alone, hipcc turns it into
-// selects on the scalar condition (every lane issues both sides — measured: MORE vector instructions than the per-lane
-// compare it replaced); an empty volatile asm in the body cannot be speculated, so the scalar branch stays a branch
-#define GMX_KEEP_BRANCH asm volatile("")
+// The tile's local CDF, the edge settle and the fill through LDS are written out here, in the words of gmx_tile_load4 /
+// gmx_tile_fixed4 / gmx_tile_local_pos (gmx_block.h) and gmx_edge_settle / gmx_fill_pass (gmx_resample.h), which every other
+// tile resampler calls: hipcc optimises a forceinline function on its own before it inlines it (sums reassociated, selects
+// hoisted), and this body's schedule — the headline's — is kept instruction for instruction.  A change to one is a change
+// to the other.
+
 // a 32-bit byte offset widened in the basic block of its access, so that the access takes the [scalar base + offset] form
 // (gmx_jit.h, gmx_jit_ctx::zext_here, says why the copy is needed; it emits nothing)
 __device__ __forceinline__ uint64_t rs_zext_here(uint32_t o) { asm volatile("" : "+v"(o)); return (uint64_t)o; }
-#define RS_BLOCK (GMX_BLOCK * RS_TPB)
-#define RS_WAVES (RS_BLOCK / GMX_WAVE)
-static_assert(RS_MAX_TILES % RS_BLOCK == 0, "tile table shape");
+#define RS_WAVES (GMX_BLOCK / GMX_WAVE)
 // PER: rows of the tile table a thread holds (PER * 256 >= n_tiles; 1, 2, 4 or 8 — the launch picks the smallest):
 // the statistics pass is unrolled over exactly the rows that exist.
-#define RS_FILL_SLOTS 2048             /* slots filled per pass (8 per thread): a tile owns ~1024 */
-// A tile's slots [T0, T1) get their ancestors through LDS: every source with a slot writes its index at its first one,
-// a max-scan fills the rest (source indices increase with the slot), and the block stores 8 consecutive slots per
-// thread (two 16-byte stores): the same cost whatever the weights (a thread writing its own sources' slots in a loop
-// diverges over the offspring counts: measured 2688 -> 34 us for N(0, 4) log-weights); a tile owning more than 2048
-// slots takes more passes (block-uniform).
+// A tile's slots [T0, T1) get their ancestors through LDS (the fill gmx_resample.h describes): the block stores 8
+// consecutive slots per thread (two 16-byte stores).
 template <int kind, int PER, bool TAGGED>
 __device__ __forceinline__ void
 gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __restrict__ lw,
@@ -111,27 +100,24 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   // PER == 0 with agg == nullptr: the tile's prefix, the total and (M, K) arrive as arguments (gmx_tile_table_pass below).
   const int blk = tile0 >= 0 ? tile0 : (int)blockIdx.x;
   const uint32_t tagw = TAGGED ? (tag << GMX_ANC_TAG_SHIFT) : 0u;
-  __shared__ uint64_t s_below[RS_WAVES], s_all[RS_WAVES], s_scan[RS_WAVES], s_g[RS_TPB];
+  __shared__ uint64_t s_below[RS_WAVES], s_all[RS_WAVES], s_scan[RS_WAVES];
   __shared__ float s_max[RS_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);      // the same number in a scalar register: selects on it are scalar
-  // which of the block's tiles / thread within it (one tile per block: the block is GMX_BLOCK threads, and tile_ok and
-  // full_tile below are WORKGROUP-uniform — said so that the compiler keeps them on the scalar unit)
-  const int grp = RS_TPB > 1 ? (int)(threadIdx.x >> 8) : 0, ltid = threadIdx.x & (GMX_BLOCK - 1);
-  const int first_tile = blk * RS_TPB;
-  const int my_tile = first_tile + grp;
-  const bool tile_ok = my_tile < n_tiles;                                        // wave-uniform
-  const int tile_c = tile_ok ? my_tile : n_tiles - 1;
-  const int64_t i0 = (int64_t)tile_c * RS_TILE + (int64_t)ltid * CDF_VEC_OT;
+  // (tile_ok and full_tile are WORKGROUP-uniform: on the scalar unit)
+  const bool tile_ok = blk < n_tiles;
+  const int tile_c = tile_ok ? blk : n_tiles - 1;
+  // (the mask tells a kernel compiled without launch bounds — a specialised site program — that 4 tid stays inside the tile)
+  const int64_t i0 = (int64_t)tile_c * RS_TILE + (int64_t)(threadIdx.x & (GMX_BLOCK - 1)) * CDF_VEC;
   // ---- issue every load first ----
-  float x[CDF_VEC_OT];
-  const bool full_tile = (int64_t)(tile_c + 1) * RS_TILE <= n;                   // wave-uniform
+  float x[CDF_VEC];
+  const bool full_tile = (int64_t)(tile_c + 1) * RS_TILE <= n;
   if (full_tile) {
     float4 v = *reinterpret_cast<const float4*>(lw + i0);
     x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
   } else {
 #pragma unroll
-    for (int c = 0; c < CDF_VEC_OT; ++c) {
+    for (int c = 0; c < CDF_VEC; ++c) {
       const int64_t ic = i0 + c < n ? i0 + c : n - 1;
       const float xv = lw[ic];
       x[c] = (i0 + c < n) ? xv : -gmx_inf();
@@ -141,8 +127,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   // own prefix, the total and (M, K) — three loads instead of a pass over the whole table.
   constexpr bool PREF = (PER == 0);
   constexpr int PERN = PREF ? 1 : PER;
-  static_assert(PER >= 0 && PER * RS_BLOCK <= RS_MAX_TILES, "rows of the tile table per thread");
-  static_assert(!PREF || RS_TPB == 1, "the prefix form works on one tile per block");
+  static_assert(PER >= 0 && PER * GMX_BLOCK <= RS_MAX_TILES, "rows of the tile table per thread");
   uint64_t ta[PERN];
   float tm[PERN];
   const uint32_t tid4 = threadIdx.x * 4u;
@@ -154,15 +139,15 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
 #pragma unroll
     for (int r = 0; r < PERN; ++r) {              // loads only (clamped rows): nothing here waits
       ta[r] = 0ull; tm[r] = -gmx_inf();
-      if (r * RS_BLOCK < n_tiles) {                // uniform: rows of the table that exist
-        if ((r + 1) * RS_BLOCK <= n_tiles) {       // uniform: a whole row — [scalar base of the row] + 8 tid / 4 tid, no
+      if (r * GMX_BLOCK < n_tiles) {                // uniform: rows of the table that exist
+        if ((r + 1) * GMX_BLOCK <= n_tiles) {       // uniform: a whole row — [scalar base of the row] + 8 tid / 4 tid, no
           GMX_KEEP_BRANCH;                         // 64-bit vector add, compare or select per row (gmx_jit.h, gmx_jit_ctx)
-          uint32_t r0 = (uint32_t)(r * RS_BLOCK);     // (opaque, in a scalar register: the row's base is a scalar add — left
+          uint32_t r0 = (uint32_t)(r * GMX_BLOCK);     // (opaque, in a scalar register: the row's base is a scalar add — left
           asm volatile("" : "+s"(r0));                //  to itself hipcc adds an offset past the immediate field per lane)
           ta[r] = *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(agg + r0) + rs_zext_here(tid4 * 2u));
           tm[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(tmax + r0) + rs_zext_here(tid4));
         } else {                                   // the table's last row: clamped
-          const int t = r * RS_BLOCK + (int)threadIdx.x;
+          const int t = r * GMX_BLOCK + (int)threadIdx.x;
           const int tc = t < n_tiles ? t : n_tiles - 1;
           ta[r] = agg[tc];
           tm[r] = tmax[tc];
@@ -183,9 +168,9 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     for (int r = 0; r < PERN; ++r) {
       // only the table's last row can run past n_tiles (uniform): the others keep what they loaded (a row that does
       // not exist holds 0 / -inf from above)
-      if (r * RS_BLOCK < n_tiles && (r + 1) * RS_BLOCK > n_tiles) {
+      if (r * GMX_BLOCK < n_tiles && (r + 1) * GMX_BLOCK > n_tiles) {
         GMX_KEEP_BRANCH;
-        const int t = r * RS_BLOCK + (int)threadIdx.x;
+        const int t = r * GMX_BLOCK + (int)threadIdx.x;
         ta[r] = (t < n_tiles) ? ta[r] : 0ull;
         tm[r] = (t < n_tiles) ? tm[r] : -gmx_inf();
       }
@@ -200,20 +185,20 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   } else {
 #pragma unroll
     for (int r = 0; r < PERN; ++r)
-      if (r * RS_BLOCK < n_tiles) M = gmx_rmax(M, tm[r]);
+      if (r * GMX_BLOCK < n_tiles) M = gmx_rmax(M, tm[r]);
     M = wave_max(M);
   }
-  uint64_t q[CDF_VEC_OT];
+  uint64_t q[CDF_VEC];
   uint64_t run = 0;
 #pragma unroll
-  for (int c = 0; c < CDF_VEC_OT; ++c) q[c] = weight_fixed(x[c], ref_b, scale);
+  for (int c = 0; c < CDF_VEC; ++c) q[c] = weight_fixed(x[c], ref_b, scale);
   if (!(tile_ok && full_tile)) {          // wave-uniform: a full tile has no lane to mask, so no compares and selects
     GMX_KEEP_BRANCH;
 #pragma unroll
-    for (int c = 0; c < CDF_VEC_OT; ++c) q[c] = (tile_ok && i0 + c < n) ? q[c] : 0ull;
+    for (int c = 0; c < CDF_VEC; ++c) q[c] = (tile_ok && i0 + c < n) ? q[c] : 0ull;
   }
 #pragma unroll
-  for (int c = 0; c < CDF_VEC_OT; ++c) {
+  for (int c = 0; c < CDF_VEC; ++c) {
     run += q[c];
     q[c] = run;
   }
@@ -228,10 +213,9 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   }
   uint64_t wave_off = 0;
 #pragma unroll
-  for (int w = 0; w < 4; ++w) wave_off += (w < (wave_s & 3)) ? s_scan[4 * grp + w] : 0ull;   // the tile's own four waves
+  for (int w = 0; w < 4; ++w) wave_off += (w < (wave_s & 3)) ? s_scan[w] : 0ull;   // the tile's own four waves
   const uint64_t loc = wave_off + (inc - run);          // tile-local mass before this thread's sources
-  // phase 2: G_t = A_t * 2^(k_t - K) for every tile -> the mass before this block's first tile, the block's own
-  // four G, and the total
+  // phase 2: G_t = A_t * 2^(k_t - K) for every tile -> the mass before this block's tile, and the total
   const int32_t K = PREF ? (int32_t)(uint32_t)(pf_mk >> 32) : gmx_tile_exp(M);
   uint64_t prefix = 0, total = 0;
   if (PREF) {
@@ -240,16 +224,14 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     uint64_t below = 0, all = 0;
 #pragma unroll
     for (int r = 0; r < PERN; ++r) {
-      if (r * RS_BLOCK < n_tiles) {
-        const int t = r * RS_BLOCK + (int)threadIdx.x;
+      if (r * GMX_BLOCK < n_tiles) {
+        const int t = r * GMX_BLOCK + (int)threadIdx.x;
         const uint64_t G = gmx_tile_scale(ta[r], gmx_tile_exp(tm[r]), K);
         all += G;
-        // workgroup-uniform: a row wholly in front of this block's first tile counts whole, a row wholly at or behind
-        // it not at all — only the row `first_tile` lies in compares per lane (sums of u64: any order, same integers)
-        if ((r + 1) * RS_BLOCK <= first_tile) { GMX_KEEP_BRANCH; below += G; }
-        else if (r * RS_BLOCK < first_tile) { GMX_KEEP_BRANCH; below += (t < first_tile) ? G : 0ull; }
-        if constexpr (RS_TPB > 1)
-          if (t >= first_tile && t < first_tile + RS_TPB) s_g[t - first_tile] = G;      // t >= n_tiles: G = 0
+        // workgroup-uniform: a row wholly in front of this block's tile counts whole, a row wholly at or behind it not
+        // at all — only the row `blk` lies in compares per lane (sums of u64: any order, same integers)
+        if ((r + 1) * GMX_BLOCK <= blk) { GMX_KEEP_BRANCH; below += G; }
+        else if (r * GMX_BLOCK < blk) { GMX_KEEP_BRANCH; below += (t < blk) ? G : 0ull; }
       }
     }
     wave_sum2_u64(below, all);
@@ -257,17 +239,13 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) { prefix += s_below[w]; total += s_all[w]; }
-    if constexpr (RS_TPB > 1) {
-#pragma unroll
-      for (int j = 0; j < RS_TPB; ++j) prefix += (j < grp) ? s_g[j] : 0ull;
-    }
   }
   if (blk == 0 && threadIdx.x == 0) { *total_out = total; *max_out = M; }
-  if (!tile_ok) return;                                  // a whole tile group past the end (uniform per wave; no barrier follows)
+  if (!tile_ok) return;                                  // a tile past the end (workgroup-uniform)
   gmx_key key; key.k0 = k0; key.k1 = k1;
   if (total == 0) {       // no mass at all (all weights -inf / NaN): every slot maps to the last particle
 #pragma unroll
-    for (int c = 0; c < CDF_VEC_OT; ++c)
+    for (int c = 0; c < CDF_VEC; ++c)
       if (i0 + c < n) {
         if (TAGGED) gmx_store_u32_sc1(reinterpret_cast<uint32_t*>(anc) + (i0 + c), (uint32_t)(n - 1) | tagw);
         else anc[i0 + c] = (int32_t)(n - 1);
@@ -278,18 +256,16 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
   const double eps = (double)n * 0x1p-44 + 0x1p-40;
   const int32_t n32 = (int32_t)n;
   // CDF values at the lower edge of the thread's first source and at the upper edge of each source
-  uint64_t cv[CDF_VEC_OT + 1];
+  uint64_t cv[CDF_VEC + 1];
   cv[0] = prefix + gmx_tile_scale(loc, k_b, K);
 #pragma unroll
-  for (int c = 0; c < CDF_VEC_OT; ++c) cv[c + 1] = prefix + gmx_tile_scale(loc + q[c], k_b, K);
+  for (int c = 0; c < CDF_VEC; ++c) cv[c + 1] = prefix + gmx_tile_scale(loc + q[c], k_b, K);
   if (!full_tile) {                       // (wave-uniform, as above)
     GMX_KEEP_BRANCH;
 #pragma unroll
-    for (int c = 0; c < CDF_VEC_OT; ++c) cv[c + 1] = (i0 + c < n) ? cv[c + 1] : total;
+    for (int c = 0; c < CDF_VEC; ++c) cv[c + 1] = (i0 + c < n) ? cv[c + 1] : total;
   }
-  int32_t e[CDF_VEC_OT + 1];
-  bool near = false;
-  uint32_t near_bits = 0;
+  int32_t e[CDF_VEC + 1];
   constexpr bool SORTED = (kind == GMX_RESAMPLE_MULTINOMIAL_SORTED);      // `uslot` is the order-statistics table
   sorted_ctx SX;
   if constexpr (SORTED) SX = sorted_ctx_of(uslot, n, total, sx_stot, sx_sh);
@@ -297,12 +273,12 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     return slots_below_est<kind == GMX_RESAMPLE_MULTINOMIAL_SORTED ? GMX_RESAMPLE_SYSTEMATIC : kind>(
         key, u0_host, c, total, n_over_total, eps, n32, uslot);              // (never called for the sorted kind)
   };
-  sb_est R[CDF_VEC_OT + 1];
+  sb_est R[CDF_VEC + 1];
   if constexpr (SORTED) {
     // the evaluations side by side: every guide read issued before any is used, then every slot probe — written one
     // evaluation after the other, the (rare) walk past the probed slots orders the loads: ten dependent round trips.
     // (cv[0]: only wave 0 evaluates its own — see below)
-    uint32_t mv[CDF_VEC_OT + 1], gv[CDF_VEC_OT + 1], lov[CDF_VEC_OT + 1], hiv[CDF_VEC_OT + 1], kv[CDF_VEC_OT + 1];
+    uint32_t mv[CDF_VEC + 1], gv[CDF_VEC + 1], lov[CDF_VEC + 1], hiv[CDF_VEC + 1], kv[CDF_VEC + 1];
     auto eval = [&](const int c0, const int c1) {
 #pragma unroll
       for (int c = c0; c <= c1; ++c) {
@@ -326,7 +302,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
         hiv[c] = hiv[c] < (uint32_t)n32 ? hiv[c] : (uint32_t)n32;
         lov[c] = lov[c] < hiv[c] ? lov[c] : hiv[c];
       }
-      rs_u32x4_a4 pa[CDF_VEC_OT + 1], pb[CDF_VEC_OT + 1];
+      rs_u32x4_a4 pa[CDF_VEC + 1], pb[CDF_VEC + 1];
 #pragma unroll
       for (int c = c0; c <= c1; ++c) {        // eight slots per evaluation (past slot n - 1: still inside the table, not counted)
         pa[c] = *reinterpret_cast<const rs_u32x4_a4*>(SX.slow + lov[c]);
@@ -359,27 +335,29 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
       }
     };
     R[0].j = 0; R[0].near = false;
-    eval(1, CDF_VEC_OT);
+    eval(1, CDF_VEC);
     if (wave == 0) eval(0, 0);
   } else {
 #pragma unroll
-    for (int c = 1; c <= CDF_VEC_OT; ++c) R[c] = below_est(cv[c]);
+    for (int c = 1; c <= CDF_VEC; ++c) R[c] = below_est(cv[c]);
     R[0].j = 0; R[0].near = false;
     if (__builtin_amdgcn_readfirstlane(wave) == 0) R[0] = below_est(cv[0]);        // wave-uniform: a scalar branch
   }
+  // lower bound of the thread's first source (cv[0]) = upper bound of the previous thread's last one (its cv[4]): lanes take
+  // it from their neighbour below (gmx_edge_settle), lane 0 of waves 1 .. 3 from the wave before through LDS (s_edge:
+  // published after the cold path, so a corrected value travels; read behind the barrier that precedes the slot fill), and
+  // only lane 0 of wave 0 uses an evaluation of its own (the tile's first edge)
+  bool near = false;
+  uint32_t near_bits = 0;
 #pragma unroll
-  for (int c = 1; c <= CDF_VEC_OT; ++c) {
+  for (int c = 1; c <= CDF_VEC; ++c) {
     e[c] = R[c].j;
     near_bits |= R[c].near ? (1u << c) : 0u;
   }
-  // lower bound of the thread's first source (cv[0]) = upper bound of the previous thread's last one (its cv[4]): lanes take
-  // it from their neighbour below, lane 0 of waves 1 .. 3 from the wave before through LDS (s_edge: published after the
-  // cold path, so a corrected value travels; read behind the barrier that precedes the slot fill), and only lane 0 of
-  // wave 0 uses an evaluation of its own (the tile's first edge)
   {
     const sb_est r = R[0];
     near_bits |= (lane == 0 && r.near) ? 1u : 0u;
-    e[0] = (int32_t)wave_shr1_u32((uint32_t)e[CDF_VEC_OT], (uint32_t)r.j);
+    e[0] = (int32_t)wave_shr1_u32((uint32_t)e[CDF_VEC], (uint32_t)r.j);
     if (lane == 0) e[0] = r.j;
   }
   near = near_bits != 0u;
@@ -388,7 +366,7 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
     const uint64_t D = (uint64_t)n << 23;
     int32_t fixed0 = e[0];
 #pragma unroll 1
-    for (int c = 0; c <= CDF_VEC_OT; ++c) {
+    for (int c = 0; c <= CDF_VEC; ++c) {
       if (near_bits & (1u << c)) {
         const uint64_t cc = c == 0 ? cv[0] : c == 1 ? cv[1] : c == 2 ? cv[2] : c == 3 ? cv[3] : cv[4];
         const int32_t j0 = c == 0 ? e[0] : c == 1 ? e[1] : c == 2 ? e[2] : c == 3 ? e[3] : e[4];
@@ -399,36 +377,32 @@ gmx_offspring_tile_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float*
       }
     }
     // a corrected upper bound is the next lane's lower bound
-    const uint32_t up = wave_shr1_u32((uint32_t)e[CDF_VEC_OT], (uint32_t)fixed0);
+    const uint32_t up = wave_shr1_u32((uint32_t)e[CDF_VEC], (uint32_t)fixed0);
     e[0] = (lane == 0) ? fixed0 : (int32_t)up;
   }
   __shared__ int32_t s_edge[RS_WAVES];
-  if (lane == 63) s_edge[wave] = e[CDF_VEC_OT];      // the (settled) upper edge of this wave, for lane 0 of the next
+  if (lane == 63) s_edge[wave] = e[CDF_VEC];      // the (settled) upper edge of this wave, for lane 0 of the next
   // Sources past n have e[c] = n = e of the last real source, so they own no slot.
   const int32_t e4 = e[4];
   // the marks carry the step's tag already: (src0 + c) | tagw == src0t + c (the index field cannot carry into bit 24), every
   // compared mark has the same tag and an empty one is 0, so the max-scan gives the tagged maxima and no store ORs anything
   const uint32_t src0t = (uint32_t)(int32_t)i0 | tagw;
-  static_assert(RS_TPB == 1, "the LDS fill works on one tile per block");
   __shared__ __attribute__((aligned(16))) uint32_t s_mark[RS_FILL_SLOTS];
   __shared__ int32_t s_rng[2];
   __shared__ uint32_t s_carry[RS_WAVES];
   if (threadIdx.x == 0) s_rng[0] = e[0];
-  if (threadIdx.x == RS_BLOCK - 1) s_rng[1] = e4;
-  reinterpret_cast<uint4*>(s_mark)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-  reinterpret_cast<uint4*>(s_mark)[threadIdx.x + RS_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
+  if (threadIdx.x == GMX_BLOCK - 1) s_rng[1] = e4;
+  gmx_fill_zero(s_mark);
+  __syncthreads();                       // the first pass's zeroes, T0 and T1, s_edge
   if (lane == 0 && wave > 0) e[0] = s_edge[wave - 1];
   const int32_t T0 = __builtin_amdgcn_readfirstlane(s_rng[0]), T1 = __builtin_amdgcn_readfirstlane(s_rng[1]);
   for (int32_t base = T0; base < T1; base += RS_FILL_SLOTS) {      // block-uniform trip count (1 unless the tile owns > 2048 slots)
     if (base != T0) {
-      reinterpret_cast<uint4*>(s_mark)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-      reinterpret_cast<uint4*>(s_mark)[threadIdx.x + RS_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
+      gmx_fill_zero(s_mark);
       __syncthreads();
     }
-    // a source's first slot inside this pass (clipped at `base`: a range that began in an earlier pass continues at 0)
 #pragma unroll
-    for (int c = 0; c < CDF_VEC_OT; ++c) {
+    for (int c = 0; c < CDF_VEC; ++c) {
       const int32_t lo = e[c] > base ? e[c] : base;
       if (e[c + 1] > lo && lo - base < RS_FILL_SLOTS) s_mark[lo - base] = src0t + (uint32_t)c;
     }
@@ -483,7 +457,7 @@ gmx_tile_table_pass(const float* __restrict__ tmax, const uint64_t* __restrict__
   __shared__ uint64_t s_acc[RS_WAVES][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float M = -gmx_inf();
-  for (int t = (int)threadIdx.x; t < n_tiles; t += RS_BLOCK) M = gmx_rmax(M, tmax[t]);
+  for (int t = (int)threadIdx.x; t < n_tiles; t += GMX_BLOCK) M = gmx_rmax(M, tmax[t]);
   M = wave_max(M);
   if (lane == 0) s_tm[wave] = M;
   __syncthreads();
@@ -496,12 +470,12 @@ gmx_tile_table_pass(const float* __restrict__ tmax, const uint64_t* __restrict__
   for (int c = 0; c < C; ++c) {
     const int lo = c * G, hi = (lo + G < n_tiles) ? lo + G : n_tiles, mine = lo + blk;
     uint64_t tot = 0, part = 0;
-    for (int tb = lo; tb < hi; tb += RS_BLOCK) {      // a row of 256 entries: wholly in front of `mine` / straddling it / behind
+    for (int tb = lo; tb < hi; tb += GMX_BLOCK) {      // a row of 256 entries: wholly in front of `mine` / straddling it / behind
       const int t = tb + (int)threadIdx.x;
       if (t < hi) {
         const uint64_t g_ = gmx_tile_scale(agg[t], gmx_tile_exp(tmax[t]), K);
         tot += g_;
-        if (tb + RS_BLOCK <= mine) { GMX_KEEP_BRANCH; part += g_; }          // (workgroup-uniform)
+        if (tb + GMX_BLOCK <= mine) { GMX_KEEP_BRANCH; part += g_; }          // (workgroup-uniform)
         else if (tb < mine) { GMX_KEEP_BRANCH; part += (t < mine) ? g_ : 0ull; }
       }
     }

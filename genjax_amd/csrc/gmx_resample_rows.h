@@ -479,8 +479,9 @@ k_rows_tile(const uint32_t* __restrict__ keys, const float* __restrict__ lw, int
   gmx_tile_prefix_block(tm, agg + r * n_tiles, n_tiles, s_pref, lds4, lds8);
   const int32_t k_b = gmx_tile_exp(tmax_mine);
   const float ref_b = gmx_tile_ref(k_b);
-  uint64_t q[4], run;
-  const uint64_t inc = pick_fixed_scan(x, base, n, ref_b, scale, q, run);
+  uint64_t q[4];
+  const uint64_t run = gmx_tile_fixed4(x, base, n, false, ref_b, scale, q);
+  const uint64_t inc = wave_scan_u64(run);
   __syncthreads();                                       // s_pref is written; lds8 has been read
   if (lane == 63) lds8[wave] = inc;
   __syncthreads();

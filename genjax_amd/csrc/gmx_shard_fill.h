@@ -9,9 +9,6 @@
 #include "gmx_peer.h"
 
 #define SHARD_MAX_WORLD 64
-#ifndef CDF_VEC
-#define CDF_VEC 4                      /* consecutive items per thread (one float4) */
-#endif
 
 // f(c) = number of slots j in [0, n_out) with P_j < c * D, i.e. with
 //   j + u_j / 2^23 < v,  v = c * n_out / total.
@@ -122,23 +119,15 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   __shared__ uint32_t s_carry[4];
   __shared__ uint32_t s_gave_up[4];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);      // the same number in a scalar register: selects on it are scalar
   const int my_tile = (int)blockIdx.x;
   const int32_t i0 = my_tile * RS_TILE + tid * CDF_VEC;
   const int32_t N = n * world, base = rank * n;
   gmx_key key; key.k0 = k0; key.k1 = k1;
   // ---- loads first: this tile's log-weights ----
   float x[CDF_VEC];
-  if ((my_tile + 1) * RS_TILE <= n) {
-    const float4 v = *reinterpret_cast<const float4*>(lw + i0);
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < CDF_VEC; ++c) {
-      const int32_t ic = i0 + c < n ? i0 + c : n - 1;
-      const float xv = lw[ic];
-      x[c] = (i0 + c < n) ? xv : -gmx_inf();
-    }
-  }
+  const bool whole = (my_tile + 1) * RS_TILE <= n;               // workgroup-uniform: every column of the tile exists
+  gmx_tile_load4(lw, i0, n, whole, x);
   // PEER: `stats_all` is this rank's own block; the other ranks' rows are granules in the landing block
   const uint8_t* own = PEER ? stats_all : stats_all + (size_t)rank * stride;
   const float tmax_mine = gmx_stats_block_at(own, n_tiles).tmax[my_tile];
@@ -200,12 +189,8 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   m = wave_max(m);
   const int32_t k_b = gmx_tile_exp(tmax_mine);
   const float ref_b = gmx_tile_ref(k_b);
-  uint64_t q[CDF_VEC], run = 0;
-#pragma unroll
-  for (int c = 0; c < CDF_VEC; ++c) {
-    run += (i0 + c < n) ? weight_fixed(x[c], ref_b, scale) : 0ull;
-    q[c] = run;
-  }
+  uint64_t q[CDF_VEC];
+  const uint64_t run = gmx_tile_fixed4(x, i0, n, whole, ref_b, scale, q);
   const uint64_t inc = wave_scan_u64(run);
   if (lane == 0) s_max[wave] = m;
   if (lane == 63) s_scan[wave] = inc;
@@ -333,10 +318,7 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   // (a) the slot runs of my 4 sources
   const double n_over_total = (double)N / (double)total;
   const double eps = (double)N * 0x1p-44 + 0x1p-40;
-  uint64_t wave_off = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) wave_off += (w < wave) ? s_scan[w] : 0ull;
-  const uint64_t loc = wave_off + (inc - run);
+  const uint64_t loc = gmx_tile_local_pos(s_scan, wave_s, inc, run);
   const uint64_t prefix = cdf_offset + ((s_below[0] + s_below[1]) + (s_below[2] + s_below[3]));
   uint64_t cv[CDF_VEC + 1];
   cv[0] = prefix + gmx_tile_scale(loc, k_b, K);
@@ -345,42 +327,19 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   // sources past the shard's end own no slot: their upper edge is the last real source's
 #pragma unroll
   for (int c = 0; c < CDF_VEC; ++c) cv[c + 1] = (i0 + c < n) ? cv[c + 1] : cv[c];
-  int32_t e[CDF_VEC + 1];
-  uint32_t near_bits = 0;
+  sb_est R[CDF_VEC + 1];
 #pragma unroll
-  for (int c = 1; c <= CDF_VEC; ++c) {
-    const sb_est r = slots_below_est<kind>(key, u0_host, cv[c], total, n_over_total, eps, N);
-    e[c] = r.j;
-    near_bits |= r.near ? (1u << c) : 0u;
-  }
-  {
-    const sb_est r = slots_below_est<kind>(key, u0_host, cv[0], total, n_over_total, eps, N);
-    near_bits |= (lane == 0 && r.near) ? 1u : 0u;
-    e[0] = (int32_t)wave_shr1_u32((uint32_t)e[CDF_VEC], (uint32_t)r.j);
-    if (lane == 0) e[0] = r.j;
-  }
-  if (__any(near_bits != 0u)) {          // cold: the exact integer predicate for the flagged evaluations
-    const uint64_t D = (uint64_t)N << 23;
-    int32_t fixed0 = e[0];
-#pragma unroll 1
-    for (int c = 0; c <= CDF_VEC; ++c) {
-      if (near_bits & (1u << c)) {
-        const uint64_t cc = c == 0 ? cv[0] : c == 1 ? cv[1] : c == 2 ? cv[2] : c == 3 ? cv[3] : cv[4];
-        const int32_t j0 = c == 0 ? e[0] : c == 1 ? e[1] : c == 2 ? e[2] : c == 3 ? e[3] : e[4];
-        const int32_t j = (int32_t)slots_below_exact(kind, key, (uint64_t)u0_host, cc, D, total, (int64_t)j0, (int64_t)N);
-        if (c == 0) fixed0 = j; else if (c == 1) e[1] = j; else if (c == 2) e[2] = j; else if (c == 3) e[3] = j; else e[4] = j;
-      }
-    }
-    const uint32_t up = wave_shr1_u32((uint32_t)e[CDF_VEC], (uint32_t)fixed0);
-    e[0] = (lane == 0) ? fixed0 : (int32_t)up;
-  }
+  for (int c = 0; c <= CDF_VEC; ++c) R[c] = slots_below_est<kind>(key, u0_host, cv[c], total, n_over_total, eps, N);
+  int32_t e[CDF_VEC + 1];
+  gmx_edge_settle(R, cv, lane, [&](uint64_t c, int32_t j0) -> int32_t {
+    return (int32_t)slots_below_exact(kind, key, (uint64_t)u0_host, c, (uint64_t)N << 23, total, (int64_t)j0, (int64_t)N);
+  }, e);
   // ---- route through LDS ----
   const int32_t e4 = e[CDF_VEC];
   if (tid == 0) s_rng[0] = e[0];
   if (tid == GMX_BLOCK - 1) s_rng[1] = e4;
-  reinterpret_cast<uint4*>(s_mark)[tid] = make_uint4(0u, 0u, 0u, 0u);
-  reinterpret_cast<uint4*>(s_mark)[tid + GMX_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
+  gmx_fill_zero(s_mark);
+  __syncthreads();                       // the first pass's zeroes, T0 and T1, s_bounds
   const int32_t T0 = __builtin_amdgcn_readfirstlane(s_rng[0]), T1 = __builtin_amdgcn_readfirstlane(s_rng[1]);
   const int32_t S = s_bounds[rank];          // the first slot whose ancestor lives on this rank
   if (blockIdx.x == 0 && tid == 0) {       // published for inspection / tests; the overflow word is left alone
@@ -412,32 +371,10 @@ gmx_shard_fill_body(uint32_t k0, uint32_t k1, uint32_t u0_host, const float* __r
   };
   if (!PEER) remote_slots();
   for (int32_t pass = T0; pass < T1; pass += RS_FILL_SLOTS) {      // block-uniform (1 pass unless the tile owns > 2048 slots)
-    if (pass != T0) {
-      __syncthreads();
-      reinterpret_cast<uint4*>(s_mark)[tid] = make_uint4(0u, 0u, 0u, 0u);
-      reinterpret_cast<uint4*>(s_mark)[tid + GMX_BLOCK] = make_uint4(0u, 0u, 0u, 0u);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < CDF_VEC; ++c) {
-      const int32_t lo = e[c] > pass ? e[c] : pass;
-      if (e[c + 1] > lo && lo - pass < RS_FILL_SLOTS) s_mark[lo - pass] = (uint32_t)(i0 + c);
-    }
-    __syncthreads();
-    uint4 a = reinterpret_cast<const uint4*>(s_mark)[2 * tid];
-    uint4 b = reinterpret_cast<const uint4*>(s_mark)[2 * tid + 1];
-    a.y = a.y > a.x ? a.y : a.x; a.z = a.z > a.y ? a.z : a.y; a.w = a.w > a.z ? a.w : a.z;
-    b.x = b.x > a.w ? b.x : a.w; b.y = b.y > b.x ? b.y : b.x; b.z = b.z > b.y ? b.z : b.y; b.w = b.w > b.z ? b.w : b.z;
-    const uint32_t incl = gmx_wave_umax_scan(b.w);
-    uint32_t carry = wave_shr1_u32(incl, 0u);
-    if (lane == 63) s_carry[wave] = incl;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 3; ++w) { const uint32_t v = s_carry[w]; carry = (w < wave && v > carry) ? v : carry; }
-    uint32_t src[8];
-    src[0] = a.x > carry ? a.x : carry; src[1] = a.y > carry ? a.y : carry; src[2] = a.z > carry ? a.z : carry;
-    src[3] = a.w > carry ? a.w : carry; src[4] = b.x > carry ? b.x : carry; src[5] = b.y > carry ? b.y : carry;
-    src[6] = b.z > carry ? b.z : carry; src[7] = b.w > carry ? b.w : carry;
+    // the marks are bare source indices (`put` ships them): a tagged store ORs the tag in
+    uint4 a, b;
+    gmx_fill_pass(pass, pass != T0, e, e + 1, (uint32_t)i0, s_mark, s_carry, a, b);
+    const uint32_t src[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     const int32_t j = pass + 8 * tid;
     if (j < T1) {
       int32_t d = 0;                                              // owner of slot j: j / n
