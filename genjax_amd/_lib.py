@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
                     c_size_t, c_uint32, c_uint64, c_void_p)
 
 import torch
@@ -275,6 +275,11 @@ class Backend:
         c.gmx_pick_rows_take.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32,
                                          c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                          c_void_p, c_void_p]
+        c.gmx_pmmh_propose.argtypes = [POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        c.gmx_pmmh_accept.argtypes = [POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int,
+                                      c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
         c.gmx_capture_begin.argtypes = [c_void_p]
         c.gmx_capture_end.argtypes = [c_void_p, POINTER(c_void_p)]
         c.gmx_graph_launch.argtypes = [c_void_p, c_void_p]

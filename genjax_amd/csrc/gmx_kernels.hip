@@ -3687,6 +3687,51 @@ extern "C" int gmx_pick_rows_take(const uint32_t* keys_d, const float* logits_d,
 }
 
 // ---------------------------------------------------------------------------
+// particle marginal Metropolis-Hastings over a bank of filters (gmx_pmmh.h): the two launches that open and close an
+// iteration.  Each entry point: its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
+// ---------------------------------------------------------------------------
+#include "gmx_pmmh.h"
+
+// (leaves_d is a table ON THE DEVICE: its entries are the kernel's to read, so a null leaf cannot be refused here)
+extern "C" int gmx_pmmh_propose(const uint32_t key[2], uint32_t* it_d, const float* theta_d, const float* scale_d, int32_t P,
+                                int64_t R, int64_t n, int32_t T, uint32_t* keys_prop_d, uint32_t* keys_res_d,
+                                float* const* leaves_d, float* theta_prop_d, gmx_stream stream) {
+  const char* who = "gmx_pmmh_propose";
+  const gmx_refusal no = gmx_pmmh_propose_refusal_(
+      !key || !it_d || !theta_d || !scale_d || !keys_prop_d || !keys_res_d || !leaves_d || !theta_prop_d, P, R, n, T);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{it_d, 3}, {theta_d, 3}, {scale_d, 3}, {theta_prop_d, 3}, {keys_prop_d, 7}, {keys_res_d, 7},
+                                      {leaves_d, 7}})) return 1;
+  const unsigned blocks = (unsigned)((R * n + GMX_PMMH_SPAN - 1) / GMX_PMMH_SPAN);
+  hipLaunchKernelGGL(k_pmmh_propose, dim3(blocks), dim3(GMX_PMMH_BLOCK), gmx_pmmh_lds_bytes_(P, n), (hipStream_t)stream, key[0],
+                     key[1], it_d, theta_d, scale_d, (uint32_t)P, (uint32_t)R, (uint32_t)n, (uint32_t)T, keys_prop_d, keys_res_d,
+                     leaves_d, theta_prop_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmx_pmmh_accept(const uint32_t key[2], uint32_t* it_d, const float* maxs_d, const uint64_t* totals_d,
+                               const int32_t* flags_d, int32_t T, int64_t R, int32_t P, int shift, double shift_ln2,
+                               double log_n, const float* lp_prop_d, float* theta_d, double* ll_d, float* lp_d,
+                               const float* theta_prop_d, float* rec_theta_d, double* rec_ll_d, uint8_t* rec_acc_d,
+                               const int64_t* rec_base_d, int64_t cap, int64_t* status_d, gmx_stream stream) {
+  const char* who = "gmx_pmmh_accept";
+  const gmx_refusal no = gmx_pmmh_accept_refusal_(
+      !key || !it_d || !maxs_d || !totals_d || !lp_prop_d || !theta_d || !ll_d || !lp_d || !theta_prop_d || !rec_theta_d ||
+          !rec_ll_d || !rec_acc_d || !rec_base_d || !status_d, P, R, T, shift, cap);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{it_d, 3}, {maxs_d, 3}, {flags_d, 3}, {lp_prop_d, 3}, {theta_d, 3}, {lp_d, 3}, {theta_prop_d, 3},
+                                      {rec_theta_d, 3}, {totals_d, 7}, {ll_d, 7}, {rec_ll_d, 7}, {rec_base_d, 7}, {status_d, 7}}))
+    return 1;
+  const gmx_pmmh_chains C = gmx_pmmh_chains_of_(maxs_d, totals_d, flags_d, T, R, P, shift_ln2, log_n, lp_prop_d, theta_d, ll_d, lp_d,
+                                               theta_prop_d, rec_theta_d, rec_ll_d, rec_acc_d);
+  hipLaunchKernelGGL(k_pmmh_accept, dim3((unsigned)((R + GMX_PMMH_BLOCK - 1) / GMX_PMMH_BLOCK)), dim3(GMX_PMMH_BLOCK), 0,
+                     (hipStream_t)stream, key[0], key[1], it_d, C, rec_base_d, cap, (unsigned long long*)status_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------
 struct gmx_graph { hipGraph_t graph; hipGraphExec_t exec; };

@@ -4,7 +4,8 @@
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
 //                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
-//                             the tile-form resamplers, the row-wise draws, the sharded / peer family, the sweep history
+//                             the tile-form resamplers, the row-wise draws, the particle-MH pair, the sharded / peer family,
+//                             the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
 // Plain host C++ (static inline): no HIP, no kernel, no algorithm.  hiprtc never sees this file (it is not among the
@@ -275,6 +276,39 @@ static inline size_t gmx_resample_rows_ess_bytes_(int kind, int64_t rows, int64_
 }
 // an ess_q8 above this resamples every row with mass (the ESS of n weights is at most n)
 static inline uint32_t gmx_ess_always_(int64_t n) { return (uint32_t)(256 * n); }
+
+// ---- particle marginal Metropolis-Hastings over a bank of filters: gmx_pmmh_propose, gmx_pmmh_accept (gmx_pmmh.h) ----
+#define GMX_PMMH_BLOCK 256             /* threads per workgroup of both kernels */
+#define GMX_PMMH_SPAN 1024             /* consecutive particles of the flat [R * n] axis a workgroup of the proposal broadcasts to */
+#define GMX_PMMH_MAX_P 8               /* parameters: the proposal parks P draws per chain of its span in LDS (<= 32 KB) */
+// chains a span of 1024 consecutive particles can touch: floor(1022 / n) + 2 (n = 1: 1024; n >= 1023: 2)
+static inline int32_t gmx_pmmh_span_chains_(int64_t n) { return (int32_t)((GMX_PMMH_SPAN - 2) / n + 2); }
+static inline size_t gmx_pmmh_lds_bytes_(int32_t P, int64_t n) { return (size_t)P * (size_t)gmx_pmmh_span_chains_(n) * sizeof(float); }
+// what both entry points say about P, R and T
+static inline gmx_refusal gmx_pmmh_shape_refusal_(int32_t P, int64_t R, int32_t T) {
+  if (P < 1 || P > GMX_PMMH_MAX_P) return {"%s: P = %lld is outside [1, 8] (the proposals of a workgroup's chains are held in LDS)", (long long)P};
+  if (R < 1 || R > 0x7fffffffLL) return {"%s: R = %lld is outside [1, 2^31)", (long long)R};
+  if (T < 1) return {"%s: T = %lld is not positive", (long long)T};
+  if ((int64_t)T * R > 0x7fffffffLL) return {"%s: T * R = %lld does not stay below 2^31", (long long)((int64_t)T * R)};
+  return {nullptr, 0};
+}
+static inline gmx_refusal gmx_pmmh_propose_refusal_(bool has_null, int32_t P, int64_t R, int64_t n, int32_t T) {
+  if (has_null) return {"%s: null argument", 0};
+  const gmx_refusal no = gmx_pmmh_shape_refusal_(P, R, T);
+  if (no.fmt) return no;
+  if (n < 1 || n > 0x7fffffffLL) return {"%s: n = %lld is outside [1, 2^31)", (long long)n};
+  if (R * n > 0x7fffffffLL) return {"%s: R * n = %lld does not stay below 2^31 (the bank's flat particle axis)", (long long)(R * n)};
+  return {nullptr, 0};
+}
+// flags_d may be null (every step counts); the iteration recorded in row cap - 1 has to fit fold_in's 32 bits
+static inline gmx_refusal gmx_pmmh_accept_refusal_(bool has_null, int32_t P, int64_t R, int32_t T, int shift, int64_t cap) {
+  if (has_null) return {"%s: null argument", 0};
+  const gmx_refusal no = gmx_pmmh_shape_refusal_(P, R, T);
+  if (no.fmt) return no;
+  if (shift < 1 || shift > 62) return {"%s: shift = %lld is outside [1, 62]", (long long)shift};
+  if (cap < 1 || cap > (1LL << 32)) return {"%s: cap = %lld is outside [1, 2^32] (an iteration is fold_in's 32-bit word)", (long long)cap};
+  return {nullptr, 0};
+}
 
 // ---- sharded resampling and the fused peer exchange: gmx_shard_plan, _route, _step, _step_sorted, _totals, _step_tiles,
 // _step_fused, gmx_peer_put_stats, gmx_shard_step_peer, gmx_peer_bump, gmx_sweep_verdict ----

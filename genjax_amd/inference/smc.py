@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from ctypes import c_uint32
 
 import numpy as np
@@ -2654,3 +2654,211 @@ class ConditionalBank(BootstrapBank):
         if self.tuple_state is not None:
             return self.tuple_state(torch.stack([o[d] for o in out]) for d in range(self.D))
         return torch.stack(out)
+
+
+# ---------------------------------------------------------------------------
+# particle marginal Metropolis-Hastings over a bank of filters
+# ---------------------------------------------------------------------------
+PMMH_MAX_PARAMS = 8                     # GMX_PMMH_MAX_P (csrc/gmx_sizes.h): the proposal kernel's LDS layout
+ParticleMHResult = namedtuple("ParticleMHResult", ["theta", "log_ml", "accepted"])
+
+
+def _prior_logpdf(prior, addrs, values, out, specialize=False, launch=True, who="ParticleMH"):
+    """out[0, r] = prior.assess({addrs[p]: values[p][r]}, ())[0] in float32 over the R = out.shape[1] chains in ONE launch:
+    the prior's `assess` traced once over a batch of R, every site constrained to a per-chain leaf values[p] ([R] each).
+    Built as _ancestor_logits builds the per-particle program: cached on the model, the leaves' kinds and `specialize`
+    (specialised once, when built); launch=False builds it only.  A prior whose sites are not exactly `addrs` is refused
+    by name."""
+    from .. import tracer as Tr
+    from ..engine import Compiled, Flat, Tracing, leaf_spec
+    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
+    batch = (int(out.shape[-1]),)
+    flat = Flat()
+    for v in values:
+        flat.add(v)
+    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
+    ck = (_gfkey(prior), specs, tuple(addrs), "prior", bool(specialize))
+    ent = _BACKWARD_CACHE.get(ck)
+    if ent is None:
+        tr = Tracing(1)
+        ctx = _Ctx(tr)
+        ctx.store_sites = False
+        with Tr.tracing(tr.graph):
+            syms = [tr.sym_leaf(s_, j) for j, s_ in enumerate(specs)]
+            con = ChoiceMap.empty()
+            for p, a in enumerate(addrs):
+                con = con.set(a, syms[p])
+            try:
+                rec, _, _, sc = call_gen_fn(ctx, "assess", prior, None, (), con, None, None, None, ())
+                sites = list(rec.sites)
+            except MissingAddress as e:
+                sites = [a for a in e.args if a != ()]
+            if set(sites) != set(addrs) or len(sites) != len(addrs):
+                extra = [a for a in sites if a not in addrs]
+                unused = [a for a in addrs if a not in sites]
+                raise ValueError(f"{who}: the prior's sites are not exactly param_addrs = {tuple(addrs)!r}"
+                                 + (f"; it samples {extra!r}, which is not a parameter" if extra else "")
+                                 + (f"; it has no site {unused!r}" if unused else ""))
+            o = tr.emit_output(Tr.as_float(sc))
+        comp = Compiled(tr)
+        if specialize:
+            comp.specialize()
+        ent = (comp, o)
+        _BACKWARD_CACHE[ck] = ent
+    if not launch:
+        return
+    comp, o = ent
+    bufs = [None] * len(comp.outputs)
+    bufs[o[1]] = out
+    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+
+
+class ParticleMH(_Sweep):
+    """Particle marginal Metropolis-Hastings (PMMH: Andrieu, Doucet & Holenstein 2010, section 2.4.2) over the P
+    parameters of a state-space model: R independent random-walk chains, chain r driving filter r of a
+    BootstrapBank(init, step, n, R, T, params=theta0, ...) it owns — the bank's programs, stores and launches untouched.
+    The models are called as the bank calls them: init(*params_r), step(x_prev, *step_extra(t), *params_r).  `prior`: a
+    `@gen` function of no arguments with one scalar site per entry of `param_addrs` (parameter p is the site
+    param_addrs[p] and the p-th entry of `params_r`); `step_size`: P positive floats, the standard deviations of the
+    random-walk proposal (no transforms, no adaptation).
+
+    One iteration, enqueue(), is a fixed chain of launches with no sync, no allocation and no host read of a device value —
+    so capture() makes it one graph replay:
+      1. gmx_pmmh_propose   the proposals theta' (iteration 0: theta' = theta, the start is evaluated), broadcast over the
+                            bank's per-particle parameter leaves, and the bank's T x R key tables;
+      2. the prior program  log prior(theta'_r) for every chain, one `assess` program over a batch of R;
+      3. bank.enqueue()     the sweep: per step one site program over the R * n particles and one row resampling;
+      4. gmx_pmmh_accept    the evidence of every chain's sweep from the exact-integer (maxs, totals) in float64 on the
+                            device, the decision log u < (float32)((ll' - ll) + (lp' - lp)), the chains' state, the record.
+    The iteration count lives in two device words.  A chain starts at ll = -inf, lp = 0: iteration 0 accepts any start
+    whose sweep carries mass.  A proposal outside the prior's support (lp' = -inf), or one whose sweep lost all mass
+    against a finite current state, is never accepted (NaN rejects).
+
+    Key schedule, under the ONE key of prepare(): k_it = fold_in(key, j) for iteration j (counted from prepare());
+    (k_bank, k_prop, k_acc) = split(k_it, 3); chain r's sweep runs under split(k_bank, R)[r], its proposal for parameter p
+    is the normal draw under split(split(k_prop, R)[r], P)[p], its uniform under split(k_acc, R)[r].
+
+    Contract: under the keys split(k_bank_j, R) and the parameters theta'_j, the sweep of iteration j is, row for row and
+    bit for bit, what BootstrapBank(..., params=theta'_j).prepare(those keys, ys) gives launched on its own; every
+    decision is gmx_mh_accept's on the float32 log_alpha.
+
+    Limits: 1 <= P <= 8 (the proposal kernel holds P draws per chain of a workgroup in LDS); whatever BootstrapBank
+    refuses (rejuvenate=, history=, comm=, ...) is refused by it, by name."""
+
+    def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
+                 state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):
+        self.param_addrs = tuple(param_addrs)
+        self.P = len(self.param_addrs)
+        if self.P < 1 or self.P > PMMH_MAX_PARAMS:
+            raise NotImplementedError(f"ParticleMH: {self.P} parameters; param_addrs names between 1 and {PMMH_MAX_PARAMS} "
+                                      "(gmx_pmmh_propose holds the draws of a workgroup's chains in LDS)")
+        if len(set(self.param_addrs)) != self.P:
+            raise ValueError(f"ParticleMH: param_addrs = {self.param_addrs!r} names a site twice")
+        try:
+            sizes = [float(s) for s in step_size]
+        except TypeError:
+            sizes = None
+        if sizes is None or len(sizes) != self.P or not all(math.isfinite(s) and s > 0.0 for s in sizes):
+            raise ValueError(f"ParticleMH: step_size is {self.P} positive floats, one per entry of param_addrs; got {step_size!r}")
+        self.step_size = tuple(sizes)
+        self.prior = prior
+        self.specialize = specialize
+        self.bank = BootstrapBank(init, step, n_particles, n_chains, T, obs_addr=obs_addr, resample=resample,
+                                  step_extra=step_extra, specialize=specialize, state_addr=state_addr,
+                                  ess_threshold=ess_threshold, **bank_kw)
+        self.n, self.R, self.T = self.bank.n, self.bank.R, self.bank.T
+        self.done = self.max_iters = 0
+
+    def prepare(self, key: Key, ys: torch.Tensor, theta0, max_iters: int):
+        """ONE key; theta0: P float32 [R] tensors, the chains' starts; max_iters: how many iterations run() may be asked
+        for in all (the record slabs hold that many rows).  Every buffer is allocated here."""
+        be = _lib.get()
+        self._drop_graph()
+        P, R, n, T = self.P, self.R, self.n, self.T
+        dev = be.device
+        if tuple(key.shape) != ():
+            raise ValueError(f"ParticleMH.prepare takes ONE key (the chains' keys are split from it); got a batch of shape "
+                             f"{tuple(key.shape)}")
+        theta0 = tuple(theta0) if isinstance(theta0, (tuple, list)) else (theta0,)
+        theta0 = tuple(torch.as_tensor(v) for v in theta0)
+        if len(theta0) != P or any(tuple(v.shape) != (R,) for v in theta0):
+            raise ValueError(f"ParticleMH.prepare: theta0 is {P} tensors of shape {(R,)}, one per entry of param_addrs; got "
+                             f"{[tuple(v.shape) for v in theta0]}")
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters >= 2 ** 32:
+            raise ValueError(f"ParticleMH.prepare: max_iters = {max_iters} is outside [1, 2^32) (an iteration is fold_in's "
+                             "32-bit word)")
+        self.key, self._key_c = key, _key_words(key)
+        self.bank.params = tuple(v.to(dev).float() for v in theta0)
+        self.bank.prepare(split(split(fold_in(key, 0), 3)[0], R), ys)
+        self.theta = torch.stack(self.bank.params).contiguous()                      # [P, R]
+        self.theta_prop = self.theta.clone()
+        self.scale = torch.tensor(self.step_size, dtype=torch.float32, device=dev)
+        self.lp_prop = torch.zeros((1, R), dtype=torch.float32, device=dev)
+        self.ll = torch.full((R,), -math.inf, dtype=torch.float64, device=dev)
+        self.lp = torch.zeros((R,), dtype=torch.float32, device=dev)
+        self.it = torch.zeros((2,), dtype=torch.int32, device=dev)                   # the iteration words (uint32)
+        self.rec_theta = torch.zeros((max_iters, P, R), dtype=torch.float32, device=dev)
+        self.rec_ll = torch.zeros((max_iters, R), dtype=torch.float64, device=dev)
+        self.rec_acc = torch.zeros((max_iters, R), dtype=torch.uint8, device=dev)
+        self.rec_base = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.status = torch.zeros((1,), dtype=torch.int64, device=dev)               # iterations outside the record
+        self.leaves = torch.tensor([v.data_ptr() for v in self.bank.params_full], dtype=torch.int64, device=dev)
+        self.shift_ln2, self.log_n = self.bank.shift * math.log(2.0), math.log(n)    # as evidence_terms computes them
+        self.max_iters, self.done = max_iters, 0
+        self._prior(launch=False)
+        return self
+
+    def _prior(self, launch=True):
+        _prior_logpdf(self.prior, self.param_addrs, [self.theta_prop[p] for p in range(self.P)], self.lp_prop,
+                      specialize=self.specialize, launch=launch)
+
+    def enqueue(self):
+        """one iteration on the current stream: gmx_pmmh_propose, the prior program, the bank's sweep, gmx_pmmh_accept —
+        no syncs, no allocations, no host read of a device value"""
+        be = _lib.get()
+        b = self.bank
+        be.check(be.c.gmx_pmmh_propose(self._key_c, be.ptr(self.it), be.ptr(self.theta), be.ptr(self.scale), self.P, self.R,
+                                       self.n, self.T, be.ptr(b.keys_prop), be.ptr(b.keys_res), be.ptr(self.leaves),
+                                       be.ptr(self.theta_prop), be.stream()), "gmx_pmmh_propose")
+        self._prior()
+        b.enqueue()
+        be.check(be.c.gmx_pmmh_accept(self._key_c, be.ptr(self.it), be.ptr(b.maxs), be.ptr(b.totals),
+                                      be.ptr(b.flags) if b.ess_q8 is not None else None, self.T, self.R, self.P, b.shift,
+                                      self.shift_ln2, self.log_n, be.ptr(self.lp_prop), be.ptr(self.theta), be.ptr(self.ll),
+                                      be.ptr(self.lp), be.ptr(self.theta_prop), be.ptr(self.rec_theta), be.ptr(self.rec_ll),
+                                      be.ptr(self.rec_acc), be.ptr(self.rec_base), self.max_iters, be.ptr(self.status),
+                                      be.stream()), "gmx_pmmh_accept")
+
+    def capture(self):
+        """Capture one iteration into a hipGraph (_Sweep.capture).  Its warm-up enqueue() runs outside the capture and
+        ADVANCES the chains by one iteration, so the iteration words, the chains' state (theta, log_ml, log_prior), the
+        record base and the status word are saved before and restored afterwards: capture() leaves the chains where
+        they were (the record row the warm-up wrote is written again by the iteration it belongs to)."""
+        saved = [(t, t.clone()) for t in (self.it, self.theta, self.ll, self.lp, self.rec_base, self.status)]
+        super().capture()
+        for t, was in saved:
+            t.copy_(was)
+        return self
+
+    def run(self, iters: int) -> ParticleMHResult:
+        """`iters` more iterations of every chain (the chains continue from where the last run() left them); one sync,
+        at the end.  Returns theta [iters, P, R] float32, log_ml [iters, R] float64 (the evidence estimate the chain
+        holds after each iteration) and accepted [iters, R] bool."""
+        iters = int(iters)
+        if iters < 0 or self.done + iters > self.max_iters:
+            raise ValueError(f"ParticleMH.run: {self.done} iterations done and {iters} asked for, past max_iters = "
+                             f"{self.max_iters} (prepare(..., max_iters=) sizes the record)")
+        self.rec_base.fill_(self.done)                 # a device write: this run's iterations land in rows 0 .. iters - 1
+        for _ in range(iters):
+            self.launch()
+        self.done += iters
+        out = ParticleMHResult(self.rec_theta[:iters].clone(), self.rec_ll[:iters].clone(), self.rec_acc[:iters] != 0)
+        missed = int(self.status.item())               # (synchronises)
+        if missed:
+            raise _lib.GenmiError(f"ParticleMH.run: {missed} iterations fell outside the record")
+        return out
+
+    def state(self):
+        """(theta [P, R] float32, log_ml [R] float64, log_prior [R] float32) of the chains now"""
+        return self.theta.clone(), self.ll.clone(), self.lp.clone()

@@ -801,6 +801,60 @@ int gmx_pick_rows_take(const uint32_t* keys_d /* [rows, 2] */, const float* logi
                        int64_t next_ld, int64_t* status_d /* [1] */, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Particle marginal Metropolis-Hastings  (additive, ABI still v8.  Reference call site: none of its own — PMMH, Andrieu,
+ * Doucet & Holenstein 2010, section 2.4.2: R independent random-walk chains over model parameters, chain r driving filter
+ * r of a bank of R filters of n particles and T steps, whose evidence the row resamplers leave as exact integers.)
+ * One iteration is  gmx_pmmh_propose | the caller's prior program (lp_prop_d) | the bank's sweep | gmx_pmmh_accept; the
+ * iteration count lives in two device words it_d[2] (the caller zeroes them), so the chain of launches is capturable.
+ * Keys of iteration j under the run key:  k_it = fold_in(key, j);  (k_bank, k_prop, k_acc) = split(k_it, 3).
+ *   gmx_pmmh_propose   j = it_d[0].  DEFINITION:
+ *                     1. keys_prop_d[t, r], keys_res_d[t, r] = children 0 and 1 of fold_in(split(k_bank, R)[r], t): the
+ *                        bank's key tables under the R keys split(k_bank, R);
+ *                     2. theta_prop_d[p, r] = theta_d[p, r] when j = 0 (the first iteration evaluates the start), else
+ *                        the normal draw at counter 0 under split(split(k_prop, R)[r], P)[p] with location theta_d[p, r]
+ *                        and scale scale_d[p]: z * scale rounded, then + theta rounded (float32);
+ *                     3. leaves_d[p][r * n + i] = theta_prop_d[p, r] for i < n — leaves_d: a table of P device pointers,
+ *                        itself ON THE DEVICE, 8-byte aligned; each leaf [R * n] float32;
+ *                     4. it_d[1] = j + 1.
+ *                   ONE launch, one workgroup per 1024 consecutive particles: the draws of the chains it touches are
+ *                   computed once and held in LDS (4 P bytes per chain, at most 32 KB), one barrier, then 16-byte stores
+ *                   where the address allows; the T * R key rows are spread over the same grid.
+ *                   Limits: 1 <= P <= 8;  1 <= R, n;  R * n < 2^31;  T >= 1, T * R < 2^31; no null pointer; every pointer
+ *                   aligned to its element (the key tables to 8 bytes).
+ *   gmx_pmmh_accept    j = it_d[1] - 1;  row = j - rec_base_d[0].  DEFINITION, for every chain r:
+ *                     1. ll' = the sum, in ascending t and in float64, over the COUNTED steps (flags_d[t, r] != 0, and
+ *                        t = T - 1 always; flags_d null: every step) of
+ *                          (((double)ref(maxs_d[t, r]) + log64(totals_d[t, r])) - shift_ln2) - log_n,
+ *                        ref(M) = ceil(M / ln 2) ln 2 in float32 (the reference of the integer CDF), log64 a float64 log
+ *                        with a fixed operation sequence (csrc/gmx_pmmh.h: the same bits on every build); -inf when a
+ *                        counted total is 0.  shift_ln2 = shift * log(2) and log_n = log(n) are the caller's doubles;
+ *                     2. log_alpha = (float)((ll' - ll_d[r]) + ((double)lp_prop_d[r] - (double)lp_d[r]));
+ *                     3. accepted iff log(u) < log_alpha, u the uniform [0, 1) draw at counter 0 under
+ *                        split(k_acc, R)[r] — gmx_mh_accept's rule; a NaN log_alpha rejects.  The caller starts a chain
+ *                        at ll = -inf, lp = 0: iteration 0 accepts any start whose sweep carries mass;
+ *                     4. accepted: theta_d[:, r] = theta_prop_d[:, r], ll_d[r] = ll', lp_d[r] = lp_prop_d[r];
+ *                     5. rec_theta_d[row, :, r], rec_ll_d[row, r], rec_acc_d[row, r] = the chain's state after the decision
+ *                        and the decision (0 / 1).
+ *                   When row is outside [0, cap) no chain is decided, nothing is recorded, and status_d[0] += 1 (once per
+ *                   launch).  Always: it_d[0] = it_d[1].  ONE launch, one thread per chain, no LDS.
+ *                   Limits: P, R and T as above; 1 <= shift <= 62; 1 <= cap <= 2^32; flags_d may be null, nothing else;
+ *                   every pointer aligned to its element.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched.
+ * ---------------------------------------------------------------------- */
+int gmx_pmmh_propose(const uint32_t key[2], uint32_t* it_d /* [2] */, const float* theta_d /* [P, R] */,
+                     const float* scale_d /* [P] */, int32_t P, int64_t R, int64_t n, int32_t T,
+                     uint32_t* keys_prop_d /* [T, R, 2] */, uint32_t* keys_res_d /* [T, R, 2] */,
+                     float* const* leaves_d /* [P] device pointers, on the device */, float* theta_prop_d /* [P, R] */,
+                     gmx_stream stream);
+int gmx_pmmh_accept(const uint32_t key[2], uint32_t* it_d /* [2] */, const float* maxs_d /* [T, R] */,
+                    const uint64_t* totals_d /* [T, R] */, const int32_t* flags_d /* [T, R] or null */, int32_t T, int64_t R,
+                    int32_t P, int shift, double shift_ln2, double log_n, const float* lp_prop_d /* [R] */,
+                    float* theta_d /* [P, R] */, double* ll_d /* [R] */, float* lp_d /* [R] */,
+                    const float* theta_prop_d /* [P, R] */, float* rec_theta_d /* [cap, P, R] */,
+                    double* rec_ll_d /* [cap, R] */, uint8_t* rec_acc_d /* [cap, R] */, const int64_t* rec_base_d /* [1] */,
+                    int64_t cap, int64_t* status_d /* [1] */, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
  * gmx_run_args.peer + gmx_shard_step_peer, no collective launch at all).  gmx_p2p_alloc / _open / _close / _free stay:
  * they are how the fused exchange's landing blocks are allocated and mapped.
