@@ -182,7 +182,7 @@ def value_and_grad(fn):
     def run(*xs):
         import torch
         from . import _lib
-        from .engine import Compiled, Flat, Tracing, leaf_spec, resolve
+        from .engine import Compiled, Flat, leaf_spec, resolve, traced
         from .static import _fnkey
         flat = Flat()
         tree = flat.add(tuple(xs))
@@ -191,15 +191,13 @@ def value_and_grad(fn):
         ck = (_fnkey(fn), tree, specs)
         ent = _VG_CACHE.get(ck)
         if ent is None:
-            tr = Tracing(len(batch))
-            with T.tracing(tr.graph):
-                syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-                ins = [T.as_float(s.value) for s in syms]
+            with traced(specs, len(batch)) as p:
+                ins = [T.as_float(s.value) for s in p.syms]
                 out = T.as_float(fn(*ins))
                 gs = grad(out, ins)
-                oo = tr.emit_output(out)
-                go = [tr.emit_output(g + 0.0) for g in gs]
-            ent = (Compiled(tr), oo, go)
+                oo = p.tr.emit_output(out)
+                go = [p.tr.emit_output(g + 0.0) for g in gs]
+            ent = (Compiled(p.tr), oo, go)
             _VG_CACHE[ck] = ent
         comp, oo, go = ent
         outs = comp.run(flat.leaves, batch, None)

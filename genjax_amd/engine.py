@@ -14,6 +14,7 @@ store in the kernel is one coalesced 256-byte wave access.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import hashlib
 
@@ -877,6 +878,53 @@ class Tracing:
                                                   else self.emit_output(getattr(value, f_.name)))
                                         for f_ in dataclasses.fields(value)})
         return ("const", value)
+
+
+class traced:
+    """THE way a traced program is opened: `with traced(specs, batch_ndim, ...) as p:` makes the Tracing `p.tr`, enters
+    tracer.tracing on its graph and creates the nodes every program starts with, in this order — the leaf symbols
+    `p.syms` in leaf order, then (key=True) OP_LDKEY as `p.key` — so what the body creates comes after them; the program
+    is compiled from `p.tr` after the block.  Options (what the builders set, no more):
+      hoist            True or a tuple of root keys: a NoiseHoist on the graph while tracing, its leaves after the given
+                       ones; taken off the graph on exit, the draws it handed out left in `p.draws`
+      step_leaf_min    Tracing.step_leaf_min (None: the default)
+      elem_from_index  the elements of ONE vector-valued site on the launch axis (distributions read it off the graph)
+      force            True / False: traced under combinators.forced_loops(force) (None: as the caller found it)"""
+
+    def __init__(self, specs, batch_ndim: int, key: bool = False, hoist=None, step_leaf_min=None, elem_from_index=False,
+                 force=None):
+        self.tr, self.specs, self.draws = Tracing(batch_ndim), specs, ()
+        self._key, self._hoist, self._force = key, hoist, force
+        if step_leaf_min is not None:
+            self.tr.step_leaf_min = step_leaf_min
+        if elem_from_index:
+            self.tr.graph.elem_from_index = True
+
+    def __enter__(self):
+        from . import tracer as T
+        from .combinators import forced_loops
+        tr, g = self.tr, self.tr.graph
+        with contextlib.ExitStack() as scopes:          # (a leaf that cannot be bound leaves nothing entered)
+            scopes.enter_context(T.tracing(g))
+            if self._force is not None:
+                scopes.enter_context(forced_loops(self._force))
+            if self._hoist:
+                g.noise_hoist = NoiseHoist(tr, len(self.specs), self._hoist)
+                scopes.callback(self._take_hoist)
+            self.syms = [tr.sym_leaf(s, j) for j, s in enumerate(self.specs)]
+            self.key = Expr(g.add("LDKEY", dtype="key")) if self._key else None
+            self._scopes = scopes.pop_all()
+        return self
+
+    def __exit__(self, *exc):
+        return self._scopes.__exit__(*exc)
+
+    def _take_hoist(self):
+        self.draws = tuple(self.tr.graph.__dict__.pop("noise_hoist").draws)
+
+    def values(self, tree):
+        """the pytree `tree` (Flat.add) of the leaves' symbolic VALUES"""
+        return unflatten(tree, lambda j: self.syms[j].value)
 
 
 class StepInput(np.ndarray):
@@ -1802,8 +1850,27 @@ def over_the_slots(e) -> bool:
     return isinstance(e, ProgramTooLarge) or (isinstance(e, ValueError) and "exceeds the ABI slot limits" in str(e))
 
 
+def fit_program(trace, one_launch: bool = False):
+    """THE size ladder: `trace(force, chain)` traces and compiles a program into a cache entry; it is tried as traced,
+    then with top-level plates and scans forced into counted loops (combinators.forced_loops), then CUT into a chain of
+    launches (program.split_graph) as traced, then the chain in the loop form — the first form that fits is returned.
+    one_launch: a program that must stay ONE launch (it leaves tile statistics, or a background program draws its
+    noise) stops after the first two.  An error of the first pass that is not about size (over_the_slots) is raised as
+    it is; when no form fits, the FIRST size error is the report."""
+    first_error = None
+    for attempt in range(2 if one_launch else 4):
+        try:
+            return trace(attempt in (1, 3), attempt >= 2)
+        except Exception as e:      # noqa: BLE001
+            if attempt == 0 and not over_the_slots(e):
+                raise
+            first_error = first_error or e
+    raise first_error from None
+
+
 def compile_fitting(tr: Tracing) -> Compiled:
     """`Compiled(tr)`, as a chain of launches when one does not hold it"""
+    # (not fit_program: ONE graph compiled twice, nothing retraced — a plain numeric function has no loop form)
     try:
         return Compiled(tr)
     except Exception as e:      # noqa: BLE001
@@ -1950,15 +2017,13 @@ def elementwise(fn, *xs, key=None):
     ck = (code, tree, specs, key is not None)
     ent = _EW_CACHE.get(ck) if code is not None else None
     if ent is None:
-        tr = Tracing(len(batch))
-        with T.tracing(tr.graph):
-            syms = [tr.sym_leaf(sp, j) for j, sp in enumerate(specs)]
-            ins = unflatten(tree, lambda j: syms[j].value)
-            out = fn(*ins) if key is None else fn(T.Expr(tr.graph.add("LDKEY", dtype="key")), *ins)
-            if isinstance(out, T.Expr) and tr.node_origin.get(id(out.node)) is not None:
+        with traced(specs, len(batch), key=key is not None) as p:
+            ins = p.values(tree)
+            out = fn(*ins) if key is None else fn(p.key, *ins)
+            if isinstance(out, T.Expr) and p.tr.node_origin.get(id(out.node)) is not None:
                 out = out + 0.0           # a pure pass-through still gets its own buffer
-            oo = tr.emit_output(out)
-        ent = (compile_fitting(tr), oo)
+            oo = p.tr.emit_output(out)
+        ent = (compile_fitting(p.tr), oo)
         if code is not None and not fn.__closure__:
             _EW_CACHE[ck] = ent
     comp, oo = ent

@@ -29,7 +29,7 @@ import torch
 from .. import _lib
 from .. import tracer as T
 from ..core.choice_map import ChoiceMap
-from ..engine import Compiled, Flat, Tracing, leaf_spec, resolve, unflatten
+from ..engine import Compiled, Flat, leaf_spec, resolve
 from ..random import Key
 from ..tracer import Expr
 from ..engine import new_cache as _new_program_cache
@@ -47,7 +47,7 @@ def gibbs_categorical(key: Key, gen_fn, args, choices: ChoiceMap, addr, n_catego
     index_offset: the GLOBAL index of this call's first datapoint — datapoints are independent, so a
     dataset sharded over ranks (or processed in chunks) gives the single-call result when every shard
     passes its offset (the Gumbel counter is (index_offset + i)*K + k); no collective is involved."""
-    from ..static import _Ctx, _gfkey, _infer_batch, _sym_constraint, call_gen_fn
+    from ..static import _gfkey, _infer_batch, _sym_constraint, _traced, call_gen_fn
     be = _lib.get()
     if tuple(key.shape) != ():
         raise ValueError("gibbs_categorical takes ONE key for the whole batch (categorical.simulate semantics)")
@@ -65,22 +65,17 @@ def gibbs_categorical(key: Key, gen_fn, args, choices: ChoiceMap, addr, n_catego
     ck = (_gfkey(gen_fn), atree, ctree, specs, addr_t, K)
     ent = _CACHE.get(ck)
     if ent is None:
-        tr = Tracing(len(batch))
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        g = tr.graph
-        with T.tracing(g):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-            sargs = unflatten(atree, lambda j: syms[j].value)
-            scon = _sym_constraint(ctree, syms)
-            kx = g.add("LDKEY", dtype="key")
+        with _traced(specs, len(batch), key=True, store_sites=False) as p:
+            g = p.tr.graph
+            sargs = p.values(atree)
+            scon = _sym_constraint(ctree, p.syms)
             base = Expr(g.add("LDIDX", dtype="i32")) * K            # row counter base i*K
             state = None
             for k in range(K):
-                _, _, _, s = call_gen_fn(ctx, "assess", gen_fn, None, sargs, scon.set(addr_t, k), None, None, None, ())
-                state = g.add("S_CATSTEP", (state, kx, T.as_float(s).node, (base + k).node), imm=k, dtype="cat")
-            out = tr.emit_output(Expr(g.add("CATIDX", (state,), dtype="i32")))
-        ent = (Compiled(tr), out)
+                _, _, _, s = call_gen_fn(p.ctx, "assess", gen_fn, None, sargs, scon.set(addr_t, k), None, None, None, ())
+                state = g.add("S_CATSTEP", (state, p.key.node, T.as_float(s).node, (base + k).node), imm=k, dtype="cat")
+            out = p.tr.emit_output(Expr(g.add("CATIDX", (state,), dtype="i32")))
+        ent = (Compiled(p.tr), out)
         _CACHE[ck] = ent
     comp, out = ent
     outs = comp.run(flat.leaves, batch, key, index_offset=int(index_offset))

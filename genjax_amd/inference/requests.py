@@ -19,9 +19,9 @@ from .. import tracer as T
 from ..autodiff import grad
 from ..core.choice_map import ChoiceMap, Selection
 from ..core.generative import Diff, DiffAnnotate, EditRequest
-from ..engine import Compiled, Flat, Tracing, leaf_spec, resolve, unflatten
-from ..static import (Rejuvenate, _broadcast_score, _build_trace, _Ctx, _emit_rec, _gfkey, _rec_score, _selkey,
-                      _trace_tree, call_gen_fn)
+from ..engine import Compiled, Flat, leaf_spec, resolve, unflatten
+from ..static import (Rejuvenate, _broadcast_score, _build_trace, _emit_rec, _gfkey, _rec_score, _selkey, _trace_tree,
+                      _traced, call_gen_fn)
 from ..tracer import Expr
 from ..engine import new_cache as _new_program_cache
 
@@ -95,14 +95,11 @@ def _run_hmc(req: HMC, key, trace, argdiffs):
     ck = (_gfkey(gen_fn), atree, ptree, etree, specs, _selkey(req.selection), req.L, len(batch))
     ent = _CACHE.get(ck)
     if ent is None:
-        tr = Tracing(len(batch))
-        ctx = _Ctx(tr)
-        g = tr.graph
-        with T.tracing(g):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-            sargs = unflatten(atree, lambda j: syms[j].value)
-            sprev = unflatten(ptree, lambda j: syms[j])
-            eps = T.as_float(unflatten(etree, lambda j: syms[j].value))
+        with _traced(specs, len(batch)) as p:          # (the key is loaded where the momenta are drawn, after the first gradient)
+            tr, ctx, g = p.tr, p.ctx, p.tr.graph
+            sargs = p.values(atree)
+            sprev = unflatten(ptree, lambda j: p.syms[j])
+            eps = T.as_float(p.values(etree))
             chm_all = _prev_choices(sprev)                        # address -> Sym
             sel_addrs = sorted((a for a in chm_all.addresses()
                                 if req.selection[a] and _is_float(chm_all[a].value)), key=repr)

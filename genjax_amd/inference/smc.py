@@ -1357,57 +1357,81 @@ BACKWARD_CHUNK_BYTES = 256 << 20       # ... and at most this much of them in me
 _BACKWARD_CACHE = engine.new_cache()
 
 
+def _assess_program(model, args, leaves, form, emit, refuse, out, specialize=False, launch=True):
+    """THE builder of the programs that score a model's `assess` under a choice map made of leaves, one output, over the
+    n = out.shape[-1] particles of ONE launch.  The leaves are those of `args` (the model's arguments), then `leaves`, one
+    each; `emit(assess, syms, tr)` fills the choice map(s) from the symbols `syms` of the latter and returns what is stored
+    as `out`, `assess(con)` being (the call's record, its score under `con` as a float expression).  A site of the model
+    that `con` does not hold goes to `refuse(addresses)`, which raises.  Cached on the model, the leaves' kinds,
+    `form` (what tells the callers' programs apart) and `specialize` (specialised once, when built); launch=False builds
+    the program only."""
+    from .. import tracer as Tr
+    from ..engine import Compiled, Flat, leaf_spec
+    from ..static import MissingAddress, _gfkey, _traced, call_gen_fn
+    batch = (int(out.shape[-1]),)
+    flat = Flat()
+    atree = flat.add(tuple(args))
+    j0 = len(flat.leaves)
+    for v in leaves:
+        flat.add(v)
+    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
+    ck = (_gfkey(model), atree, specs, form, bool(specialize))
+    ent = _BACKWARD_CACHE.get(ck)
+    if ent is None:
+        with _traced(specs, 1, store_sites=False) as p:
+            sargs = p.values(atree)
+
+            def assess(con):
+                try:
+                    rec, _, _, s = call_gen_fn(p.ctx, "assess", model, None, sargs, con, None, None, None, ())
+                except MissingAddress as e:
+                    refuse([a for a in e.args if a != ()])
+                return rec, Tr.as_float(s)
+            o = p.tr.emit_output(emit(assess, p.syms[j0:], p.tr))
+        comp = Compiled(p.tr)
+        if specialize:
+            comp.specialize()
+        ent = _BACKWARD_CACHE[ck] = (comp, o)
+    if launch:
+        comp, o = ent
+        bufs = [None] * len(comp.outputs)
+        bufs[o[1]] = out
+        comp.run(flat.leaves, batch, None, out_buffers=bufs)
+
+
+def _transition_refusal(who, sites, obs_addr):
+    def refuse(addr):
+        raise NotImplementedError(
+            f"{who}: the step model samples {addr[0] if len(addr) == 1 else tuple(addr)!r}, "
+            f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
+            "transition density would have to integrate it out") from None
+    return refuse
+
+
+def _transition_choices(sites, obs_addr, y, x_next):
+    con = ChoiceMap.empty().set(obs_addr, y)
+    for a, x in zip(sites, x_next):
+        con = con.set(a, x)
+    return con
+
+
 def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
     """out[k, i] = lw[i] + step.assess({sites[d]: x_next[d][k], obs_addr: y}, (x_prev[i], *extra))[0] in float32, for the
     R = out.shape[0] rows in ONE launch: the model's `assess` traced R times, row k's constrained state read from the
     launch-uniform short vectors x_next[d] (as inference/gibbs.py traces K categories), the R sums stored as the rows
     of `out` ([R, n], rows contiguous).  The program is cached on the model, the leaves' kinds and R."""
-    from .. import tracer as Tr
-    from ..engine import Broadcast, Compiled, Flat, Sym, Tracing, leaf_spec, unflatten
-    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
-    R, n = int(out.shape[0]), int(lw.shape[0])
-    batch = (n,)
-    flat = Flat()
-    atree = flat.add((x_prev,) + tuple(extra))
-    jy = len(flat.leaves)
-    flat.add(y)
-    jx = len(flat.leaves)
-    for v in x_next:
-        flat.add(Broadcast(v))
-    jl = len(flat.leaves)
-    flat.add(lw)
-    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-    ck = (_gfkey(step), atree, specs, tuple(sites), obs_addr, R)
-    ent = _BACKWARD_CACHE.get(ck)
-    if ent is None:
-        tr = Tracing(1)
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        with Tr.tracing(tr.graph):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-            sargs = unflatten(atree, lambda j: syms[j].value)
-            rows = np.empty((R,), dtype=object)
-            for k in range(R):
-                con = ChoiceMap.empty().set(obs_addr, syms[jy])
-                for d, a in enumerate(sites):
-                    con = con.set(a, Sym(syms[jx + d].value[k], None))
-                try:
-                    _, _, _, s = call_gen_fn(ctx, "assess", step, None, sargs, con, None, None, None, ())
-                except MissingAddress as e:
-                    addr = tuple(a for a in e.args if a != ())
-                    raise NotImplementedError(
-                        f"SweepHistory.backward_sample: the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
-                        f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
-                        "transition density would have to integrate it out") from None
-                rows[k] = syms[jl].value + Tr.as_float(s)
-                tr.prestore(rows[k])            # (stored now: the row's register dies here)
-            o = tr.emit_output(rows)
-        ent = (Compiled(tr), o)
-        _BACKWARD_CACHE[ck] = ent
-    comp, o = ent
-    bufs = [None] * len(comp.outputs)
-    bufs[o[1]] = out
-    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+    from ..engine import Broadcast, Sym
+    R, D = int(out.shape[0]), len(x_next)
+
+    def emit(assess, syms, tr):            # syms: y, the D short vectors, lw
+        rows = np.empty((R,), dtype=object)
+        for k in range(R):
+            con = _transition_choices(sites, obs_addr, syms[0], [Sym(x.value[k], None) for x in syms[1:1 + D]])
+            rows[k] = syms[1 + D].value + assess(con)[1]
+            tr.prestore(rows[k])            # (stored now: the row's register dies here)
+        return rows
+    _assess_program(step, (x_prev,) + tuple(extra), [y] + [Broadcast(v) for v in x_next] + [lw], (tuple(sites), obs_addr, R),
+                    emit, _transition_refusal("SweepHistory.backward_sample", sites, obs_addr), out)
 
 
 def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, specialize=False, launch=True,
@@ -1419,52 +1443,12 @@ def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, s
     program is cached on the model, the leaves' kinds and `specialize` (specialised once, when built); launch=False
     builds it only.  who: the caller a refusal names (ConditionalBank.draw(backward=True) runs the same program over the
     recorded steps)."""
-    from .. import tracer as Tr
-    from ..engine import Compiled, Flat, Tracing, leaf_spec, unflatten
-    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
-    batch = (int(lw.shape[0]),)
-    flat = Flat()
-    atree = flat.add((x_prev,) + tuple(extra))
-    jy = len(flat.leaves)
-    flat.add(y)
-    jx = len(flat.leaves)
-    for v in x_next:
-        flat.add(v)
-    jl = len(flat.leaves)
-    flat.add(lw)
-    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-    ck = (_gfkey(step), atree, specs, tuple(sites), obs_addr, "per-particle", bool(specialize))
-    ent = _BACKWARD_CACHE.get(ck)
-    if ent is None:
-        tr = Tracing(1)
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        with Tr.tracing(tr.graph):
-            syms = [tr.sym_leaf(s_, j) for j, s_ in enumerate(specs)]
-            sargs = unflatten(atree, lambda j: syms[j].value)
-            con = ChoiceMap.empty().set(obs_addr, syms[jy])
-            for d, a in enumerate(sites):
-                con = con.set(a, syms[jx + d])
-            try:
-                _, _, _, sc = call_gen_fn(ctx, "assess", step, None, sargs, con, None, None, None, ())
-            except MissingAddress as e:
-                addr = tuple(a for a in e.args if a != ())
-                raise NotImplementedError(
-                    f"{who}: the step model samples {addr[0] if len(addr) == 1 else addr!r}, "
-                    f"which is neither one of the state's sites {tuple(sites)!r} nor the observation {obs_addr!r}: the "
-                    "transition density would have to integrate it out") from None
-            o = tr.emit_output(syms[jl].value + Tr.as_float(sc))
-        comp = Compiled(tr)
-        if specialize:
-            comp.specialize()
-        ent = (comp, o)
-        _BACKWARD_CACHE[ck] = ent
-    if not launch:
-        return
-    comp, o = ent
-    bufs = [None] * len(comp.outputs)
-    bufs[o[1]] = out
-    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+    D = len(x_next)
+
+    def emit(assess, syms, tr):            # syms: y, the D per-particle states, lw
+        return syms[1 + D].value + assess(_transition_choices(sites, obs_addr, syms[0], syms[1:1 + D]))[1]
+    _assess_program(step, (x_prev,) + tuple(extra), [y] + list(x_next) + [lw], (tuple(sites), obs_addr, "per-particle"),
+                    emit, _transition_refusal(who, sites, obs_addr), out, specialize, launch)
 
 
 class SweepHistory:
@@ -2669,48 +2653,22 @@ def _prior_logpdf(prior, addrs, values, out, specialize=False, launch=True, who=
     Built as _ancestor_logits builds the per-particle program: cached on the model, the leaves' kinds and `specialize`
     (specialised once, when built); launch=False builds it only.  A prior whose sites are not exactly `addrs` is refused
     by name."""
-    from .. import tracer as Tr
-    from ..engine import Compiled, Flat, Tracing, leaf_spec
-    from ..static import MissingAddress, _Ctx, _gfkey, call_gen_fn
-    batch = (int(out.shape[-1]),)
-    flat = Flat()
-    for v in values:
-        flat.add(v)
-    specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-    ck = (_gfkey(prior), specs, tuple(addrs), "prior", bool(specialize))
-    ent = _BACKWARD_CACHE.get(ck)
-    if ent is None:
-        tr = Tracing(1)
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        with Tr.tracing(tr.graph):
-            syms = [tr.sym_leaf(s_, j) for j, s_ in enumerate(specs)]
-            con = ChoiceMap.empty()
-            for p, a in enumerate(addrs):
-                con = con.set(a, syms[p])
-            try:
-                rec, _, _, sc = call_gen_fn(ctx, "assess", prior, None, (), con, None, None, None, ())
-                sites = list(rec.sites)
-            except MissingAddress as e:
-                sites = [a for a in e.args if a != ()]
-            if set(sites) != set(addrs) or len(sites) != len(addrs):
-                extra = [a for a in sites if a not in addrs]
-                unused = [a for a in addrs if a not in sites]
-                raise ValueError(f"{who}: the prior's sites are not exactly param_addrs = {tuple(addrs)!r}"
-                                 + (f"; it samples {extra!r}, which is not a parameter" if extra else "")
-                                 + (f"; it has no site {unused!r}" if unused else ""))
-            o = tr.emit_output(Tr.as_float(sc))
-        comp = Compiled(tr)
-        if specialize:
-            comp.specialize()
-        ent = (comp, o)
-        _BACKWARD_CACHE[ck] = ent
-    if not launch:
-        return
-    comp, o = ent
-    bufs = [None] * len(comp.outputs)
-    bufs[o[1]] = out
-    comp.run(flat.leaves, batch, None, out_buffers=bufs)
+    def refuse(sites):
+        extra = [a for a in sites if a not in addrs]
+        unused = [a for a in addrs if a not in sites]
+        raise ValueError(f"{who}: the prior's sites are not exactly param_addrs = {tuple(addrs)!r}"
+                         + (f"; it samples {extra!r}, which is not a parameter" if extra else "")
+                         + (f"; it has no site {unused!r}" if unused else "")) from None
+
+    def emit(assess, syms, tr):            # syms: the P per-chain parameter leaves
+        con = ChoiceMap.empty()
+        for a, v in zip(addrs, syms):
+            con = con.set(a, v)
+        rec, score = assess(con)
+        if set(rec.sites) != set(addrs) or len(rec.sites) != len(addrs):
+            refuse(list(rec.sites))
+        return score
+    _assess_program(prior, (), list(values), (tuple(addrs), "prior"), emit, refuse, out, specialize, launch)
 
 
 class ParticleMH(_Sweep):

@@ -38,7 +38,8 @@ from .core.choice_map import ChoiceMap, Selection, _norm
 from .core.mask import Mask
 from .core.generative import (Diff, EditRequest, EmptyRequest, GenerativeFunction, IndexRequest, NoChange,
                               NotSupportedEditRequest, Regenerate, Trace, Update)
-from .engine import Broadcast, Compiled, Flat, Gathered, Sym, Tracing, leaf_spec, materialize, resolve, unflatten
+from .engine import (Broadcast, Compiled, Flat, Gathered, Sym, Tracing, fit_program, leaf_spec, materialize, over_the_slots,
+                     resolve, traced, unflatten)
 from .random import Key
 from .tracer import Expr
 from .engine import new_cache as _new_program_cache
@@ -1412,6 +1413,34 @@ def _sym_constraint(tree, syms) -> ChoiceMap:
     return unflatten(tree, lambda j: syms[j])
 
 
+class _traced(traced):
+    """engine.traced for a program that calls generative functions: `p.ctx` is the state its handlers share.
+      store_sites  False: the program stores only what the caller emits
+      sitewise     ONE trace of a `@gen` function: a large plate inside it ends the trace with sitewise.NeedsSiteBySite
+      defer        the plate-deferral record (combinators.Vmap._defer)"""
+
+    def __init__(self, specs, batch_ndim, store_sites=True, sitewise=False, defer=None, **options):
+        super().__init__(specs, batch_ndim, **options)
+        self.ctx = _Ctx(self.tr)
+        self.ctx.store_sites = store_sites
+        if sitewise:
+            self.ctx.sitewise = True
+        if defer is not None:
+            self.ctx.defer = defer
+
+    def call(self, mode, gen_fn, atree, ctree):
+        """`mode` of gen_fn under p.key, its arguments and its choice map the leaves the two trees name"""
+        return call_gen_fn(self.ctx, mode, gen_fn, self.key, self.values(atree), _sym_constraint(ctree, self.syms),
+                           None, None, None, ())
+
+
+def _emit_gfi(tr: Tracing, mode, rec, retval, w, s):
+    """The outputs of a simulate / generate / assess program: the origins (sites, weight, score, return value)."""
+    if mode == "assess":
+        return None, None, tr.emit_output(s), _emit_retval(tr, retval)
+    return _emit_rec(tr, rec), (tr.emit_output(w) if (mode == "generate" and w is not None) else None), None, None
+
+
 def _emit_rec(tr: Tracing, rec):
     """Origins of every site (stores were emitted as the sites were traced;
     anything not stored yet is stored here); mirrors rec."""
@@ -1635,16 +1664,15 @@ class NoiseAheadContext:
         return [z[k] for k in range(n_draws)]
 
 
-def _noise_split(tr: Tracing, batch, ctx):
-    """after tracing with a NoiseHoist: (draws, background program or None)"""
-    hoist = tr.graph.__dict__.pop("noise_hoist", None)
-    if hoist is None or not hoist.draws:
+def _noise_split(draws, batch, ctx):
+    """the draws a program traced with hoist= takes from memory (traced.draws) -> (draws, background program or None)"""
+    if not draws:
         return (), None
-    q = NoiseProgram(hoist.draws, batch)
+    q = NoiseProgram(draws, batch)
     if _lib.get().uses_streams and not torch.cuda.is_current_stream_capturing():
         q.comp.set_background(ctx.lds_pad)
         q.comp.specialize()
-    return tuple(hoist.draws), q
+    return draws, q
 
 
 @_unrolled_when_values_are_used
@@ -1682,63 +1710,34 @@ def run_gfi(gen_fn, mode, key: Key | None, args, constraint: ChoiceMap | None = 
     ck = (_gfkey(gen_fn), mode, atree, ctree, specs, len(batch), key is not None, weight_stats, na is not None, elem_index,
           defer_B)
     ent = _CACHE.get(ck)
-    if ent is _SITE_BY_SITE:
-        return sitewise.run_gfi(gen_fn, mode, key, args, constraint)
     if ent is None and defer_B is not None and ck not in _NO_DEFER:
         try:
-            ent = _trace_gfi(gen_fn, mode, key, batch, specs, atree, ctree, weight_stats, None, elem_index, defer_B)
+            ent = _trace_gfi(gen_fn, mode, key, batch, specs, atree, ctree, elem_index, defer_B)
             _CACHE[ck] = ent
         except DeferralAbort:
             _NO_DEFER.add(ck)
             ent = None
-    first_error, attempt = None, 0
-    while ent is None:
-        # (second pass, when the program did not fit the launch slots / registers: top-level plates and scans as loops;
-        #  third and fourth pass: the program CUT into a chain of launches — program.split_graph — as traced at first,
-        #  then in the loop form)
-        force, chain = attempt in (1, 3), attempt >= 2
-        tr = Tracing(len(batch))
-        tr.step_leaf_min = 0 if force else getattr(gen_fn, "step_leaf_min", tr.step_leaf_min)
-        if na is not None:
-            from .engine import NoiseHoist
-            tr.graph.noise_hoist = NoiseHoist(tr, len(specs))
-        tr.graph.elem_from_index = bool(elem_index)
-        ctx = _Ctx(tr)
-        ctx.store_sites = mode != "assess"
+    if ent is None:
         # ONE trace of a `@gen` function: a large plate inside it sends the call to the site-by-site form (sitewise.py)
-        ctx.sitewise = (len(batch) == 0 and isinstance(gen_fn, StaticGenerativeFunction) and not weight_stats and na is None
-                        and (key is None or tuple(key.shape) == ()))
-        try:
-            from .combinators import forced_loops
+        one_trace = (len(batch) == 0 and isinstance(gen_fn, StaticGenerativeFunction) and not weight_stats and na is None
+                     and (key is None or tuple(key.shape) == ()))
+
+        def trace(force, chain):
             try:
-                with T.tracing(tr.graph), forced_loops(force):
-                    syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-                    sargs = unflatten(atree, lambda j: syms[j].value)
-                    scon = _sym_constraint(ctree, syms)
-                    kexpr = Expr(tr.graph.add("LDKEY", dtype="key")) if key is not None else None
-                    rec, retval, w, s = call_gen_fn(ctx, mode, gen_fn, kexpr, sargs, scon, None, None, None, ())
+                with _traced(specs, len(batch), key=key is not None, store_sites=mode != "assess", sitewise=one_trace,
+                             hoist=na is not None, step_leaf_min=0 if force else getattr(gen_fn, "step_leaf_min", None),
+                             elem_from_index=elem_index, force=force) as p:
+                    rec, retval, w, s = p.call(mode, gen_fn, atree, ctree)
+                    origins = _emit_gfi(p.tr, mode, rec, retval, w, s)
+                    if weight_stats and isinstance(w, Expr) and w.node.op != "CONST":
+                        p.tr.graph.add("REDMAX", (w.node,), dtype="none")
             except sitewise.NeedsSiteBySite:
-                _CACHE[ck] = _SITE_BY_SITE
-                return sitewise.run_gfi(gen_fn, mode, key, args, constraint)
-            with T.tracing(tr.graph):
-                otree = _emit_rec(tr, rec) if mode != "assess" else None
-                wo = tr.emit_output(w) if (mode == "generate" and w is not None) else None
-                so = tr.emit_output(s) if mode == "assess" else None
-                ro = tr.emit_output(retval) if mode == "assess" else None
-                if weight_stats and isinstance(w, Expr) and w.node.op != "CONST":
-                    tr.graph.add("REDMAX", (w.node,), dtype="none")
-            ent = (Compiled(tr, chain=chain), otree, wo, so, ro) + (_noise_split(tr, batch, na) if na is not None else ((), None)) + ((),)
-        except Exception as e:      # noqa: BLE001
-            if attempt == 0 and not _over_the_slots(e):
-                raise
-            if attempt == 3 or (chain and (weight_stats or na is not None)):
-                raise first_error from None        # no form fits (or applies): the first report stands
-            first_error = first_error or e
-            attempt += 1
-            if attempt == 2 and (weight_stats or na is not None):
-                raise first_error from None        # (a sweep's programs leave tile statistics: one launch or none)
-            continue
-        _CACHE[ck] = ent
+                return _SITE_BY_SITE
+            return (Compiled(p.tr, chain=chain),) + origins + _noise_split(p.draws, batch, na) + ((),)
+        # (a sweep's programs leave tile statistics, a noise context's read what a background program draws: one launch)
+        ent = _CACHE[ck] = fit_program(trace, one_launch=weight_stats or na is not None)
+    if ent is _SITE_BY_SITE:
+        return sitewise.run_gfi(gen_fn, mode, key, args, constraint)
     comp, otree, wo, so, ro, draws, nprog, plates = ent
     leaves = flat.leaves + (na.draw(nprog, batch, key, len(draws), mode) if nprog is not None else [])
     stats = None
@@ -1804,39 +1803,55 @@ class _AssessedPlate:
         return self._r
 
 
-def _trace_gfi(gen_fn, mode, key, batch, specs, atree, ctree, weight_stats, na, elem_index, defer_B):
+def _trace_gfi(gen_fn, mode, key, batch, specs, atree, ctree, elem_index, defer_B):
     """run_gfi's tracing step with plate deferral switched on; raises DeferralAbort when it does not apply"""
-    tr = Tracing(len(batch))
-    tr.step_leaf_min = getattr(gen_fn, "step_leaf_min", tr.step_leaf_min)
-    tr.graph.elem_from_index = bool(elem_index)
-    ctx = _Ctx(tr)
-    ctx.store_sites = mode != "assess"
-    ctx.defer = {"B": defer_B, "plates": [], "depth": len(_HANDLERS) + 1}
-    with T.tracing(tr.graph):
-        syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-        sargs = unflatten(atree, lambda j: syms[j].value)
-        scon = _sym_constraint(ctree, syms)
-        kexpr = Expr(tr.graph.add("LDKEY", dtype="key")) if key is not None else None
-        rec, retval, w, s = call_gen_fn(ctx, mode, gen_fn, kexpr, sargs, scon, None, None, None, ())
-        plates = ctx.defer["plates"]           # (none: this IS the ordinary trace)
+    plates = []
+    with _traced(specs, len(batch), key=key is not None, store_sites=mode != "assess",
+                 defer={"B": defer_B, "plates": plates, "depth": len(_HANDLERS) + 1},
+                 step_leaf_min=getattr(gen_fn, "step_leaf_min", None), elem_from_index=elem_index) as p:
+        rec, retval, w, s = p.call(mode, gen_fn, atree, ctree)
+        # (no plates: this IS the ordinary trace)
         if plates and (not rec.sites or list(rec.sites.values())[-1] is not plates[0]):
             raise DeferralAbort()              # sites after the plate: their weights would be added in another order
-        otree = _emit_rec(tr, rec) if mode != "assess" else None
-        wo = tr.emit_output(w) if (mode == "generate" and w is not None) else None
-        so = tr.emit_output(s if s is not None else 0.0) if mode == "assess" else None
-        ro = _emit_retval(tr, retval) if mode == "assess" else None
+        origins = _emit_gfi(p.tr, mode, rec, retval, w, s)
     try:
-        comp = Compiled(tr)
+        comp = Compiled(p.tr)
     except Exception as e:      # noqa: BLE001
-        if not _over_the_slots(e):
+        if not over_the_slots(e):
             raise
         if not plates:
             raise DeferralAbort() from None      # (nothing deferred: run_gfi's ordinary passes deal with the size)
-        comp = Compiled(tr, chain=True)          # the part in front of the deferred plate as a chain of launches
-    return (comp, otree, wo, so, ro, (), None, tuple(plates))
+        comp = Compiled(p.tr, chain=True)        # the part in front of the deferred plate as a chain of launches
+    return (comp,) + origins + ((), None, tuple(plates))
 
 
-class MinimalGenerate:
+def _weight_or_zero(g, w):
+    return w if w is not None else Expr(g.const_f32(0.0)) + 0.0
+
+
+def _emit_step_weight(tr: Tracing, w):
+    """The importance weight of a sweep's step (zero when nothing is constrained) stored, and reduced per workgroup for
+    the resampler (OP_REDMAX); returns its origin."""
+    w = _weight_or_zero(tr.graph, w)
+    wo = tr.emit_output(w)
+    tr.graph.add("REDMAX", (w.node,), dtype="none")
+    return wo
+
+
+class _Minimal:
+    """What the Minimal* programs share.  `_flatten(*call)` -> (Flat, trees, ...) states ONCE how a call becomes leaves:
+    __init__ compiles for the `self.trees` it gives, leaves() holds a later call to them."""
+    noise = ()
+
+    def _leaves_of(self, flat, trees, noise=()):
+        if trees != self.trees:
+            raise ValueError(f"{type(self).__name__}: call structure differs from the compiled one")
+        if len(noise) != len(self.noise):
+            raise ValueError(f"{type(self).__name__}: the program reads {len(self.noise)} noise leaves, got {len(noise)}")
+        return flat.leaves + list(noise)
+
+
+class MinimalGenerate(_Minimal):
     """`generate` compiled to store ONLY the return value and the importance
     weight (plus per-block max partials of the weight for the resampler): the
     program BootstrapSweep launches once per SMC step.  Per particle-step this
@@ -1846,42 +1861,23 @@ class MinimalGenerate:
         """hoist_noise: the program takes the standard-normal draws of its `normal` sites from memory (one extra
         f32 leaf per draw, `self.noise`: engine.NoiseHoist.draws; pass them to leaves(..., noise=[...])) — drawn by
         NoiseProgram(self.noise, batch) from the same keys, so every value is the one the plain program computes."""
-        flat = Flat()
-        self.atree = flat.add(tuple(args))
-        self.ctree = flat.add(constraint)
+        flat, self.trees = self._flatten(args, constraint)
         self.specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-        tr = Tracing(len(batch))
-        hoist = None
-        if hoist_noise:
-            from .engine import NoiseHoist
-            hoist = tr.graph.noise_hoist = NoiseHoist(tr, len(self.specs), hoist_noise)
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        with T.tracing(tr.graph):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(self.specs)]
-            sargs = unflatten(self.atree, lambda j: syms[j].value)
-            scon = _sym_constraint(self.ctree, syms)
-            kexpr = Expr(tr.graph.add("LDKEY", dtype="key"))
-            rec, retval, w, _ = call_gen_fn(ctx, "generate", gen_fn, kexpr, sargs, scon, None, None, None, ())
-            self.ro = tr.emit_output(retval)
-            if w is None:
-                w = Expr(tr.graph.const_f32(0.0)) + 0.0
-            self.wo = tr.emit_output(w)
-            tr.graph.add("REDMAX", (w.node,), dtype="none")
-        self.noise = tuple(hoist.draws) if hoist is not None else ()
-        tr.graph.__dict__.pop("noise_hoist", None)
-        self.comp = Compiled(tr)
+        with _traced(self.specs, len(batch), key=True, store_sites=False, hoist=hoist_noise) as p:
+            rec, retval, w, _ = p.call("generate", gen_fn, *self.trees)
+            self.ro = p.tr.emit_output(retval)
+            self.wo = _emit_step_weight(p.tr, w)
+        self.noise = p.draws
+        self.comp = Compiled(p.tr)
         self.gen_fn = gen_fn
 
-    def leaves(self, args, constraint, noise=()):
+    @staticmethod
+    def _flatten(args, constraint):
         flat = Flat()
-        a = flat.add(tuple(args))
-        c = flat.add(constraint)
-        if a != self.atree or c != self.ctree:
-            raise ValueError("MinimalGenerate: call structure differs from the compiled one")
-        if len(noise) != len(self.noise):
-            raise ValueError(f"MinimalGenerate: the program reads {len(self.noise)} noise leaves, got {len(noise)}")
-        return flat.leaves + list(noise)
+        return flat, (flat.add(tuple(args)), flat.add(constraint))
+
+    def leaves(self, args, constraint, noise=()):
+        return self._leaves_of(*self._flatten(args, constraint), noise)
 
 
 class NoiseProgram:
@@ -1897,19 +1893,17 @@ class NoiseProgram:
         if len({d[0] for d in draws}) != 1:
             raise ValueError("NoiseProgram: the draws of one program come from one launch key")
         self.draws = tuple(draws)
-        tr = Tracing(len(batch))
-        g = tr.graph
-        with T.tracing(g):
-            root = g.add("LDKEY", dtype="key")
+        with traced((), len(batch), key=True) as p:          # (no leaves, no handlers: the launch key and nothing else)
+            g = p.tr.graph
             self.outs = []
             for _, chain, e, kind in self.draws:
-                k = root
+                k = p.key.node
                 for c in chain:
                     k = g.add("KDERIVE", (k,), imm=c, dtype="key")
                 z = g.add("S_NORMAL" if kind == "normal" else "S_UNIFORM", (k, g.const_f32(0.0), g.const_f32(1.0)),
                           imm=e, dtype="f32")
-                self.outs.append(tr.emit_output(Expr(z)))
-        self.comp = Compiled(tr)
+                self.outs.append(p.tr.emit_output(Expr(z)))
+        self.comp = Compiled(p.tr)
 
     def run(self, batch: tuple, key, out_tensors):
         """out_tensors[k]: a [1, n] float tensor for draw k"""
@@ -1939,27 +1933,42 @@ def _rec_to_prev(rec):
     return {"sub": {a: _rec_to_prev(r) for a, r in rec.sites.items()}, "retval": ret}
 
 
-def _trace_mh_move(tr, ctx, gen_fn, sargs, scon, rspec, syms):
-    """Trace one MH move on the trace of `gen_fn(*sargs)` with choices `scon` into tr.graph (MinimalMH's program body):
-    returns (the selected return value, the accept flag) as expressions."""
-    g = tr.graph
-    rec0, ret0, _, _ = call_gen_fn(ctx, "generate", gen_fn, None, sargs, scon, None, None, None, ())
-    sprev = _rec_to_prev(rec0)
-    kexpr = Expr(g.add("LDKEY", dtype="key"))
-    k_acc = Expr(g.add("KDERIVE", (kexpr.node,), imm=1, dtype="key"))      # (k_edit, k_acc) = split(key_i)
-    k_edit = Expr(g.add("KDERIVE", (kexpr.node,), imm=0, dtype="key"))
+def _split_key(g, key):
+    """(k_edit, k_acc) = split(particle key) of an MH move (k_acc is derived first)"""
+    k_acc = Expr(g.add("KDERIVE", (key.node,), imm=1, dtype="key"))
+    return Expr(g.add("KDERIVE", (key.node,), imm=0, dtype="key")), k_acc
+
+
+def _edit_mode(rspec, syms):
+    """(mode, constraint) of the edit a request asks for; Update constraints nested in it are bound to the leaves"""
     mode, constraint = "static_edit", ChoiceMap.empty()
     if rspec.kind == "update":
         mode, constraint = "update", _sym_constraint(rspec.tree, syms)
     elif rspec.kind == "regen":
         mode = "regen"
     _bind_request_leaves(rspec, syms)
-    rec, retval, w, _ = call_gen_fn(ctx, mode, gen_fn, k_edit, sargs, constraint, sprev, rspec, syms, ())
+    return mode, constraint
+
+
+def _accept_expr(g, k_acc, w):
+    """(the move's weight — zero when the edit has none —, the accept flag log U(k_acc) < weight)"""
     from .distributions import uniform as _uniform
-    if w is None:
-        w = Expr(g.const_f32(0.0)) + 0.0
+    w = _weight_or_zero(g, w)
     u = _uniform.sym_sample(k_acc, (0.0, 1.0))
-    acc = Expr(g.add("LOG", (u.node,), dtype="f32")) < w
+    return w, Expr(g.add("LOG", (u.node,), dtype="f32")) < w
+
+
+def _trace_mh_move(p, gen_fn, atree, ctree, rspec):
+    """Trace one MH move on the trace of `gen_fn` called with the arguments and choices the two trees make of p's leaves
+    (MinimalMH's program body): returns (the selected return value, the accept flag) as expressions."""
+    g = p.tr.graph
+    sargs = p.values(atree)
+    rec0, ret0, _, _ = call_gen_fn(p.ctx, "generate", gen_fn, None, sargs, _sym_constraint(ctree, p.syms),
+                                   None, None, None, ())
+    k_edit, k_acc = _split_key(g, Expr(g.add("LDKEY", dtype="key")))      # (the key is loaded AFTER the old scores)
+    mode, constraint = _edit_mode(rspec, p.syms)
+    rec, retval, w, _ = call_gen_fn(p.ctx, mode, gen_fn, k_edit, sargs, constraint, _rec_to_prev(rec0), rspec, p.syms, ())
+    _, acc = _accept_expr(g, k_acc, w)
 
     def sel(new, old):
         if isinstance(new, tuple):
@@ -1968,7 +1977,14 @@ def _trace_mh_move(tr, ctx, gen_fn, sargs, scon, rspec, syms):
     return sel(retval, ret0), acc
 
 
-class MinimalMH:
+def _flatten_mh(flat, args, choices, request):
+    """an MH move's leaves: arguments, choices, the request's -> ((trees), the request's spec)"""
+    atree, ctree = flat.add(tuple(args)), flat.add(choices)
+    rspec, rkey = _flatten_request(request, flat)
+    return (atree, ctree, rkey), rspec
+
+
+class MinimalMH(_Minimal):
     """One Metropolis-Hastings move per particle (`run_mh`'s program) on a trace that is never
     materialised: the inputs are the particle's arguments and choice VALUES (typically gathered
     through the ancestors of a resampling step); the old scores are recomputed from them — the same
@@ -1977,36 +1993,24 @@ class MinimalMH:
     the next extension."""
 
     def __init__(self, gen_fn, args, choices: ChoiceMap, request, batch: tuple):
-        flat = Flat()
-        self.atree = flat.add(tuple(args))
-        self.ctree = flat.add(choices)
-        rspec, self.rkey = _flatten_request(request, flat)
-        self.n_fixed = len(flat.leaves)
+        flat, self.trees, rspec = self._flatten(args, choices, request)
         self.specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-        tr = Tracing(len(batch))
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        g = tr.graph
-        with T.tracing(g):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(self.specs)]
-            sargs = unflatten(self.atree, lambda j: syms[j].value)
-            scon = _sym_constraint(self.ctree, syms)
-            selected, acc = _trace_mh_move(tr, ctx, gen_fn, sargs, scon, rspec, syms)
-            self.ro = tr.emit_output(selected)
-            self.ao = tr.emit_output(acc)
-        self.comp = Compiled(tr)
+        with _traced(self.specs, len(batch), store_sites=False) as p:
+            selected, acc = _trace_mh_move(p, gen_fn, self.trees[0], self.trees[1], rspec)
+            self.ro = p.tr.emit_output(selected)
+            self.ao = p.tr.emit_output(acc)
+        self.comp = Compiled(p.tr)
+
+    @staticmethod
+    def _flatten(args, choices, request):
+        flat = Flat()
+        return (flat,) + _flatten_mh(flat, args, choices, request)
 
     def leaves(self, args, choices, request):
-        flat = Flat()
-        a = flat.add(tuple(args))
-        c = flat.add(choices)
-        _, rkey = _flatten_request(request, flat)
-        if a != self.atree or c != self.ctree or rkey != self.rkey:
-            raise ValueError("MinimalMH: call structure differs from the compiled one")
-        return flat.leaves
+        return self._leaves_of(*self._flatten(args, choices, request)[:2])
 
 
-class MinimalMHGenerate:
+class MinimalMHGenerate(_Minimal):
     """MinimalMH on `mh_fn`'s trace, THEN MinimalGenerate of `gen_fn` from the moved state — one program, one launch:
     what BootstrapSweep(rejuvenate=...) issues per step (the MH move on the resampled particles of step t-1, then the
     extension to step t).  The two calls keep their own keys: the move draws from the launch key (OP_LDKEY), the
@@ -2019,58 +2023,35 @@ class MinimalMHGenerate:
         """hoist_noise: as MinimalGenerate — `self.noise` lists the draws taken from memory: root "LDKEY" ones (the
         move: proposal, accept) come from the launch key, root "KSPLITU" ones (the extension) from `key_words`.
         A tuple of roots instead of True hoists the draws of those keys only."""
-        flat = Flat()
-        self.atree = flat.add(tuple(mh_args))
-        self.ctree = flat.add(choices)
-        rspec, self.rkey = _flatten_request(request, flat)
-        self.etree = flat.add(tuple(gen_extra))
-        self.gtree = flat.add(gen_constraint)
-        self.ktree = flat.add((0, 0))                 # the extension's launch key, two 32-bit words
+        flat, self.trees, rspec, ktree = self._flatten(mh_args, choices, request, gen_extra, gen_constraint, (0, 0))
+        (atree, ctree, _), etree, gtree = self.trees
         self.specs = tuple(leaf_spec(v, batch) for v in flat.leaves)
-        tr = Tracing(len(batch))
-        hoist = None
-        if hoist_noise:
-            from .engine import NoiseHoist
-            hoist = tr.graph.noise_hoist = NoiseHoist(tr, len(self.specs), hoist_noise)
-        ctx = _Ctx(tr)
-        ctx.store_sites = False
-        g = tr.graph
-        with T.tracing(g):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(self.specs)]
-            sargs = unflatten(self.atree, lambda j: syms[j].value)
-            scon = _sym_constraint(self.ctree, syms)
-            moved, acc = _trace_mh_move(tr, ctx, mh_fn, sargs, scon, rspec, syms)
-            self.mo = tr.emit_output(moved)
-            self.ao = tr.emit_output(acc)
-            extra = unflatten(self.etree, lambda j: syms[j].value)
-            gcon = _sym_constraint(self.gtree, syms)
-            kw = unflatten(self.ktree, lambda j: syms[j].value)
+        with _traced(self.specs, len(batch), store_sites=False, hoist=hoist_noise) as p:
+            g = p.tr.graph
+            moved, acc = _trace_mh_move(p, mh_fn, atree, ctree, rspec)
+            self.mo = p.tr.emit_output(moved)
+            self.ao = p.tr.emit_output(acc)
+            kw = p.values(ktree)
             k2 = Expr(g.add("KSPLITU", (kw[0].node, kw[1].node), dtype="key"))
-            ctx2 = _Ctx(tr)
+            ctx2 = _Ctx(p.tr)
             ctx2.store_sites = False
-            rec, retval, w, _ = call_gen_fn(ctx2, "generate", gen_fn, k2, (moved,) + tuple(extra), gcon, None, None, None, ())
-            self.ro = tr.emit_output(retval)
-            if w is None:
-                w = Expr(g.const_f32(0.0)) + 0.0
-            self.wo = tr.emit_output(w)
-            g.add("REDMAX", (w.node,), dtype="none")
-        self.noise = tuple(hoist.draws) if hoist is not None else ()
-        g.__dict__.pop("noise_hoist", None)
-        self.comp = Compiled(tr)
+            rec, retval, w, _ = call_gen_fn(ctx2, "generate", gen_fn, k2, (moved,) + tuple(p.values(etree)),
+                                            _sym_constraint(gtree, p.syms), None, None, None, ())
+            self.ro = p.tr.emit_output(retval)
+            self.wo = _emit_step_weight(p.tr, w)
+        self.noise = p.draws
+        self.comp = Compiled(p.tr)
+
+    @staticmethod
+    def _flatten(mh_args, choices, request, gen_extra, gen_constraint, key_words):
+        flat = Flat()
+        mh, rspec = _flatten_mh(flat, mh_args, choices, request)
+        trees = (mh, flat.add(tuple(gen_extra)), flat.add(gen_constraint))
+        # the extension's launch key, two 32-bit words (values only: not part of the call structure)
+        return flat, trees, rspec, flat.add((_as_i32(key_words[0]), _as_i32(key_words[1])))
 
     def leaves(self, mh_args, choices, request, gen_extra, gen_constraint, key_words, noise=()):
-        flat = Flat()
-        a = flat.add(tuple(mh_args))
-        c = flat.add(choices)
-        _, rkey = _flatten_request(request, flat)
-        e = flat.add(tuple(gen_extra))
-        gc = flat.add(gen_constraint)
-        flat.add((_as_i32(key_words[0]), _as_i32(key_words[1])))
-        if a != self.atree or c != self.ctree or rkey != self.rkey or e != self.etree or gc != self.gtree:
-            raise ValueError("MinimalMHGenerate: call structure differs from the compiled one")
-        if len(noise) != len(self.noise):
-            raise ValueError(f"MinimalMHGenerate: the program reads {len(self.noise)} noise leaves, got {len(noise)}")
-        return flat.leaves + list(noise)
+        return self._leaves_of(*self._flatten(mh_args, choices, request, gen_extra, gen_constraint, key_words)[:2], noise)
 
 
 def _as_i32(u):
@@ -2151,25 +2132,15 @@ def run_edit(gen_fn, key: Key, trace: Trace, request: EditRequest, argdiffs, mh:
     ck = (_gfkey(gen_fn), "mh" if mh else "edit", atree, ptree, rkey, specs, tkey, len(batch), key is not None,
           na is not None)
     ent = _CACHE.get(ck)
+    if ent is None:
+        def trace_(force, chain):
+            try:
+                return _trace_edit(gen_fn, key, mh, na, specs, batch, atree, ptree, rspec, tangents, force, chain)
+            except _Unfused:
+                return _MH_UNFUSED
+        ent = _CACHE[ck] = fit_program(trace_, one_launch=na is not None)
     if ent is _MH_UNFUSED:
         return _run_mh_unfused(gen_fn, key, trace, request, argdiffs)
-    first_error, attempt = None, 0
-    while ent is None:
-        force, chain = attempt in (1, 3), attempt >= 2        # (the passes of run_gfi)
-        try:
-            ent = _trace_edit(gen_fn, key, trace, request, argdiffs, mh, na, specs, batch, atree, ptree, rspec, tangents, ck,
-                              force, chain)
-        except _Unfused:
-            return _run_mh_unfused(gen_fn, key, trace, request, argdiffs)
-        except Exception as e:      # noqa: BLE001
-            if attempt == 0 and not _over_the_slots(e):
-                raise
-            if attempt == 3 or (attempt >= 1 and na is not None):
-                raise first_error from None
-            first_error = first_error or e
-            attempt += 1
-            continue
-        _CACHE[ck] = ent
     comp, otree, wo, ao, draws, nprog, ret_changed = ent
     outs = comp.run(flat.leaves + (na.draw(nprog, batch, key, len(draws), "mh") if nprog is not None else []), batch, key)
     return _finish_edit(request, mh, otree, wo, ao, outs, flat, args, batch, be, ret_changed)
@@ -2179,81 +2150,51 @@ class _Unfused(Exception):
     pass
 
 
-def _over_the_slots(e) -> bool:
-    from .program import ProgramTooLarge
-    return isinstance(e, ProgramTooLarge) or (isinstance(e, ValueError) and "exceeds the ABI slot limits" in str(e))
+def _trace_edit(gen_fn, key, mh, na, specs, batch, atree, ptree, rspec, tangents, force, chain=False):
+    """run_edit's tracing step -> the cache entry; raises _Unfused for an MH move that cannot be one program"""
+    with _traced(specs, len(batch), key=key is not None, store_sites=not mh, hoist=na is not None,
+                 step_leaf_min=0 if force else getattr(gen_fn, "step_leaf_min", None), force=force) as p:
+        tr, ctx, kexpr, k_acc = p.tr, p.ctx, p.key, None
+        if mh:
+            kexpr, k_acc = _split_key(tr.graph, kexpr)
+        sargs = p.values(atree)
+        # arguments flagged as changed seed the change set
+        _seed_changed(ctx, sargs, tangents)
+        sprev = unflatten(ptree, lambda j: p.syms[j])
+        mode, constraint = _edit_mode(rspec, p.syms)
+        rec, retval, w, _ = call_gen_fn(ctx, mode, gen_fn, kexpr, sargs, constraint, sprev, rspec, p.syms, ())
+        ao = None
+        if mh and any(nd.op == "LOOP" for nd in tr.graph.nodes):
+            # sites written INSIDE a counted loop (a long scan, a large plate) are in memory before the move is
+            # accepted or refused: no selecting in registers — the move runs unfused (edit, accept, select)
+            raise _Unfused()
+        if mh:
+            w, acc = _accept_expr(tr.graph, k_acc, w)
+            otree = _mh_select(tr, acc, rec, sprev)
+            ao = tr.emit_output(acc)
+        else:
+            otree = _emit_rec(tr, rec)
+        wo = tr.emit_output(w) if w is not None else None
+        # the retdiff (static.py:948-981 returns the incremental interpreter's): NoChange only when the return value is
+        # made of program values none of which depends on anything this edit changed
+        ret_changed = True
+        if not mh:
+            flat_ret = []
 
-
-def _trace_edit(gen_fn, key, trace, request, argdiffs, mh, na, specs, batch, atree, ptree, rspec, tangents, ck, force,
-                chain=False):
-    """run_edit's tracing step -> the cache entry"""
-    if True:
-        from .combinators import forced_loops
-        tr = Tracing(len(batch))
-        if na is not None:
-            from .engine import NoiseHoist
-            tr.graph.noise_hoist = NoiseHoist(tr, len(specs))
-        ctx = _Ctx(tr)
-        ctx.store_sites = not mh
-        tr.step_leaf_min = 0 if force else getattr(gen_fn, "step_leaf_min", tr.step_leaf_min)
-        with T.tracing(tr.graph), forced_loops(force):
-            syms = [tr.sym_leaf(s, j) for j, s in enumerate(specs)]
-            sargs = unflatten(atree, lambda j: syms[j].value)
-            # arguments flagged as changed seed the change set
-            _seed_changed(ctx, sargs, tangents)
-            sprev = unflatten(ptree, lambda j: syms[j])
-            kexpr = Expr(tr.graph.add("LDKEY", dtype="key")) if key is not None else None
-            k_acc = None
-            if mh:          # (k_edit, k_acc) = split(particle key)
-                k_acc = Expr(tr.graph.add("KDERIVE", (kexpr.node,), imm=1, dtype="key"))
-                kexpr = Expr(tr.graph.add("KDERIVE", (kexpr.node,), imm=0, dtype="key"))
-            mode, constraint = "static_edit", ChoiceMap.empty()
-            req = rspec
-            if rspec.kind == "update":
-                mode = "update"
-                constraint = _sym_constraint(rspec.tree, syms)
-            elif rspec.kind == "regen":
-                mode = "regen"
-            _bind_request_leaves(rspec, syms)
-            rec, retval, w, _ = call_gen_fn(ctx, mode, gen_fn, kexpr, sargs, constraint, sprev, req, syms, ())
-            ao = None
-            if mh and any(nd.op == "LOOP" for nd in tr.graph.nodes):
-                # sites written INSIDE a counted loop (a long scan, a large plate) are in memory before the move is
-                # accepted or refused: no selecting in registers — the move runs unfused (edit, accept, select)
-                _CACHE[ck] = _MH_UNFUSED
-                raise _Unfused()
-            if mh:
-                from .distributions import uniform as _uniform
-                if w is None:
-                    w = Expr(tr.graph.const_f32(0.0)) + 0.0
-                u = _uniform.sym_sample(k_acc, (0.0, 1.0))
-                acc = Expr(tr.graph.add("LOG", (u.node,), dtype="f32")) < w
-                otree = _mh_select(tr, acc, rec, sprev)
-                ao = tr.emit_output(acc)
-            else:
-                otree = _emit_rec(tr, rec)
-            wo = tr.emit_output(w) if w is not None else None
-            # the retdiff (static.py:948-981 returns the incremental interpreter's): NoChange only when the return value is
-            # made of program values none of which depends on anything this edit changed
-            ret_changed = True
-            if not mh:
-                flat_ret = []
-
-                def walk(v):
-                    if isinstance(v, Sym):
-                        v = v.value
-                    if v is None or isinstance(v, (bool, int, float, np.number)):
-                        return True
-                    if isinstance(v, Expr) or (isinstance(v, np.ndarray) and v.dtype == object):
-                        flat_ret.append(v)
-                        return True
-                    if isinstance(v, (tuple, list)):
-                        return all(walk(x) for x in v)
-                    return False              # (stacked loop outputs, masks, pytrees: conservatively "changed")
-                if walk(retval):
-                    ret_changed = ctx.args_changed(flat_ret)
-        return (Compiled(tr, chain=chain), otree, wo, ao) + (_noise_split(tr, batch, na) if na is not None else ((), None)) \
-            + (ret_changed,)
+            def walk(v):
+                if isinstance(v, Sym):
+                    v = v.value
+                if v is None or isinstance(v, (bool, int, float, np.number)):
+                    return True
+                if isinstance(v, Expr) or (isinstance(v, np.ndarray) and v.dtype == object):
+                    flat_ret.append(v)
+                    return True
+                if isinstance(v, (tuple, list)):
+                    return all(walk(x) for x in v)
+                return False              # (stacked loop outputs, masks, pytrees: conservatively "changed")
+            if walk(retval):
+                ret_changed = ctx.args_changed(flat_ret)
+    return (Compiled(tr, chain=chain), otree, wo, ao) + _noise_split(p.draws, batch, na) + (ret_changed,)
 
 
 def _finish_edit(request, mh, otree, wo, ao, outs, flat, args, batch, be, ret_changed=True):
