@@ -280,6 +280,11 @@ class Backend:
         c.gmx_pmmh_accept.argtypes = [POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int,
                                       c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+        c.gmx_pg_open.argtypes = [POINTER(c_uint32), c_uint32, c_void_p, c_int32, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]
+        c.gmx_pg_propose.argtypes = [POINTER(c_uint32), c_uint32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]
+        c.gmx_pg_accept.argtypes = [POINTER(c_uint32), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]
         c.gmx_capture_begin.argtypes = [c_void_p]
         c.gmx_capture_end.argtypes = [c_void_p, POINTER(c_void_p)]
         c.gmx_graph_launch.argtypes = [c_void_p, c_void_p]

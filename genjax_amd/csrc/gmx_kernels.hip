@@ -3732,6 +3732,58 @@ extern "C" int gmx_pmmh_accept(const uint32_t key[2], uint32_t* it_d, const floa
 }
 
 // ---------------------------------------------------------------------------
+// particle Gibbs over a bank of conditional filters (gmx_pgibbs.h): the three launches of an iteration around the bank's
+// sweep and the score programs.  Each entry point: its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
+// ---------------------------------------------------------------------------
+#include "gmx_pgibbs.h"
+
+// (leaves_d is a table ON THE DEVICE, as gmx_pmmh_propose's; keys_as_d may be null)
+extern "C" int gmx_pg_open(const uint32_t key[2], uint32_t j, const float* theta_d, int32_t P, int64_t R, int64_t n, int32_t T,
+                           uint32_t* keys_prop_d, uint32_t* keys_res_d, uint32_t* keys_as_d, float* const* leaves_d,
+                           gmx_stream stream) {
+  const char* who = "gmx_pg_open";
+  const gmx_refusal no = gmx_pg_open_refusal_(!key || !theta_d || !keys_prop_d || !keys_res_d || !leaves_d, P, R, n, T);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{theta_d, 3}, {keys_prop_d, 7}, {keys_res_d, 7}, {keys_as_d, 7}, {leaves_d, 7}})) return 1;
+  const unsigned blocks = (unsigned)((R * n + GMX_PMMH_SPAN - 1) / GMX_PMMH_SPAN);
+  hipLaunchKernelGGL(k_pg_open, dim3(blocks), dim3(GMX_PMMH_BLOCK), gmx_pmmh_lds_bytes_(P, n), (hipStream_t)stream, key[0], key[1],
+                     j, theta_d, (uint32_t)P, (uint32_t)R, (uint32_t)n, (uint32_t)T, keys_prop_d, keys_res_d, keys_as_d, leaves_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmx_pg_propose(const uint32_t key[2], uint32_t j, const float* theta_d, const float* scale_d, int32_t P, int64_t R,
+                              float* theta_pair_d, gmx_stream stream) {
+  const char* who = "gmx_pg_propose";
+  const gmx_refusal no = gmx_pg_propose_refusal_(!key || !theta_d || !scale_d || !theta_pair_d, P, R);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{theta_d, 3}, {scale_d, 3}, {theta_pair_d, 3}})) return 1;
+  hipLaunchKernelGGL(k_pg_propose, dim3((unsigned)((P * R + GMX_PMMH_BLOCK - 1) / GMX_PMMH_BLOCK)), dim3(GMX_PMMH_BLOCK), 0,
+                     (hipStream_t)stream, key[0], key[1], j, theta_d, scale_d, P, R, theta_pair_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmx_pg_accept(const uint32_t key[2], uint32_t j, const float* joint_d, const float* obs_d, const float* lp_d,
+                             const float* theta_pair_d, int32_t T, int64_t R, int32_t P, float* theta_d, double* log_joint_d,
+                             float* ref_lw_d, float* rec_theta_d, double* rec_lj_d, uint8_t* rec_acc_d, int64_t row, int64_t cap,
+                             gmx_stream stream) {
+  const char* who = "gmx_pg_accept";
+  const gmx_refusal no = gmx_pg_accept_refusal_(
+      !key || !joint_d || !obs_d || !lp_d || !theta_pair_d || !theta_d || !log_joint_d || !ref_lw_d || !rec_theta_d || !rec_lj_d ||
+          !rec_acc_d, P, R, T, row, cap);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{joint_d, 3}, {obs_d, 3}, {lp_d, 3}, {theta_pair_d, 3}, {theta_d, 3}, {ref_lw_d, 3},
+                                      {rec_theta_d, 3}, {log_joint_d, 7}, {rec_lj_d, 7}})) return 1;
+  const gmx_pg_chains C = gmx_pg_chains_of_(joint_d, obs_d, lp_d, theta_pair_d, T, R, P, theta_d, log_joint_d, ref_lw_d, rec_theta_d,
+                                           rec_lj_d, rec_acc_d);
+  hipLaunchKernelGGL(k_pg_accept, dim3((unsigned)((R + GMX_PMMH_BLOCK - 1) / GMX_PMMH_BLOCK)), dim3(GMX_PMMH_BLOCK), 0,
+                     (hipStream_t)stream, key[0], key[1], j, C, row);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // graph capture + timers
 // ---------------------------------------------------------------------------
 struct gmx_graph { hipGraph_t graph; hipGraphExec_t exec; };

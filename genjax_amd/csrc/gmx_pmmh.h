@@ -11,6 +11,8 @@
 //                    written-out gmx_log64 below: the same bits on the device and on a host), the Metropolis-Hastings
 //                    decision, the chain's state and its record row.  Block 0 writes it[0] = it[1].
 // No workgroup reads an iteration word another workgroup of the same launch writes.
+// The span of a workgroup, the fill of the key tables and the broadcast through LDS are device helpers (gmx_pmmh_span_of,
+// gmx_pmmh_put_keys, gmx_pmmh_broadcast) that k_pg_open of gmx_pgibbs.h, which includes this file, runs on as well.
 // The arithmetic — the key schedule, the draw, gmx_log64, the evidence term, the decision — is stated ONCE, in the shared
 // part below, as GMX_HD functions: the kernels (hipcc; included by gmx_kernels.hip only, not among the headers embedded
 // for hiprtc) and the two ENTRY POINTS a plain host compiler gets (sequential loops over chains; gmx_vm.h includes this
@@ -65,17 +67,22 @@ GMX_HD gmx_pmmh_keys gmx_pmmh_iter_keys(gmx_key key, uint32_t j) {
   K.acc = gmx_split_child(k_it, 2);
   return K;
 }
-// Row (t, r) of the bank's two key tables under split(k_bank, R)[r] (BootstrapBank._key_tables): children 0 and 1 of the
-// step key fold_in(., t)
-GMX_HD void gmx_pmmh_step_keys(gmx_key k_bank, uint32_t r, uint32_t t, gmx_key* prop, gmx_key* res) {
+// Row (t, r) of the bank's key tables under split(k_bank, R)[r] (BootstrapBank._key_tables): children 0 and 1 of the
+// step key fold_in(., t); `last` given: also child 2 (ConditionalBank's ancestor draws)
+GMX_HD void gmx_pmmh_step_keys(gmx_key k_bank, uint32_t r, uint32_t t, gmx_key* prop, gmx_key* res, gmx_key* last = nullptr) {
   const gmx_key k_step = gmx_fold_in(gmx_split_child(k_bank, r), t);
   *prop = gmx_split_child(k_step, 0);
   *res = gmx_split_child(k_step, 1);
+  if (last) *last = gmx_split_child(k_step, 2);
 }
-// theta'[p, r]: iteration 0 evaluates the start; after it a random-walk step under split(split(k_prop, R)[r], P)[p] —
-// gmx_normal_sample: z * scale rounded, then + theta rounded
+// A random-walk step of parameter p of chain r under split(split(k_prop, R)[r], P)[p] — gmx_normal_sample: z * scale
+// rounded, then + theta rounded
+GMX_HD float gmx_pmmh_walk(gmx_key k_prop, uint32_t r, uint32_t p, float theta, float scale) {
+  return gmx_normal_sample(gmx_split_child(gmx_split_child(k_prop, r), p), 0, theta, scale);
+}
+// theta'[p, r]: iteration 0 evaluates the start; after it the step
 GMX_HD float gmx_pmmh_proposal(gmx_key k_prop, uint32_t j, uint32_t r, uint32_t p, float theta, float scale) {
-  const float v = gmx_normal_sample(gmx_split_child(gmx_split_child(k_prop, r), p), 0, theta, scale);
+  const float v = gmx_pmmh_walk(k_prop, r, p, theta, scale);
   return j == 0u ? theta : v;
 }
 
@@ -139,8 +146,53 @@ GMX_HD void gmx_pmmh_accept_chain(const gmx_pmmh_chains& C, gmx_key k_acc, int64
 
 #if defined(__HIPCC__)
 
-// blockIdx.x: the span of GMX_PMMH_SPAN particles.  s_draw: [P, nch] floats, nch the chains the span touches (dynamic LDS,
-// gmx_pmmh_lds_bytes_).  R * n < 2^31 and T * R < 2^31 (the refusal): 32-bit indices throughout.
+// What a workgroup of the span form works on — k_pmmh_propose and k_pg_open (gmx_pgibbs.h) —: blockIdx.x is the span of
+// GMX_PMMH_SPAN consecutive particles of the flat [R * n] axis, chains r0 .. r0 + nch - 1 are those it touches, and the
+// dynamic LDS holds [P, nch] floats (gmx_pmmh_lds_bytes_).  R * n < 2^31 and T * R < 2^31 (the refusal): 32-bit indices
+// throughout.
+struct gmx_pmmh_span { uint32_t N, base, r0, nch; };
+__device__ __forceinline__ gmx_pmmh_span gmx_pmmh_span_of(uint32_t R, uint32_t n) {
+  gmx_pmmh_span S;
+  S.N = R * n;
+  S.base = blockIdx.x * GMX_PMMH_SPAN;                            // < N
+  const uint32_t last = S.N - S.base > GMX_PMMH_SPAN ? S.base + (GMX_PMMH_SPAN - 1) : S.N - 1;
+  S.r0 = S.base / n;
+  S.nch = last / n - S.r0 + 1;
+  return S;
+}
+// the bank's key tables under k_bank, spread over the grid; keys_as (the third child's table) may be null
+__device__ __forceinline__ void gmx_pmmh_put_keys(gmx_key k_bank, uint32_t T, uint32_t R, uint32_t* __restrict__ keys_prop,
+                                                  uint32_t* __restrict__ keys_res, uint32_t* __restrict__ keys_as) {
+  for (uint32_t i = blockIdx.x * GMX_PMMH_BLOCK + threadIdx.x; i < T * R; i += gridDim.x * GMX_PMMH_BLOCK) {
+    const uint32_t t = i / R;
+    gmx_key kp, kr, ka;
+    gmx_pmmh_step_keys(k_bank, i - t * R, t, &kp, &kr, keys_as ? &ka : nullptr);
+    reinterpret_cast<uint2*>(keys_prop)[i] = make_uint2(kp.k0, kp.k1);
+    reinterpret_cast<uint2*>(keys_res)[i] = make_uint2(kr.k0, kr.k1);
+    if (keys_as) reinterpret_cast<uint2*>(keys_as)[i] = make_uint2(ka.k0, ka.k1);
+  }
+}
+// after the barrier: four consecutive particles per thread, each reading its chain's value from s_val [P, nch]
+__device__ __forceinline__ void gmx_pmmh_broadcast(const float* s_val, const gmx_pmmh_span& S, uint32_t P, uint32_t n,
+                                                   float* const* __restrict__ leaves) {
+  const uint32_t i0 = S.base + threadIdx.x * 4u;
+  if (i0 >= S.N) return;
+  uint32_t c = i0 / n - S.r0;
+  uint32_t rem = i0 - (c + S.r0) * n;
+  uint32_t cc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cc[k] = c < S.nch ? c : S.nch - 1;                             // (past the last particle: not stored)
+    if (++rem == n) { rem = 0; ++c; }
+  }
+  for (uint32_t p = 0; p < P; ++p) {
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = s_val[p * S.nch + cc[k]];
+    rows_store4(leaves[p], (int64_t)i0, (int64_t)S.N, v);
+  }
+}
+
 __global__ void __launch_bounds__(GMX_PMMH_BLOCK)
 k_pmmh_propose(uint32_t k0, uint32_t k1, uint32_t* __restrict__ it, const float* __restrict__ theta,
                const float* __restrict__ scale, uint32_t P, uint32_t R, uint32_t n, uint32_t T, uint32_t* __restrict__ keys_prop,
@@ -150,45 +202,18 @@ k_pmmh_propose(uint32_t k0, uint32_t k1, uint32_t* __restrict__ it, const float*
   const uint32_t j = it[0];
   gmx_key key; key.k0 = k0; key.k1 = k1;
   const gmx_pmmh_keys K = gmx_pmmh_iter_keys(key, j);
-  const uint32_t N = R * n;
-  const uint32_t base = blockIdx.x * GMX_PMMH_SPAN;               // < N
-  const uint32_t last = N - base > GMX_PMMH_SPAN ? base + (GMX_PMMH_SPAN - 1) : N - 1;
-  const uint32_t r0 = base / n;
-  const uint32_t nch = last / n - r0 + 1;
+  const gmx_pmmh_span S = gmx_pmmh_span_of(R, n);
   // the draws of the span's chains, once per workgroup; the workgroup holding a chain's first particle stores them
-  for (uint32_t q = tid; q < nch * P; q += GMX_PMMH_BLOCK) {
-    const uint32_t p = q / nch, c = q - p * nch, r = r0 + c;
+  for (uint32_t q = tid; q < S.nch * P; q += GMX_PMMH_BLOCK) {
+    const uint32_t p = q / S.nch, c = q - p * S.nch, r = S.r0 + c;
     const float v = gmx_pmmh_proposal(K.prop, j, r, p, theta[p * R + r], scale[p]);
     s_draw[q] = v;
-    if (r * n >= base) theta_prop[p * R + r] = v;
+    if (r * n >= S.base) theta_prop[p * R + r] = v;
   }
-  // the bank's key tables, spread over the grid
-  for (uint32_t i = blockIdx.x * GMX_PMMH_BLOCK + tid; i < T * R; i += gridDim.x * GMX_PMMH_BLOCK) {
-    const uint32_t t = i / R;
-    gmx_key kp, kr;
-    gmx_pmmh_step_keys(K.bank, i - t * R, t, &kp, &kr);
-    reinterpret_cast<uint2*>(keys_prop)[i] = make_uint2(kp.k0, kp.k1);
-    reinterpret_cast<uint2*>(keys_res)[i] = make_uint2(kr.k0, kr.k1);
-  }
+  gmx_pmmh_put_keys(K.bank, T, R, keys_prop, keys_res, nullptr);
   if (blockIdx.x == 0 && tid == 0) it[1] = j + 1u;
   __syncthreads();
-  // four consecutive particles per thread, each reading its chain's draw
-  const uint32_t i0 = base + tid * 4u;
-  if (i0 >= N) return;
-  uint32_t c = i0 / n - r0;
-  uint32_t rem = i0 - (c + r0) * n;
-  uint32_t cc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    cc[k] = c < nch ? c : nch - 1;                                 // (past the last particle: not stored)
-    if (++rem == n) { rem = 0; ++c; }
-  }
-  for (uint32_t p = 0; p < P; ++p) {
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = s_draw[p * nch + cc[k]];
-    rows_store4(leaves[p], (int64_t)i0, (int64_t)N, v);
-  }
+  gmx_pmmh_broadcast(s_draw, S, P, n, leaves);
 }
 
 // one thread per chain.  The record row is j - rec_base[0]; outside [0, cap) no chain is touched and block 0 counts the

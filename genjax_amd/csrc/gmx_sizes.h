@@ -4,8 +4,8 @@
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
 //                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
-//                             the tile-form resamplers, the row-wise draws, the particle-MH pair, the sharded / peer family,
-//                             the sweep history
+//                             the tile-form resamplers, the row-wise draws, the particle-MH pair, the particle-Gibbs three, the
+//                             sharded / peer family, the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
 // Plain host C++ (static inline): no HIP, no kernel, no algorithm.  hiprtc never sees this file (it is not among the
@@ -307,6 +307,25 @@ static inline gmx_refusal gmx_pmmh_accept_refusal_(bool has_null, int32_t P, int
   if (no.fmt) return no;
   if (shift < 1 || shift > 62) return {"%s: shift = %lld is outside [1, 62]", (long long)shift};
   if (cap < 1 || cap > (1LL << 32)) return {"%s: cap = %lld is outside [1, 2^32] (an iteration is fold_in's 32-bit word)", (long long)cap};
+  return {nullptr, 0};
+}
+
+// ---- particle Gibbs over a bank of conditional filters: gmx_pg_open, gmx_pg_propose, gmx_pg_accept (gmx_pgibbs.h) ----
+// gmx_pg_open runs on gmx_pmmh_propose's grid, span and LDS layout and refuses what it refuses (keys_as_d may be null)
+static inline gmx_refusal gmx_pg_open_refusal_(bool has_null, int32_t P, int64_t R, int64_t n, int32_t T) {
+  return gmx_pmmh_propose_refusal_(has_null, P, R, n, T);
+}
+static inline gmx_refusal gmx_pg_propose_refusal_(bool has_null, int32_t P, int64_t R) {
+  if (has_null) return {"%s: null argument", 0};
+  return gmx_pmmh_shape_refusal_(P, R, 1);
+}
+// the record row is the caller's: the iteration is an argument
+static inline gmx_refusal gmx_pg_accept_refusal_(bool has_null, int32_t P, int64_t R, int32_t T, int64_t row, int64_t cap) {
+  if (has_null) return {"%s: null argument", 0};
+  const gmx_refusal no = gmx_pmmh_shape_refusal_(P, R, T);
+  if (no.fmt) return no;
+  if (cap < 1 || cap > (1LL << 32)) return {"%s: cap = %lld is outside [1, 2^32] (an iteration is fold_in's 32-bit word)", (long long)cap};
+  if (row < 0 || row >= cap) return {"%s: row = %lld is outside the record [0, cap)", (long long)row};
   return {nullptr, 0};
 }
 

@@ -337,12 +337,13 @@ GMX_HD bool gmx_op_needs_full(uint32_t op) {
 // A plain host compiler building the C-ABI from these headers (the CPU mirror the host-logic tests load) also gets the
 // sweep-history entry points as sequential loops (gmx_history.h) and the row-wise draw and the row-wise resampling as
 // loops over the per-row paths (gmx_backward.h, gmx_resample_rows.h), the normal draw's tail over chosen bits
-// (gmx_draw_tail.h), and the two launches of a particle-MH iteration as loops over chains (gmx_pmmh.h); hipcc and hiprtc
-// see nothing here.
+// (gmx_draw_tail.h), and the two launches of a particle-MH iteration and the three of a particle-Gibbs iteration as loops
+// over chains (gmx_pmmh.h, gmx_pgibbs.h); hipcc and hiprtc see nothing here.
 #if defined(__cplusplus) && !defined(__HIPCC__) && !defined(__HIPCC_RTC__)
 #include "gmx_draw_tail.h"
 #include "gmx_history.h"
 #include "gmx_backward.h"
 #include "gmx_resample_rows.h"
 #include "gmx_pmmh.h"
+#include "gmx_pgibbs.h"
 #endif

@@ -1358,17 +1358,20 @@ _BACKWARD_CACHE = engine.new_cache()
 
 
 def _assess_program(model, args, leaves, form, emit, refuse, out, specialize=False, launch=True):
-    """THE builder of the programs that score a model's `assess` under a choice map made of leaves, one output, over the
-    n = out.shape[-1] particles of ONE launch.  The leaves are those of `args` (the model's arguments), then `leaves`, one
-    each; `emit(assess, syms, tr)` fills the choice map(s) from the symbols `syms` of the latter and returns what is stored
+    """THE builder of the programs that score a model's `assess` under a choice map made of leaves, one output (or a tuple
+    of them: `emit` returns a tuple and `out` is the tuple of their buffers), over the n = out.shape[-1] particles of ONE
+    launch.  The leaves are those of `args` (the model's arguments), then `leaves`, one each; `emit(assess, syms, tr)` fills the choice map(s) from the symbols `syms` of the latter and returns what is stored
     as `out`, `assess(con)` being (the call's record, its score under `con` as a float expression).  A site of the model
     that `con` does not hold goes to `refuse(addresses)`, which raises.  Cached on the model, the leaves' kinds,
     `form` (what tells the callers' programs apart) and `specialize` (specialised once, when built); launch=False builds
-    the program only."""
+    the program only.  Returns a launcher for callers whose leaves and outputs are persistent buffers: its first call is
+    this launch, every later one re-launches ONE binding of those buffers (Compiled.bind / launch), with none of the
+    per-call flattening and cache look-up."""
     from .. import tracer as Tr
     from ..engine import Compiled, Flat, leaf_spec
     from ..static import MissingAddress, _gfkey, _traced, call_gen_fn
-    batch = (int(out.shape[-1]),)
+    outs = out if isinstance(out, tuple) else (out,)
+    batch = (int(outs[0].shape[-1]),)
     flat = Flat()
     atree = flat.add(tuple(args))
     j0 = len(flat.leaves)
@@ -1387,16 +1390,29 @@ def _assess_program(model, args, leaves, form, emit, refuse, out, specialize=Fal
                 except MissingAddress as e:
                     refuse([a for a in e.args if a != ()])
                 return rec, Tr.as_float(s)
-            o = p.tr.emit_output(emit(assess, p.syms[j0:], p.tr))
+            res = emit(assess, p.syms[j0:], p.tr)
+            o = tuple(p.tr.emit_output(v) for v in (res if isinstance(res, tuple) else (res,)))
         comp = Compiled(p.tr)
         if specialize:
             comp.specialize()
         ent = _BACKWARD_CACHE[ck] = (comp, o)
+    comp, o = ent
+    bufs = [None] * len(comp.outputs)
+    for oi, buf in zip(o, outs):
+        bufs[oi[1]] = buf
     if launch:
-        comp, o = ent
-        bufs = [None] * len(comp.outputs)
-        bufs[o[1]] = out
         comp.run(flat.leaves, batch, None, out_buffers=bufs)
+    bound = []
+    # (a strided leaf — a vector state's [n, D] view of a [D, n] slab — is copied when it is bound: launched afresh)
+    fixed = all(v.is_contiguous() for v in flat.leaves if isinstance(v, torch.Tensor))
+
+    def again():
+        if bound:
+            return comp.launch(bound[0])
+        comp.run(flat.leaves, batch, None, out_buffers=bufs)           # (a specialised program's cross-check is in run())
+        if fixed:
+            bound.append(comp.bind(flat.leaves, batch, None, out_buffers=bufs))
+    return again
 
 
 def _transition_refusal(who, sites, obs_addr):
@@ -2431,7 +2447,8 @@ class ConditionalBank(BootstrapBank):
         k = torch.empty((R,), dtype=torch.int32, device=dev)
         status = torch.zeros((2,), dtype=torch.int64, device=dev)       # rows without mass; indices outside the history
         lw_last = self.hist_lws[T - 1]
-        be.check(be.c.gmx_pick_rows(be.ptr(split(key, R).data()), be.ptr(lw_last), R, n, n, be.ptr(k), be.ptr(status[0:]),
+        keys = split(key, R).data()                                      # (held until the call has returned)
+        be.check(be.c.gmx_pick_rows(be.ptr(keys), be.ptr(lw_last), R, n, n, be.ptr(k), be.ptr(status[0:]),
                                     be.ptr(self.pick_ws), be.stream()), "gmx_pick_rows")
         start = (k + torch.arange(R, dtype=torch.int32, device=dev) * n).contiguous()
         paths = torch.empty((T, R), dtype=torch.int32, device=dev)
@@ -2668,7 +2685,7 @@ def _prior_logpdf(prior, addrs, values, out, specialize=False, launch=True, who=
         if set(rec.sites) != set(addrs) or len(rec.sites) != len(addrs):
             refuse(list(rec.sites))
         return score
-    _assess_program(prior, (), list(values), (tuple(addrs), "prior"), emit, refuse, out, specialize, launch)
+    return _assess_program(prior, (), list(values), (tuple(addrs), "prior"), emit, refuse, out, specialize, launch)
 
 
 class ParticleMH(_Sweep):
@@ -2820,3 +2837,234 @@ class ParticleMH(_Sweep):
     def state(self):
         """(theta [P, R] float32, log_ml [R] float64, log_prior [R] float32) of the chains now"""
         return self.theta.clone(), self.ll.clone(), self.lp.clone()
+
+
+# ---------------------------------------------------------------------------
+# particle Gibbs over a bank of conditional filters
+# ---------------------------------------------------------------------------
+ParticleGibbsResult = namedtuple("ParticleGibbsResult", ["theta", "log_joint", "accepted", "paths"])
+
+
+def _trajectory_scores(model, sites, obs_addr, args, x, y, out, specialize=False, launch=True, who="ParticleGibbs"):
+    """out = (joint, obs), each [1, B]:  joint[0, c] = model.assess({sites[d]: x[d][c], obs_addr: y}, args_c)[0] and
+    obs[0, c] = the observation site's score inside that call, in float32, over the B columns in ONE launch — one step of
+    a trajectory scored under per-column arguments (ParticleGibbs: the drawn path on both halves of B = 2R, theta on one
+    and theta' on the other).  x: the D per-column state leaves; `args` may hold per-column leaves.  Built on
+    _assess_program with two outputs: cached on the model, the leaves' kinds and `specialize` (specialised once, when
+    built); launch=False builds it only.  A model that samples anything besides `sites` and the observation is refused."""
+    from .. import tracer as Tr
+    D = len(x)
+
+    def emit(assess, syms, tr):            # syms: y, the D per-column states
+        rec, score = assess(_transition_choices(sites, obs_addr, syms[0], syms[1:1 + D]))
+        site = rec.sites.get(obs_addr)
+        if site is None or getattr(site, "score", None) is None:
+            raise NotImplementedError(f"{who}: the model has no site {obs_addr!r} of its own to score the observation at")
+        return score, Tr.as_float(site.score)
+    return _assess_program(model, tuple(args), [y] + list(x), (tuple(sites), obs_addr, "trajectory"), emit,
+                           _transition_refusal(who, sites, obs_addr), out, specialize, launch)
+
+
+class ParticleGibbs:
+    """Particle Gibbs (Andrieu, Doucet & Holenstein 2010, section 2.4.3) over the P parameters of a state-space model: R
+    independent chains, the state of chain r being (theta[:, r], x_ref[:, :, r]) — its parameters and the retained path of
+    chain r of a ConditionalBank(init, step, n, R, T, params=theta0, state_sites=, ancestor_sampling=) it owns, the bank's
+    programs, stores and launches untouched.  An iteration alternates x | theta, y by conditional SMC with a random-walk
+    Metropolis-Hastings move of theta | x, y.  The models are called as the bank calls them: init(*params_r),
+    step(x_prev, *step_extra(t), *params_r).  `prior`, `param_addrs` and `step_size` are ParticleMH's: a `@gen` function of
+    no arguments with one scalar site per entry of `param_addrs`, and P positive standard deviations (no transforms, no
+    adaptation).  ancestor_sampling=True is PGAS, backward=True draws every new path by backward simulation (PGBS).
+
+    Iteration j, counted from prepare(), is host-driven (the draw synchronises); j is an argument of the entry points:
+      1. gmx_pg_open        the bank's key tables (keys_prop, keys_res, and keys_as with ancestor sampling) for the chain
+                            keys split(k_sweep, R) — BootstrapBank._key_tables(keys, third=True), on the device — and
+                            theta[p, r] broadcast over the bank's P per-particle parameter leaves: ONE launch;
+      2. bank.launch(); x = bank.draw(k_draw, backward); bank.retain() — unchanged; with nothing retained, iteration 0 is
+                            the unconditional sweep, as in ConditionalBank.run;
+      3. gmx_pg_propose     theta_pair[p] = [theta[p] | theta'[p]], theta' a random-walk step at EVERY j: ONE launch;
+      4. the prior program  lp[0:R] under theta, lp[R:2R] under theta': one `assess` program over a batch of 2R;
+      5. the scores         for t = 0 .. T - 1 one program over a batch of 2R, the drawn path on both halves:
+                              joint[t, c] = model_t.assess({state_sites[d]: x[t][d], obs_addr: y_t}, args_t(c))[0]   (float32)
+                              obs[t, c]   = the observation site's score inside that call                             (float32)
+                            model_0 = init, args_0 = theta_c; t >= 1: model_t = step, args_t = (x[t-1], *step_extra(t), *theta_c);
+      6. gmx_pg_accept      per chain S = sum_t (double)joint[t, r] and S' = sum_t (double)joint[t, R + r], ascending t, in
+                            float64; log_alpha = (float)((S' - S) + ((double)lp[R + r] - (double)lp[r])); taken iff
+                            log u < log_alpha (gmx_mh_accept's rule; NaN rejects); then theta[:, r], log_joint[r] =
+                            (taken ? S' + lp' : S + lp), the record row — and ref_lw[t, r] = obs[t, taken ? R + r : r] for
+                            every t: the pinned weights are those of the parameters the next sweep runs under, whatever
+                            the decision.  ONE launch.
+
+    Key schedule, under the ONE key of prepare(): k_it = fold_in(key, j); (k_sweep, k_draw, k_prop, k_acc) =
+    split(k_it, 4); chain r's sweep runs under split(k_sweep, R)[r], the draw under k_draw, the proposal for parameter p
+    under split(split(k_prop, R)[r], P)[p], the uniform under split(k_acc, R)[r].
+
+    Contract: run() is, bit for bit, the Python loop over public parts — per iteration a fresh ConditionalBank(...,
+    params=theta_j).prepare(split(k_sweep, R), ys, retained=x_{j-1}), launch(), draw(k_draw, backward); the public
+    init.assess / step.assess / prior.assess over a batch of R under theta_j and theta'_j, summed sequentially in float64;
+    gmx_mh_accept's decision.  In particular ref_lw after the move equals what ConditionalBank.set_retained(x) computes
+    under params = the accepted theta.
+
+    capture() captures the bank's sweep (ConditionalBank.capture) in its current form: after iteration 0 (or with
+    `retained=`) that is the conditional sweep every later iteration replays; the rest of an iteration is not capturable.
+
+    Limits: 1 <= P <= 8 (gmx_pg_open holds the values of a workgroup's chains in LDS); a model that samples anything besides
+    the state sites and the observation is refused; a state of more than one component needs state_sites=; whatever
+    ConditionalBank refuses (resample=, ess_threshold=, n > 1024 once a path is retained, ...) is refused by it, by name.
+    Not here: adaptive or correlated proposals, transforms, conjugate updates, several moves per sweep, per-chain
+    observations, sharding."""
+
+    def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
+                 state_addr="x", state_sites=None, step_extra=None, ancestor_sampling=False, backward=False, specialize=True,
+                 **bank_kw):
+        self.param_addrs = tuple(param_addrs)
+        self.P = len(self.param_addrs)
+        if self.P < 1 or self.P > PMMH_MAX_PARAMS:
+            raise NotImplementedError(f"ParticleGibbs: {self.P} parameters; param_addrs names between 1 and {PMMH_MAX_PARAMS} "
+                                      "(gmx_pg_open holds the values of a workgroup's chains in LDS)")
+        if len(set(self.param_addrs)) != self.P:
+            raise ValueError(f"ParticleGibbs: param_addrs = {self.param_addrs!r} names a site twice")
+        try:
+            sizes = [float(s) for s in step_size]
+        except TypeError:
+            sizes = None
+        if sizes is None or len(sizes) != self.P or not all(math.isfinite(s) and s > 0.0 for s in sizes):
+            raise ValueError(f"ParticleGibbs: step_size is {self.P} positive floats, one per entry of param_addrs; got {step_size!r}")
+        self.step_size = tuple(sizes)
+        self.init, self.step, self.prior = init, step, prior
+        self.specialize, self.backward = specialize, bool(backward)
+        self.bank = ConditionalBank(init, step, n_particles, n_chains, T, obs_addr=obs_addr, step_extra=step_extra,
+                                    specialize=specialize, state_addr=state_addr, state_sites=state_sites,
+                                    ancestor_sampling=ancestor_sampling, **bank_kw)
+        self.n, self.R, self.T = self.bank.n, self.bank.R, self.bank.T
+        self.done = self.max_iters = 0
+
+    def prepare(self, key: Key, ys: torch.Tensor, theta0, max_iters: int, retained=None):
+        """ONE key; theta0: P float32 [R] tensors, the chains' starts; max_iters: how many iterations run() may be asked
+        for in all (the record slabs hold that many rows); retained: a path per chain in draw()'s layout
+        (ConditionalBank.set_retained under theta0), or None: iteration 0 sweeps unconditionally.  Every buffer is
+        allocated here."""
+        be = _lib.get()
+        P, R, T = self.P, self.R, self.T
+        dev = be.device
+        b = self.bank
+        if tuple(key.shape) != ():
+            raise ValueError(f"ParticleGibbs.prepare takes ONE key (the chains' keys are split from it); got a batch of shape "
+                             f"{tuple(key.shape)}")
+        theta0 = tuple(theta0) if isinstance(theta0, (tuple, list)) else (theta0,)
+        theta0 = tuple(torch.as_tensor(v) for v in theta0)
+        if len(theta0) != P or any(tuple(v.shape) != (R,) for v in theta0):
+            raise ValueError(f"ParticleGibbs.prepare: theta0 is {P} tensors of shape {(R,)}, one per entry of param_addrs; got "
+                             f"{[tuple(v.shape) for v in theta0]}")
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters >= 2 ** 32:
+            raise ValueError(f"ParticleGibbs.prepare: max_iters = {max_iters} is outside [1, 2^32) (an iteration is fold_in's "
+                             "32-bit word)")
+        self.key, self._key_c = key, _key_words(key)
+        self.theta = torch.stack([v.to(dev).float() for v in theta0]).contiguous()   # [P, R]
+        b.params = tuple(self.theta[p] for p in range(P))                            # (views: the bank sees the chains' theta)
+        b.prepare(split(split(fold_in(key, 0), 4)[0], R), ys, retained)
+        D = b.D
+        sites = b.state_sites
+        if sites is None:
+            if D > 1:
+                raise NotImplementedError("ParticleGibbs: a state of more than one component needs state_sites= (the address "
+                                          "of each component, in order)")
+            sites = (b.state_addr,)
+        if len(sites) != D:
+            raise ValueError(f"ParticleGibbs: state_sites names {len(sites)} addresses for a state of {D} components")
+        self._sites = tuple(sites)
+        self.theta_pair = torch.zeros((P, 2 * R), dtype=torch.float32, device=dev)
+        self.scale = torch.tensor(self.step_size, dtype=torch.float32, device=dev)
+        self.lp = torch.zeros((1, 2 * R), dtype=torch.float32, device=dev)
+        self.joint = torch.zeros((T, 2 * R), dtype=torch.float32, device=dev)
+        self.obs = torch.zeros((T, 2 * R), dtype=torch.float32, device=dev)
+        self.x_pair = torch.zeros((T, D, 2 * R), dtype=torch.float32, device=dev)    # the drawn path on both halves
+        self.log_joint = torch.full((R,), -math.inf, dtype=torch.float64, device=dev)
+        self.rec_theta = torch.zeros((max_iters, P, R), dtype=torch.float32, device=dev)
+        self.rec_lj = torch.zeros((max_iters, R), dtype=torch.float64, device=dev)
+        self.rec_acc = torch.zeros((max_iters, R), dtype=torch.uint8, device=dev)
+        self.leaves = torch.tensor([v.data_ptr() for v in b.params_full], dtype=torch.int64, device=dev)
+        self.max_iters, self.done = max_iters, 0
+        self._launchers = [self._prior()] + self._scores()
+        return self
+
+    def _prior(self):
+        """the launcher of lp: the prior's program over the batch of 2R, built here"""
+        return _prior_logpdf(self.prior, self.param_addrs, [self.theta_pair[p] for p in range(self.P)], self.lp,
+                             specialize=self.specialize, launch=False, who="ParticleGibbs")
+
+    def _scores(self):
+        """the launchers of joint[t], obs[t] for every step: T launches over the batch of 2R (two programs, init's and
+        step's, built here; every leaf and output is a persistent buffer, so each launcher keeps ONE binding)"""
+        b = self.bank
+        theta_c = tuple(self.theta_pair[p] for p in range(self.P))
+        out = []
+        for t in range(self.T):
+            if t == 0:
+                model, args = self.init, theta_c
+            else:
+                prev = b._views._state_view(self.x_pair[t - 1:t], 0)
+                prev = type(prev)(v[0] for v in prev) if b.tuple_state is not None else prev[0]
+                model, args = self.step, (prev,) + tuple(b.step_extra(t)) + theta_c
+            out.append(_trajectory_scores(model, self._sites, b.obs_addr, args, list(self.x_pair[t]), b.ys[t],
+                                          (self.joint[t:t + 1], self.obs[t:t + 1]), specialize=self.specialize, launch=False))
+        return out
+
+    def _iterate(self, j):
+        """iteration j: the class docstring's six steps; returns the draw"""
+        be = _lib.get()
+        b = self.bank
+        P, R, T = self.P, self.R, self.T
+        be.check(be.c.gmx_pg_open(self._key_c, j, be.ptr(self.theta), P, R, self.n, T, be.ptr(b.keys_prop), be.ptr(b.keys_res),
+                                  be.ptr(b.keys_as) if b.ancestor_sampling else None, be.ptr(self.leaves), be.stream()),
+                 "gmx_pg_open")
+        b.launch()
+        x = b.draw(split(fold_in(self.key, j), 4)[1], backward=self.backward)
+        b.retain()
+        traj = b._last[0]
+        self.x_pair[:, :, :R].copy_(traj)
+        self.x_pair[:, :, R:].copy_(traj)
+        be.check(be.c.gmx_pg_propose(self._key_c, j, be.ptr(self.theta), be.ptr(self.scale), P, R, be.ptr(self.theta_pair),
+                                     be.stream()), "gmx_pg_propose")
+        for launch in self._launchers:
+            launch()
+        be.check(be.c.gmx_pg_accept(self._key_c, j, be.ptr(self.joint), be.ptr(self.obs), be.ptr(self.lp), be.ptr(self.theta_pair),
+                                    T, R, P, be.ptr(self.theta), be.ptr(self.log_joint), be.ptr(b.ref_lw), be.ptr(self.rec_theta),
+                                    be.ptr(self.rec_lj), be.ptr(self.rec_acc), j, self.max_iters, be.stream()), "gmx_pg_accept")
+        return x
+
+    def capture(self):
+        """capture the bank's sweep in its current form (ConditionalBank.capture); the chains stay where they are"""
+        self.bank.capture()
+        return self
+
+    def run(self, iters: int, paths=False) -> ParticleGibbsResult:
+        """`iters` more iterations of every chain (the chains continue from where the last run() left them).  Returns
+        theta [iters, P, R] float32, log_joint [iters, R] float64 (log p(theta, x, y) of the state each iteration ends
+        in), accepted [iters, R] bool, and with paths=True the stacked draws as ConditionalBank.run returns them
+        ([iters, R, T], [iters, R, T, D] or a tuple of [iters, R, T]), else None."""
+        iters = int(iters)
+        if not self.max_iters:
+            raise RuntimeError("ParticleGibbs.run: prepare(key, ys, theta0, max_iters) first")
+        if iters < 0 or self.done + iters > self.max_iters:
+            raise ValueError(f"ParticleGibbs.run: {self.done} iterations done and {iters} asked for, past max_iters = "
+                             f"{self.max_iters} (prepare(..., max_iters=) sizes the record)")
+        b = self.bank
+        first, out = self.done, []
+        for _ in range(iters):
+            x = self._iterate(self.done)
+            self.done += 1
+            if paths:
+                out.append(x)
+        stacked = None
+        if paths and out:
+            stacked = b.tuple_state(torch.stack([o[d] for o in out]) for d in range(b.D)) if b.tuple_state is not None \
+                else torch.stack(out)
+        rows = slice(first, first + iters)
+        return ParticleGibbsResult(self.rec_theta[rows].clone(), self.rec_lj[rows].clone(), self.rec_acc[rows] != 0, stacked)
+
+    def state(self):
+        """(theta [P, R] float32, log_joint [R] float64, the retained paths in draw()'s layout) of the chains now"""
+        b = self.bank
+        x = b._views._state_view(b.ref_x.clone(), 1)
+        return self.theta.clone(), self.log_joint.clone(), x

@@ -855,6 +855,57 @@ int gmx_pmmh_accept(const uint32_t key[2], uint32_t* it_d /* [2] */, const float
                     int64_t cap, int64_t* status_d /* [1] */, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Particle Gibbs  (additive, ABI still v8.  Reference call site: none of its own — particle Gibbs, Andrieu, Doucet &
+ * Holenstein 2010, section 2.4.3: R independent chains, chain r holding P parameters and the retained path of chain r of a
+ * bank of R conditional filters of n particles and T steps.)
+ * One iteration j is  gmx_pg_open | the bank's sweep, a trajectory draw, its retention | gmx_pg_propose | the caller's
+ * programs over a batch of 2R (columns 0 .. R - 1 under theta, R .. 2R - 1 under theta': the prior's log-density lp_d, and
+ * per step t the drawn path's joint score joint_d[t] and its observation term obs_d[t]) | gmx_pg_accept.  The draw reads
+ * on the host, so j is an ARGUMENT: nothing counts iterations on the device.
+ * Keys of iteration j under the run key:  k_it = fold_in(key, j);  (k_sweep, k_draw, k_prop, k_acc) = split(k_it, 4);
+ * k_draw is the caller's, for the draw.
+ *   gmx_pg_open      DEFINITION:
+ *                     1. keys_prop_d[t, r], keys_res_d[t, r], keys_as_d[t, r] = children 0, 1 and 2 of
+ *                        fold_in(split(k_sweep, R)[r], t): the bank's key tables under the R keys split(k_sweep, R);
+ *                        keys_as_d may be null (a bank without ancestor sampling): two tables are written;
+ *                     2. leaves_d[p][r * n + i] = theta_d[p, r] for i < n — leaves_d as gmx_pmmh_propose's: P device
+ *                        pointers in a table ON THE DEVICE, 8-byte aligned; each leaf [R * n] float32.
+ *                   ONE launch on gmx_pmmh_propose's grid: a workgroup per 1024 consecutive particles, the values of the
+ *                   chains it touches held in LDS (4 P bytes per chain, at most 32 KB), one barrier, 16-byte stores where
+ *                   the address allows; the T * R key rows spread over the same grid.
+ *                   Limits: those of gmx_pmmh_propose.
+ *   gmx_pg_propose   DEFINITION: theta_pair_d[p, r] = theta_d[p, r]; theta_pair_d[p, R + r] = the normal draw at counter
+ *                   0 under split(split(k_prop, R)[r], P)[p] with location theta_d[p, r] and scale scale_d[p] — z * scale
+ *                   rounded, then + theta rounded (float32), at EVERY j.  ONE launch, one thread per (p, r).
+ *                   Limits: 1 <= P <= 8; 1 <= R < 2^31.
+ *   gmx_pg_accept    DEFINITION, for every chain r:
+ *                     1. S = sum over t, ascending, in float64, of (double)joint_d[t, r]; S' likewise of joint_d[t, R + r];
+ *                     2. log_alpha = (float)((S' - S) + ((double)lp_d[R + r] - (double)lp_d[r]));
+ *                     3. taken iff log(u) < log_alpha, u the uniform [0, 1) draw at counter 0 under split(k_acc, R)[r] —
+ *                        gmx_mh_accept's rule; a NaN log_alpha rejects.  c = R + r when taken, else r;
+ *                     4. theta_d[:, r] = theta_pair_d[:, c];  log_joint_d[r] = (taken ? S' : S) + (double)lp_d[c];
+ *                     5. rec_theta_d[row, :, r], rec_lj_d[row, r], rec_acc_d[row, r] = the state after the decision and
+ *                        the decision (0 / 1);
+ *                     6. ref_lw_d[t, r] = obs_d[t, c] for every t: the retained path's pinned weights under the
+ *                        parameters the next sweep runs under, whatever the decision.
+ *                   ONE launch, one thread per chain, no LDS.
+ *                   Limits: P, R; T >= 1, T * R < 2^31; 1 <= cap <= 2^32, 0 <= row < cap; no null pointer.
+ * Every pointer aligned to its element (the key tables to 8 bytes).  A null pointer or an out-of-range size returns
+ * non-zero before anything is launched.
+ * ---------------------------------------------------------------------- */
+int gmx_pg_open(const uint32_t key[2], uint32_t j, const float* theta_d /* [P, R] */, int32_t P, int64_t R, int64_t n, int32_t T,
+                uint32_t* keys_prop_d /* [T, R, 2] */, uint32_t* keys_res_d /* [T, R, 2] */,
+                uint32_t* keys_as_d /* [T, R, 2] or null */, float* const* leaves_d /* [P] device pointers, on the device */,
+                gmx_stream stream);
+int gmx_pg_propose(const uint32_t key[2], uint32_t j, const float* theta_d /* [P, R] */, const float* scale_d /* [P] */, int32_t P,
+                   int64_t R, float* theta_pair_d /* [P, 2R] */, gmx_stream stream);
+int gmx_pg_accept(const uint32_t key[2], uint32_t j, const float* joint_d /* [T, 2R] */, const float* obs_d /* [T, 2R] */,
+                  const float* lp_d /* [2R] */, const float* theta_pair_d /* [P, 2R] */, int32_t T, int64_t R, int32_t P,
+                  float* theta_d /* [P, R] */, double* log_joint_d /* [R] */, float* ref_lw_d /* [T, R] */,
+                  float* rec_theta_d /* [cap, P, R] */, double* rec_lj_d /* [cap, R] */, uint8_t* rec_acc_d /* [cap, R] */,
+                  int64_t row, int64_t cap, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * DEPRECATED as a collective (gmx_p2p_exchange: one launch per collective; superseded by the fused peer exchange above —
  * gmx_run_args.peer + gmx_shard_step_peer, no collective launch at all).  gmx_p2p_alloc / _open / _close / _free stay:
  * they are how the fused exchange's landing blocks are allocated and mapped.

@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 
 
 def workloads(be):
-    from tests import ancestor_checks, backward_checks, grad_checks, parity, pgbs_checks, pmmh_checks
+    from tests import ancestor_checks, backward_checks, grad_checks, parity, pgbs_checks, pgibbs_checks, pmmh_checks
     sweep = dict(ancestors_equal=True, x_equal=True, totals_equal=True)
 
     def lgssm(**kw):
@@ -55,6 +55,9 @@ def workloads(be):
           for n in (200,) for r in (False, True) for a in (False, True)]
     W += [("pmmh_checks.check_chain_is_the_composition(%s)" % c,
            lambda c=c: pmmh_checks.check_chain_is_the_composition(be, c, specialize=False)) for c in ("tiny", "ess")]
+    W += [("pgibbs_checks.check_chain_is_the_composition(%s)" % pgibbs_checks.chain_id(c),
+           lambda c=c: pgibbs_checks.check_chain_is_the_composition(be, c, specialize=False))
+          for c in (("tiny", False, False), ("tiny", True, False), ("one", False, False))]
     return W
 
 
