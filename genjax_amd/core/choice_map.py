@@ -51,6 +51,9 @@ def _index_array(a):
     if isinstance(a, (_IndexArray, DynamicIndex)):
         return a
     if getattr(a, "_gmx_mapped", False) and "int" in str(getattr(a, "dtype", "")):
+        host = getattr(a, "_host", None)
+        if host is not None:               # a HOST index array that genjax.vmap mapped: the static array it is outside a map
+            return _index_array(host)
         return DynamicIndex(a)             # an integer tensor mapped by genjax.vmap: one index per instance
     if isinstance(a, (str, int, bytes)) or a is Ellipsis or isinstance(a, slice) or isinstance(a, tuple):
         return None
@@ -852,3 +855,12 @@ class _ChoiceMapBuilder:
 
 ChoiceMapBuilder = _ChoiceMapBuilder()
 ChoiceMap.builder = ChoiceMapBuilder
+
+
+# The builders only STORE values: under `transforms.vmap` they see the values it tagged as the plain arrays they are
+# (_glue: an address component's shape, the elements of an index array's values).
+from .._glue import internal as _internal  # noqa: E402
+ChoiceMap.set = _internal(ChoiceMap.set)
+ChoiceMap.merge = _internal(ChoiceMap.merge)
+ChoiceMap.choice = ChoiceMap.value = ChoiceMap.v = staticmethod(_internal(ChoiceMap.choice))
+_ChoiceMapBuilder.set = _ChoiceMapBuilder.v = _ChoiceMapBuilder.choice = ChoiceMap.__dict__["choice"]

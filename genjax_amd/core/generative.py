@@ -258,6 +258,14 @@ class DiffAnnotate(EditRequest):
 class GenerativeFunction:
     """GenerativeFunction ABC (generative_function.py:232-689)."""
 
+    # the interface methods, as glue under `transforms.vmap` calls them: every class's own definitions are entry
+    # points of the package (engine.gfi_entry: mapped values arrive untagged, the tags are inert inside)
+    _ENTRY_POINTS = ("simulate", "assess", "generate", "importance", "project", "edit", "update", "propose")
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        _wrap_entry_points(cls)
+
     # abstract interface ---------------------------------------------------------
     def simulate(self, key, args): raise NotImplementedError
     def assess(self, sample: ChoiceMap, args): raise NotImplementedError
@@ -328,6 +336,17 @@ class GenerativeFunction:
     def reduce(self):
         from ..combinators import reduce
         return reduce()(self)
+
+
+def _wrap_entry_points(cls):
+    from .._glue import gfi_entry
+    for name in GenerativeFunction._ENTRY_POINTS:
+        fn = cls.__dict__.get(name)
+        if callable(fn) and not isinstance(fn, (staticmethod, classmethod)) and not getattr(fn, "_gmx_entry", False):
+            setattr(cls, name, gfi_entry(fn))
+
+
+_wrap_entry_points(GenerativeFunction)
 
 
 def _args_equal(a, b) -> bool:

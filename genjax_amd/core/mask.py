@@ -255,3 +255,10 @@ def _check_prefix(value, flag):
             continue
         if ls[:len(fs)] != fs:
             raise ValueError(f"Vectorized flag's shape {fs} must be a prefix of all leaf shapes. Found {ls}.")
+
+
+# `Mask.build` is batch polymorphic by construction (leaf shapes against flag shapes): under `transforms.vmap` it sees
+# the values the map tagged as the plain arrays they are (_glue)
+from .._glue import internal as _internal  # noqa: E402
+Mask.build = staticmethod(_internal(Mask.build))
+Mask.__init__ = _internal(Mask.__init__)

@@ -329,7 +329,6 @@ static std::string jit_source(const gmx_program* p, bool* gathers_prefetched = n
     pre_of[pc] = k;
     if (b & GMX_F_GATHER) { any_gather = true; if (pc < first_gather_pc) first_gather_pc = pc; }
   }
-  if (const char* e_ = getenv("GENMI_JIT_NOPRE")) { if (e_[0] == '1' && !p->fuse_rs && !p->fuse_sh) fits = false; }   // (diagnosis)
   if (!fits) { pres.clear(); pre_of.assign(p->n_instr, -1); any_gather = false; }
   if (gathers_prefetched) {          // every gathered load goes through the prologue's ancestors (GMX_JIT_PRE_ANC)
     *gathers_prefetched = any_gather;

@@ -27,7 +27,7 @@ from ctypes import POINTER, c_uint32, c_void_p, cast
 import numpy as np
 import torch
 
-from . import _lib
+from . import _glue, _lib
 from .core.choice_map import ChoiceMap
 from .core.mask import Indexed, Mask
 from .program import F_BCAST, F_GATHER, Graph, ProgramTooLarge, compile_graph, split_graph
@@ -176,6 +176,8 @@ class Broadcast(torch.Tensor):
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
+        if _glue.strict() and any(issubclass(t, Mapped) for t in types):
+            return Mapped.__torch_function__(func, types, args, kwargs)      # (a mapped operand guards the batch axis)
         shared = [True]
 
         def look(v):
@@ -203,22 +205,152 @@ class Broadcast(torch.Tensor):
         return mark(out)
 
 
+# torch functions that act on every element alone: on a mapped tensor they keep the batch axis where it is
+_MAPPED_ELEMENTWISE = frozenset("""
+add sub mul div true_divide floor_divide remainder fmod pow neg negative abs absolute exp exp2 expm1 log log2 log10 log1p
+sqrt rsqrt square reciprocal sin cos tan tanh sinh cosh asin acos atan atan2 sigmoid erf erfc erfinv lgamma digamma
+floor ceil round trunc sign clamp clip maximum minimum fmax fmin where logaddexp nan_to_num isnan isfinite isinf
+eq ne lt le gt ge logical_and logical_or logical_not logical_xor bitwise_and bitwise_or bitwise_not bitwise_xor
+to type_as float double half int long bool clone detach cpu cuda contiguous relu softplus
+__add__ __radd__ __sub__ __rsub__ __mul__ __rmul__ __truediv__ __rtruediv__ __floordiv__ __rfloordiv__ __mod__ __rmod__
+__pow__ __rpow__ __neg__ __pos__ __abs__ __eq__ __ne__ __lt__ __le__ __gt__ __ge__ __and__ __rand__ __or__ __ror__
+__xor__ __rxor__ __invert__
+""".split())
+# ... that say nothing about the batch axis: answered as for the plain tensor
+_MAPPED_NEUTRAL = frozenset("""is_floating_point is_complex is_signed element_size get_device as_subclass __repr__ __str__
+__hash__ data_ptr untyped_storage requires_grad_ __reduce_ex__ __deepcopy__""".split())
+_MAPPED_AXIS_GETTERS = frozenset(("shape", "ndim", "T", "mT", "H", "mH", "data", "grad", "real", "imag"))   # (`.data`: the untagged tensor)
+
+
+def _elementwise_operands_agree(operands, what):
+    """The operands of an elementwise call, checked: the batched call equals the per-instance one only when every mapped
+    operand belongs to the same `vmap`, all of them have the same number of axes, and every other array has fewer
+    (it then broadcasts against the instance's own axes, never against the batch axis)."""
+    mapped = [v for v in operands if isinstance(v, Mapped)]
+    lvl, nd = mapped[0]._lvl, mapped[0].plain.ndim
+    for v in operands:
+        if isinstance(v, Mapped):
+            if v._lvl != lvl or v.plain.ndim != nd:
+                _glue.refuse(f"{what}: mapped operands of two maps or two ranks")
+        elif isinstance(v, torch.Tensor):
+            if v.ndim >= nd:
+                _glue.refuse(f"{what}: an operand that would broadcast against the batch axis")
+        elif isinstance(v, np.ndarray):
+            if v.ndim > 0:
+                _glue.refuse(f"{what}: a host array operand")
+        elif isinstance(v, (list, tuple)):
+            _glue.refuse(f"{what}: a sequence operand")
+    return lvl
+
+
+def _flat_operands(args, kwargs):
+    out = []
+
+    def look(v):
+        if isinstance(v, (tuple, list)):
+            for x in v:
+                look(x)
+        else:
+            out.append(v)
+    look(tuple(args))
+    look(tuple(kwargs.values()))
+    return out
+
+
 class Mapped(torch.Tensor):
-    """A tensor `genjax.vmap` maps over its leading axis (one entry per instance).  Only a tag: an integer tensor
-    carrying it, used as an address component (`C["ys", idx, "y"].set(v)`), is a RUN-TIME per-instance index
-    (core.choice_map.DynamicIndex) rather than a static array of indices."""
+    """A tensor `genjax.vmap` maps over its leading axis (one entry per instance).  An integer tensor carrying the tag,
+    used as an address component (`C["ys", idx, "y"].set(v)`), is a RUN-TIME per-instance index
+    (core.choice_map.DynamicIndex) rather than a static array of indices.
+
+    While the mapped function's own glue runs (_glue.strict()), the tag also guards the batch axis: elementwise
+    operations keep it, and everything that would see the axis — a reduction, an index, `.shape`, `len`, `reshape`,
+    `cat`, `matmul`, `cumsum`, ... — raises _glue.NotBatchPolymorphic, on which `vmap` runs the instances one by one.
+    Inside this package's entry points the tag is inert: any operation answers as for the plain tensor."""
     _gmx_mapped = True
+    _lvl = 0
+    _host = None          # the host array (numpy, `jnp.array / arange`) this leaf was lifted from when it was mapped: the
+    #                       instances are ITS elements, and as an address component it stays the static index array it is
 
     @staticmethod
-    def __new__(cls, t):
-        return t if isinstance(t, Mapped) else t.as_subclass(cls)
+    def __new__(cls, t, lvl=0, host=None):
+        if isinstance(t, Mapped):
+            return t
+        out = t.as_subclass(cls)
+        out._lvl, out._host = lvl, host
+        return out
 
-    def __init__(self, t):
+    def __init__(self, t, lvl=0, host=None):
         pass
 
     @property
     def plain(self) -> torch.Tensor:
-        return self.as_subclass(torch.Tensor)
+        with torch._C.DisableTorchFunctionSubclass():
+            return self.as_subclass(torch.Tensor)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        name = getattr(func, "__name__", "")
+        if name == "__get__":
+            name = getattr(getattr(func, "__self__", None), "__name__", "")
+            getter = True
+        else:
+            getter = False
+        if _glue.strict():
+            if getter:
+                if name in _MAPPED_AXIS_GETTERS:
+                    _glue.refuse(f"`.{name}` of a mapped tensor")
+            elif name in _MAPPED_ELEMENTWISE:
+                ops = _flat_operands(args, kwargs)
+                lvl = _elementwise_operands_agree(ops, f"torch {name}")
+                with torch._C.DisableTorchFunctionSubclass():
+                    out = func(*args, **kwargs)
+                return Mapped(out.as_subclass(torch.Tensor), lvl) if isinstance(out, torch.Tensor) else out
+            elif name not in _MAPPED_NEUTRAL:
+                _glue.refuse(f"torch `{name}` on a mapped tensor")
+        with torch._C.DisableTorchFunctionSubclass():
+            return func(*args, **kwargs)
+
+
+def _host_to_device(a: np.ndarray) -> torch.Tensor:
+    """a mapped host array on the device, in the types a launch reads: float32 (a float64 array is narrowed, as
+    `jnp.array` narrows it), int32, bool"""
+    a = np.ascontiguousarray(a)
+    a = a.astype(np.float32) if a.dtype.kind == "f" else (a.astype(np.int32) if a.dtype.kind in "iu" else a)
+    t = torch.from_numpy(a.copy())
+    if _lib._backend is None and not torch.cuda.is_available():
+        return t          # no backend in this process: host glue only (a generative function raises there, mapped or not)
+    return t.to(_lib.get().device)
+
+
+def _walk(v, fn):
+    """fn over the leaves of the containers a mapped function hands to a generative function"""
+    if isinstance(v, tuple):
+        return tuple(_walk(x, fn) for x in v)
+    if isinstance(v, list):
+        return [_walk(x, fn) for x in v]
+    if isinstance(v, dict):
+        return {k: _walk(x, fn) for k, x in v.items()}
+    if isinstance(v, ChoiceMap):
+        return v.map_values(lambda x: _walk(x, fn))
+    if isinstance(v, Mask):
+        return Mask(_walk(v.value, fn), _walk(v.flag, fn))
+    if isinstance(v, Indexed):
+        return Indexed(_walk(v.value, fn), _walk(v.idx, fn))
+    from .core.generative import Update
+    if isinstance(v, Update):
+        return Update(_walk(v.constraint, fn))
+    return fn(v)
+
+
+def untag(v):
+    """What a generative function's entry point makes of the values a mapped function hands it: a mapped tensor is the
+    plain tensor (an integer one keeps its tag: a run-time index)."""
+    def leaf(x):
+        if isinstance(x, Mapped):
+            return x if x.dtype in (torch.int32, torch.int64) else x.plain
+        return x
+    return _walk(v, leaf)
 
 
 class Expanded(torch.Tensor):
@@ -244,6 +376,8 @@ class Expanded(torch.Tensor):
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
+        if _glue.strict() and any(issubclass(t, Mapped) for t in types):
+            return Mapped.__torch_function__(func, types, args, kwargs)      # (a mapped operand guards the batch axis)
         with torch._C.DisableTorchFunctionSubclass():
             return func(*args, **(kwargs or {}))
 

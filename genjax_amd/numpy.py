@@ -239,6 +239,14 @@ def table_slot(g, arr) -> int:
     return len(tabs) - 1
 
 
+def _refuse_mapped(what, *xs):
+    """Under `transforms.vmap`, a call whose operands numpy would read as plain arrays whatever tag they carry (an index
+    argument is no operand numpy dispatches on): with a mapped operand it takes the per-instance loop."""
+    from . import _glue
+    if _glue.strict() and builtins_any(getattr(v, "_gmx_mapped", False) for v in xs):
+        _glue.refuse(f"jnp.{what} with a mapped operand")
+
+
 def _is_torch(x):
     return isinstance(x, torch.Tensor)
 
@@ -588,7 +596,7 @@ def logsumexp(x, axis=-1):
             acc = t if acc is None else acc + t
         return log(acc) + m
     if _is_torch(x):
-        return torch.logsumexp(x, dim=axis)
+        return torch.logsumexp(x.reshape(-1), dim=0) if axis is None else torch.logsumexp(x, dim=axis)
     from scipy.special import logsumexp as _l
     return _l(x, axis=axis)
 
@@ -803,6 +811,7 @@ def reshape(x, shape):
 
 
 def tile(x, reps):
+    _refuse_mapped("tile", x)
     return np.tile(np.asarray(x, dtype=object), reps) if is_symbolic(x) else (x.repeat(reps) if _is_torch(x) else np.tile(x, reps))
 
 
@@ -819,6 +828,7 @@ def eye(n, m=None, dtype=np.float32):
 
 
 def broadcast_to(x, shape):
+    _refuse_mapped("broadcast_to", x)
     if is_symbolic(x):
         return np.broadcast_to(np.asarray(x, dtype=object), shape)
     if _is_torch(x):
@@ -827,6 +837,7 @@ def broadcast_to(x, shape):
 
 
 def repeat(x, repeats, axis=None):
+    _refuse_mapped("repeat", x)
     if is_symbolic(x):
         return np.repeat(np.asarray(x, dtype=object), repeats, axis=axis)
     if _is_torch(x):
@@ -849,28 +860,46 @@ def transpose(x, axes=None):
 
 
 def array_equal(a, b):
+    _refuse_mapped("array_equal", a, b)
     return bool(np.array_equal(np.asarray(a.detach().cpu() if _is_torch(a) else a), np.asarray(b.detach().cpu() if _is_torch(b) else b)))
 
 
 def allclose(a, b, rtol=1e-5, atol=1e-8):
+    _refuse_mapped("allclose", a, b)
     return bool(np.allclose(np.asarray(a.detach().cpu() if _is_torch(a) else a), np.asarray(b.detach().cpu() if _is_torch(b) else b),
                             rtol=rtol, atol=atol))
 
 
 def all(x, axis=None):                                                # noqa: A001
     """concrete arrays only (a truth value of launch values belongs to the host, not to a site program)"""
+    _refuse_mapped("all", x)
     a = np.asarray(x.detach().cpu() if _is_torch(x) else x)
     return bool(a.all()) if axis is None else a.all(axis=axis)
 
 
 def any(x, axis=None):                                                # noqa: A001
+    _refuse_mapped("any", x)
     a = np.asarray(x.detach().cpu() if _is_torch(x) else x)
     return bool(a.any()) if axis is None else a.any(axis=axis)
+
+
+def take(a, indices, axis=None):
+    """jnp.take on concrete arrays (a traced index into a table is `table[idx]`)"""
+    _refuse_mapped("take", a, indices)
+    if _is_torch(a) or _is_torch(indices):
+        dev = a.device if _is_torch(a) else indices.device
+        t = a if _is_torch(a) else torch.as_tensor(np.asarray(a), device=dev)
+        i = (indices if _is_torch(indices) else torch.as_tensor(np.asarray(indices), device=dev)).to(torch.int64)
+        if axis is None:
+            return torch.take(t, i)
+        return torch.index_select(t, int(axis), i.reshape(-1)).squeeze(int(axis)) if i.ndim == 0 else torch.index_select(t, int(axis), i)
+    return np.take(np.asarray(a), indices, axis=axis)
 
 
 def bincount(x, weights=None, minlength=0, length=None):
     """jnp.bincount (7_application_dirichlet_mixture_model.ipynb c10: `length=` fixes the output size under jit)"""
     n = int(length if length is not None else minlength)
+    _refuse_mapped("bincount", x, weights)
     if _is_torch(x):
         out = torch.bincount(x.to(torch.int64).reshape(-1), weights=weights, minlength=n)
         return out[:n] if length is not None else out

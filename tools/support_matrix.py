@@ -378,6 +378,38 @@ def generate(sample=None):
     return rows
 
 
+# (prose, not measured cells: held by tests/test_vmap_cpu.py and tests/test_vmap_gpu.py)
+VMAP_GLUE = [
+    "",
+    "## Glue under `genjax.vmap(f)`: what stays one call, what runs per instance",
+    "",
+    "`vmap(f, in_axes, out_axes)(xs)[i] == f(xs[i])`, bit for bit for the glue listed here and short of the three cases under \"Not",
+    "guarded\" (`tests/vmap_checks.py`: a corpus of mapped functions against their instances, on the mirror and on the device).",
+    "Every mapped leaf carries a tag while `f` runs (`engine.Mapped`; a numpy / `jnp.array` value moves to the device as float32 /\nint32 / bool when it is mapped and carries the same tag); the tag decides between ONE call of `f` on the batched",
+    "values and one call per instance (results stacked; a `warnings.warn` above 64 instances).",
+    "",
+    "| what `f` does with a mapped value | how it runs |",
+    "|---|---|",
+    "| hands it to a generative function: `simulate / importance / assess / update / edit / project / propose` as an argument, a constraint, a `ChoiceMap` / `Mask` leaf, an integer tensor as an address component; a mapped HOST array arrives as a device tensor with the batch axis in front | one call, one launch per method |",
+    "| stores it: `C[...].set(v)`, `ChoiceMap.d / kw`, `Mask.build` | one call |",
+    "| elementwise arithmetic, comparisons, `jnp.where`, `jnp.exp / log / ...`, dtype casts, with scalars, with other values of the same map and rank, with unmapped arrays of LOWER rank | one call |",
+    "| returns a value that does not depend on the batch (a Python constant, an unmapped argument, a host array; a fresh or closed-over tensor of any length when `f` was handed no `Key` and called no generative function, otherwise one whose leading length is not B: see \"Not guarded\") | one call, broadcast along the new axis |",
+    "| reductions (`jnp.sum / mean / max / min / prod / logsumexp / cumsum`, `v.sum()`, `torch.sum(v, 0)`) whatever the axis, `jnp.dot / matmul`, `jnp.take`, `jnp.bincount`, `reshape`, `cat / stack` | per instance |",
+    "| `v[0]`, `v[-1]`, `v[1:3]`, `v.shape`, `v.ndim`, `len(v)`, `v.item()`, `float(v)`, `bool(v)` | per instance |",
+    "| arithmetic with an unmapped array of the same or higher rank (`x + w`, `idx == i`), or with a value of an enclosing map | per instance (the inner map; then its result is stacked inside the outer axis) |",
+    "| maps a mapped value again with an inner `vmap` | the OUTER map runs per instance |",
+    "",
+    "Errors: only the tags' own signal and torch's size-mismatch errors take the per-instance loop.  `NotImplementedError`,",
+    "`GenmiError`, `ValueError` and everything else `f` raises propagate from the first call.",
+    "",
+    "Not guarded (wrong values, no error).  (1) A value a generative function RETURNS inside `f` (`tr.get_retval()`, a weight) is a plain batched tensor, so",
+    "`f` reducing or indexing IT acts on the batch axis unseen.  (2) For the same reason an untagged TENSOR in the result whose leading\nlength happens to equal B — `torch.ones(B)`, a closed-over constant of length B — is taken for batched and not broadcast when\n`f` was handed a `Key` or called a generative function (`vmap(lambda k: torch.ones(3))(keys(3))` has shape [3], not [3, 3]).\n(3) An integer HOST array used as an address component",
+    "(`C[\"ys\", jnp.arange(3), \"y\"]`) stays the static index array it is outside a map (map an integer TENSOR for one run-time",
+    "index per instance).  `GENMI_VMAP_CHECK=1` compares the first min(B, 4) instances with the result at every call and",
+    "raises `AssertionError` on a difference (`profiles/vmap_check_cpu.txt`).",
+]
+
+
 def render(rows):
     out = ["# SUPPORT.md — which model form runs under which method, and how",
            "",
@@ -397,7 +429,7 @@ def render(rows):
            "|---|---|---|" + "---|" * len(METHODS)]
     for name, size, batch, cells in rows:
         out.append(f"| {name} | {size} | {batch} | " + " | ".join(cells) + " |")
-    return "\n".join(out) + "\n"
+    return "\n".join(out + VMAP_GLUE) + "\n"
 
 
 if __name__ == "__main__":
