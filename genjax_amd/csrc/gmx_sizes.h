@@ -4,8 +4,8 @@
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
 //                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
-//                             the tile-form resamplers, the row-wise draws, the particle-MH pair, the particle-Gibbs three, the
-//                             sharded / peer family, the sweep history
+//                             the tile-form resamplers, the row-wise draws and moments, the particle-MH pair, the
+//                             particle-Gibbs three, the sharded / peer family, the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
 // Plain host C++ (static inline): no HIP, no kernel, no algorithm.  hiprtc never sees this file (it is not among the
@@ -276,6 +276,36 @@ static inline size_t gmx_resample_rows_ess_bytes_(int kind, int64_t rows, int64_
 }
 // an ess_q8 above this resamples every row with mass (the ESS of n weights is at most n)
 static inline uint32_t gmx_ess_always_(int64_t n) { return (uint32_t)(256 * n); }
+
+// ---- row-wise weighted moments: gmx_rows_moments (gmx_moments.h) ----
+// Its workspace past one tile: rec f64 [rows * tiles, 2 + 2 D] (a tile's S0, S2, then A_d, B_d per component, relative to
+// the tile's own maximum) | tmax f32 [rows * tiles], rounded up to 16 bytes; nothing for n <= 1024 (one launch)
+struct gmx_moments_ws { double* rec; float* tmax; };
+static inline uint64_t gmx_moments_rec_(int32_t D) { return 2u + 2u * (uint64_t)D; }
+static inline size_t gmx_rows_moments_bytes_(int64_t rows, int64_t n, int32_t D) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N || D < 0) return 16;
+  return (size_t)((gmx_rows_cells_(rows, n) * (gmx_moments_rec_(D) * 8u + 4u) + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_moments_ws gmx_rows_moments_carve_(void* workspace, int64_t rows, int64_t n, int32_t D) {
+  gmx_moments_ws w;
+  w.rec = (double*)workspace;
+  w.tmax = (float*)(w.rec + gmx_rows_cells_(rows, n) * gmx_moments_rec_(D));
+  return w;
+}
+// rows = 0 is a call that does nothing; the store is gmx_rows_pin's (here: read), the outputs 1 + 2 D doubles per row
+static inline gmx_refusal gmx_rows_moments_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                    int64_t x_row_stride, int64_t out_ld, bool no_x) {
+  if (has_null) return {"%s: null argument", 0};
+  if (n < 1 || n > GMX_ROWS_MAX_N) return {"%s: n = %lld is outside [1, 2^21]", (long long)n};
+  if (rows < 0) return {"%s: rows = %lld is negative", (long long)rows};
+  if (rows > 0x7fffffffLL / n) return {"%s: rows = %lld does not keep rows * n below 2^31", (long long)rows};
+  if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  const gmx_refusal no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return no;
+  if (out_ld < 1 + 2 * (int64_t)D) return {"%s: out_ld = %lld is smaller than 1 + 2 D", (long long)out_ld};
+  if (D > 0 && no_x) return {"%s: null argument (x_d with D > 0)", 0};
+  return {nullptr, 0};
+}
 
 // ---- particle marginal Metropolis-Hastings over a bank of filters: gmx_pmmh_propose, gmx_pmmh_accept (gmx_pmmh.h) ----
 #define GMX_PMMH_BLOCK 256             /* threads per workgroup of both kernels */

@@ -797,6 +797,63 @@ def resample_rows_pinned(keys: Key, lw: torch.Tensor, pin_lw: torch.Tensor, pin_
     return anc, total, mx, cdf_shift(n), status
 
 
+RowMoments = namedtuple("RowMoments", ["ess", "mean", "var"])
+
+
+def _component_major(x, R, n):
+    """(tensor that owns the words, D, x_ld, x_row_stride, scalar) of a state in one of the forms BootstrapBank.state() returns
+    — [R, n], [R, n, D] or a tuple of [R, n] — as gmx_rows_moments addresses it (component d of particle i of row r at
+    d * x_ld + r * x_row_stride + i): through its strides where they say exactly that, else copied ONCE to a contiguous
+    [D, R, n]"""
+    if isinstance(x, (tuple, list)):
+        first = x[0]
+        step = (x[1].data_ptr() - first.data_ptr()) // 4 if len(x) > 1 else first.stride(0) * (R - 1) + n
+        same = all(tuple(v.shape) == (R, n) and v.dtype == torch.float32 and v.stride() == first.stride() and
+                   v.data_ptr() - first.data_ptr() == 4 * d * step for d, v in enumerate(x))
+        if same and first.stride(1) == 1 and first.stride(0) >= n and step >= first.stride(0) * (R - 1) + n:
+            return first, len(x), step, first.stride(0), False
+        return torch.stack([v.float() for v in x]).contiguous(), len(x), R * n, n, False
+    scalar = x.ndim == 2
+    x3 = x.reshape(R, n, 1) if scalar else x
+    if tuple(x3.shape[:2]) != (R, n) or x3.ndim != 3:
+        raise ValueError(f"row_moments: x is [R, n], [R, n, D] or a tuple of [R, n] with [R, n] = {(R, n)}; got {tuple(x.shape)}")
+    D = int(x3.shape[2])
+    rs, cs, ds = x3.stride()
+    if D == 1:
+        ds = rs * (R - 1) + n
+    if x3.dtype == torch.float32 and cs == 1 and rs >= n and ds >= rs * (R - 1) + n:
+        return x3, D, ds, rs, scalar
+    return x3.float().permute(2, 0, 1).contiguous(), D, R * n, n, scalar
+
+
+def row_moments(lw: torch.Tensor, x=None, *, carry=None, out=None, workspace=None):
+    """gmx_rows_moments: the effective sample size and the weighted mean and variance of every row, in one call.  lw [R, n]
+    float32 log-weights (unit column stride); x: None, [R, n], [R, n, D] or a tuple of D [R, n] — the forms
+    BootstrapBank.state() returns; carry [R, n] (lw's strides): added to lw in float32 first, as the adaptive row resampler
+    adds it.  -> RowMoments(ess [R], mean, var), float64 on lw's device; mean and var are [R] for an [R, n] state, [R, D]
+    otherwise, None without x.  A row without mass: ess 0, NaN mean and variance.  out ([R, >= 1 + 2 D] float64) and workspace:
+    persistent buffers instead of fresh ones."""
+    be = _lib.get()
+    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
+        raise ValueError(f"row_moments: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
+    R, n = (int(v) for v in lw.shape)
+    ld = int(lw.stride(0)) if R > 1 else n
+    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
+        raise ValueError("row_moments: carry is a float32 matrix of lw's shape and strides")
+    xt, D, x_ld, x_rs, scalar = (None, 0, 0, 0, False) if x is None else _component_major(x, R, n)
+    if out is None:
+        out = torch.empty((R, 1 + 2 * D), dtype=torch.float64, device=lw.device)
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=lw.device)
+    be.check(be.c.gmx_rows_moments(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(out),
+                                   int(out.stride(0)) if R > 1 else 1 + 2 * D, be.ptr(workspace), be.stream()),
+             "gmx_rows_moments")
+    if x is None:
+        return RowMoments(out[:, 0], None, None)
+    mean, var = out[:, 1:1 + D], out[:, 1 + D:1 + 2 * D]
+    return RowMoments(out[:, 0], mean[:, 0], var[:, 0]) if scalar else RowMoments(out[:, 0], mean, var)
+
+
 def _row_kind(kind, who):
     kind = _KINDS[kind] if isinstance(kind, str) else int(kind)
     if kind in (MULTINOMIAL_TILED, MULTINOMIAL_SORTED):
@@ -2052,11 +2109,19 @@ class BootstrapBank(_Sweep):
     PRODUCT of its incremental weights, so its mean over the row at the next resampling (or at the end) estimates the
     ratio of normalisers across the whole stretch at once, and the product of those means over the stretches — each
     started from an equally weighted population — is the usual product-form estimate of Z (Del Moral, Doucet & Jasra
-    2012, section 2); a skipped step's own term is already inside the next counted one."""
+    2012, section 2); a skipped step's own term is already inside the next counted one.
+
+    moments=True (False: nothing is allocated and the sweep is launch for launch the one above): per step ONE more launch
+    (gmx_rows_moments; two past n = 1024) between the site program and the row resampler writes each filter's effective
+    sample size and the weighted mean and variance of its particles — the filtering mean and variance of step t — into a
+    [T, R, 1 + 2 D] float64 table on the device: 1 + 2 D doubles per filter and step instead of the particles, no host read,
+    still one graph.  filter_mean(), filter_var() and ess() read it after a sweep.  The weights are the ones the resampler
+    acts on (with ess_threshold=: accumulated since the row's last resampling); a filter without mass at a step has ESS 0
+    and NaN moments there."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
-                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None):
+                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2077,6 +2142,7 @@ class BootstrapBank(_Sweep):
         self.step_extra = step_extra or (lambda t: ())
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
+        self.moments = bool(moments)
         self.ess_threshold, self.ess_q8 = None, None
         if ess_threshold is not None:
             tau = float(ess_threshold)
@@ -2148,7 +2214,21 @@ class BootstrapBank(_Sweep):
             self.p_init.comp.specialize()
             self.p_step.comp.specialize()
         self.partials = torch.zeros((2, (N + 255) // 256), dtype=torch.float32, device=dev)
+        if self.moments:
+            D = self.store.D
+            self.mom = torch.zeros((T, R, 1 + 2 * D), dtype=torch.float64, device=dev)     # per step and row: ESS, D means, D variances
+            self.mom_ws = torch.zeros(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
         return self
+
+    def _moments(self, t):
+        """step t's ESS, filtering mean and variance of every row, from the weights the resampler is about to act on (with
+        ess_threshold=: lw + carry) and the state the step program has just written (gmx_rows_moments)"""
+        be = _lib.get()
+        R, n = self.R, self.n
+        x = self.store.rows[t % 2]
+        be.check(be.c.gmx_rows_moments(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
+                                       be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.mom[t]), int(self.mom.shape[2]),
+                                       be.ptr(self.mom_ws), be.stream()), "gmx_rows_moments")
 
     def _resample(self, t):
         if self.ess_q8 is not None:
@@ -2167,7 +2247,8 @@ class BootstrapBank(_Sweep):
 
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
-        ess_threshold=: gmx_resample_rows_ess) — no syncs, no allocations, no host read of a device value"""
+        ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two) — no syncs, no
+        allocations, no host read of a device value"""
         N = self.R * self.n
         self.status.zero_()
         if self.ess_q8 is not None:
@@ -2176,7 +2257,32 @@ class BootstrapBank(_Sweep):
             _mh, prog, leaves, key, bufs = self._programs(t)
             bufs[prog.wo[1]] = self.lw.reshape(1, N)
             prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
+            if self.moments:
+                self._moments(t)
             self._resample(t)
+
+    def _recorded_moments(self, who, lo, hi):
+        if not self.moments:
+            raise ValueError(f"BootstrapBank.{who}: no moments were recorded (build the bank with moments=True)")
+        out = self.mom[:, :, lo:hi].cpu()
+        return out[:, :, 0] if hi - lo == 1 else out
+
+    def filter_mean(self) -> torch.Tensor:
+        """float64 [T, R] ([T, R, D] for a state of D > 1 components), on the host: E[x_t | y_1..t] of filter r, the weighted
+        mean of step t's particles before its resampling (moments=True only; synchronises)"""
+        D = self.store.D if self.moments else 1
+        return self._recorded_moments("filter_mean", 1, 1 + D)
+
+    def filter_var(self) -> torch.Tensor:
+        """filter_mean()'s shapes: the weighted variance of step t's particles, per component (moments=True only; synchronises)"""
+        D = self.store.D if self.moments else 1
+        return self._recorded_moments("filter_var", 1 + D, 1 + 2 * D)
+
+    def ess(self) -> torch.Tensor:
+        """float64 [T, R], on the host: the effective sample size (sum w)^2 / sum w^2 of filter r's weights at step t, before
+        its resampling — with ess_threshold=, of the accumulated weights the decision is taken on (moments=True only;
+        synchronises)"""
+        return self._recorded_moments("ess", 0, 1)
 
     def log_ml(self) -> np.ndarray:
         """float64 [R]: row r is BootstrapSweep.log_ml() of that filter — sum_t [ ref(M_t) + log(total_t 2^-shift) - log n ]
@@ -2290,7 +2396,11 @@ class ConditionalBank(BootstrapBank):
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
-                 ess_threshold=None):
+                 ess_threshold=None, moments=False):
+        if moments:
+            raise NotImplementedError("ConditionalBank: moments=True is not supported (the pin is written inside the pinned "
+                                      "resampler: the weights before it are not the conditional system's; BootstrapBank "
+                                      "takes it)")
         if ess_threshold is not None:
             raise NotImplementedError("ConditionalBank: ess_threshold= is not supported (the pinned slot and the recorded "
                                       "history assume a resampling after every step; BootstrapBank takes it)")
@@ -2718,7 +2828,11 @@ class ParticleMH(_Sweep):
     decision is gmx_mh_accept's on the float32 log_alpha.
 
     Limits: 1 <= P <= 8 (the proposal kernel holds P draws per chain of a workgroup in LDS); whatever BootstrapBank
-    refuses (rejuvenate=, history=, comm=, ...) is refused by it, by name."""
+    refuses (rejuvenate=, history=, comm=, ...) is refused by it, by name.
+
+    moments=True (with every other keyword BootstrapBank takes) reaches the bank: the filtering means, variances and ESS of the
+    LAST sweep — the proposal's, accepted or not — are then read from pmh.bank (filter_mean(), filter_var(), ess()); nothing
+    of them is recorded across iterations."""
 
     def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
                  state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):

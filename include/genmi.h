@@ -801,6 +801,39 @@ int gmx_pick_rows_take(const uint32_t* keys_d /* [rows, 2] */, const float* logi
                        int64_t next_ld, int64_t* status_d /* [1] */, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Row-wise weighted moments  (additive, ABI still v8.  Reference call site: none of its own — the filtering mean, variance
+ * and effective sample size of each of R filters at a step, from the weights and the state the step has just written.)
+ *   gmx_rows_moments   Row r's weights are lw_d[r * ld + i], i < n; component d of particle i of row r is
+ *                   x_d[d * x_ld + r * x_row_stride + i] (gmx_rows_pin's addressing).  Nothing is written into lw_d, carry_d
+ *                   or x_d.  DEFINITION, for every row r:
+ *                     1. a_i = lw_i when carry_d is null, else lw_i + carry_i — ONE float32 add, the one
+ *                        gmx_resample_rows_ess performs: the moments are those of the weights that resampler acts on;
+ *                     2. M = max_i a_i (a NaN is ignored);
+ *                     3. e_i = (double) exp(a_i - M), the subtraction and the exponential in float32 (the library's own exp:
+ *                        every build computes the same e_i bit for bit); e_i = 0 where a_i - M is NaN (a_i = -inf = M, a NaN
+ *                        weight): what carries no weight in the resamplers carries none here;
+ *                     4. in float64: S0 = sum e_i, S2 = sum e_i^2, A_d = sum e_i x_{d,i}, B_d = sum e_i x_{d,i}^2;
+ *                     5. out_d[r * out_ld] = S0^2 / S2 (the ESS); out_d[r * out_ld + 1 + d] = A_d / S0 (the mean);
+ *                        out_d[r * out_ld + 1 + D + d] = B_d / S0 - (A_d / S0)^2, clamped at 0 (the variance);
+ *                     6. a row without mass (S0 = 0) writes ESS = 0 and NaN means and variances.  It is not an error.
+ *                   The summation order is fixed (a thread's four columns in order, a wave butterfly, the waves in order,
+ *                   the tiles in order): a row's result depends on n alone, not on rows or the row's position.
+ *                   n <= 1024: ONE launch with gmx_resample_rows' packing, e_i exactly as defined; nothing in the workspace.
+ *                   n > 1024: two launches — per (row, tile of 1024 columns) the tile's maximum m_b and its sums relative to
+ *                   it, then per row their combination under s_b = exp(m_b - M) taken in float64; equal to the definition
+ *                   up to that rescaling (the float32 subtraction a_i - m_b rounds where a_i - M would not).
+ *                   Limits: 1 <= n <= 2^21; rows >= 0 (0: nothing is done), rows * n < 2^31; ld >= n; 0 <= D <= 65533; x_ld
+ *                   and x_row_stride as gmx_rows_pin; out_ld >= 1 + 2 D; x_d may be null only when D = 0; carry_d may be
+ *                   null; every pointer aligned to its element; workspace_d: gmx_rows_moments_workspace(rows, n, D) bytes
+ *                   (16 for n <= 1024), 8-byte aligned, not null, contents irrelevant on entry.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+size_t gmx_rows_moments_workspace(int64_t rows, int64_t n, int32_t D);
+int gmx_rows_moments(const float* lw_d, const float* carry_d /* may be NULL */, int64_t rows, int64_t n, int64_t ld,
+                     const float* x_d /* [D, x_ld], null iff D = 0 */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                     double* out_d /* [rows, out_ld] */, int64_t out_ld, void* workspace_d, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Particle marginal Metropolis-Hastings  (additive, ABI still v8.  Reference call site: none of its own — PMMH, Andrieu,
  * Doucet & Holenstein 2010, section 2.4.2: R independent random-walk chains over model parameters, chain r driving filter
  * r of a bank of R filters of n particles and T steps, whose evidence the row resamplers leave as exact integers.)
