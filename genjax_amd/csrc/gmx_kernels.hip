@@ -3723,6 +3723,45 @@ extern "C" int gmx_rows_moments(const float* lw_d, const float* carry_d, int64_t
 }
 
 // ---------------------------------------------------------------------------
+// row-wise weighted quantiles (gmx_quantiles.h): per row, component and level the state word at which the sorted
+// fixed-point weights cross the level.  Its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
+// ---------------------------------------------------------------------------
+#include "gmx_quantiles.h"
+
+// The levels live where the kernel reads them; the host checks them only where it can read them too — memory the runtime
+// does not know as device memory (a plain host array: the case of a caller without a device).  Nothing is copied and
+// nothing waits, so a capture is not disturbed; levels in device memory are bounded by the kernel itself.
+static const uint64_t* quantile_levels_on_host_(const uint64_t* level_q32_d) {
+  hipPointerAttribute_t at;
+  const hipError_t e = hipPointerGetAttributes(&at, level_q32_d);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();                                     // (not an error of ours: unknown to the runtime, or no device)
+    return level_q32_d;
+  }
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray ? nullptr : level_q32_d;
+}
+
+extern "C" int gmx_rows_quantiles(const float* lw_d, const float* carry_d, int64_t rows, int64_t n, int64_t ld, const float* x_d,
+                                  int32_t D, int64_t x_ld, int64_t x_row_stride, const uint64_t* level_q32_d, int32_t Q,
+                                  float* out_d, int64_t out_ld, gmx_stream stream) {
+  const char* who = "gmx_rows_quantiles";
+  const bool has_null = !lw_d || !x_d || !level_q32_d || !out_d;
+  gmx_refusal no = gmx_rows_quantiles_refusal_(has_null, rows, n, ld, D, x_ld, x_row_stride, Q, out_ld, nullptr);
+  if (!no.fmt)                                                   // (the sizes first: Q entries are read)
+    no = gmx_rows_quantiles_refusal_(has_null, rows, n, ld, D, x_ld, x_row_stride, Q, out_ld, quantile_levels_on_host_(level_q32_d));
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, nullptr, {{lw_d, 3}, {carry_d, 3}, {x_d, 3}, {level_q32_d, 7}, {out_d, 3}})) return 1;
+  if (rows == 0) return 0;
+  const float scale = gmx_pow2i(gmx_pick_rows_shift_(n));
+  rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+    hipLaunchKernelGGL((k_rows_quantiles_small<decltype(w)::value>), grid, dim3(GMX_QNT_BLOCK), 0, (hipStream_t)stream, lw_d,
+                       carry_d, rows, n, ld, x_d, D, x_ld, x_row_stride, level_q32_d, Q, scale, out_d, out_ld);
+  });
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // particle marginal Metropolis-Hastings over a bank of filters (gmx_pmmh.h): the two launches that open and close an
 // iteration.  Each entry point: its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
 // ---------------------------------------------------------------------------

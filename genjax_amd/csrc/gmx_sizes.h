@@ -4,7 +4,7 @@
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
 //                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
-//                             the tile-form resamplers, the row-wise draws and moments, the particle-MH pair, the
+//                             the tile-form resamplers, the row-wise draws, moments and quantiles, the particle-MH pair, the
 //                             particle-Gibbs three, the sharded / peer family, the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
@@ -304,6 +304,31 @@ static inline gmx_refusal gmx_rows_moments_refusal_(bool has_null, int64_t rows,
   if (no.fmt) return no;
   if (out_ld < 1 + 2 * (int64_t)D) return {"%s: out_ld = %lld is smaller than 1 + 2 D", (long long)out_ld};
   if (D > 0 && no_x) return {"%s: null argument (x_d with D > 0)", 0};
+  return {nullptr, 0};
+}
+
+// ---- row-wise weighted quantiles: gmx_rows_quantiles (gmx_quantiles.h) ----
+#define GMX_ROWS_QUANTILES_MAX_Q 16    /* levels per call: a row's thresholds are parked in LDS */
+// One tile only: past it a quantile needs the two-level block-floating-point weights and a selection across tiles.  rows as
+// gmx_rows_moments; the store is gmx_rows_pin's (read) with at least one component; the outputs D * Q floats per row.
+// `levels`: the Q levels where the host can read them (the mirror: always; the HIP build: host memory only), else null —
+// the kernel then takes min(level, 2^32).
+static inline gmx_refusal gmx_rows_quantiles_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                      int64_t x_row_stride, int32_t Q, int64_t out_ld, const uint64_t* levels) {
+  if (has_null) return {"%s: null argument", 0};
+  if (n < 1 || n > GMX_TILE)
+    return {"%s: n = %lld is outside [1, 1024] (past one tile a quantile needs the two-level weights and a selection across "
+            "tiles: not built)", (long long)n};
+  if (rows < 0) return {"%s: rows = %lld is negative", (long long)rows};
+  if (rows > 0x7fffffffLL / n) return {"%s: rows = %lld does not keep rows * n below 2^31", (long long)rows};
+  if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  if (D < 1 || D > GMX_ROWS_PIN_MAX_D) return {"%s: D = %lld is outside [1, 65533]", (long long)D};
+  const gmx_refusal no = gmx_resample_rows_pin_refusal_(rows, n, D, x_ld, x_row_stride);
+  if (no.fmt) return no;
+  if (Q < 1 || Q > GMX_ROWS_QUANTILES_MAX_Q) return {"%s: Q = %lld is outside [1, 16]", (long long)Q};
+  if (out_ld < (int64_t)D * Q) return {"%s: out_ld = %lld is smaller than D * Q", (long long)out_ld};
+  for (int32_t j = 0; levels && j < Q; ++j)
+    if (levels[j] > (1ull << 32)) return {"%s: a level of %lld is above 2^32", (long long)levels[j]};
   return {nullptr, 0};
 }
 

@@ -800,7 +800,7 @@ def resample_rows_pinned(keys: Key, lw: torch.Tensor, pin_lw: torch.Tensor, pin_
 RowMoments = namedtuple("RowMoments", ["ess", "mean", "var"])
 
 
-def _component_major(x, R, n):
+def _component_major(x, R, n, who="row_moments"):
     """(tensor that owns the words, D, x_ld, x_row_stride, scalar) of a state in one of the forms BootstrapBank.state() returns
     — [R, n], [R, n, D] or a tuple of [R, n] — as gmx_rows_moments addresses it (component d of particle i of row r at
     d * x_ld + r * x_row_stride + i): through its strides where they say exactly that, else copied ONCE to a contiguous
@@ -816,7 +816,7 @@ def _component_major(x, R, n):
     scalar = x.ndim == 2
     x3 = x.reshape(R, n, 1) if scalar else x
     if tuple(x3.shape[:2]) != (R, n) or x3.ndim != 3:
-        raise ValueError(f"row_moments: x is [R, n], [R, n, D] or a tuple of [R, n] with [R, n] = {(R, n)}; got {tuple(x.shape)}")
+        raise ValueError(f"{who}: x is [R, n], [R, n, D] or a tuple of [R, n] with [R, n] = {(R, n)}; got {tuple(x.shape)}")
     D = int(x3.shape[2])
     rs, cs, ds = x3.stride()
     if D == 1:
@@ -852,6 +852,51 @@ def row_moments(lw: torch.Tensor, x=None, *, carry=None, out=None, workspace=Non
         return RowMoments(out[:, 0], None, None)
     mean, var = out[:, 1:1 + D], out[:, 1 + D:1 + 2 * D]
     return RowMoments(out[:, 0], mean[:, 0], var[:, 0]) if scalar else RowMoments(out[:, 0], mean, var)
+
+
+ROWS_QUANTILES_N_MAX = 1024      # gmx_rows_quantiles sorts a row of one tile
+ROWS_QUANTILES_Q_MAX = 16        # levels per call (GMX_ROWS_QUANTILES_MAX_Q)
+
+
+def _quantile_levels(levels, who):
+    """probabilities in [0, 1] -> (them as a tuple, the int64 words of gmx_rows_quantiles' level table: round(p * 2^32) each)"""
+    try:
+        ps = [float(p) for p in levels]
+    except TypeError:
+        ps = None
+    if not ps or len(ps) > ROWS_QUANTILES_Q_MAX or not all(0.0 <= p <= 1.0 for p in ps):
+        raise ValueError(f"{who}: between 1 and {ROWS_QUANTILES_Q_MAX} probabilities in [0, 1]; got {levels!r}")
+    return tuple(ps), torch.tensor([int(round(p * 2.0 ** 32)) for p in ps], dtype=torch.int64)
+
+
+def row_quantiles(lw: torch.Tensor, x, levels, *, carry=None, out=None):
+    """gmx_rows_quantiles: the weighted quantiles of every row's particles at the probabilities `levels`, in one launch.  lw
+    [R, n <= 1024] float32 log-weights (unit column stride); x: [R, n], [R, n, D] or a tuple of D [R, n] — the forms
+    BootstrapBank.state() returns; carry [R, n] (lw's strides): added to lw in float32 first, as the adaptive row resampler
+    adds it.  -> float32 on lw's device, [R, Q] for an [R, n] state, [R, D, Q] otherwise: per component the particle value at
+    which the sorted exact-integer weights of the row reach the level (level 0: the smallest value that carries weight,
+    level 1: the largest) — one of the row's own values, bit for bit.  A row without mass: NaN.  out ([R, >= D * Q] float32):
+    a persistent buffer instead of a fresh one."""
+    be = _lib.get()
+    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
+        raise ValueError(f"row_quantiles: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
+    R, n = (int(v) for v in lw.shape)
+    ld = int(lw.stride(0)) if R > 1 else n
+    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
+        raise ValueError("row_quantiles: carry is a float32 matrix of lw's shape and strides")
+    table = _quantile_levels(levels, "row_quantiles: levels")[1].to(lw.device)
+    Q = int(table.numel())
+    if x is None:
+        raise ValueError("row_quantiles: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
+    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_quantiles")
+    if out is None:
+        out = torch.empty((R, D * Q), dtype=torch.float32, device=lw.device)
+    elif out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != R or out.shape[1] < D * Q or out.stride(1) != 1:
+        raise ValueError(f"row_quantiles: out is a float32 [R, >= D * Q] = [{R}, >= {D * Q}] matrix with unit column stride")
+    be.check(be.c.gmx_rows_quantiles(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(table), Q,
+                                     be.ptr(out), int(out.stride(0)) if R > 1 else D * Q, be.stream()), "gmx_rows_quantiles")
+    res = out[:, :D * Q].unflatten(1, (D, Q))
+    return res[:, 0] if scalar else res
 
 
 def _row_kind(kind, who):
@@ -2117,11 +2162,18 @@ class BootstrapBank(_Sweep):
     [T, R, 1 + 2 D] float64 table on the device: 1 + 2 D doubles per filter and step instead of the particles, no host read,
     still one graph.  filter_mean(), filter_var() and ess() read it after a sweep.  The weights are the ones the resampler
     acts on (with ess_threshold=: accumulated since the row's last resampling); a filter without mass at a step has ESS 0
-    and NaN moments there."""
+    and NaN moments there.
+
+    quantiles=(p, ...) (None: nothing is allocated and the sweep is launch for launch the one above): up to 16 probabilities;
+    per step ONE more launch (gmx_rows_quantiles, n <= 1024) in the same place writes, per filter and state component, the
+    particle value at which the sorted exact-integer weights reach each probability — the credible band of x_t | y_1..t,
+    which a mean and a variance do not give for a skewed or bimodal filter — into a [T, R, D, Q] float32 table on the
+    device: D Q words per filter and step instead of the particles, no host read, still one graph.  filter_quantiles()
+    reads it after a sweep.  The weights are the ones moments=True sees; a filter without mass at a step has NaN there."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
-                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False):
+                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False, quantiles=None):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2143,6 +2195,12 @@ class BootstrapBank(_Sweep):
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
         self.moments = bool(moments)
+        self.quantiles = None
+        if quantiles is not None:
+            self.quantiles, self.q_levels = _quantile_levels(quantiles, "BootstrapBank(quantiles=)")
+            if self.n > ROWS_QUANTILES_N_MAX:
+                raise NotImplementedError(f"BootstrapBank(quantiles=): n_particles = {self.n} > {ROWS_QUANTILES_N_MAX} "
+                                          "(gmx_rows_quantiles sorts a row of one tile)")
         self.ess_threshold, self.ess_q8 = None, None
         if ess_threshold is not None:
             tau = float(ess_threshold)
@@ -2218,7 +2276,21 @@ class BootstrapBank(_Sweep):
             D = self.store.D
             self.mom = torch.zeros((T, R, 1 + 2 * D), dtype=torch.float64, device=dev)     # per step and row: ESS, D means, D variances
             self.mom_ws = torch.zeros(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
+        if self.quantiles is not None:
+            self.q_table = self.q_levels.to(dev)                 # the levels where the kernel reads them: nothing from the host
+            self.qnt = torch.zeros((T, R, self.store.D, len(self.quantiles)), dtype=torch.float32, device=dev)
         return self
+
+    def _quantiles(self, t):
+        """step t's weighted quantiles of every row and state component, from the weights and the state _moments reads
+        (gmx_rows_quantiles)"""
+        be = _lib.get()
+        R, n = self.R, self.n
+        x = self.store.rows[t % 2]
+        D, Q = int(self.qnt.shape[2]), int(self.qnt.shape[3])
+        be.check(be.c.gmx_rows_quantiles(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
+                                         be.ptr(x), D, int(x.shape[1]), n, be.ptr(self.q_table), Q, be.ptr(self.qnt[t]), D * Q,
+                                         be.stream()), "gmx_rows_quantiles")
 
     def _moments(self, t):
         """step t's ESS, filtering mean and variance of every row, from the weights the resampler is about to act on (with
@@ -2247,8 +2319,8 @@ class BootstrapBank(_Sweep):
 
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
-        ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two) — no syncs, no
-        allocations, no host read of a device value"""
+        ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with quantiles=:
+        gmx_rows_quantiles there too) — no syncs, no allocations, no host read of a device value"""
         N = self.R * self.n
         self.status.zero_()
         if self.ess_q8 is not None:
@@ -2259,6 +2331,8 @@ class BootstrapBank(_Sweep):
             prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
             if self.moments:
                 self._moments(t)
+            if self.quantiles is not None:
+                self._quantiles(t)
             self._resample(t)
 
     def _recorded_moments(self, who, lo, hi):
@@ -2283,6 +2357,14 @@ class BootstrapBank(_Sweep):
         its resampling — with ess_threshold=, of the accumulated weights the decision is taken on (moments=True only;
         synchronises)"""
         return self._recorded_moments("ess", 0, 1)
+
+    def filter_quantiles(self) -> torch.Tensor:
+        """float32 [T, R, Q] ([T, R, D, Q] for a state of D > 1 components), on the host: the quantiles of x_t | y_1..t of filter
+        r at the probabilities of quantiles=, from step t's particles before its resampling (quantiles= only; synchronises)"""
+        if self.quantiles is None:
+            raise ValueError("BootstrapBank.filter_quantiles: no quantiles were recorded (build the bank with quantiles=(p, ...))")
+        out = self.qnt.cpu()
+        return out[:, :, 0] if out.shape[2] == 1 else out
 
     def log_ml(self) -> np.ndarray:
         """float64 [R]: row r is BootstrapSweep.log_ml() of that filter — sum_t [ ref(M_t) + log(total_t 2^-shift) - log n ]
@@ -2396,7 +2478,10 @@ class ConditionalBank(BootstrapBank):
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
-                 ess_threshold=None, moments=False):
+                 ess_threshold=None, moments=False, quantiles=None):
+        if quantiles is not None:
+            raise NotImplementedError("ConditionalBank: quantiles= is not supported (as moments=True: the weights before the "
+                                      "pinned resampler are not the conditional system's; BootstrapBank takes it)")
         if moments:
             raise NotImplementedError("ConditionalBank: moments=True is not supported (the pin is written inside the pinned "
                                       "resampler: the weights before it are not the conditional system's; BootstrapBank "
@@ -2832,7 +2917,7 @@ class ParticleMH(_Sweep):
 
     moments=True (with every other keyword BootstrapBank takes) reaches the bank: the filtering means, variances and ESS of the
     LAST sweep — the proposal's, accepted or not — are then read from pmh.bank (filter_mean(), filter_var(), ess()); nothing
-    of them is recorded across iterations."""
+    of them is recorded across iterations.  quantiles=(p, ...) reaches the bank the same way (pmh.bank.filter_quantiles())."""
 
     def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
                  state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):

@@ -834,6 +834,44 @@ int gmx_rows_moments(const float* lw_d, const float* carry_d /* may be NULL */, 
                      double* out_d /* [rows, out_ld] */, int64_t out_ld, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Row-wise weighted quantiles  (additive, ABI still v8.  Reference call site: none of its own — the credible band of each of
+ * R filters at a step: the median and the tail quantiles of x_t | y_1..t, from the weights and the state the step has just
+ * written, where a mean and a variance would describe a Gaussian.)
+ *   gmx_rows_quantiles   Weights and state are addressed as gmx_rows_moments addresses them: row r's weights are
+ *                   lw_d[r * ld + i], i < n; component d of particle i of row r is x_d[d * x_ld + r * x_row_stride + i].
+ *                   Nothing is written into lw_d, carry_d, x_d or level_q32_d.  DEFINITION, for every row r:
+ *                     1. a_i = lw_i when carry_d is null, else lw_i + carry_i — ONE float32 add, the one
+ *                        gmx_resample_rows_ess and gmx_rows_moments perform;
+ *                     2. q_i = the row's fixed-point weights: the increments of gmx_weight_cdf of that row alone — one
+ *                        tile, shift = 62 - ceil(log2 n), q_i = floor(exp(a_i - ceil(max a / ln 2) ln 2) 2^shift); a NaN
+ *                        weight counts 0; total = sum q_i;
+ *                     3. the ORDER of state words is that of key(bits) = bits ^ 0x80000000 for a non-negative float, ~bits
+ *                        for a negative one, compared as unsigned integers: the order of the reals on finite values, with
+ *                        -0 < +0, -NaN first and +NaN last — a total order on bit patterns;
+ *                     4. level_q32_d[j] in [0, 2^32] is a probability p as round(p 2^32); its threshold is
+ *                        T = max(1, ceil(level total / 2^32)), the product in 128 bits;
+ *                     5. out_d[r * out_ld + d * Q + j] = the state word x (its 32 bits, unchanged) of component d with the
+ *                        smallest key such that sum { q_i : key(x_{d,i}) <= key(x) } >= T.  The value does not depend on how
+ *                        equal words are ordered.  Level 0 gives the smallest state that carries weight, level 2^32 the
+ *                        largest;
+ *                     6. a row without mass (total = 0) writes NaN (0x7fc00000) for every (d, j).  It is not an error.
+ *                   Integers throughout after the per-column exp: every build gives the same bits.
+ *                   ONE launch with gmx_resample_rows' packing, no workspace: the row's weights once, then per component
+ *                   a bitonic sort of (key, column) words — inside one wave for n <= 256 — and a scan of the sorted weights.
+ *                   Limits: 1 <= n <= 1024 (past one tile a quantile needs the two-level weights and a selection across
+ *                   tiles: refused, naming n); rows >= 0 (0: nothing is done), rows * n < 2^31; ld >= n; 1 <= D <= 65533;
+ *                   x_ld and x_row_stride as gmx_rows_pin; 1 <= Q <= 16; out_ld >= D * Q; every level <= 2^32 — checked
+ *                   where the host can read level_q32_d (the CPU build: always; the HIP build: host memory), while levels
+ *                   in device memory are read by the kernel alone, which takes min(level, 2^32), so that a captured graph
+ *                   reads nothing from the host; carry_d may be null, no other pointer; every pointer aligned to its element.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+int gmx_rows_quantiles(const float* lw_d, const float* carry_d /* may be NULL */, int64_t rows, int64_t n, int64_t ld,
+                       const float* x_d /* [D, x_ld] */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                       const uint64_t* level_q32_d /* [Q] */, int32_t Q, float* out_d /* [rows, out_ld] */, int64_t out_ld,
+                       gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Particle marginal Metropolis-Hastings  (additive, ABI still v8.  Reference call site: none of its own — PMMH, Andrieu,
  * Doucet & Holenstein 2010, section 2.4.2: R independent random-walk chains over model parameters, chain r driving filter
  * r of a bank of R filters of n particles and T steps, whose evidence the row resamplers leave as exact integers.)
