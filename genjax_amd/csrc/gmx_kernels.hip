@@ -3723,6 +3723,43 @@ extern "C" int gmx_rows_moments(const float* lw_d, const float* carry_d, int64_t
 }
 
 // ---------------------------------------------------------------------------
+// row-wise weighted covariance (gmx_covariance.h): mean and full covariance matrix per row of a bank's weights and state
+// store, the row's Gram matrix on the float64 matrix instruction.  Its refusal (gmx_sizes.h), the HIP build's alignment
+// check, then ONE launch for n <= 1024 and two past it.
+// ---------------------------------------------------------------------------
+#include "gmx_covariance.h"
+
+extern "C" size_t gmx_rows_covariance_workspace(int64_t rows, int64_t n, int32_t D) { return gmx_rows_cov_bytes_(rows, n, D); }
+
+extern "C" int gmx_rows_covariance(const float* lw_d, const float* carry_d, int64_t rows, int64_t n, int64_t ld, const float* x_d,
+                                   int32_t D, int64_t x_ld, int64_t x_row_stride, double* out_d, int64_t out_ld,
+                                   void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_rows_covariance";
+  const gmx_refusal no = gmx_rows_cov_refusal_(!lw_d || !out_d || !workspace_d, rows, n, ld, D, x_ld, x_row_stride, out_ld, !x_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {carry_d, 3}, {x_d, 3}, {out_d, 7}})) return 1;
+  if (rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_cov_small<decltype(w)::value>), grid, dim3(GMX_COV_BLOCK), 0, st, lw_d, carry_d, rows, n, ld,
+                         x_d, D, x_ld, x_row_stride, out_d, out_ld);
+    });
+  } else {
+    const int64_t tiles = gmx_tiles_(n);
+    const gmx_moments_ws w = gmx_rows_cov_carve_(workspace_d, rows, n);
+    rows_for_chunks_(rows, [&](int64_t row0, unsigned cnt) {
+      hipLaunchKernelGGL(k_rows_cov_part, dim3((unsigned)tiles, cnt), dim3(GMX_COV_BLOCK), 0, st, lw_d, carry_d, n, ld, tiles,
+                         row0, x_d, D, x_ld, x_row_stride, w.rec, w.tmax);
+    });
+    hipLaunchKernelGGL(k_rows_cov_finish, dim3((unsigned)rows), dim3(GMX_COV_BLOCK), 0, st, (const double*)w.rec,
+                       (const float*)w.tmax, tiles, D, out_d, out_ld);
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // row-wise weighted quantiles (gmx_quantiles.h): per row, component and level the state word at which the sorted
 // fixed-point weights cross the level.  Its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
 // ---------------------------------------------------------------------------

@@ -307,6 +307,34 @@ static inline gmx_refusal gmx_rows_moments_refusal_(bool has_null, int64_t rows,
   return {nullptr, 0};
 }
 
+// ---- row-wise weighted covariance: gmx_rows_covariance (gmx_covariance.h) ----
+#define GMX_COV_MAX_D 15               /* 1 + D <= 16: the Gram matrix of (1, x_0 .. x_{D-1}) is ONE 16 x 16 MFMA tile */
+#define GMX_COV_REC 136                /* the upper triangle of that tile, 16 * 17 / 2 doubles per (row, tile of 1024 columns) */
+// Its workspace past one tile: rec f64 [rows * tiles, 136] (a tile's Gram matrix relative to the tile's own maximum) |
+// tmax f32 [rows * tiles], rounded up to 16 bytes; nothing for n <= 1024 (one launch)
+static inline size_t gmx_rows_cov_bytes_(int64_t rows, int64_t n, int32_t D) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N || D < 1 || D > GMX_COV_MAX_D) return 16;
+  return (size_t)((gmx_rows_cells_(rows, n) * ((uint64_t)GMX_COV_REC * 8u + 4u) + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_moments_ws gmx_rows_cov_carve_(void* workspace, int64_t rows, int64_t n) {
+  gmx_moments_ws w;
+  w.rec = (double*)workspace;
+  w.tmax = (float*)(w.rec + gmx_rows_cells_(rows, n) * (uint64_t)GMX_COV_REC);
+  return w;
+}
+// gmx_rows_moments' refusal, but: 1 <= D <= 15, the store is required, the outputs D + D^2 doubles per row
+static inline gmx_refusal gmx_rows_cov_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                int64_t x_row_stride, int64_t out_ld, bool no_x) {
+  if (has_null) return {"%s: null argument", 0};
+  if (no_x) return {"%s: null argument (x_d)", 0};
+  if (D < 1 || D > GMX_COV_MAX_D)
+    return {"%s: D = %lld is outside [1, 15] (past 15 the Gram matrix of (1, x) leaves one 16 x 16 MFMA tile)", (long long)D};
+  const gmx_refusal no = gmx_rows_moments_refusal_(false, rows, n, ld, D, x_ld, x_row_stride, 1 + 2 * (int64_t)D, false);
+  if (no.fmt) return no;
+  if (out_ld < (int64_t)D + (int64_t)D * D) return {"%s: out_ld = %lld is smaller than D + D^2", (long long)out_ld};
+  return {nullptr, 0};
+}
+
 // ---- row-wise weighted quantiles: gmx_rows_quantiles (gmx_quantiles.h) ----
 #define GMX_ROWS_QUANTILES_MAX_Q 16    /* levels per call: a row's thresholds are parked in LDS */
 // One tile only: past it a quantile needs the two-level block-floating-point weights and a selection across tiles.  rows as

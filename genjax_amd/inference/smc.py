@@ -854,6 +854,39 @@ def row_moments(lw: torch.Tensor, x=None, *, carry=None, out=None, workspace=Non
     return RowMoments(out[:, 0], mean[:, 0], var[:, 0]) if scalar else RowMoments(out[:, 0], mean, var)
 
 
+ROWS_COV_D_MAX = 15              # gmx_rows_covariance: (1, x) is one 16 x 16 tile of the float64 matrix instruction
+
+
+def row_covariance(lw: torch.Tensor, x, *, carry=None, out=None, workspace=None):
+    """gmx_rows_covariance: the weighted mean and the full covariance matrix of every row's particles, in one call (two
+    launches past n = 1024).  lw, x and carry as row_moments takes them (x is required, at most 15 components) — the same
+    weights bit for bit.  -> (mean [R, D], cov [R, D, D]), float64 on lw's device; a scalar state ([R, n]) gives [R] and
+    [R, 1, 1].  cov[r] is symmetric bit for bit with a diagonal >= 0; a row without mass: NaN.  out ([R, >= D + D^2] float64)
+    and workspace: persistent buffers instead of fresh ones."""
+    be = _lib.get()
+    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
+        raise ValueError(f"row_covariance: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
+    R, n = (int(v) for v in lw.shape)
+    ld = int(lw.stride(0)) if R > 1 else n
+    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
+        raise ValueError("row_covariance: carry is a float32 matrix of lw's shape and strides")
+    if x is None:
+        raise ValueError("row_covariance: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
+    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_covariance")
+    W = D + D * D
+    if out is None:
+        out = torch.empty((R, W), dtype=torch.float64, device=lw.device)
+    elif out.dtype != torch.float64 or out.ndim != 2 or out.shape[0] != R or out.shape[1] < W or out.stride(1) != 1:
+        raise ValueError(f"row_covariance: out is a float64 [R, >= D + D^2] = [{R}, >= {W}] matrix with unit column stride")
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_rows_covariance_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=lw.device)
+    be.check(be.c.gmx_rows_covariance(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(out),
+                                      int(out.stride(0)) if R > 1 else W, be.ptr(workspace), be.stream()),
+             "gmx_rows_covariance")
+    mean, cov = out[:, :D], out[:, D:W].unflatten(1, (D, D))
+    return (mean[:, 0], cov) if scalar else (mean, cov)
+
+
 ROWS_QUANTILES_N_MAX = 1024      # gmx_rows_quantiles sorts a row of one tile
 ROWS_QUANTILES_Q_MAX = 16        # levels per call (GMX_ROWS_QUANTILES_MAX_Q)
 
@@ -2169,11 +2202,19 @@ class BootstrapBank(_Sweep):
     particle value at which the sorted exact-integer weights reach each probability — the credible band of x_t | y_1..t,
     which a mean and a variance do not give for a skewed or bimodal filter — into a [T, R, D, Q] float32 table on the
     device: D Q words per filter and step instead of the particles, no host read, still one graph.  filter_quantiles()
-    reads it after a sweep.  The weights are the ones moments=True sees; a filter without mass at a step has NaN there."""
+    reads it after a sweep.  The weights are the ones moments=True sees; a filter without mass at a step has NaN there.
+
+    covariance=True (False: nothing is allocated and the sweep is launch for launch the one above): per step ONE more launch
+    (gmx_rows_covariance; two past n = 1024) in the same place writes each filter's weighted mean and the FULL covariance
+    matrix of its particles — what a Kalman filter's P_t is compared with for a state of several components (at most 15),
+    where moments=True gives the diagonal — into a [T, R, D + D^2] float64 table on the device, no host read, still one
+    graph.  filter_cov() reads it after a sweep.  The weights are the ones moments=True sees; a filter without mass at a
+    step has NaN there."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
-                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False, quantiles=None):
+                 noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False, quantiles=None,
+                 covariance=False):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2195,6 +2236,7 @@ class BootstrapBank(_Sweep):
         self.params = tuple(params) if params is not None else ()
         self.specialize = specialize
         self.moments = bool(moments)
+        self.covariance = bool(covariance)
         self.quantiles = None
         if quantiles is not None:
             self.quantiles, self.q_levels = _quantile_levels(quantiles, "BootstrapBank(quantiles=)")
@@ -2276,6 +2318,13 @@ class BootstrapBank(_Sweep):
             D = self.store.D
             self.mom = torch.zeros((T, R, 1 + 2 * D), dtype=torch.float64, device=dev)     # per step and row: ESS, D means, D variances
             self.mom_ws = torch.zeros(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
+        if self.covariance:
+            D = self.store.D
+            if D > ROWS_COV_D_MAX:
+                raise NotImplementedError(f"BootstrapBank(covariance=True): a state of D = {D} > {ROWS_COV_D_MAX} components "
+                                          "(gmx_rows_covariance holds (1, x) in one 16 x 16 matrix tile)")
+            self.cov = torch.zeros((T, R, D + D * D), dtype=torch.float64, device=dev)     # per step and row: D means, D x D covariances
+            self.cov_ws = torch.zeros(((int(be.c.gmx_rows_covariance_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
         if self.quantiles is not None:
             self.q_table = self.q_levels.to(dev)                 # the levels where the kernel reads them: nothing from the host
             self.qnt = torch.zeros((T, R, self.store.D, len(self.quantiles)), dtype=torch.float32, device=dev)
@@ -2302,6 +2351,16 @@ class BootstrapBank(_Sweep):
                                        be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.mom[t]), int(self.mom.shape[2]),
                                        be.ptr(self.mom_ws), be.stream()), "gmx_rows_moments")
 
+    def _covariance(self, t):
+        """step t's filtering mean and full covariance matrix of every row, from the weights and the state _moments reads
+        (gmx_rows_covariance)"""
+        be = _lib.get()
+        R, n = self.R, self.n
+        x = self.store.rows[t % 2]
+        be.check(be.c.gmx_rows_covariance(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
+                                          be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.cov[t]), int(self.cov.shape[2]),
+                                          be.ptr(self.cov_ws), be.stream()), "gmx_rows_covariance")
+
     def _resample(self, t):
         if self.ess_q8 is not None:
             return self._resample_adaptive(t)
@@ -2319,8 +2378,8 @@ class BootstrapBank(_Sweep):
 
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
-        ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with quantiles=:
-        gmx_rows_quantiles there too) — no syncs, no allocations, no host read of a device value"""
+        ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with covariance=True:
+        gmx_rows_covariance, with quantiles=: gmx_rows_quantiles there too) — no syncs, no allocations, no host read of a device value"""
         N = self.R * self.n
         self.status.zero_()
         if self.ess_q8 is not None:
@@ -2331,6 +2390,8 @@ class BootstrapBank(_Sweep):
             prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
             if self.moments:
                 self._moments(t)
+            if self.covariance:
+                self._covariance(t)
             if self.quantiles is not None:
                 self._quantiles(t)
             self._resample(t)
@@ -2357,6 +2418,15 @@ class BootstrapBank(_Sweep):
         its resampling — with ess_threshold=, of the accumulated weights the decision is taken on (moments=True only;
         synchronises)"""
         return self._recorded_moments("ess", 0, 1)
+
+    def filter_cov(self) -> torch.Tensor:
+        """float64 [T, R, D, D], on the host: Cov[x_t | y_1..t] of filter r, the weighted covariance matrix of step t's particles
+        before its resampling, symmetric bit for bit (covariance=True only; synchronises).  The means recorded beside it are
+        self.cov[:, :, :D], filter_mean()'s values up to the order of the float64 sums."""
+        if not self.covariance:
+            raise ValueError("BootstrapBank.filter_cov: no covariance was recorded (build the bank with covariance=True)")
+        D = self.store.D
+        return self.cov[:, :, D:].cpu().unflatten(2, (D, D))
 
     def filter_quantiles(self) -> torch.Tensor:
         """float32 [T, R, Q] ([T, R, D, Q] for a state of D > 1 components), on the host: the quantiles of x_t | y_1..t of filter
@@ -2478,7 +2548,10 @@ class ConditionalBank(BootstrapBank):
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
-                 ess_threshold=None, moments=False, quantiles=None):
+                 ess_threshold=None, moments=False, quantiles=None, covariance=False):
+        if covariance:
+            raise NotImplementedError("ConditionalBank: covariance=True is not supported (as moments=True: the weights before "
+                                      "the pinned resampler are not the conditional system's; BootstrapBank takes it)")
         if quantiles is not None:
             raise NotImplementedError("ConditionalBank: quantiles= is not supported (as moments=True: the weights before the "
                                       "pinned resampler are not the conditional system's; BootstrapBank takes it)")
@@ -2917,7 +2990,8 @@ class ParticleMH(_Sweep):
 
     moments=True (with every other keyword BootstrapBank takes) reaches the bank: the filtering means, variances and ESS of the
     LAST sweep — the proposal's, accepted or not — are then read from pmh.bank (filter_mean(), filter_var(), ess()); nothing
-    of them is recorded across iterations.  quantiles=(p, ...) reaches the bank the same way (pmh.bank.filter_quantiles())."""
+    of them is recorded across iterations.  quantiles=(p, ...) and covariance=True reach the bank the same way
+    (pmh.bank.filter_quantiles(), pmh.bank.filter_cov())."""
 
     def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
                  state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):

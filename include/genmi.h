@@ -834,6 +834,35 @@ int gmx_rows_moments(const float* lw_d, const float* carry_d /* may be NULL */, 
                      double* out_d /* [rows, out_ld] */, int64_t out_ld, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Row-wise weighted covariance  (additive, ABI still v8.  Reference call site: none of its own — the filtering mean and the
+ * full covariance matrix of each of R filters at a step: what a Kalman filter's P_t is compared with, where the moments
+ * above give only its diagonal.)
+ *   gmx_rows_covariance   Weights and state are addressed as gmx_rows_moments addresses them, and steps 1 to 3 of its
+ *                   definition give a_i, M and e_i: the same weights bit for bit.  Nothing is written into lw_d, carry_d or
+ *                   x_d.  Then, for every row r, with z_0 = 1 and z_d = (double) x_{d-1,i} for 1 <= d <= D:
+ *                     4. in float64 the Gram matrix G_jk = sum_i (e_i z_j) z_k, 0 <= j <= k <= D; S0 = G_00;
+ *                     5. out_d[r * out_ld + d] = G_0,d+1 / S0 (the mean of component d);
+ *                        out_d[r * out_ld + D + j * D + k] = G_j+1,k+1 / S0 - mean_j mean_k (the covariance), computed for
+ *                        j <= k and stored at (j, k) and (k, j): the same bits; the diagonal clamped at 0;
+ *                     6. a row without mass (S0 = 0) writes NaN into all D + D^2 outputs.  It is not an error.
+ *                   The summation order is fixed (the four columns of a matrix instruction, a wave's blocks of 16 columns in
+ *                   order, the waves in order, the tiles in order): a row's result depends on n alone, not on rows or the
+ *                   row's position.  The CPU build sums in column order.
+ *                   n <= 1024: ONE launch with gmx_resample_rows' packing, the Gram matrix as one 16 x 16 accumulator tile
+ *                   of the float64 matrix instruction (v_mfma_f64_16x16x4_f64) per wave; nothing in the workspace.
+ *                   n > 1024: two launches — per (row, tile of 1024 columns) the tile's maximum m_b and its Gram matrix
+ *                   relative to it, then per row their combination under s_b = exp(m_b - M) taken in float64.
+ *                   Limits: those of gmx_rows_moments, but 1 <= D <= 15 (1 + D components are one 16 x 16 tile), x_d not
+ *                   null, out_ld >= D + D^2; workspace_d: gmx_rows_covariance_workspace(rows, n, D) bytes (16 for
+ *                   n <= 1024; past it 136 doubles and a float per (row, tile)), 8-byte aligned, not null.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+size_t gmx_rows_covariance_workspace(int64_t rows, int64_t n, int32_t D);
+int gmx_rows_covariance(const float* lw_d, const float* carry_d /* may be NULL */, int64_t rows, int64_t n, int64_t ld,
+                        const float* x_d /* [D, x_ld] */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                        double* out_d /* [rows, out_ld] */, int64_t out_ld, void* workspace_d, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Row-wise weighted quantiles  (additive, ABI still v8.  Reference call site: none of its own — the credible band of each of
  * R filters at a step: the median and the tail quantiles of x_t | y_1..t, from the weights and the state the step has just
  * written, where a mean and a variance would describe a Gaussian.)
