@@ -3760,6 +3760,54 @@ extern "C" int gmx_rows_covariance(const float* lw_d, const float* carry_d, int6
 }
 
 // ---------------------------------------------------------------------------
+// fixed-lag smoothed moments (gmx_lag.h): one call per step records the step into the caller's rings, walks the last lag_hi
+// ancestor tables and writes mean and variance per row and lag.  Its refusal (gmx_sizes.h), the HIP build's alignment
+// check, then ONE launch for n <= 1024 (its tables in dynamic LDS, sized by lag_hi) and two past it (one for an empty range).
+// ---------------------------------------------------------------------------
+#include "gmx_lag.h"
+
+extern "C" size_t gmx_rows_lag_moments_workspace(int64_t rows, int64_t n, int32_t D, int32_t L) {
+  return gmx_rows_lag_bytes_(rows, n, D, L);
+}
+
+extern "C" int gmx_rows_lag_moments(const float* lw_d, const float* carry_d, int64_t rows, int64_t n, int64_t ld, const float* x_d,
+                                    int32_t D, int64_t x_ld, int64_t x_row_stride, const int32_t* ancestors_d, int64_t a_ld,
+                                    int64_t index_stride, int64_t t, int32_t L, int32_t lag_lo, int32_t lag_hi, float* hist_x_d,
+                                    int64_t hist_x_ld, int32_t* hist_a_d, int64_t hist_a_ld, double* out_d, int64_t out_ld,
+                                    int64_t out_lag_stride, void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_rows_lag_moments";
+  const gmx_refusal no = gmx_rows_lag_moments_refusal_(!lw_d || !hist_x_d || !hist_a_d || !out_d || !workspace_d, rows, n, ld, D, x_ld,
+                                                       x_row_stride, a_ld, index_stride, t, L, lag_lo, lag_hi, hist_x_ld, hist_a_ld,
+                                                       out_ld, !x_d, !ancestors_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {carry_d, 3}, {x_d, 3}, {ancestors_d, 3}, {hist_x_d, 3}, {hist_a_d, 3}, {out_d, 7}}))
+    return 1;
+  if (rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= GMX_PICK_TILE) {                                      // one launch, nothing in the workspace
+    const unsigned lds = lag_hi > 1 ? (unsigned)(lag_hi - 1) * GMX_LAG_TABLE_BYTES : 0u;
+    rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+      hipLaunchKernelGGL((k_rows_lag_small<decltype(w)::value>), grid, dim3(GMX_LAG_BLOCK), lds, st, lw_d, carry_d, rows, n, ld,
+                         x_d, D, x_ld, x_row_stride, ancestors_d, a_ld, index_stride, t, L, lag_lo, lag_hi, hist_x_d, hist_x_ld,
+                         hist_a_d, hist_a_ld, out_d, out_ld, out_lag_stride);
+    });
+  } else {
+    const int64_t tiles = gmx_tiles_(n);
+    const gmx_moments_ws w = gmx_rows_lag_carve_(workspace_d, rows, n, D, L);
+    rows_for_chunks_(rows, [&](int64_t row0, unsigned cnt) {
+      hipLaunchKernelGGL(k_rows_lag_part, dim3((unsigned)tiles, cnt), dim3(GMX_LAG_BLOCK), 0, st, lw_d, carry_d, rows, n, ld, tiles,
+                         row0, x_d, D, x_ld, x_row_stride, ancestors_d, a_ld, index_stride, t, L, lag_lo, lag_hi, hist_x_d,
+                         hist_x_ld, hist_a_d, hist_a_ld, w.rec, w.tmax);
+    });
+    if (lag_hi >= 0)
+      hipLaunchKernelGGL(k_rows_lag_finish, dim3((unsigned)rows), dim3(GMX_LAG_BLOCK), 0, st, (const double*)w.rec,
+                         (const float*)w.tmax, tiles, D, lag_lo, lag_hi, out_d, out_ld, out_lag_stride);
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // row-wise weighted quantiles (gmx_quantiles.h): per row, component and level the state word at which the sorted
 // fixed-point weights cross the level.  Its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
 // ---------------------------------------------------------------------------

@@ -335,6 +335,50 @@ static inline gmx_refusal gmx_rows_cov_refusal_(bool has_null, int64_t rows, int
   return {nullptr, 0};
 }
 
+// ---- fixed-lag smoothed moments: gmx_rows_lag_moments (gmx_lag.h) ----
+#define GMX_ROWS_LAG_MAX 32            /* L: hops 2 .. L of a workgroup's 1024 columns are parked in LDS, 2 KB each (<= 62 KB) */
+// Pairs of sums a call with nl lags reduces: (S0, -), then (A, B) per lag and component
+static inline uint64_t gmx_lag_pairs_(int32_t D, int32_t nl) { return 1u + (uint64_t)D * (uint64_t)nl; }
+// Its workspace past one tile, sized for the L + 1 lags of a flush: rec f64 [rows * tiles, 2 + 2 D (L + 1)] (a tile's sums
+// relative to the tile's own maximum) | tmax f32 [rows * tiles], rounded up to 16 bytes; nothing for n <= 1024 (one launch)
+static inline size_t gmx_rows_lag_bytes_(int64_t rows, int64_t n, int32_t D, int32_t L) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N || D < 1 || L < 1 || L > GMX_ROWS_LAG_MAX) return 16;
+  return (size_t)((gmx_rows_cells_(rows, n) * (gmx_lag_pairs_(D, L + 1) * 16u + 4u) + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_moments_ws gmx_rows_lag_carve_(void* workspace, int64_t rows, int64_t n, int32_t D, int32_t L) {
+  gmx_moments_ws w;
+  w.rec = (double*)workspace;
+  w.tmax = (float*)(w.rec + gmx_rows_cells_(rows, n) * gmx_lag_pairs_(D, L + 1) * 2u);
+  return w;
+}
+// the empty lag range (record only) is (lag_lo, lag_hi) = (0, -1)
+static inline bool gmx_lag_empty_(int32_t lag_lo, int32_t lag_hi) { return lag_lo == 0 && lag_hi == -1; }
+// gmx_rows_moments' refusal with D >= 1 and the store required, then the ancestors, the rings, the step and the lags
+static inline gmx_refusal gmx_rows_lag_moments_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                        int64_t x_row_stride, int64_t a_ld, int64_t index_stride, int64_t t,
+                                                        int32_t L, int32_t lag_lo, int32_t lag_hi, int64_t hist_x_ld,
+                                                        int64_t hist_a_ld, int64_t out_ld, bool no_x, bool no_anc) {
+  if (has_null) return {"%s: null argument", 0};
+  if (no_x) return {"%s: null argument (x_d)", 0};
+  if (D < 1 || D > GMX_ROWS_PIN_MAX_D) return {"%s: D = %lld is outside [1, 65533]", (long long)D};
+  gmx_refusal no = gmx_rows_moments_refusal_(false, rows, n, ld, D, x_ld, x_row_stride, 1 + 2 * (int64_t)D, false);
+  if (!no.fmt && rows > 0) no = gmx_index_stride_refusal_(rows, n, index_stride);
+  if (no.fmt) return no;
+  if (L < 1 || L > GMX_ROWS_LAG_MAX) return {"%s: L = %lld is outside [1, 32]", (long long)L};
+  if (t < 0) return {"%s: t = %lld is negative", (long long)t};
+  if (!gmx_lag_empty_(lag_lo, lag_hi)) {
+    if (lag_lo < 0 || lag_lo > lag_hi) return {"%s: lag_lo = %lld is outside [0, lag_hi] (the empty range is (0, -1))", (long long)lag_lo};
+    if (lag_hi > L || lag_hi > t) return {"%s: lag_hi = %lld is above min(L, t)", (long long)lag_hi};
+  }
+  if (a_ld < n) return {"%s: a_ld = %lld is smaller than n", (long long)a_ld};
+  if (hist_a_ld < n) return {"%s: hist_a_ld = %lld is smaller than n", (long long)hist_a_ld};
+  if (gmx_resample_rows_pin_refusal_(rows, n, D, hist_x_ld, x_row_stride).fmt)
+    return {"%s: hist_x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)hist_x_ld};
+  if (out_ld < 2 * (int64_t)D) return {"%s: out_ld = %lld is smaller than 2 D", (long long)out_ld};
+  if (t > 0 && no_anc) return {"%s: null argument (ancestors_d with t = %lld > 0)", (long long)t};
+  return {nullptr, 0};
+}
+
 // ---- row-wise weighted quantiles: gmx_rows_quantiles (gmx_quantiles.h) ----
 #define GMX_ROWS_QUANTILES_MAX_Q 16    /* levels per call: a row's thresholds are parked in LDS */
 // One tile only: past it a quantile needs the two-level block-floating-point weights and a selection across tiles.  rows as

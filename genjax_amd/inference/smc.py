@@ -887,6 +887,65 @@ def row_covariance(lw: torch.Tensor, x, *, carry=None, out=None, workspace=None)
     return (mean[:, 0], cov) if scalar else (mean, cov)
 
 
+ROWS_LAG_MAX = 32                # gmx_rows_lag_moments: L (GMX_ROWS_LAG_MAX)
+
+
+def lag_rings(R: int, n: int, D: int, L: int, device):
+    """the two rings gmx_rows_lag_moments keeps for a lag of L: (hist_x float32 [L + 1, D, R * n], hist_a int32 [L + 1, R, n]),
+    (L + 1) (D + 1) R n 4 bytes"""
+    return (torch.zeros((L + 1, D, R * n), dtype=torch.float32, device=device),
+            torch.zeros((L + 1, R, n), dtype=torch.int32, device=device))
+
+
+def row_lag_moments(lw: torch.Tensor, x, ancestors, t: int, L: int, lags, rings, *, carry=None, index_stride=0, out=None,
+                    out_lag_stride=None, workspace=None):
+    """gmx_rows_lag_moments for ONE step t of a sweep, on caller-supplied rings (lag_rings(R, n, D, L, device), handed
+    unchanged to the calls of steps 0, 1, 2, ... in order): records step t — the state x (the forms row_moments takes) and
+    `ancestors`, int32 [R, n], x[r, i] extending the previous step's column ancestors[r, i] - r * index_stride (None at
+    t = 0) — and writes, for every lag l of lags = (lag_lo, lag_hi), 0 <= lag_lo <= lag_hi <= min(L, t), the mean and the
+    variance of x_{t-l} along the ancestry of step t's particles under step t's weights lw (+ carry): the fixed-lag
+    smoothed moments E[x_{t-l} | y_1..t].  lags=None records only.  -> (mean, var), float64 [lag_hi + 1, R, D] views of out
+    on lw's device (rows below lag_lo are not written; an [R, n] state gives [lag_hi + 1, R]), or None.  out: a float64
+    [>= lag_hi + 1, R, >= 2 D] buffer with lag l at out[l] — or, with out_lag_stride (in doubles, may be negative), any
+    float64 tensor whose first element is lag 0's."""
+    be = _lib.get()
+    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
+        raise ValueError(f"row_lag_moments: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
+    R, n = (int(v) for v in lw.shape)
+    ld = int(lw.stride(0)) if R > 1 else n
+    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
+        raise ValueError("row_lag_moments: carry is a float32 matrix of lw's shape and strides")
+    if x is None:
+        raise ValueError("row_lag_moments: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
+    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_lag_moments")
+    if x_rs != n:                                                # the rings are [.., R * n]: rows n apart
+        parts = list(x) if isinstance(x, (tuple, list)) else ([x] if x.ndim == 2 else list(x.unbind(2)))
+        xt, x_ld, x_rs = torch.stack([v.float() for v in parts]).contiguous(), R * n, n
+    if ancestors is not None and (ancestors.dtype != torch.int32 or tuple(ancestors.shape) != (R, n) or not ancestors.is_contiguous()):
+        raise ValueError("row_lag_moments: ancestors is a contiguous int32 [R, n] matrix (None at t = 0)")
+    hist_x, hist_a = rings
+    if (tuple(hist_x.shape) != (L + 1, D, R * n) or hist_x.dtype != torch.float32 or not hist_x.is_contiguous() or
+            tuple(hist_a.shape) != (L + 1, R, n) or hist_a.dtype != torch.int32 or not hist_a.is_contiguous()):
+        raise ValueError(f"row_lag_moments: rings are lag_rings(R, n, D, L) = float32 {(L + 1, D, R * n)}, int32 {(L + 1, R, n)}")
+    lo, hi = (0, -1) if lags is None else (int(lags[0]), int(lags[1]))
+    if out is None:
+        out = torch.full((max(hi, 0) + 1, R, 2 * D), math.nan, dtype=torch.float64, device=lw.device)
+    if out.dtype != torch.float64 or (out_lag_stride is None and (out.ndim != 3 or out.shape[0] < hi + 1 or out.shape[1] != R or
+                                                                  out.shape[2] < 2 * D or out.stride(2) != 1)):
+        raise ValueError(f"row_lag_moments: out is a float64 [>= lag_hi + 1, R, >= 2 D] = [>= {hi + 1}, {R}, >= {2 * D}] buffer")
+    out_ld = int(out.stride(1)) if out_lag_stride is None and R > 1 else 2 * D
+    if workspace is None:
+        workspace = torch.empty(((int(be.c.gmx_rows_lag_moments_workspace(R, n, D, L)) + 7) // 8,), dtype=torch.int64, device=lw.device)
+    be.check(be.c.gmx_rows_lag_moments(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(ancestors), n,
+                                       int(index_stride), int(t), int(L), lo, hi, be.ptr(hist_x), R * n, be.ptr(hist_a), n,
+                                       be.ptr(out), out_ld, int(out.stride(0)) if out_lag_stride is None else int(out_lag_stride),
+                                       be.ptr(workspace), be.stream()), "gmx_rows_lag_moments")
+    if lags is None or out_lag_stride is not None:
+        return None
+    mean, var = out[:hi + 1, :, :D], out[:hi + 1, :, D:2 * D]
+    return (mean[:, :, 0], var[:, :, 0]) if scalar else (mean, var)
+
+
 ROWS_QUANTILES_N_MAX = 1024      # gmx_rows_quantiles sorts a row of one tile
 ROWS_QUANTILES_Q_MAX = 16        # levels per call (GMX_ROWS_QUANTILES_MAX_Q)
 
@@ -2209,12 +2268,22 @@ class BootstrapBank(_Sweep):
     matrix of its particles — what a Kalman filter's P_t is compared with for a state of several components (at most 15),
     where moments=True gives the diagonal — into a [T, R, D + D^2] float64 table on the device, no host read, still one
     graph.  filter_cov() reads it after a sweep.  The weights are the ones moments=True sees; a filter without mass at a
-    step has NaN there."""
+    step has NaN there.
+
+    smooth_lag=L, 1 <= L <= 32 (None: nothing is allocated and the sweep is launch for launch the one above): the FIXED-LAG
+    SMOOTHER, E[x_s | y_1..min(s+L, T-1)] and its variance per filter and step — the smoothed estimate a state-space model
+    is plotted with, without a recorded particle system: per step ONE more launch (gmx_rows_lag_moments; two past n = 1024)
+    in the same place copies the step's state and the ancestors it was gathered through into two rings of L + 1 slots,
+    (L + 1) (D + 1) R n 4 bytes, walks step t's particles back through the last L ancestor tables and writes the weighted
+    mean and variance of x_{t-L} along them into row t - L of a [T, R, 2 D] float64 table; the last step writes lags
+    0 .. min(L, T - 1), so every time step is written exactly once.  No host read, still one graph.  smoothed_mean() and
+    smoothed_var() read it after a sweep.  The weights are the ones moments=True sees at step min(s + L, T - 1), and with
+    ess_threshold= the identity ancestors of a row that was not resampled make the walk pass straight through it."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
                  noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False, quantiles=None,
-                 covariance=False):
+                 covariance=False, smooth_lag=None):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2237,6 +2306,12 @@ class BootstrapBank(_Sweep):
         self.specialize = specialize
         self.moments = bool(moments)
         self.covariance = bool(covariance)
+        self.smooth_lag = None
+        if smooth_lag is not None:
+            self.smooth_lag = int(smooth_lag)
+            if self.smooth_lag != smooth_lag or not 1 <= self.smooth_lag <= ROWS_LAG_MAX:
+                raise ValueError(f"BootstrapBank(smooth_lag={smooth_lag!r}): an integer in [1, {ROWS_LAG_MAX}] "
+                                 "(gmx_rows_lag_moments parks the ancestor tables of a lag in LDS)")
         self.quantiles = None
         if quantiles is not None:
             self.quantiles, self.q_levels = _quantile_levels(quantiles, "BootstrapBank(quantiles=)")
@@ -2325,6 +2400,11 @@ class BootstrapBank(_Sweep):
                                           "(gmx_rows_covariance holds (1, x) in one 16 x 16 matrix tile)")
             self.cov = torch.zeros((T, R, D + D * D), dtype=torch.float64, device=dev)     # per step and row: D means, D x D covariances
             self.cov_ws = torch.zeros(((int(be.c.gmx_rows_covariance_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
+        if self.smooth_lag is not None:
+            D, L = self.store.D, self.smooth_lag
+            self.lag_rings = lag_rings(R, n, D, L, dev)          # the last L + 1 state slabs and ancestor tables
+            self.smo = torch.zeros((T, R, 2 * D), dtype=torch.float64, device=dev)         # per time and row: D means, D variances
+            self.smo_ws = torch.zeros(((int(be.c.gmx_rows_lag_moments_workspace(R, n, D, L)) + 7) // 8,), dtype=torch.int64, device=dev)
         if self.quantiles is not None:
             self.q_table = self.q_levels.to(dev)                 # the levels where the kernel reads them: nothing from the host
             self.qnt = torch.zeros((T, R, self.store.D, len(self.quantiles)), dtype=torch.float32, device=dev)
@@ -2361,6 +2441,16 @@ class BootstrapBank(_Sweep):
                                           be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.cov[t]), int(self.cov.shape[2]),
                                           be.ptr(self.cov_ws), be.stream()), "gmx_rows_covariance")
 
+    def _smooth(self, t):
+        """step t into the rings, and the smoothed mean and variance of time t - L from step t's weights — at the last step
+        of times T - 1 - min(L, T - 1) .. T - 1 (gmx_rows_lag_moments; lag l lands in row t - l of the table)"""
+        T, L = self.T, self.smooth_lag
+        lags = (0, min(L, T - 1)) if t == T - 1 else ((L, L) if t >= L else None)
+        x = tuple(row.reshape(self.R, self.n) for row in self.store.rows[t % 2])
+        row_lag_moments(self.lw.reshape(self.R, self.n), x, self.anc if t > 0 else None, t, L, lags,
+                        self.lag_rings, carry=self.carry.reshape(self.R, self.n) if self.ess_q8 is not None else None,
+                        index_stride=self.n, out=self.smo[t], out_lag_stride=-int(self.smo.stride(0)), workspace=self.smo_ws)
+
     def _resample(self, t):
         if self.ess_q8 is not None:
             return self._resample_adaptive(t)
@@ -2379,7 +2469,8 @@ class BootstrapBank(_Sweep):
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
         ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with covariance=True:
-        gmx_rows_covariance, with quantiles=: gmx_rows_quantiles there too) — no syncs, no allocations, no host read of a device value"""
+        gmx_rows_covariance, with quantiles=: gmx_rows_quantiles, with smooth_lag=: gmx_rows_lag_moments there too) — no syncs,
+        no allocations, no host read of a device value"""
         N = self.R * self.n
         self.status.zero_()
         if self.ess_q8 is not None:
@@ -2394,6 +2485,8 @@ class BootstrapBank(_Sweep):
                 self._covariance(t)
             if self.quantiles is not None:
                 self._quantiles(t)
+            if self.smooth_lag is not None:
+                self._smooth(t)
             self._resample(t)
 
     def _recorded_moments(self, who, lo, hi):
@@ -2427,6 +2520,23 @@ class BootstrapBank(_Sweep):
             raise ValueError("BootstrapBank.filter_cov: no covariance was recorded (build the bank with covariance=True)")
         D = self.store.D
         return self.cov[:, :, D:].cpu().unflatten(2, (D, D))
+
+    def _smoothed(self, who, lo):
+        if self.smooth_lag is None:
+            raise ValueError(f"BootstrapBank.{who}: nothing smoothed was recorded (build the bank with smooth_lag=L)")
+        D = self.store.D
+        out = self.smo[:, :, lo * D:(lo + 1) * D].cpu()
+        return out[:, :, 0] if D == 1 else out
+
+    def smoothed_mean(self) -> torch.Tensor:
+        """float64 [T, R] ([T, R, D] for a state of D > 1 components), on the host: the fixed-lag smoothed mean
+        E[x_s | y_1..min(s+L, T-1)] of filter r — row T - 1 is the filtering mean of the last step (smooth_lag=L only;
+        synchronises)"""
+        return self._smoothed("smoothed_mean", 0)
+
+    def smoothed_var(self) -> torch.Tensor:
+        """smoothed_mean()'s shapes: the fixed-lag smoothed variance, per component (smooth_lag=L only; synchronises)"""
+        return self._smoothed("smoothed_var", 1)
 
     def filter_quantiles(self) -> torch.Tensor:
         """float32 [T, R, Q] ([T, R, D, Q] for a state of D > 1 components), on the host: the quantiles of x_t | y_1..t of filter
@@ -2548,7 +2658,11 @@ class ConditionalBank(BootstrapBank):
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
-                 ess_threshold=None, moments=False, quantiles=None, covariance=False):
+                 ess_threshold=None, moments=False, quantiles=None, covariance=False, smooth_lag=None):
+        if smooth_lag is not None:
+            raise NotImplementedError("ConditionalBank: smooth_lag= is not supported (as moments=True: the weights before the "
+                                      "pinned resampler are not the conditional system's — and every step is recorded here: "
+                                      "draw(backward=True) smooths; BootstrapBank takes it)")
         if covariance:
             raise NotImplementedError("ConditionalBank: covariance=True is not supported (as moments=True: the weights before "
                                       "the pinned resampler are not the conditional system's; BootstrapBank takes it)")
@@ -2990,8 +3104,8 @@ class ParticleMH(_Sweep):
 
     moments=True (with every other keyword BootstrapBank takes) reaches the bank: the filtering means, variances and ESS of the
     LAST sweep — the proposal's, accepted or not — are then read from pmh.bank (filter_mean(), filter_var(), ess()); nothing
-    of them is recorded across iterations.  quantiles=(p, ...) and covariance=True reach the bank the same way
-    (pmh.bank.filter_quantiles(), pmh.bank.filter_cov())."""
+    of them is recorded across iterations.  quantiles=(p, ...), covariance=True and smooth_lag=L reach the bank the same way
+    (pmh.bank.filter_quantiles(), pmh.bank.filter_cov(), pmh.bank.smoothed_mean() and smoothed_var())."""
 
     def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
                  state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):

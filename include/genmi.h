@@ -863,6 +863,47 @@ int gmx_rows_covariance(const float* lw_d, const float* carry_d /* may be NULL *
                         double* out_d /* [rows, out_ld] */, int64_t out_ld, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Fixed-lag smoothed moments  (additive, ABI still v8.  Reference call site: none of its own — the fixed-lag smoother of each
+ * of R filters, E[x_s | y_1..s+L] and its variance, from the last L ancestor tables and state slabs instead of a recorded
+ * particle system.)
+ *   gmx_rows_lag_moments   ONE call per step t of a sweep, between the step's weights and its resampling, so that
+ *                   ancestors_d still holds a_{t-1} (x_t[i] extends x_{t-1}[a_{t-1}[i] - r * index_stride]; null at t = 0).
+ *                   Weights and state are addressed as gmx_rows_moments addresses them, and steps 1 to 3 of its definition
+ *                   give a_i, M and e_i: the same weights bit for bit.  Nothing is written into lw_d, carry_d, x_d or
+ *                   ancestors_d.  The caller owns two rings and passes them to every call of the sweep unchanged:
+ *                   hist_x_d [L + 1, D, hist_x_ld] (rows x_row_stride apart, as x_d) and hist_a_d [L + 1, rows, hist_a_ld].
+ *                     1. record: x_d's words of every row and ancestors_d's rows (a_ld apart) are copied into slot
+ *                        t mod (L + 1) of the rings (at t = 0 no ancestors);
+ *                     2. walk: b_0(i) = i; b_l(i) = col(a_{t-l}[b_{l-1}(i)]), a_{t-l} the rows recorded at step t - l + 1 (for
+ *                        l = 1 ancestors_d itself), col(a) = a - r * index_stride clamped into [0, n - 1];
+ *                     3. summarise: S0 = sum e_i and, for every lag l in [lag_lo, lag_hi] and component d, in float64
+ *                        A = sum e_i z_i, B = sum e_i z_i^2 with z_i = x_{t-l,d}[b_l(i)] (slot (t - l) mod (L + 1) of hist_x_d;
+ *                        lag 0: x_d);  out_d[l * out_lag_stride + r * out_ld + d] = A / S0,
+ *                        out_d[l * out_lag_stride + r * out_ld + D + d] = max(B / S0 - (A / S0)^2, 0): gmx_rows_moments'
+ *                        forms.  out_lag_stride is signed (a negative one puts lag l into the record of time t - l);
+ *                     4. a row without mass (S0 = 0) writes NaN into the 2 D outputs of every lag.  It is not an error.
+ *                   (lag_lo, lag_hi) = (0, -1) is the empty range: the call records only.  The summation order is
+ *                   gmx_rows_moments' (lag 0 gives its mean and variance bit for bit); the CPU build sums in column order.
+ *                   n <= 1024: ONE launch with gmx_resample_rows' packing, the tables of hops 2 .. lag_hi parked in LDS as
+ *                   16-bit columns (2 KB each); nothing in the workspace.  n > 1024: per (row, tile of 1024 columns) the
+ *                   record, the walk through hist_a_d in global memory and the tile's sums relative to its own maximum, then
+ *                   per row their combination under s_b = exp(m_b - M) taken in float64 (an empty range: the first alone).
+ *                   Limits: those of gmx_rows_moments with 1 <= D and x_d not null; the index_stride rule of
+ *                   gmx_resample_rows; 1 <= L <= 32 (GMX_ROWS_LAG_MAX); t >= 0; 0 <= lag_lo <= lag_hi <= min(L, t) unless
+ *                   empty; a_ld >= n, hist_a_ld >= n; hist_x_ld as x_ld; out_ld >= 2 D; ancestors_d not null when t > 0;
+ *                   workspace_d: gmx_rows_lag_moments_workspace(rows, n, D, L) bytes (16 for n <= 1024; past it
+ *                   2 + 2 D (L + 1) doubles and a float per (row, tile)), 8-byte aligned, not null.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+size_t gmx_rows_lag_moments_workspace(int64_t rows, int64_t n, int32_t D, int32_t L);
+int gmx_rows_lag_moments(const float* lw_d, const float* carry_d /* may be NULL */, int64_t rows, int64_t n, int64_t ld,
+                         const float* x_d /* [D, x_ld] */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                         const int32_t* ancestors_d /* [rows, a_ld], null iff t = 0 */, int64_t a_ld, int64_t index_stride,
+                         int64_t t, int32_t L, int32_t lag_lo, int32_t lag_hi, float* hist_x_d /* [L + 1, D, hist_x_ld] */,
+                         int64_t hist_x_ld, int32_t* hist_a_d /* [L + 1, rows, hist_a_ld] */, int64_t hist_a_ld,
+                         double* out_d, int64_t out_ld, int64_t out_lag_stride, void* workspace_d, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Row-wise weighted quantiles  (additive, ABI still v8.  Reference call site: none of its own — the credible band of each of
  * R filters at a step: the median and the tail quantiles of x_t | y_1..t, from the weights and the state the step has just
  * written, where a mean and a variance would describe a Gaussian.)
