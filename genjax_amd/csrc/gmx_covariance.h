@@ -19,7 +19,7 @@
 // C[4 q + v][c]: the two differ by exactly the wrong 4-row block a test with D >= 3 distinct components shows.)
 //   n <= 1024   k_rows_cov_small<W>: ONE launch, no workspace traffic, the packing of rows_small_body — W = 1, 2 or 4 waves
 //               per row, 4 / W rows per 256-thread workgroup.  Phase 1, as k_rows_moments_small: a thread loads its four
-//               columns of lw (and carry), the row's maximum goes through pick1_put_max and 4 LDS words, and the thread
+//               columns of lw (and carry), the row's maximum is gmx_moments.h's mom_row_max (4 LDS words), and the thread
 //               parks its four e_i in LDS by column as the float32 values they are (4 KB a workgroup; columns >= n: 0).
 //               Phase 2: a wave owns 256 consecutive columns, 16 to a block: lane (c, q) with 1 <= c <= D issues ONE
 //               16-byte load of component c - 1 at columns blk + 4 q .. + 3 (c = 0 holds 1, c > D holds 0 and loads
@@ -39,7 +39,7 @@
 // host compiler: the ENTRY POINTS as a sequential loop over rows implementing the definition literally, sums in column
 // order, with the same refusals (gmx_sizes.h); gmx_vm.h includes this file there.
 #pragma once
-#include "gmx_moments.h"               /* gmx_mom_weight; under hipcc mom_add, pick_load4, pick1_put_max */
+#include "gmx_moments.h"               /* gmx_mom_weight, gmx_mom_tile_scale; under hipcc mom_row_max, pick_load4 */
 
 // entry (i <= j) of the 16 x 16 upper triangle, rows in order: 0 .. 135
 GMX_HD int gmx_cov_tri(int i, int j) { return 16 * i - i * (i - 1) / 2 + (j - i); }
@@ -109,15 +109,7 @@ __device__ __forceinline__ float cov_gram(const float* __restrict__ lw, const fl
         if (zrow != nullptr && cb + k < n) z[b][k] = zrow[cb + k];
     }
   }
-  if (carry != nullptr) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = mom_add(a[k], cy[k]);
-  }
-  pick1_put_max(a, s.max, lane, wave);
-  __syncthreads();
-  float M = s.max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s.max[grp * W + w]);
+  const float M = mom_row_max<W>(a, cy, carry != nullptr, s.max, grp, lane, wave);
   float4 e4;                                                     // (a column >= n was loaded as -inf: weight 0)
   e4.x = gmx_mom_weight(a[0], M); e4.y = gmx_mom_weight(a[1], M);
   e4.z = gmx_mom_weight(a[2], M); e4.w = gmx_mom_weight(a[3], M);
@@ -206,10 +198,7 @@ k_rows_cov_finish(const double* __restrict__ rec, const float* __restrict__ tmax
   float M = -gmx_inf();
   for (int64_t t = tid; t < n_tiles; t += GMX_COV_BLOCK) M = gmx_rmax(M, tm[t]);
   M = block_max(M, lds4);
-  for (int64_t t = tid; t < n_tiles; t += GMX_COV_BLOCK) {
-    const double dm = (double)tm[t] - (double)M;
-    s_scale[t] = dm == dm ? exp(dm) : 0.0;                       // (a tile without mass under a row without: -inf - -inf)
-  }
+  for (int64_t t = tid; t < n_tiles; t += GMX_COV_BLOCK) s_scale[t] = gmx_mom_tile_scale(tm[t], M);
   __syncthreads();
   if (tid < GMX_COV_REC) {
     const double* __restrict__ mine = rec + r * n_tiles * GMX_COV_REC + tid;
@@ -240,11 +229,7 @@ extern "C" __attribute__((used)) inline int gmx_rows_covariance(const float* lw_
   if (no.fmt) return gmx_fail(no.fmt, "gmx_rows_covariance", no.v);
   std::vector<float> a((size_t)n);
   for (int64_t r = 0; r < rows; ++r) {
-    float M = -gmx_inf();
-    for (int64_t i = 0; i < n; ++i) {
-      a[(size_t)i] = carry_d ? lw_d[r * ld + i] + carry_d[r * ld + i] : lw_d[r * ld + i];
-      M = gmx_rmax(M, a[(size_t)i]);
-    }
+    const float M = gmx_mom_row_(lw_d + r * ld, carry_d ? carry_d + r * ld : nullptr, n, a.data());
     double G[16][16] = {}, z[16];
     z[0] = 1.0;
     for (int64_t i = 0; i < n; ++i) {

@@ -27,7 +27,7 @@
 //               then the D record copies.  The walk is lag_hi dependent LDS reads per particle, a thread's four chains
 //               side by side; only lags in [lag_lo, lag_hi] gather state words from hist_x (lag 0: from x), the gather of
 //               pair p + 1 issued before pair p is reduced.  Steady state lag_lo = lag_hi = L: L hops, D gathers, one
-//               batch.  BARRIERS: 1 (the row maxima and the tables) + ceil((1 + D * lags) / 8) (lag_reduce); 0 for an
+//               batch.  BARRIERS: 1 (the row maxima and the tables) + ceil((1 + D * lags) / 8) (mom_reduce); 0 for an
 //               empty range.
 //   n > 1024    k_rows_lag_part, one workgroup per (row, tile of 1024 columns): records its columns, walks through hist_a
 //               in GLOBAL memory (a row's table is up to 8 MB: no LDS form), four chains side by side, and writes the tile's
@@ -36,10 +36,8 @@
 //               k_rows_moments_finish does and for its reason.  Hop 1 reads the call's own ancestors, every further hop and
 //               every gather a slot an EARLIER call wrote, so no workgroup reads what another writes in the same launch.
 //               An empty range launches the first kernel alone.
-// SHARED with gmx_moments.h: gmx_mom_weight, gmx_mom_mean_var, mom_wave_sum, mom_add, mom_load4, mom_pair, pick_load4,
-// pick1_put_max, block_max, rows_store4 and the workspace struct; lag_reduce is mom_reduce's scheme (batches of pairs, two
-// LDS buffers, one barrier a batch) over a flat pair index with the outputs left to the caller, since a pair's place depends
-// on its lag.
+// SHARED with gmx_moments.h: the weights, the weight heads, the reduction (at C = GMX_LAG_C), the tile scales, the outputs'
+// arithmetic and the mirror's row head are that header's; only a pair's place, which depends on its lag, is stated here.
 // Under hipcc: the kernels, included by gmx_kernels.hip only (not among the headers embedded for hiprtc).  Under a plain
 // host compiler: the ENTRY POINTS as a sequential loop over rows implementing the definition literally, sums in column
 // order, with the same refusals (gmx_sizes.h); gmx_vm.h includes this file there.
@@ -71,40 +69,6 @@ __device__ __forceinline__ void lag_load4i(const int32_t* row, int64_t base, int
   } else {
 #pragma unroll
     for (int c = 0; c < 4; ++c) v[c] = (base + c < n) ? row[base + c] : 0;
-  }
-}
-
-// P pairs of sums of a row held by waves grp * W .. grp * W + W - 1: every thread calls pair_of(p, u, v) for p = 0 .. P - 1 in
-// order (its share of pair p); `writer`, the one thread of the group that adds the waves in order, calls emit(p, u, v) in
-// the same order.  Every thread of the workgroup calls it (one barrier per batch of GMX_LAG_C pairs; gmx_moments.h says why
-// one is enough).
-template <int W, class F, class O>
-__device__ __forceinline__ void lag_reduce(int32_t P, F pair_of, O emit, int grp, int lane, int wave, bool writer) {
-  __shared__ double s_buf[2][4][2 * GMX_LAG_C];
-  int k = 0;
-  for (int32_t p0 = 0; p0 < P; p0 += GMX_LAG_C, k ^= 1) {
-    const int32_t p1 = p0 + GMX_LAG_C < P ? p0 + GMX_LAG_C : P;
-    for (int32_t p = p0; p < p1; ++p) {
-      double u, v;
-      pair_of(p, u, v);
-      u = mom_wave_sum(u);
-      v = mom_wave_sum(v);
-      if (lane == 0) {
-        s_buf[k][wave][2 * (p - p0)] = u;
-        s_buf[k][wave][2 * (p - p0) + 1] = v;
-      }
-    }
-    __syncthreads();
-    if (!writer) continue;
-    for (int32_t p = p0; p < p1; ++p) {
-      double u = s_buf[k][grp * W][2 * (p - p0)], v = s_buf[k][grp * W][2 * (p - p0) + 1];
-#pragma unroll
-      for (int w = 1; w < W; ++w) {
-        u += s_buf[k][grp * W + w][2 * (p - p0)];
-        v += s_buf[k][grp * W + w][2 * (p - p0) + 1];
-      }
-      emit(p, u, v);
-    }
   }
 }
 
@@ -182,15 +146,8 @@ k_rows_lag_small(const float* __restrict__ lw, const float* __restrict__ carry, 
     lag_record(x + row_off, D, x_ld, base, n, hist_x + gmx_lag_slot(t, L) * hx_slot + row_off, hx_ld,
                hist_a + gmx_lag_slot(t, L) * ha_slot + r * ha_ld, a0, anc != nullptr);
   if (!sums) return;                                             // (uniform: before any barrier)
-  if (carry != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
-  }
-  pick1_put_max(a, s_max, lane, wave);
-  __syncthreads();                                               // the waves' maxima and the tables
-  float M = s_max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  // (its barrier also publishes the tables written above: they stay before this call)
+  const float M = mom_row_max<W>(a, cy, carry != nullptr, s_max, grp, lane, wave);
   double e[4];
   bool in[4];
   lag_walk wk;
@@ -210,7 +167,7 @@ k_rows_lag_small(const float* __restrict__ lw, const float* __restrict__ carry, 
   float xn[4];
   lag_gather(wk, hop, x, x_ld, hist_x, hx_ld, row_off, D, t, L, in, xn);
   lag_place at = {lag_lo, 0, 0.0};
-  lag_reduce<W>(P, [&](int32_t p, double& u, double& v) {
+  mom_reduce<W, GMX_LAG_C>(P, [&](int32_t p, double& u, double& v) {
     if (p == 0) { u = ((e[0] + e[1]) + e[2]) + e[3]; v = 0.0; return; }
     float xc[4];
 #pragma unroll
@@ -250,12 +207,7 @@ k_rows_lag_part(const float* __restrict__ lw, const float* __restrict__ carry, i
   lag_record(x + row_off, D, x_ld, base, n, hist_x + gmx_lag_slot(t, L) * hx_slot + row_off, hx_ld,
              hist_a + gmx_lag_slot(t, L) * ha_slot + r * ha_ld, a0, anc != nullptr);
   if (!sums) return;
-  if (carry != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
-  }
-  const float m = block_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])), lds4);
-  if (tid == 0) tmax[cell] = m;
+  const float m = mom_tile_max(a, cy, carry != nullptr, lds4, tmax + cell, tid);
   double e[4];
   bool in[4];
   lag_walk wk;
@@ -278,7 +230,7 @@ k_rows_lag_part(const float* __restrict__ lw, const float* __restrict__ carry, i
   double* __restrict__ mine = rec + cell * 2 * (int64_t)P;
   float xn[4];
   lag_gather(wk, hop, x, x_ld, hist_x, hx_ld, row_off, D, t, L, in, xn);
-  lag_reduce<4>(P, [&](int32_t p, double& u, double& v) {
+  mom_reduce<4, GMX_LAG_C>(P, [&](int32_t p, double& u, double& v) {
     if (p == 0) { u = ((e[0] + e[1]) + e[2]) + e[3]; v = 0.0; return; }
     float xc[4];
 #pragma unroll
@@ -303,17 +255,12 @@ k_rows_lag_finish(const double* __restrict__ rec, const float* __restrict__ tmax
   for (int64_t b = tid; b < n_tiles; b += GMX_LAG_BLOCK) M = gmx_rmax(M, tm[b]);
   M = block_max(M, lds4);
   double s[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int64_t b = (int64_t)tid + (int64_t)j * GMX_LAG_BLOCK;
-    const double dm = b < n_tiles ? (double)tm[b] - (double)M : 0.0;
-    s[j] = (b < n_tiles && dm == dm) ? exp(dm) : 0.0;          // (a tile without mass under a row without: -inf - -inf)
-  }
+  mom_tile_scales(tm, n_tiles, M, tid, s);
   const int32_t P = 1 + D * (lag_hi - lag_lo + 1);
   const int64_t stride = 2 * (int64_t)P;
   const double* __restrict__ mine = rec + (r * n_tiles + tid) * stride;
   lag_place at = {lag_lo, 0, 0.0};
-  lag_reduce<4>(P, [&](int32_t p, double& u, double& v) {
+  mom_reduce<4, GMX_LAG_C>(P, [&](int32_t p, double& u, double& v) {
     u = 0.0; v = 0.0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -352,6 +299,7 @@ extern "C" __attribute__((used)) inline int gmx_rows_lag_moments(
                                                        out_ld, !x_d, !ancestors_d);
   if (no.fmt) return gmx_fail(no.fmt, "gmx_rows_lag_moments", no.v);
   const int64_t ha_slot = rows * hist_a_ld, hx_slot = (int64_t)D * hist_x_ld;
+  std::vector<float> a((size_t)n);
   std::vector<double> e((size_t)n);
   std::vector<int64_t> b((size_t)n);
   for (int64_t r = 0; r < rows; ++r) {
@@ -362,15 +310,10 @@ extern "C" __attribute__((used)) inline int gmx_rows_lag_moments(
         hist_x_d[gmx_lag_slot(t, L) * hx_slot + (int64_t)d * hist_x_ld + row_off + i] = x_d[(int64_t)d * x_ld + row_off + i];
     }
     if (lag_hi < 0) continue;
-    float M = -gmx_inf();
-    for (int64_t i = 0; i < n; ++i) {
-      const float a = carry_d ? lw_d[r * ld + i] + carry_d[r * ld + i] : lw_d[r * ld + i];
-      e[(size_t)i] = (double)a;                                  // (parked; its weight below)
-      M = gmx_rmax(M, a);
-    }
+    const float M = gmx_mom_row_(lw_d + r * ld, carry_d ? carry_d + r * ld : nullptr, n, a.data());
     double S0 = 0.0;
     for (int64_t i = 0; i < n; ++i) {
-      e[(size_t)i] = (double)gmx_mom_weight((float)e[(size_t)i], M);
+      e[(size_t)i] = (double)gmx_mom_weight(a[(size_t)i], M);
       S0 += e[(size_t)i];
       b[(size_t)i] = i;
     }

@@ -24,9 +24,11 @@
 //               exp(fl(a - m_b)) exp(m_b - M) is still not the definition's exp(fl(a - M)) bit for bit — the float32
 //               subtraction rounds elsewhere — so the tiled form is held to the float64 reference with a tolerance, not
 //               bit for bit to the definition the one-tile form follows.
-// THE REDUCTION (mom_reduce, all three kernels): the D + 1 pairs — (S0, S2), then (A_d, B_d) — are reduced in batches of
-// C = GMX_MOM_C = 16 pairs: each wave sums a pair across its lanes by cross-lane moves and lane 0 parks it in LDS; ONE
-// barrier per batch; one thread of the row's group then adds the W waves in order and writes the batch's outputs.  The
+// THE REDUCTION (mom_reduce, all three kernels and gmx_lag.h's at C = 8): the D + 1 pairs — (S0, S2), then (A_d, B_d) —
+// are handed over by a pair_of callback and reduced in batches of C = GMX_MOM_C = 16 pairs, the writer's results going to
+// an emit callback (a tile's record, or mom_row_out: the row's outputs): each wave sums a pair across its lanes by
+// cross-lane moves and lane 0 parks it in LDS; ONE barrier per batch; one thread of the row's group then adds the W waves
+// in order and writes the batch's outputs.  The
 // batches alternate between two LDS buffers, so the writer reads batch k while the waves fill batch k + 1 and no second
 // barrier is needed.  C by LDS budget: a buffer is 4 waves x 2 C doubles, 2 x 1 KB for C = 16 — far below what would limit
 // the eight 256-thread workgroups a CU can hold (160 KB / 8), while D <= 15 (every state this project's sweeps carry) still
@@ -52,6 +54,13 @@ GMX_HD void gmx_mom_mean_var(double S0, double A, double B, double* mean, double
   const double v = S0 > 0.0 ? B / S0 - m * m : (double)gmx_nan();
   *mean = m;
   *var = v < 0.0 ? 0.0 : v;                              // (false for NaN)
+}
+
+// a tile's scale s_b = exp(m_b - M) in FLOAT64 (the header says why); 0 for a tile without mass under a row without
+// (-inf - -inf)
+GMX_HD double gmx_mom_tile_scale(float m_b, float M) {
+  const double dm = (double)m_b - (double)M;
+  return dm == dm ? exp(dm) : 0.0;
 }
 
 #if defined(__HIPCC__)
@@ -97,49 +106,82 @@ __device__ __forceinline__ void mom_pair(const double e[4], const float x[4], do
   v = ((q[0] + q[1]) + q[2]) + q[3];
 }
 
-// The D + 1 pairs of a row held by waves grp * W .. grp * W + W - 1: pair_of(d, u, v) gives the calling thread's share of
-// pair d (d = -1: (S0, S2)); `writer`: the one thread of the group that adds the waves and writes.  RAW: the sums themselves,
-// dst[2 (d + 1)], dst[2 (d + 1) + 1] (a tile's record); otherwise the row's outputs dst[0], dst[1 + d], dst[1 + D + d].
-// Every thread of the workgroup calls it (one barrier per batch of GMX_MOM_C pairs; the header says why one is enough).
-template <int W, bool RAW, class F>
-__device__ __forceinline__ void mom_reduce(F pair_of, int32_t D, int grp, int lane, int wave, bool writer, double* __restrict__ dst) {
-  __shared__ double s_buf[2][4][2 * GMX_MOM_C];
-  const int32_t E = D + 1;
-  double S0 = 0.0;
+// P pairs of sums of a row held by waves grp * W .. grp * W + W - 1, C pairs per barrier: every thread calls
+// pair_of(p, u, v) for p = 0 .. P - 1 in order (its share of pair p); `writer`, the one thread of the group that adds the
+// waves in order, calls emit(p, u, v) in the same order.  Every thread of the workgroup calls it (the header says why one
+// barrier per batch is enough).
+template <int W, int C, class F, class O>
+__device__ __forceinline__ void mom_reduce(int32_t P, F pair_of, O emit, int grp, int lane, int wave, bool writer) {
+  __shared__ double s_buf[2][4][2 * C];
   int k = 0;
-  for (int32_t e0 = 0; e0 < E; e0 += GMX_MOM_C, k ^= 1) {
-    const int32_t e1 = e0 + GMX_MOM_C < E ? e0 + GMX_MOM_C : E;
-    for (int32_t e = e0; e < e1; ++e) {
+  for (int32_t p0 = 0; p0 < P; p0 += C, k ^= 1) {
+    const int32_t p1 = p0 + C < P ? p0 + C : P;
+    for (int32_t p = p0; p < p1; ++p) {
       double u, v;
-      pair_of(e - 1, u, v);
+      pair_of(p, u, v);
       u = mom_wave_sum(u);
       v = mom_wave_sum(v);
       if (lane == 0) {
-        s_buf[k][wave][2 * (e - e0)] = u;
-        s_buf[k][wave][2 * (e - e0) + 1] = v;
+        s_buf[k][wave][2 * (p - p0)] = u;
+        s_buf[k][wave][2 * (p - p0) + 1] = v;
       }
     }
     __syncthreads();
     if (!writer) continue;
-    for (int32_t e = e0; e < e1; ++e) {
-      double u = s_buf[k][grp * W][2 * (e - e0)], v = s_buf[k][grp * W][2 * (e - e0) + 1];
+    for (int32_t p = p0; p < p1; ++p) {
+      double u = s_buf[k][grp * W][2 * (p - p0)], v = s_buf[k][grp * W][2 * (p - p0) + 1];
 #pragma unroll
       for (int w = 1; w < W; ++w) {
-        u += s_buf[k][grp * W + w][2 * (e - e0)];
-        v += s_buf[k][grp * W + w][2 * (e - e0) + 1];
+        u += s_buf[k][grp * W + w][2 * (p - p0)];
+        v += s_buf[k][grp * W + w][2 * (p - p0) + 1];
       }
-      if (RAW) {
-        dst[2 * (int64_t)e] = u;
-        dst[2 * (int64_t)e + 1] = v;
-      } else if (e == 0) {
-        S0 = u;
-        dst[0] = gmx_mom_ess(u, v);
-      } else {
-        gmx_mom_mean_var(S0, u, v, dst + e, dst + (int64_t)D + e);
-      }
+      emit(p, u, v);
     }
   }
 }
+
+// THE WEIGHT HEAD of a one-tile kernel, after the caller has issued its loads: a (+ cy when with_carry: mom_add), the W
+// wave maxima through s_max [4], ONE barrier — which also publishes whatever the caller wrote to LDS before the call —
+// and the row's maximum M to every thread of the row's group.  Every thread of the workgroup calls it.
+template <int W>
+__device__ __forceinline__ float mom_row_max(float a[4], const float cy[4], bool with_carry, float* s_max, int grp, int lane, int wave) {
+  if (with_carry) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
+  }
+  pick1_put_max(a, s_max, lane, wave);
+  __syncthreads();
+  float M = s_max[grp * W];
+#pragma unroll
+  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  return M;
+}
+// ... of a tiled kernel's first launch: the tile's maximum m_b to every thread, and into *tmax_cell by thread 0
+__device__ __forceinline__ float mom_tile_max(float a[4], const float cy[4], bool with_carry, float* lds4, float* tmax_cell, int tid) {
+  if (with_carry) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
+  }
+  const float m = block_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])), lds4);
+  if (tid == 0) *tmax_cell = m;
+  return m;
+}
+// a finish kernel's eight scale factors of thread tid: tiles tid, tid + 256, ... (0 past the last tile)
+__device__ __forceinline__ void mom_tile_scales(const float* __restrict__ tm, int64_t n_tiles, float M, int tid, double s[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int64_t t = (int64_t)tid + (int64_t)j * GMX_MOM_BLOCK;
+    s[j] = t < n_tiles ? gmx_mom_tile_scale(tm[t], M) : 0.0;
+  }
+}
+// the emit of a row's outputs: pair 0 is (S0, S2) -> the ESS, pair 1 + d is (A_d, B_d) -> mean and variance of component d
+struct mom_row_out {
+  double* dst; int32_t D; double S0;
+  __device__ __forceinline__ void operator()(int32_t p, double u, double v) {
+    if (p == 0) { S0 = u; dst[0] = gmx_mom_ess(u, v); }
+    else gmx_mom_mean_var(S0, u, v, dst + p, dst + (int64_t)D + p);
+  }
+};
 
 // n <= 1024: W waves per row, 4 / W rows per workgroup; thread gt of a row's group holds columns 4 gt .. 4 gt + 3.  Every
 // thread reaches every barrier (a group past the last row works on the last row again and writes nothing).
@@ -162,26 +204,18 @@ k_rows_moments_small(const float* __restrict__ lw, const float* __restrict__ car
   pick_load4(lw + r * ld, base, n, a);
   if (carry != nullptr) pick_load4(carry + r * ld, base, n, cy);     // (every load below is out before the first wait)
   if (D > 0) mom_load4(xrow, base, n, xn);
-  if (carry != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
-  }
-  pick1_put_max(a, s_max, lane, wave);
-  __syncthreads();
-  float M = s_max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  const float M = mom_row_max<W>(a, cy, carry != nullptr, s_max, grp, lane, wave);
   double e[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) e[c] = (double)gmx_mom_weight(a[c], M);
-  mom_reduce<W, false>([&](int32_t d, double& u, double& v) {
-    if (d < 0) { mom_pair0(e, u, v); return; }
+  mom_reduce<W, GMX_MOM_C>(D + 1, [&](int32_t p, double& u, double& v) {
+    if (p == 0) { mom_pair0(e, u, v); return; }
     float xc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) xc[c] = xn[c];
-    if (d + 1 < D) mom_load4(xrow + (int64_t)(d + 1) * x_ld, base, n, xn);     // (out before this component's reduction)
+    if (p < D) mom_load4(xrow + (int64_t)p * x_ld, base, n, xn);               // (out before this component's reduction)
     mom_pair(e, xc, u, v);
-  }, D, grp, lane, wave, live && gt == 0, out + r * out_ld);
+  }, mom_row_out{out + r * out_ld, D, 0.0}, grp, lane, wave, live && gt == 0);
 }
 
 // n > 1024, first launch: blockIdx.x the tile, blockIdx.y the row (row0 + y); cell = r * n_tiles + b
@@ -199,23 +233,22 @@ k_rows_moments_part(const float* __restrict__ lw, const float* __restrict__ carr
   pick_load4(lw + r * ld, base, n, a);
   if (carry != nullptr) pick_load4(carry + r * ld, base, n, cy);
   if (D > 0) mom_load4(xrow, base, n, xn);
-  if (carry != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
-  }
-  const float m = block_max(gmx_rmax(gmx_rmax(a[0], a[1]), gmx_rmax(a[2], a[3])), lds4);
-  if (tid == 0) tmax[cell] = m;
+  const float m = mom_tile_max(a, cy, carry != nullptr, lds4, tmax + cell, tid);
   double e[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) e[c] = (double)gmx_mom_weight(a[c], m);
-  mom_reduce<4, true>([&](int32_t d, double& u, double& v) {
-    if (d < 0) { mom_pair0(e, u, v); return; }
+  double* __restrict__ mine = rec + cell * (2 + 2 * (int64_t)D);
+  mom_reduce<4, GMX_MOM_C>(D + 1, [&](int32_t p, double& u, double& v) {
+    if (p == 0) { mom_pair0(e, u, v); return; }
     float xc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) xc[c] = xn[c];
-    if (d + 1 < D) mom_load4(xrow + (int64_t)(d + 1) * x_ld, base, n, xn);
+    if (p < D) mom_load4(xrow + (int64_t)p * x_ld, base, n, xn);
     mom_pair(e, xc, u, v);
-  }, D, 0, lane, wave, tid == 0, rec + cell * (2 + 2 * (int64_t)D));
+  }, [&](int32_t p, double u, double v) {
+    mine[2 * (int64_t)p] = u;
+    mine[2 * (int64_t)p + 1] = v;
+  }, 0, lane, wave, tid == 0);
 }
 
 // n > 1024, second launch: one workgroup per row.  Thread t takes tiles t, t + 256, ... in ascending order.
@@ -230,25 +263,20 @@ k_rows_moments_finish(const double* __restrict__ rec, const float* __restrict__ 
   for (int64_t t = tid; t < n_tiles; t += GMX_MOM_BLOCK) M = gmx_rmax(M, tm[t]);
   M = block_max(M, lds4);
   double s[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int64_t t = (int64_t)tid + (int64_t)j * GMX_MOM_BLOCK;
-    const double dm = t < n_tiles ? (double)tm[t] - (double)M : 0.0;
-    s[j] = (t < n_tiles && dm == dm) ? exp(dm) : 0.0;        // (a tile without mass under a row without: -inf - -inf)
-  }
+  mom_tile_scales(tm, n_tiles, M, tid, s);
   const int64_t stride = 2 + 2 * (int64_t)D;
   const double* __restrict__ mine = rec + (r * n_tiles + tid) * stride;
-  mom_reduce<4, false>([&](int32_t d, double& u, double& v) {
+  mom_reduce<4, GMX_MOM_C>(D + 1, [&](int32_t p, double& u, double& v) {
     u = 0.0; v = 0.0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if ((int64_t)tid + (int64_t)j * GMX_MOM_BLOCK < n_tiles) {
-        const double* __restrict__ p = mine + (int64_t)j * GMX_MOM_BLOCK * stride + 2 * (int64_t)(d + 1);
-        u += s[j] * p[0];
-        v += (d < 0 ? s[j] * s[j] : s[j]) * p[1];
+        const double* __restrict__ q = mine + (int64_t)j * GMX_MOM_BLOCK * stride + 2 * (int64_t)p;
+        u += s[j] * q[0];
+        v += (p == 0 ? s[j] * s[j] : s[j]) * q[1];
       }
     }
-  }, D, 0, lane, wave, tid == 0, out + r * out_ld);
+  }, mom_row_out{out + r * out_ld, D, 0.0}, 0, lane, wave, tid == 0);
 }
 
 #elif defined(__cplusplus) && !defined(__HIPCC_RTC__)
@@ -261,6 +289,17 @@ extern "C" __attribute__((used)) inline size_t gmx_rows_moments_workspace(int64_
   return gmx_rows_moments_bytes_(rows, n, D);
 }
 
+// a row's a_i = lw_i (+ carry_i: ONE float32 add) into a[0 .. n), and their maximum M — how every row summary's mirror
+// (gmx_rows_moments, _covariance, _quantiles, _lag_moments) starts a row
+inline float gmx_mom_row_(const float* lw, const float* carry, int64_t n, float* a) {
+  float M = -gmx_inf();
+  for (int64_t i = 0; i < n; ++i) {
+    a[i] = carry ? lw[i] + carry[i] : lw[i];
+    M = gmx_rmax(M, a[i]);
+  }
+  return M;
+}
+
 // the definition, literally: the sums of a row in column order
 extern "C" __attribute__((used)) inline int gmx_rows_moments(const float* lw_d, const float* carry_d, int64_t rows, int64_t n, int64_t ld,
                                                           const float* x_d, int32_t D, int64_t x_ld, int64_t x_row_stride,
@@ -271,11 +310,7 @@ extern "C" __attribute__((used)) inline int gmx_rows_moments(const float* lw_d, 
   std::vector<float> a((size_t)n);
   std::vector<double> A((size_t)D), B((size_t)D);
   for (int64_t r = 0; r < rows; ++r) {
-    float M = -gmx_inf();
-    for (int64_t i = 0; i < n; ++i) {
-      a[(size_t)i] = carry_d ? lw_d[r * ld + i] + carry_d[r * ld + i] : lw_d[r * ld + i];
-      M = gmx_rmax(M, a[(size_t)i]);
-    }
+    const float M = gmx_mom_row_(lw_d + r * ld, carry_d ? carry_d + r * ld : nullptr, n, a.data());
     double S0 = 0.0, S2 = 0.0;
     for (int32_t d = 0; d < D; ++d) A[(size_t)d] = B[(size_t)d] = 0.0;
     for (int64_t i = 0; i < n; ++i) {

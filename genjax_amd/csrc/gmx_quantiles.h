@@ -11,7 +11,7 @@
 //               a thread holds 4 consecutive columns (one 16-byte load), a row takes W = 1, 2 or 4 waves, a 256-thread
 //               workgroup holds 4 / W rows; a group past the last row redoes the last row and writes nothing.
 //     weights, once per row   the weight, carry and first component loads leave before the first wait; the maximum and the
-//               fixed-point weights are pick1_put_max and gmx_tile_fixed4 (what pick1_put_scan calls); a thread's four q are
+//               fixed-point weights are mom_row_max and gmx_tile_fixed4 (what pick1_put_scan calls); a thread's four q are
 //               parked in LDS BY COLUMN (s_q: 8 bytes x 1024 columns per workgroup at every W); the Q thresholds are
 //               computed once per row by Q threads of its group and parked too.  Three barriers.
 //     sort, once per component   a bitonic network over the 256 W words (key << 32 | column) of the row: the column makes
@@ -36,7 +36,7 @@
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
-#include "gmx_math.h"
+#include "gmx_moments.h"               /* gmx_math.h; hipcc: gmx_backward.h, mom_row_max; the mirror: gmx_mom_row_ */
 
 // the order: bits ^ 0x80000000 for a non-negative float, ~bits for a negative one (-NaN first, -0 < +0, +NaN last)
 GMX_HD uint32_t gmx_qnt_key(uint32_t bits) { return (bits >> 31) ? ~bits : (bits ^ 0x80000000u); }
@@ -44,7 +44,6 @@ GMX_HD uint32_t gmx_qnt_bits(uint32_t key) { return (key >> 31) ? (key ^ 0x80000
 #define GMX_QNT_ONE (1ull << 32)       /* the level of probability 1 */
 
 #if defined(__HIPCC__)
-#include "gmx_moments.h"               /* gmx_backward.h (pick_load4, pick1_put_max, pick_group_offsets, mul64), mom_add */
 
 #define GMX_QNT_BLOCK 256
 static_assert(GMX_ROWS_QUANTILES_MAX_Q <= 64, "the thresholds of a row are computed by the first Q threads of its group");
@@ -163,16 +162,8 @@ k_rows_quantiles_small(const float* __restrict__ lw, const float* __restrict__ c
   pick_load4(lw + r * ld, base, n, a);
   if (carry != nullptr) pick_load4(carry + r * ld, base, n, cy);       // (every load below is out before the first wait)
   pick_load4(xrow, base, n, xn);
-  if (carry != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a[c] = mom_add(a[c], cy[c]);
-  }
   // ---- the row's fixed-point weights, parked by column; its thresholds ----
-  pick1_put_max(a, s_max, lane, wave);
-  __syncthreads();
-  float M = s_max[grp * W];
-#pragma unroll
-  for (int w = 1; w < W; ++w) M = gmx_rmax(M, s_max[grp * W + w]);
+  const float M = mom_row_max<W>(a, cy, carry != nullptr, s_max, grp, lane, wave);
   uint64_t* qrow = s_q + grp * (GT * 4);
   {
     uint64_t q[4];
@@ -264,11 +255,7 @@ extern "C" __attribute__((used)) inline int gmx_rows_quantiles(const float* lw_d
   std::vector<uint64_t> q((size_t)n), word((size_t)n), T((size_t)Q);
   uint32_t* out = reinterpret_cast<uint32_t*>(out_d);
   for (int64_t r = 0; r < rows; ++r) {
-    float M = -gmx_inf();
-    for (int64_t i = 0; i < n; ++i) {
-      a[(size_t)i] = carry_d ? lw_d[r * ld + i] + carry_d[r * ld + i] : lw_d[r * ld + i];
-      M = gmx_rmax(M, a[(size_t)i]);
-    }
+    const float M = gmx_mom_row_(lw_d + r * ld, carry_d ? carry_d + r * ld : nullptr, n, a.data());
     const float ref = gmx_tile_ref(gmx_tile_exp(M));             // one tile: the row's reference is the tile's
     uint64_t total = 0;
     for (int64_t i = 0; i < n; ++i) total += q[(size_t)i] = gmx_exp_fixed(a[(size_t)i] - ref, shift);

@@ -41,7 +41,7 @@ import torch
 from .. import _lib
 from ..core.choice_map import ChoiceMap
 from ..random import Key, lazy_split, split
-from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _StateStore, _Sweep, _key_words, cdf_shift, evidence_terms
+from .smc import MULTINOMIAL_SORTED, STRATIFIED, SYSTEMATIC, _StateStore, _Sweep, _key_words, _workspace, cdf_shift, evidence_terms
 
 
 def systematic_slot_bounds(offsets, total: int, n_total: int, u0: int):
@@ -135,7 +135,7 @@ class _ShardRouter:
         if form == "cdf":
             self.cdf = zeros((self.n,), torch.int64)
             self.total_d = zeros((1,), torch.int64)
-            self.ws = zeros(((be.c.gmx_weight_cdf_workspace(self.n) + 7) // 8,), torch.int64)
+            self.ws = _workspace(be.c.gmx_weight_cdf_workspace(self.n), dev, zero=True)
             if kind == MULTINOMIAL_SORTED:      # every rank draws the SAME table of the N global slots from the step's key
                 self.sorted_tab = zeros((int(be.c.gmx_sorted_uniforms_words(self.n * W)),), torch.int32)
             return

@@ -516,6 +516,11 @@ def _key_words(key: Key):
     return (c_uint32 * 2)(int(kh[0]), int(kh[1]))
 
 
+def _workspace(nbytes, device, zero=False):
+    """a kernel workspace of what a gmx_*_workspace query answered (bytes), as whole int64 words"""
+    return (torch.zeros if zero else torch.empty)(((int(nbytes) + 7) // 8,), dtype=torch.int64, device=device)
+
+
 def weight_cdf(lw: torch.Tensor, n_total=None, max_partials=None):
     """gmx_weight_cdf: returns (cdf int64-bits [n], total [1], max [1], shift)."""
     be = _lib.get()
@@ -528,7 +533,7 @@ def weight_cdf(lw: torch.Tensor, n_total=None, max_partials=None):
     cdf = torch.empty((n,), dtype=torch.int64, device=lw.device)
     total = torch.empty((1,), dtype=torch.int64, device=lw.device)
     mx = torch.empty((1,), dtype=torch.float32, device=lw.device)
-    ws = torch.zeros(((be.c.gmx_weight_cdf_workspace(n) + 7) // 8,), dtype=torch.int64, device=lw.device)
+    ws = _workspace(be.c.gmx_weight_cdf_workspace(n), lw.device, zero=True)
     partials, rows = None, 0
     if max_partials is None:
         # max via the deterministic LSE kernel's max output
@@ -753,8 +758,7 @@ def _rows_buffers(be, kind, lw, out, workspace):
         out = (torch.empty((R, n), dtype=torch.int32, device=lw.device), torch.empty((R,), dtype=torch.int64, device=lw.device),
                torch.empty((R,), dtype=torch.float32, device=lw.device), torch.zeros((1,), dtype=torch.int64, device=lw.device))
     if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_resample_rows_workspace(int(kind), R, n)) + 7) // 8,), dtype=torch.int64,
-                                device=lw.device)
+        workspace = _workspace(be.c.gmx_resample_rows_workspace(int(kind), R, n), lw.device)
     return out, workspace
 
 
@@ -826,6 +830,39 @@ def _component_major(x, R, n, who="row_moments"):
     return x3.float().permute(2, 0, 1).contiguous(), D, R * n, n, scalar
 
 
+def _row_inputs(who, lw, carry, x, need_x=True):
+    """what every row_* call checks of its weights, carry and state -> (R, n, ld, then what _component_major gives of x: the
+    tensor, D, x_ld, x_row_stride, scalar — None, 0, 0, 0, False without a state, where the caller can do without one)"""
+    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
+        raise ValueError(f"{who}: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
+    R, n = (int(v) for v in lw.shape)
+    ld = int(lw.stride(0)) if R > 1 else n
+    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
+        raise ValueError(f"{who}: carry is a float32 matrix of lw's shape and strides")
+    if x is None and need_x:
+        raise ValueError(f"{who}: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
+    return (R, n, ld) + ((None, 0, 0, 0, False) if x is None else _component_major(x, R, n, who))
+
+
+def _row_out(who, out, R, width, dtype, what, device):
+    """out= of a row_* call, a [R, >= width] matrix (`what`: the width in the docstring's letters), or a fresh one -> (out,
+    its row stride as the C call takes it)"""
+    if out is None:
+        out = torch.empty((R, width), dtype=dtype, device=device)
+    elif out.dtype != dtype or out.ndim != 2 or out.shape[0] != R or out.shape[1] < width or out.stride(1) != 1:
+        raise ValueError(f"{who}: out is a {str(dtype).split('.')[1]} [R, >= {what}] = [{R}, >= {width}] matrix with unit column stride")
+    return out, int(out.stride(0)) if R > 1 else width
+
+
+def _rows_launch(symbol, head, *tail):
+    """ONE gmx_rows_* summary call on the current stream — the road of the public row_* functions after their checks and of a
+    bank's steps.  head: (lw, carry, R, n, ld, x, D, x_ld, x_row_stride), the nine arguments the four entry points open with;
+    tail: the symbol's own, in the C order; a tensor (or None) goes as its pointer, everything else as an integer."""
+    be = _lib.get()
+    args = [be.ptr(a) if a is None or isinstance(a, torch.Tensor) else int(a) for a in head + tail]
+    be.check(getattr(be.c, symbol)(*args, be.stream()), symbol)
+
+
 def row_moments(lw: torch.Tensor, x=None, *, carry=None, out=None, workspace=None):
     """gmx_rows_moments: the effective sample size and the weighted mean and variance of every row, in one call.  lw [R, n]
     float32 log-weights (unit column stride); x: None, [R, n], [R, n, D] or a tuple of D [R, n] — the forms
@@ -834,20 +871,11 @@ def row_moments(lw: torch.Tensor, x=None, *, carry=None, out=None, workspace=Non
     otherwise, None without x.  A row without mass: ess 0, NaN mean and variance.  out ([R, >= 1 + 2 D] float64) and workspace:
     persistent buffers instead of fresh ones."""
     be = _lib.get()
-    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
-        raise ValueError(f"row_moments: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
-    R, n = (int(v) for v in lw.shape)
-    ld = int(lw.stride(0)) if R > 1 else n
-    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
-        raise ValueError("row_moments: carry is a float32 matrix of lw's shape and strides")
-    xt, D, x_ld, x_rs, scalar = (None, 0, 0, 0, False) if x is None else _component_major(x, R, n)
-    if out is None:
-        out = torch.empty((R, 1 + 2 * D), dtype=torch.float64, device=lw.device)
+    R, n, ld, xt, D, x_ld, x_rs, scalar = _row_inputs("row_moments", lw, carry, x, need_x=False)
+    out, out_ld = _row_out("row_moments", out, R, 1 + 2 * D, torch.float64, "1 + 2 D", lw.device)
     if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=lw.device)
-    be.check(be.c.gmx_rows_moments(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(out),
-                                   int(out.stride(0)) if R > 1 else 1 + 2 * D, be.ptr(workspace), be.stream()),
-             "gmx_rows_moments")
+        workspace = _workspace(be.c.gmx_rows_moments_workspace(R, n, D), lw.device)
+    _rows_launch("gmx_rows_moments", (lw, carry, R, n, ld, xt, D, x_ld, x_rs), out, out_ld, workspace)
     if x is None:
         return RowMoments(out[:, 0], None, None)
     mean, var = out[:, 1:1 + D], out[:, 1 + D:1 + 2 * D]
@@ -864,25 +892,12 @@ def row_covariance(lw: torch.Tensor, x, *, carry=None, out=None, workspace=None)
     [R, 1, 1].  cov[r] is symmetric bit for bit with a diagonal >= 0; a row without mass: NaN.  out ([R, >= D + D^2] float64)
     and workspace: persistent buffers instead of fresh ones."""
     be = _lib.get()
-    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
-        raise ValueError(f"row_covariance: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
-    R, n = (int(v) for v in lw.shape)
-    ld = int(lw.stride(0)) if R > 1 else n
-    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
-        raise ValueError("row_covariance: carry is a float32 matrix of lw's shape and strides")
-    if x is None:
-        raise ValueError("row_covariance: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
-    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_covariance")
+    R, n, ld, xt, D, x_ld, x_rs, scalar = _row_inputs("row_covariance", lw, carry, x)
     W = D + D * D
-    if out is None:
-        out = torch.empty((R, W), dtype=torch.float64, device=lw.device)
-    elif out.dtype != torch.float64 or out.ndim != 2 or out.shape[0] != R or out.shape[1] < W or out.stride(1) != 1:
-        raise ValueError(f"row_covariance: out is a float64 [R, >= D + D^2] = [{R}, >= {W}] matrix with unit column stride")
+    out, out_ld = _row_out("row_covariance", out, R, W, torch.float64, "D + D^2", lw.device)
     if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_rows_covariance_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=lw.device)
-    be.check(be.c.gmx_rows_covariance(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(out),
-                                      int(out.stride(0)) if R > 1 else W, be.ptr(workspace), be.stream()),
-             "gmx_rows_covariance")
+        workspace = _workspace(be.c.gmx_rows_covariance_workspace(R, n, D), lw.device)
+    _rows_launch("gmx_rows_covariance", (lw, carry, R, n, ld, xt, D, x_ld, x_rs), out, out_ld, workspace)
     mean, cov = out[:, :D], out[:, D:W].unflatten(1, (D, D))
     return (mean[:, 0], cov) if scalar else (mean, cov)
 
@@ -909,15 +924,7 @@ def row_lag_moments(lw: torch.Tensor, x, ancestors, t: int, L: int, lags, rings,
     [>= lag_hi + 1, R, >= 2 D] buffer with lag l at out[l] — or, with out_lag_stride (in doubles, may be negative), any
     float64 tensor whose first element is lag 0's."""
     be = _lib.get()
-    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
-        raise ValueError(f"row_lag_moments: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
-    R, n = (int(v) for v in lw.shape)
-    ld = int(lw.stride(0)) if R > 1 else n
-    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
-        raise ValueError("row_lag_moments: carry is a float32 matrix of lw's shape and strides")
-    if x is None:
-        raise ValueError("row_lag_moments: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
-    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_lag_moments")
+    R, n, ld, xt, D, x_ld, x_rs, scalar = _row_inputs("row_lag_moments", lw, carry, x)
     if x_rs != n:                                                # the rings are [.., R * n]: rows n apart
         parts = list(x) if isinstance(x, (tuple, list)) else ([x] if x.ndim == 2 else list(x.unbind(2)))
         xt, x_ld, x_rs = torch.stack([v.float() for v in parts]).contiguous(), R * n, n
@@ -935,11 +942,9 @@ def row_lag_moments(lw: torch.Tensor, x, ancestors, t: int, L: int, lags, rings,
         raise ValueError(f"row_lag_moments: out is a float64 [>= lag_hi + 1, R, >= 2 D] = [>= {hi + 1}, {R}, >= {2 * D}] buffer")
     out_ld = int(out.stride(1)) if out_lag_stride is None and R > 1 else 2 * D
     if workspace is None:
-        workspace = torch.empty(((int(be.c.gmx_rows_lag_moments_workspace(R, n, D, L)) + 7) // 8,), dtype=torch.int64, device=lw.device)
-    be.check(be.c.gmx_rows_lag_moments(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(ancestors), n,
-                                       int(index_stride), int(t), int(L), lo, hi, be.ptr(hist_x), R * n, be.ptr(hist_a), n,
-                                       be.ptr(out), out_ld, int(out.stride(0)) if out_lag_stride is None else int(out_lag_stride),
-                                       be.ptr(workspace), be.stream()), "gmx_rows_lag_moments")
+        workspace = _workspace(be.c.gmx_rows_lag_moments_workspace(R, n, D, L), lw.device)
+    _rows_launch("gmx_rows_lag_moments", (lw, carry, R, n, ld, xt, D, x_ld, x_rs), ancestors, n, index_stride, t, L, lo, hi,
+                 hist_x, R * n, hist_a, n, out, out_ld, out.stride(0) if out_lag_stride is None else out_lag_stride, workspace)
     if lags is None or out_lag_stride is not None:
         return None
     mean, var = out[:hi + 1, :, :D], out[:hi + 1, :, D:2 * D]
@@ -969,24 +974,11 @@ def row_quantiles(lw: torch.Tensor, x, levels, *, carry=None, out=None):
     which the sorted exact-integer weights of the row reach the level (level 0: the smallest value that carries weight,
     level 1: the largest) — one of the row's own values, bit for bit.  A row without mass: NaN.  out ([R, >= D * Q] float32):
     a persistent buffer instead of a fresh one."""
-    be = _lib.get()
-    if lw.ndim != 2 or lw.dtype != torch.float32 or (lw.shape[1] > 1 and lw.stride(1) != 1):
-        raise ValueError(f"row_quantiles: lw is a float32 [R, n] matrix with unit column stride; got {tuple(lw.shape)} {lw.dtype}")
-    R, n = (int(v) for v in lw.shape)
-    ld = int(lw.stride(0)) if R > 1 else n
-    if carry is not None and (carry.dtype != torch.float32 or tuple(carry.shape) != (R, n) or carry.stride() != lw.stride()):
-        raise ValueError("row_quantiles: carry is a float32 matrix of lw's shape and strides")
+    R, n, ld, xt, D, x_ld, x_rs, scalar = _row_inputs("row_quantiles", lw, carry, x)
     table = _quantile_levels(levels, "row_quantiles: levels")[1].to(lw.device)
     Q = int(table.numel())
-    if x is None:
-        raise ValueError("row_quantiles: x is [R, n], [R, n, D] or a tuple of [R, n]; got None")
-    xt, D, x_ld, x_rs, scalar = _component_major(x, R, n, "row_quantiles")
-    if out is None:
-        out = torch.empty((R, D * Q), dtype=torch.float32, device=lw.device)
-    elif out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != R or out.shape[1] < D * Q or out.stride(1) != 1:
-        raise ValueError(f"row_quantiles: out is a float32 [R, >= D * Q] = [{R}, >= {D * Q}] matrix with unit column stride")
-    be.check(be.c.gmx_rows_quantiles(be.ptr(lw), be.ptr(carry), R, n, ld, be.ptr(xt), D, int(x_ld), int(x_rs), be.ptr(table), Q,
-                                     be.ptr(out), int(out.stride(0)) if R > 1 else D * Q, be.stream()), "gmx_rows_quantiles")
+    out, out_ld = _row_out("row_quantiles", out, R, D * Q, torch.float32, "D * Q", lw.device)
+    _rows_launch("gmx_rows_quantiles", (lw, carry, R, n, ld, xt, D, x_ld, x_rs), table, Q, out, out_ld)
     res = out[:, :D * Q].unflatten(1, (D, Q))
     return res[:, 0] if scalar else res
 
@@ -1776,7 +1768,7 @@ class SweepHistory:
             extra = self._step_extra or (lambda t: ())
             R = max(1, min(BACKWARD_ROWS_MAX, m, BACKWARD_CHUNK_BYTES // (4 * n), 40 // D))
             logits = torch.empty((R, n), dtype=torch.float32, device=dev)
-            ws = torch.empty(((be.c.gmx_pick_rows_workspace(R, n) + 7) // 8,), dtype=torch.int64, device=dev)
+            ws = _workspace(be.c.gmx_pick_rows_workspace(R, n), dev)
             for t in range(T_ - 2, -1, -1):
                 keys = split(fold_in(key, t), m).data()
                 x_t = self._state_view(self._xs[t:t + 1], 0)
@@ -2213,6 +2205,71 @@ class BootstrapSweep(_Sweep):
         return self.store.view((self.T - 1) % 2), self.lw_pp[(self.T - 1) % 2 if self.fuse else 0], self.anc
 
 
+def _refuse_wide_covariance(b, D, dev):
+    if D > ROWS_COV_D_MAX:
+        raise NotImplementedError(f"BootstrapBank(covariance=True): a state of D = {D} > {ROWS_COV_D_MAX} components "
+                                  "(gmx_rows_covariance holds (1, x) in one 16 x 16 matrix tile)")
+
+
+def _quantile_table(b, D, dev):
+    b.q_table = b.q_levels.to(dev)                       # the levels where the kernel reads them: nothing from the host
+
+
+def _smooth_rings(b, D, dev):
+    b.lag_rings = lag_rings(b.R, b.n, D, b.smooth_lag, dev)                    # the last L + 1 state slabs and ancestor tables
+
+
+def _smooth_tail(b, t):
+    """step t into the rings, and the smoothed mean and variance of time t - L from step t's weights — at the last step of
+    times T - 1 - min(L, T - 1) .. T - 1: lag l lands in row t - l of the table (the negative lag stride)"""
+    R, n, T, L = b.R, b.n, b.T, b.smooth_lag
+    lo, hi = (0, min(L, T - 1)) if t == T - 1 else ((L, L) if t >= L else (0, -1))
+    hist_x, hist_a = b.lag_rings
+    return (b.anc if t > 0 else None, n, n, t, L, lo, hi, hist_x, R * n, hist_a, n, b.smo[t], b.smo.shape[2], -b.smo.stride(0),
+            b.smo_ws)
+
+
+# BootstrapBank's per-step summaries, in LAUNCH ORDER (the order is behaviour): one gmx_rows_* call each between the site
+# program and the row resampler, on the weights the resampler is about to act on (with ess_threshold=: lw + carry) and the
+# state the step program has just written.
+#   kw           the constructor's keyword and the bank's attribute of that name; on(value): was it given
+#   spelled      the keyword as the refusals write it
+#   symbol       the C entry point; tail(bank, t): step t's arguments after the nine every gmx_rows_* call opens with
+#   table        the bank's attribute of its [T, R, *shape(D, bank)] device table of `dtype`, zeroed by prepare()
+#   ws           the bank's attribute of its workspace, <symbol>_workspace(R, n, D, *ws_args(bank)) bytes (None: it has none)
+#   setup        (bank, D, device) at prepare(): a refusal that needs D, or what else the keyword owns
+#   missing      what its readers raise on a bank built without it
+#   conditional  why ConditionalBank refuses it
+_Summary = namedtuple("_Summary", ["kw", "on", "spelled", "table", "shape", "dtype", "symbol", "tail", "missing", "conditional",
+                                   "ws", "ws_args", "setup"], defaults=(None, lambda b: (), None))
+_PINNED = "the weights before the pinned resampler are not the conditional system's"
+_SUMMARIES = (
+    _Summary(kw="moments", on=bool, spelled="moments=True", symbol="gmx_rows_moments",
+             table="mom", shape=lambda D, b: (1 + 2 * D,), dtype=torch.float64,          # ESS, D means, D variances
+             ws="mom_ws", tail=lambda b, t: (b.mom[t], b.mom.shape[2], b.mom_ws),
+             missing="no moments were recorded (build the bank with moments=True)",
+             conditional="the pin is written inside the pinned resampler: " + _PINNED),
+    _Summary(kw="covariance", on=bool, spelled="covariance=True", symbol="gmx_rows_covariance",
+             table="cov", shape=lambda D, b: (D + D * D,), dtype=torch.float64,          # D means, D x D covariances
+             ws="cov_ws", tail=lambda b, t: (b.cov[t], b.cov.shape[2], b.cov_ws),
+             setup=_refuse_wide_covariance,
+             missing="no covariance was recorded (build the bank with covariance=True)",
+             conditional="as moments=True: " + _PINNED),
+    _Summary(kw="quantiles", on=lambda v: v is not None, spelled="quantiles=", symbol="gmx_rows_quantiles",
+             table="qnt", shape=lambda D, b: (D, len(b.quantiles)), dtype=torch.float32,
+             tail=lambda b, t: (b.q_table, b.qnt.shape[3], b.qnt[t], b.qnt.shape[2] * b.qnt.shape[3]),
+             setup=_quantile_table,
+             missing="no quantiles were recorded (build the bank with quantiles=(p, ...))",
+             conditional="as moments=True: " + _PINNED),
+    _Summary(kw="smooth_lag", on=lambda v: v is not None, spelled="smooth_lag=", symbol="gmx_rows_lag_moments",
+             table="smo", shape=lambda D, b: (2 * D,), dtype=torch.float64,              # per TIME and row: D means, D variances
+             ws="smo_ws", ws_args=lambda b: (b.smooth_lag,), tail=_smooth_tail,
+             setup=_smooth_rings,
+             missing="nothing smoothed was recorded (build the bank with smooth_lag=L)",
+             conditional="as moments=True: " + _PINNED + " — and every step is recorded here: draw(backward=True) smooths"),
+)
+
+
 class BootstrapBank(_Sweep):
     """R independent bootstrap particle filters of n particles each as ONE chain of launches (the reference's
     `jax.vmap(smc_run)(keys)`: replicate keys for the variance of the evidence estimate, a grid or a chain over model
@@ -2318,6 +2375,7 @@ class BootstrapBank(_Sweep):
             if self.n > ROWS_QUANTILES_N_MAX:
                 raise NotImplementedError(f"BootstrapBank(quantiles=): n_particles = {self.n} > {ROWS_QUANTILES_N_MAX} "
                                           "(gmx_rows_quantiles sorts a row of one tile)")
+        self.summaries = tuple(s for s in _SUMMARIES if s.on(getattr(self, s.kw)))
         self.ess_threshold, self.ess_q8 = None, None
         if ess_threshold is not None:
             tau = float(ess_threshold)
@@ -2368,7 +2426,7 @@ class BootstrapBank(_Sweep):
         self.totals = torch.zeros((T, R), dtype=torch.int64, device=dev)
         self.status = torch.zeros((1,), dtype=torch.int64, device=dev)         # rows without mass, over the last sweep
         self.shift = cdf_shift(n)
-        self.ws = torch.zeros(((int(be.c.gmx_resample_rows_workspace(self.kind, R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
+        self.ws = _workspace(be.c.gmx_resample_rows_workspace(self.kind, R, n), dev, zero=True)
         if self.ess_q8 is not None:
             self.carry = torch.zeros((N,), dtype=torch.float32, device=dev)    # log-weights since the row's last resampling
             self.flags = torch.zeros((T, R), dtype=torch.int32, device=dev)    # was row r resampled after step t
@@ -2389,67 +2447,14 @@ class BootstrapBank(_Sweep):
             self.p_init.comp.specialize()
             self.p_step.comp.specialize()
         self.partials = torch.zeros((2, (N + 255) // 256), dtype=torch.float32, device=dev)
-        if self.moments:
-            D = self.store.D
-            self.mom = torch.zeros((T, R, 1 + 2 * D), dtype=torch.float64, device=dev)     # per step and row: ESS, D means, D variances
-            self.mom_ws = torch.zeros(((int(be.c.gmx_rows_moments_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
-        if self.covariance:
-            D = self.store.D
-            if D > ROWS_COV_D_MAX:
-                raise NotImplementedError(f"BootstrapBank(covariance=True): a state of D = {D} > {ROWS_COV_D_MAX} components "
-                                          "(gmx_rows_covariance holds (1, x) in one 16 x 16 matrix tile)")
-            self.cov = torch.zeros((T, R, D + D * D), dtype=torch.float64, device=dev)     # per step and row: D means, D x D covariances
-            self.cov_ws = torch.zeros(((int(be.c.gmx_rows_covariance_workspace(R, n, D)) + 7) // 8,), dtype=torch.int64, device=dev)
-        if self.smooth_lag is not None:
-            D, L = self.store.D, self.smooth_lag
-            self.lag_rings = lag_rings(R, n, D, L, dev)          # the last L + 1 state slabs and ancestor tables
-            self.smo = torch.zeros((T, R, 2 * D), dtype=torch.float64, device=dev)         # per time and row: D means, D variances
-            self.smo_ws = torch.zeros(((int(be.c.gmx_rows_lag_moments_workspace(R, n, D, L)) + 7) // 8,), dtype=torch.int64, device=dev)
-        if self.quantiles is not None:
-            self.q_table = self.q_levels.to(dev)                 # the levels where the kernel reads them: nothing from the host
-            self.qnt = torch.zeros((T, R, self.store.D, len(self.quantiles)), dtype=torch.float32, device=dev)
+        D = self.store.D
+        for s in self.summaries:
+            if s.setup is not None:
+                s.setup(self, D, dev)
+            setattr(self, s.table, torch.zeros((T, R) + s.shape(D, self), dtype=s.dtype, device=dev))
+            if s.ws is not None:
+                setattr(self, s.ws, _workspace(getattr(be.c, s.symbol + "_workspace")(R, n, D, *s.ws_args(self)), dev, zero=True))
         return self
-
-    def _quantiles(self, t):
-        """step t's weighted quantiles of every row and state component, from the weights and the state _moments reads
-        (gmx_rows_quantiles)"""
-        be = _lib.get()
-        R, n = self.R, self.n
-        x = self.store.rows[t % 2]
-        D, Q = int(self.qnt.shape[2]), int(self.qnt.shape[3])
-        be.check(be.c.gmx_rows_quantiles(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
-                                         be.ptr(x), D, int(x.shape[1]), n, be.ptr(self.q_table), Q, be.ptr(self.qnt[t]), D * Q,
-                                         be.stream()), "gmx_rows_quantiles")
-
-    def _moments(self, t):
-        """step t's ESS, filtering mean and variance of every row, from the weights the resampler is about to act on (with
-        ess_threshold=: lw + carry) and the state the step program has just written (gmx_rows_moments)"""
-        be = _lib.get()
-        R, n = self.R, self.n
-        x = self.store.rows[t % 2]
-        be.check(be.c.gmx_rows_moments(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
-                                       be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.mom[t]), int(self.mom.shape[2]),
-                                       be.ptr(self.mom_ws), be.stream()), "gmx_rows_moments")
-
-    def _covariance(self, t):
-        """step t's filtering mean and full covariance matrix of every row, from the weights and the state _moments reads
-        (gmx_rows_covariance)"""
-        be = _lib.get()
-        R, n = self.R, self.n
-        x = self.store.rows[t % 2]
-        be.check(be.c.gmx_rows_covariance(be.ptr(self.lw), be.ptr(self.carry) if self.ess_q8 is not None else None, R, n, n,
-                                          be.ptr(x), self.store.D, int(x.shape[1]), n, be.ptr(self.cov[t]), int(self.cov.shape[2]),
-                                          be.ptr(self.cov_ws), be.stream()), "gmx_rows_covariance")
-
-    def _smooth(self, t):
-        """step t into the rings, and the smoothed mean and variance of time t - L from step t's weights — at the last step
-        of times T - 1 - min(L, T - 1) .. T - 1 (gmx_rows_lag_moments; lag l lands in row t - l of the table)"""
-        T, L = self.T, self.smooth_lag
-        lags = (0, min(L, T - 1)) if t == T - 1 else ((L, L) if t >= L else None)
-        x = tuple(row.reshape(self.R, self.n) for row in self.store.rows[t % 2])
-        row_lag_moments(self.lw.reshape(self.R, self.n), x, self.anc if t > 0 else None, t, L, lags,
-                        self.lag_rings, carry=self.carry.reshape(self.R, self.n) if self.ess_q8 is not None else None,
-                        index_stride=self.n, out=self.smo[t], out_lag_stride=-int(self.smo.stride(0)), workspace=self.smo_ws)
 
     def _resample(self, t):
         if self.ess_q8 is not None:
@@ -2471,7 +2476,8 @@ class BootstrapBank(_Sweep):
         ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with covariance=True:
         gmx_rows_covariance, with quantiles=: gmx_rows_quantiles, with smooth_lag=: gmx_rows_lag_moments there too) — no syncs,
         no allocations, no host read of a device value"""
-        N = self.R * self.n
+        R, n = self.R, self.n
+        N = R * n
         self.status.zero_()
         if self.ess_q8 is not None:
             self.carry.zero_()
@@ -2479,71 +2485,65 @@ class BootstrapBank(_Sweep):
             _mh, prog, leaves, key, bufs = self._programs(t)
             bufs[prog.wo[1]] = self.lw.reshape(1, N)
             prog.comp.run(leaves, (N,), key, red_out=self.partials, out_buffers=bufs)
-            if self.moments:
-                self._moments(t)
-            if self.covariance:
-                self._covariance(t)
-            if self.quantiles is not None:
-                self._quantiles(t)
-            if self.smooth_lag is not None:
-                self._smooth(t)
+            x = self.store.rows[t % 2]       # the summaries: the weights the resampler is about to act on, the state just written
+            head = (self.lw, self.carry if self.ess_q8 is not None else None, R, n, n, x, self.store.D, x.shape[1], n)
+            for s in self.summaries:
+                _rows_launch(s.symbol, head, *s.tail(self, t))
             self._resample(t)
 
-    def _recorded_moments(self, who, lo, hi):
-        if not self.moments:
-            raise ValueError(f"BootstrapBank.{who}: no moments were recorded (build the bank with moments=True)")
-        out = self.mom[:, :, lo:hi].cpu()
+    def _recorded(self, keyword, who):
+        """(the device table of a summary, D), or the refusal of a bank built without the keyword"""
+        s = next(s for s in _SUMMARIES if s.kw == keyword)
+        if s not in self.summaries:
+            raise ValueError(f"BootstrapBank.{who}: {s.missing}")
+        return getattr(self, s.table), self.store.D
+
+    @staticmethod
+    def _columns(table, lo, hi):
+        """columns lo .. hi - 1 of every [T, R] row, on the host; a single column without its axis"""
+        out = table[:, :, lo:hi].cpu()
         return out[:, :, 0] if hi - lo == 1 else out
 
     def filter_mean(self) -> torch.Tensor:
         """float64 [T, R] ([T, R, D] for a state of D > 1 components), on the host: E[x_t | y_1..t] of filter r, the weighted
         mean of step t's particles before its resampling (moments=True only; synchronises)"""
-        D = self.store.D if self.moments else 1
-        return self._recorded_moments("filter_mean", 1, 1 + D)
+        mom, D = self._recorded("moments", "filter_mean")
+        return self._columns(mom, 1, 1 + D)
 
     def filter_var(self) -> torch.Tensor:
         """filter_mean()'s shapes: the weighted variance of step t's particles, per component (moments=True only; synchronises)"""
-        D = self.store.D if self.moments else 1
-        return self._recorded_moments("filter_var", 1 + D, 1 + 2 * D)
+        mom, D = self._recorded("moments", "filter_var")
+        return self._columns(mom, 1 + D, 1 + 2 * D)
 
     def ess(self) -> torch.Tensor:
         """float64 [T, R], on the host: the effective sample size (sum w)^2 / sum w^2 of filter r's weights at step t, before
         its resampling — with ess_threshold=, of the accumulated weights the decision is taken on (moments=True only;
         synchronises)"""
-        return self._recorded_moments("ess", 0, 1)
+        return self._columns(self._recorded("moments", "ess")[0], 0, 1)
 
     def filter_cov(self) -> torch.Tensor:
         """float64 [T, R, D, D], on the host: Cov[x_t | y_1..t] of filter r, the weighted covariance matrix of step t's particles
         before its resampling, symmetric bit for bit (covariance=True only; synchronises).  The means recorded beside it are
         self.cov[:, :, :D], filter_mean()'s values up to the order of the float64 sums."""
-        if not self.covariance:
-            raise ValueError("BootstrapBank.filter_cov: no covariance was recorded (build the bank with covariance=True)")
-        D = self.store.D
-        return self.cov[:, :, D:].cpu().unflatten(2, (D, D))
-
-    def _smoothed(self, who, lo):
-        if self.smooth_lag is None:
-            raise ValueError(f"BootstrapBank.{who}: nothing smoothed was recorded (build the bank with smooth_lag=L)")
-        D = self.store.D
-        out = self.smo[:, :, lo * D:(lo + 1) * D].cpu()
-        return out[:, :, 0] if D == 1 else out
+        cov, D = self._recorded("covariance", "filter_cov")
+        return cov[:, :, D:].cpu().unflatten(2, (D, D))
 
     def smoothed_mean(self) -> torch.Tensor:
         """float64 [T, R] ([T, R, D] for a state of D > 1 components), on the host: the fixed-lag smoothed mean
         E[x_s | y_1..min(s+L, T-1)] of filter r — row T - 1 is the filtering mean of the last step (smooth_lag=L only;
         synchronises)"""
-        return self._smoothed("smoothed_mean", 0)
+        smo, D = self._recorded("smooth_lag", "smoothed_mean")
+        return self._columns(smo, 0, D)
 
     def smoothed_var(self) -> torch.Tensor:
         """smoothed_mean()'s shapes: the fixed-lag smoothed variance, per component (smooth_lag=L only; synchronises)"""
-        return self._smoothed("smoothed_var", 1)
+        smo, D = self._recorded("smooth_lag", "smoothed_var")
+        return self._columns(smo, D, 2 * D)
 
     def filter_quantiles(self) -> torch.Tensor:
         """float32 [T, R, Q] ([T, R, D, Q] for a state of D > 1 components), on the host: the quantiles of x_t | y_1..t of filter
         r at the probabilities of quantiles=, from step t's particles before its resampling (quantiles= only; synchronises)"""
-        if self.quantiles is None:
-            raise ValueError("BootstrapBank.filter_quantiles: no quantiles were recorded (build the bank with quantiles=(p, ...))")
-        out = self.qnt.cpu()
+        out = self._recorded("quantiles", "filter_quantiles")[0].cpu()
         return out[:, :, 0] if out.shape[2] == 1 else out
 
     def log_ml(self) -> np.ndarray:
@@ -2659,20 +2659,10 @@ class ConditionalBank(BootstrapBank):
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
                  ess_threshold=None, moments=False, quantiles=None, covariance=False, smooth_lag=None):
-        if smooth_lag is not None:
-            raise NotImplementedError("ConditionalBank: smooth_lag= is not supported (as moments=True: the weights before the "
-                                      "pinned resampler are not the conditional system's — and every step is recorded here: "
-                                      "draw(backward=True) smooths; BootstrapBank takes it)")
-        if covariance:
-            raise NotImplementedError("ConditionalBank: covariance=True is not supported (as moments=True: the weights before "
-                                      "the pinned resampler are not the conditional system's; BootstrapBank takes it)")
-        if quantiles is not None:
-            raise NotImplementedError("ConditionalBank: quantiles= is not supported (as moments=True: the weights before the "
-                                      "pinned resampler are not the conditional system's; BootstrapBank takes it)")
-        if moments:
-            raise NotImplementedError("ConditionalBank: moments=True is not supported (the pin is written inside the pinned "
-                                      "resampler: the weights before it are not the conditional system's; BootstrapBank "
-                                      "takes it)")
+        given = dict(moments=moments, covariance=covariance, quantiles=quantiles, smooth_lag=smooth_lag)
+        for s in _SUMMARIES:
+            if s.on(given[s.kw]):
+                raise NotImplementedError(f"ConditionalBank: {s.spelled} is not supported ({s.conditional}; BootstrapBank takes it)")
         if ess_threshold is not None:
             raise NotImplementedError("ConditionalBank: ess_threshold= is not supported (the pinned slot and the recorded "
                                       "history assume a resampling after every step; BootstrapBank takes it)")
@@ -2704,7 +2694,7 @@ class ConditionalBank(BootstrapBank):
         self.hist_lws = torch.zeros((T, N), dtype=torch.float32, device=dev)
         self.hist_ancs = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.hist_status = torch.zeros((1,), dtype=torch.int64, device=dev)
-        self.pick_ws = torch.zeros(((int(be.c.gmx_pick_rows_workspace(R, n)) + 7) // 8,), dtype=torch.int64, device=dev)
+        self.pick_ws = _workspace(be.c.gmx_pick_rows_workspace(R, n), dev, zero=True)
         self._views = SweepHistory(self.hist_xs, self.hist_lws, self.hist_ancs, self.event, self.tuple_state)
         if self.ancestor_sampling:
             self._prepare_ancestors(keys)
@@ -2733,9 +2723,8 @@ class ConditionalBank(BootstrapBank):
         self.as_lw = torch.zeros((N,), dtype=torch.float32, device=dev)
         self.next_x = torch.zeros((D, N), dtype=torch.float32, device=dev)
         self.status = torch.zeros((2,), dtype=torch.int64, device=dev)       # rows without mass; rows without ancestor mass
-        self.ws = torch.zeros(((max(int(be.c.gmx_resample_rows_as_workspace(R, n)),
-                                    int(be.c.gmx_resample_rows_workspace(self.kind, R, n))) + 7) // 8,), dtype=torch.int64,
-                              device=dev)
+        self.ws = _workspace(max(int(be.c.gmx_resample_rows_as_workspace(R, n)),
+                                 int(be.c.gmx_resample_rows_workspace(self.kind, R, n))), dev, zero=True)
         if T > 1:
             self._ancestor_logits(0, launch=False)
 
@@ -2870,7 +2859,7 @@ class ConditionalBank(BootstrapBank):
                   logits=torch.zeros((R * n,), dtype=torch.float32, device=dev),
                   status=torch.zeros((T,), dtype=torch.int64, device=dev),
                   keys=torch.zeros((T, R, 2), dtype=torch.int32, device=dev),
-                  ws=torch.zeros(((int(be.c.gmx_pick_rows_take_workspace(R, n)) + 7) // 8,), dtype=torch.int64, device=dev))
+                  ws=_workspace(be.c.gmx_pick_rows_take_workspace(R, n), dev, zero=True))
         self._bw = bw
         return bw
 

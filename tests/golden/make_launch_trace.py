@@ -12,6 +12,9 @@ the commit it was exported from is named with --exported-from and goes into the 
 that only exist with streams, the state-layout and the bank cases: the GPU suite's time budget has no room for all).
 The mirror's "state/" and "bank/" cases are in a file of their own, made at a later parent than the rest:
   --only state/ bank/ --out tests/golden/launch_trace_cpu_state.json
+The "bank/summary/" cases of both backends likewise, at the parent of the commit that gave the bank one table of summaries
+(the cases were added to tests/launch_trace.py first, the library code still the parent's):
+  [--gpu] --only bank/summary/ --out tests/golden/launch_trace_{cpu,gpu}_summaries.json
 """
 import argparse
 import json

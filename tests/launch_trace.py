@@ -22,8 +22,11 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = {"cpu": os.path.join(HERE, "golden", "launch_trace_cpu.json"),
           "gpu": os.path.join(HERE, "golden", "launch_trace_gpu.json")}
-# (the "state/" and "bank/" cases of the mirror were recorded later, at another parent: a file of their own)
-LATER = {"cpu": [os.path.join(HERE, "golden", "launch_trace_cpu_state.json")], "gpu": []}
+# (the "state/" and "bank/" cases of the mirror were recorded later, at another parent: a file of their own; so were the
+#  "bank/summary/" cases of both backends, at the parent of the commit that gave the bank one table of summaries)
+LATER = {"cpu": [os.path.join(HERE, "golden", "launch_trace_cpu_state.json"),
+                 os.path.join(HERE, "golden", "launch_trace_cpu_summaries.json")],
+         "gpu": [os.path.join(HERE, "golden", "launch_trace_gpu_summaries.json")]}
 KINDS = ("systematic", "stratified", "multinomial", "multinomial_tiled", "multinomial_sorted")
 TILE_KINDS = ("systematic", "stratified", "multinomial_tiled", "multinomial_sorted")
 
@@ -237,6 +240,15 @@ def bank_cases():
             cases[f"bank/{kind}/n{n}"] = bank("lgssm", n, resample=kind)
     for model in ("vector", "tuple", "params"):
         cases[f"bank/systematic/{model}"] = bank(model, 1500)
+    # the per-step summaries between the site program and the row resampler: n = 200 is one launch each, n = 1500 the
+    # tiled forms (quantiles sorts a row of one tile: n = 200 only)
+    one = {"moments": dict(moments=True), "covariance": dict(covariance=True), "smooth_lag": dict(smooth_lag=2),
+           "quantiles": dict(quantiles=(0.1, 0.5, 0.9))}
+    for name, kw in one.items():
+        for n in (200, 1500) if name != "quantiles" else (200,):
+            cases[f"bank/summary/{name}/n{n}"] = bank("lgssm", n, **kw)
+    cases["bank/summary/all/ess/n200"] = bank("lgssm", 200, ess_threshold=0.5, **{k: v for kw in one.values() for k, v in kw.items()})
+    cases["bank/summary/vector/cov_lag/n1500"] = bank("vector", 1500, covariance=True, smooth_lag=2)
     return cases
 
 

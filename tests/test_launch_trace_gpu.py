@@ -2,7 +2,8 @@
 one-launch step and its chained MH form, captured sweeps, the one-launch single-GPU step, the chained MH program — and
 of the state-layout and BootstrapBank cases, on an MI355X, against the record made there at the parent of the commit
 that gave the sweeps one state store and one table of step programs (tests/golden/launch_trace_gpu.json, written by
-tests/golden/make_launch_trace.py --gpu): same calls, same order, same integers, same sharing of buffers."""
+tests/golden/make_launch_trace.py --gpu; the "bank/summary/" cases at the parent of the commit that gave BootstrapBank one
+table of summaries: launch_trace_gpu_summaries.json): same calls, same order, same integers, same sharing of buffers."""
 import pytest
 
 from tests import launch_trace as L
