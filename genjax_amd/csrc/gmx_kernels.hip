@@ -3808,6 +3808,56 @@ extern "C" int gmx_rows_lag_moments(const float* lw_d, const float* carry_d, int
 }
 
 // ---------------------------------------------------------------------------
+// lag-one smoothed pair moments (gmx_lag_pairs.h): after gmx_rows_lag_moments has recorded step t, the joint second moments
+// of (x_{t-l}, x_{t-l+1}) per row and lag from the rings, three Gram matrices on the float64 matrix instruction.  Its
+// refusal (gmx_sizes.h), the HIP build's alignment check, then for n <= 1024 ONE launch per range of lags whose tables and
+// accumulators fit the 64 KB of dynamic LDS a launch may ask for (a step's one lag, a flush up to lag 20: one launch) and
+// two launches past n = 1024.  An empty range launches nothing.
+// ---------------------------------------------------------------------------
+#include "gmx_lag_pairs.h"
+
+extern "C" size_t gmx_rows_lag_pairs_workspace(int64_t rows, int64_t n, int32_t D, int32_t L) {
+  return gmx_rows_pairs_bytes_(rows, n, D, L);
+}
+
+extern "C" int gmx_rows_lag_pairs(const float* lw_d, const float* carry_d, int64_t rows, int64_t n, int64_t ld, const float* x_d,
+                                  int32_t D, int64_t x_ld, int64_t x_row_stride, int64_t index_stride, int64_t t, int32_t L,
+                                  int32_t lag_lo, int32_t lag_hi, const float* hist_x_d, int64_t hist_x_ld,
+                                  const int32_t* hist_a_d, int64_t hist_a_ld, double* out_d, int64_t out_ld,
+                                  int64_t out_lag_stride, void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_rows_lag_pairs";
+  (void)x_d;
+  const gmx_refusal no = gmx_rows_lag_pairs_refusal_(!lw_d || !hist_x_d || !hist_a_d || !out_d || !workspace_d, rows, n, ld, D, x_ld,
+                                                     x_row_stride, index_stride, t, L, lag_lo, lag_hi, hist_x_ld, hist_a_ld, out_ld);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{lw_d, 3}, {carry_d, 3}, {hist_x_d, 3}, {hist_a_d, 3}, {out_d, 7}})) return 1;
+  if (rows == 0 || lag_lo > lag_hi) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= GMX_PICK_TILE) {                                      // nothing in the workspace
+    for (int32_t lo = lag_lo, hi; lo <= lag_hi; lo = hi + 1) {
+      hi = lo >= GMX_PAIRS_RANGE_MAX ? lo : (lag_hi < GMX_PAIRS_RANGE_MAX ? lag_hi : GMX_PAIRS_RANGE_MAX);
+      rows_for_packing_(rows, n, [&](auto w, dim3 grid) {
+        hipLaunchKernelGGL((k_rows_pairs_small<decltype(w)::value>), grid, dim3(GMX_PAIRS_BLOCK), gmx_rows_pairs_lds_(lo, hi), st,
+                           lw_d, carry_d, rows, n, ld, D, x_row_stride, index_stride, t, L, lo, hi, hist_x_d, hist_x_ld, hist_a_d,
+                           hist_a_ld, out_d, out_ld, out_lag_stride, gmx_rows_pairs_acc_off_(lo, hi));
+      });
+    }
+  } else {
+    const int64_t tiles = gmx_tiles_(n);
+    const gmx_moments_ws w = gmx_rows_pairs_carve_(workspace_d, rows, n, L);
+    rows_for_chunks_(rows, [&](int64_t row0, unsigned cnt) {
+      hipLaunchKernelGGL(k_rows_pairs_part, dim3((unsigned)tiles, cnt), dim3(GMX_PAIRS_BLOCK), 0, st, lw_d, carry_d, rows, n, ld,
+                         tiles, row0, D, x_row_stride, index_stride, t, L, lag_lo, lag_hi, hist_x_d, hist_x_ld, hist_a_d,
+                         hist_a_ld, w.rec, w.tmax);
+    });
+    hipLaunchKernelGGL(k_rows_pairs_finish, dim3((unsigned)rows), dim3(GMX_PAIRS_BLOCK), 0, st, (const double*)w.rec,
+                       (const float*)w.tmax, tiles, D, lag_lo, lag_hi, out_d, out_ld, out_lag_stride);
+  }
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // row-wise weighted quantiles (gmx_quantiles.h): per row, component and level the state word at which the sorted
 // fixed-point weights cross the level.  Its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
 // ---------------------------------------------------------------------------

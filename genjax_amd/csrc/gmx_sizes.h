@@ -379,6 +379,54 @@ static inline gmx_refusal gmx_rows_lag_moments_refusal_(bool has_null, int64_t r
   return {nullptr, 0};
 }
 
+// ---- lag-one smoothed pair moments: gmx_rows_lag_pairs (gmx_lag_pairs.h) ----
+#define GMX_PAIRS_REC (2 * GMX_COV_REC + 256)    /* per (row, tile, lag): the triangles of Guu and Gvv, all of Guv */
+#define GMX_PAIRS_ACC_BYTES 24576      /* a workgroup's accumulators in LDS: 4 waves x 3 tiles x 256 doubles */
+#define GMX_PAIRS_RANGE_MAX 20         /* lag_hi of a one-tile launch of SEVERAL lags: 2 KB (lag_hi - 1) + 24 KB within 64 KB */
+// Its workspace past one tile, sized for the L lags of a flush: rec f64 [rows * tiles, L, 528] (a tile's Gram matrices
+// relative to the tile's own maximum) | tmax f32 [rows * tiles], rounded up to 16 bytes; nothing for n <= 1024 (one launch)
+static inline size_t gmx_rows_pairs_bytes_(int64_t rows, int64_t n, int32_t D, int32_t L) {
+  if (rows < 1 || n <= GMX_TILE || n > GMX_ROWS_MAX_N || D < 1 || D > GMX_COV_MAX_D || L < 1 || L > GMX_ROWS_LAG_MAX) return 16;
+  return (size_t)((gmx_rows_cells_(rows, n) * ((uint64_t)L * GMX_PAIRS_REC * 8u + 4u) + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_moments_ws gmx_rows_pairs_carve_(void* workspace, int64_t rows, int64_t n, int32_t L) {
+  gmx_moments_ws w;
+  w.rec = (double*)workspace;
+  w.tmax = (float*)(w.rec + gmx_rows_cells_(rows, n) * (uint64_t)L * GMX_PAIRS_REC);
+  return w;
+}
+// The dynamic LDS of a one-tile launch of lags .. lag_hi and where its accumulators start: ONE lag's reuse the tables' space
+// (dead after the last hop), a range's lie behind the tables
+static inline unsigned gmx_rows_pairs_acc_off_(int32_t lag_lo, int32_t lag_hi) {
+  return lag_lo == lag_hi ? 0u : (unsigned)(lag_hi - 1) * 2u * GMX_TILE;
+}
+static inline unsigned gmx_rows_pairs_lds_(int32_t lag_lo, int32_t lag_hi) {
+  const unsigned tables = (unsigned)(lag_hi - 1) * 2u * GMX_TILE, acc = gmx_rows_pairs_acc_off_(lag_lo, lag_hi) + GMX_PAIRS_ACC_BYTES;
+  return tables > acc ? tables : acc;
+}
+// gmx_rows_covariance's D and gmx_rows_lag_moments' shapes, rings, step and lags — but a pair starts at lag 1, the empty
+// range is any lag_lo > lag_hi, and nothing but the rings is read of the state
+static inline gmx_refusal gmx_rows_lag_pairs_refusal_(bool has_null, int64_t rows, int64_t n, int64_t ld, int32_t D, int64_t x_ld,
+                                                      int64_t x_row_stride, int64_t index_stride, int64_t t, int32_t L,
+                                                      int32_t lag_lo, int32_t lag_hi, int64_t hist_x_ld, int64_t hist_a_ld,
+                                                      int64_t out_ld) {
+  if (has_null) return {"%s: null argument", 0};
+  if (D < 1 || D > GMX_COV_MAX_D)
+    return {"%s: D = %lld is outside [1, 15] (past 15 the Gram matrix of (1, x) leaves one 16 x 16 MFMA tile)", (long long)D};
+  gmx_refusal no = gmx_rows_moments_refusal_(false, rows, n, ld, D, x_ld, x_row_stride, 1 + 2 * (int64_t)D, false);
+  if (!no.fmt && rows > 0) no = gmx_index_stride_refusal_(rows, n, index_stride);
+  if (no.fmt) return no;
+  if (L < 1 || L > GMX_ROWS_LAG_MAX) return {"%s: L = %lld is outside [1, 32]", (long long)L};
+  if (t < 0) return {"%s: t = %lld is negative", (long long)t};
+  if (lag_lo < 1) return {"%s: lag_lo = %lld is below 1 (a pair is (t - l, t - l + 1); the empty range is lag_lo > lag_hi)", (long long)lag_lo};
+  if (lag_hi > L || lag_hi > t) return {"%s: lag_hi = %lld is above min(L, t)", (long long)lag_hi};
+  if (hist_a_ld < n) return {"%s: hist_a_ld = %lld is smaller than n", (long long)hist_a_ld};
+  if (gmx_resample_rows_pin_refusal_(rows, n, D, hist_x_ld, x_row_stride).fmt)
+    return {"%s: hist_x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)hist_x_ld};
+  if (out_ld < 2 * (int64_t)D + 3 * (int64_t)D * D) return {"%s: out_ld = %lld is smaller than 2 D + 3 D^2", (long long)out_ld};
+  return {nullptr, 0};
+}
+
 // ---- row-wise weighted quantiles: gmx_rows_quantiles (gmx_quantiles.h) ----
 #define GMX_ROWS_QUANTILES_MAX_Q 16    /* levels per call: a row's thresholds are parked in LDS */
 // One tile only: past it a quantile needs the two-level block-floating-point weights and a selection across tiles.  rows as

@@ -951,6 +951,46 @@ def row_lag_moments(lw: torch.Tensor, x, ancestors, t: int, L: int, lags, rings,
     return (mean[:, :, 0], var[:, :, 0]) if scalar else (mean, var)
 
 
+RowLagPairs = namedtuple("RowLagPairs", ["mean_s", "mean_next", "cov_s", "cross", "cov_next"])
+
+
+def _pair_blocks(out, D):
+    """the five blocks of records of 2 D + 3 D^2 doubles (the last axis): two [.., D] means, three [.., D, D] matrices"""
+    DD = D * D
+    return RowLagPairs(out[..., :D], out[..., D:2 * D], *(out[..., 2 * D + k * DD:2 * D + (k + 1) * DD].unflatten(-1, (D, D))
+                                                          for k in range(3)))
+
+
+def row_lag_pairs(lw: torch.Tensor, t: int, L: int, lags, rings, *, carry=None, index_stride=0, out=None, workspace=None):
+    """gmx_rows_lag_pairs for ONE step t of a sweep, AFTER row_lag_moments has recorded step t into `rings` with the same lw,
+    carry and index_stride: for every lag l of lags = (lag_lo, lag_hi), 1 <= lag_lo, lag_hi <= min(L, t), the joint second
+    moments of the consecutive states (x_{t-l}, x_{t-l+1}) along the ancestry of step t's particles under step t's weights —
+    the smoothed pair moments given y_1..t that an EM step for a state-space model sums.  It reads the rings (at most 15
+    state components) and writes out only.  -> RowLagPairs(mean_s, mean_next [lag_hi + 1, R, D], cov_s, cross, cov_next
+    [lag_hi + 1, R, D, D]), float64 views of out on lw's device (rows below lag_lo are not written); cov_s and cov_next are
+    symmetric bit for bit with a diagonal >= 0, cross[j, k] = Cov(x_{t-l, j}, x_{t-l+1, k}) is neither; a row without mass:
+    NaN.  lag_lo > lag_hi launches nothing.  out: a float64 [>= lag_hi + 1, R, >= 2 D + 3 D^2] buffer with lag l at out[l]."""
+    be = _lib.get()
+    R, n, ld = _row_inputs("row_lag_pairs", lw, carry, None, need_x=False)[:3]
+    hist_x, hist_a = rings
+    D = int(hist_x.shape[1]) if hist_x.ndim == 3 else 0
+    if (tuple(hist_x.shape) != (L + 1, D, R * n) or hist_x.dtype != torch.float32 or not hist_x.is_contiguous() or
+            tuple(hist_a.shape) != (L + 1, R, n) or hist_a.dtype != torch.int32 or not hist_a.is_contiguous()):
+        raise ValueError(f"row_lag_pairs: rings are lag_rings(R, n, D, L) = float32 {(L + 1, D, R * n)}, int32 {(L + 1, R, n)}")
+    lo, hi = int(lags[0]), int(lags[1])
+    W = 2 * D + 3 * D * D
+    if out is None:
+        out = torch.full((max(hi, 0) + 1, R, W), math.nan, dtype=torch.float64, device=lw.device)
+    if out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] < hi + 1:
+        raise ValueError(f"row_lag_pairs: out is a float64 [>= lag_hi + 1, R, >= 2 D + 3 D^2] = [>= {hi + 1}, {R}, >= {W}] buffer")
+    out_ld = _row_out("row_lag_pairs", out[0], R, W, torch.float64, "2 D + 3 D^2", lw.device)[1]
+    if workspace is None:
+        workspace = _workspace(be.c.gmx_rows_lag_pairs_workspace(R, n, D, L), lw.device)
+    _rows_launch("gmx_rows_lag_pairs", (lw, carry, R, n, ld, None, D, R * n, n), index_stride, t, L, lo, hi, hist_x, R * n,
+                 hist_a, n, out, out_ld, out.stride(0), workspace)
+    return _pair_blocks(out[:max(hi, 0) + 1, :, :W], D)
+
+
 ROWS_QUANTILES_N_MAX = 1024      # gmx_rows_quantiles sorts a row of one tile
 ROWS_QUANTILES_Q_MAX = 16        # levels per call (GMX_ROWS_QUANTILES_MAX_Q)
 
@@ -2229,6 +2269,21 @@ def _smooth_tail(b, t):
             b.smo_ws)
 
 
+def _refuse_wide_pairs(b, D, dev):
+    if D > ROWS_COV_D_MAX:
+        raise NotImplementedError(f"BootstrapBank(smooth_pairs=True): a state of D = {D} > {ROWS_COV_D_MAX} components "
+                                  "(gmx_rows_lag_pairs holds (1, x) in one 16 x 16 matrix tile)")
+
+
+def _pairs_tail(b, t):
+    """the pair (t - L, t - L + 1) from step t's weights and the rings _smooth_tail's launch has just filled — at the last step
+    the pairs of the lags 1 .. min(L, T - 1): lag l lands in row t - l of the table (the negative lag stride)"""
+    R, n, T, L = b.R, b.n, b.T, b.smooth_lag
+    lo, hi = (1, min(L, T - 1)) if t == T - 1 else ((L, L) if t >= L else (1, 0))
+    hist_x, hist_a = b.lag_rings
+    return (n, t, L, lo, hi, hist_x, R * n, hist_a, n, b.smp[t], b.smp.shape[2], -b.smp.stride(0), b.smp_ws)
+
+
 # BootstrapBank's per-step summaries, in LAUNCH ORDER (the order is behaviour): one gmx_rows_* call each between the site
 # program and the row resampler, on the weights the resampler is about to act on (with ess_threshold=: lw + carry) and the
 # state the step program has just written.
@@ -2267,6 +2322,12 @@ _SUMMARIES = (
              setup=_smooth_rings,
              missing="nothing smoothed was recorded (build the bank with smooth_lag=L)",
              conditional="as moments=True: " + _PINNED + " — and every step is recorded here: draw(backward=True) smooths"),
+    _Summary(kw="smooth_pairs", on=bool, spelled="smooth_pairs=True", symbol="gmx_rows_lag_pairs",      # (reads smooth_lag's rings)
+             table="smp", shape=lambda D, b: (2 * D + 3 * D * D,), dtype=torch.float64,  # row s: the pair of times (s, s + 1)
+             ws="smp_ws", ws_args=lambda b: (b.smooth_lag,), tail=_pairs_tail,
+             setup=_refuse_wide_pairs,
+             missing="no smoothed pairs were recorded (build the bank with smooth_lag=L, smooth_pairs=True)",
+             conditional="as smooth_lag=: " + _PINNED),
 )
 
 
@@ -2335,12 +2396,22 @@ class BootstrapBank(_Sweep):
     mean and variance of x_{t-L} along them into row t - L of a [T, R, 2 D] float64 table; the last step writes lags
     0 .. min(L, T - 1), so every time step is written exactly once.  No host read, still one graph.  smoothed_mean() and
     smoothed_var() read it after a sweep.  The weights are the ones moments=True sees at step min(s + L, T - 1), and with
-    ess_threshold= the identity ancestors of a row that was not resampled make the walk pass straight through it."""
+    ess_threshold= the identity ancestors of a row that was not resampled make the walk pass straight through it.
+
+    smooth_lag=L, smooth_pairs=True (False: nothing more is allocated or launched): the smoothed JOINT second moments of
+    consecutive states, E[x_s x_s^T], E[x_{s+1} x_{s+1}^T] and the lag-one cross moment E[x_s x_{s+1}^T] given
+    y_1..min(s+L, T-1) as means and (cross-)covariances — the sufficient statistics an EM or gradient step for the model's
+    parameters sums (Olsson, Cappe, Douc & Moulines 2008), for an LGSSM what the RTS smoother gives as P_{s|T} and
+    P_{s,s+1|T} — for a state of at most 15 components and T >= 2.  From step L on ONE more launch (gmx_rows_lag_pairs; two
+    past n = 1024) right after smooth_lag's reads the rings that launch has just filled, walks as it walks, gathers both
+    states of the pair (t - L, t - L + 1) along the walk and forms their three Gram matrices on the float64 matrix
+    instruction; the last step writes the pairs of lags 1 .. min(L, T - 1).  Row s of the [T, R, 2 D + 3 D^2] float64 table
+    holds the pair (s, s + 1); row T - 1 is never written.  smoothed_pairs() and smoothed_cov() read it after a sweep."""
 
     def __init__(self, init, step, n_particles: int, n_filters: int, T: int, obs_addr="y", resample="systematic",
                  step_extra=None, params=None, specialize=True, state_addr="x", rejuvenate=None, history=False,
                  noise_ahead=None, fuse_resample=None, comm=None, ess_threshold=None, moments=False, quantiles=None,
-                 covariance=False, smooth_lag=None):
+                 covariance=False, smooth_lag=None, smooth_pairs=False):
         for name, given in (("rejuvenate=", rejuvenate is not None), ("history=", bool(history)),
                             ("noise_ahead= (the background noise stream)", bool(noise_ahead)),
                             ("fuse_resample= (the one-launch fused step)", bool(fuse_resample)),
@@ -2369,6 +2440,11 @@ class BootstrapBank(_Sweep):
             if self.smooth_lag != smooth_lag or not 1 <= self.smooth_lag <= ROWS_LAG_MAX:
                 raise ValueError(f"BootstrapBank(smooth_lag={smooth_lag!r}): an integer in [1, {ROWS_LAG_MAX}] "
                                  "(gmx_rows_lag_moments parks the ancestor tables of a lag in LDS)")
+        self.smooth_pairs = bool(smooth_pairs)
+        if self.smooth_pairs and self.smooth_lag is None:
+            raise ValueError("BootstrapBank(smooth_pairs=True): needs smooth_lag=L (the pairs are read from its rings)")
+        if self.smooth_pairs and self.T < 2:
+            raise ValueError(f"BootstrapBank(smooth_pairs=True): T = {self.T} has no pair of consecutive steps (T >= 2)")
         self.quantiles = None
         if quantiles is not None:
             self.quantiles, self.q_levels = _quantile_levels(quantiles, "BootstrapBank(quantiles=)")
@@ -2474,7 +2550,8 @@ class BootstrapBank(_Sweep):
     def enqueue(self):
         """every launch of the sweep on the current stream: per step the site program and gmx_resample_rows (with
         ess_threshold=: gmx_resample_rows_ess; with moments=True: gmx_rows_moments between the two, with covariance=True:
-        gmx_rows_covariance, with quantiles=: gmx_rows_quantiles, with smooth_lag=: gmx_rows_lag_moments there too) — no syncs,
+        gmx_rows_covariance, with quantiles=: gmx_rows_quantiles, with smooth_lag=: gmx_rows_lag_moments there too, with
+        smooth_pairs=True: gmx_rows_lag_pairs after it, from the first step that has a pair to write) — no syncs,
         no allocations, no host read of a device value"""
         R, n = self.R, self.n
         N = R * n
@@ -2539,6 +2616,20 @@ class BootstrapBank(_Sweep):
         """smoothed_mean()'s shapes: the fixed-lag smoothed variance, per component (smooth_lag=L only; synchronises)"""
         smo, D = self._recorded("smooth_lag", "smoothed_var")
         return self._columns(smo, D, 2 * D)
+
+    def smoothed_pairs(self) -> "RowLagPairs":
+        """RowLagPairs(mean_s, mean_next [T - 1, R, D], cov_s, cross, cov_next [T - 1, R, D, D]), float64 on the host: row s holds
+        the pair of times (s, s + 1) of filter r given y_1..min(s+L, T-1) — the smoothed means and covariances of x_s and of
+        x_{s+1} and cross[j, k] = Cov(x_{s, j}, x_{s+1, k}) (smooth_lag=L, smooth_pairs=True only; synchronises)"""
+        smp, D = self._recorded("smooth_pairs", "smoothed_pairs")
+        return _pair_blocks(smp[:self.T - 1].cpu(), D)
+
+    def smoothed_cov(self) -> torch.Tensor:
+        """float64 [T, R, D, D], on the host: the fixed-lag smoothed covariance matrix of x_s — cov_s of the pair (s, s + 1),
+        and for s = T - 1 cov_next of the last pair, the filter covariance of the last step (smooth_lag=L, smooth_pairs=True
+        only; synchronises)"""
+        p = self.smoothed_pairs()
+        return torch.cat([p.cov_s, p.cov_next[-1:]])
 
     def filter_quantiles(self) -> torch.Tensor:
         """float32 [T, R, Q] ([T, R, D, Q] for a state of D > 1 components), on the host: the quantiles of x_t | y_1..t of filter
@@ -2658,8 +2749,8 @@ class ConditionalBank(BootstrapBank):
 
     def __init__(self, init, step, n_particles: int, n_chains: int, T: int, obs_addr="y", step_extra=None, params=None,
                  specialize=True, state_addr="x", state_sites=None, resample="multinomial", ancestor_sampling=False,
-                 ess_threshold=None, moments=False, quantiles=None, covariance=False, smooth_lag=None):
-        given = dict(moments=moments, covariance=covariance, quantiles=quantiles, smooth_lag=smooth_lag)
+                 ess_threshold=None, moments=False, quantiles=None, covariance=False, smooth_lag=None, smooth_pairs=False):
+        given = dict(moments=moments, covariance=covariance, quantiles=quantiles, smooth_lag=smooth_lag, smooth_pairs=smooth_pairs)
         for s in _SUMMARIES:
             if s.on(given[s.kw]):
                 raise NotImplementedError(f"ConditionalBank: {s.spelled} is not supported ({s.conditional}; BootstrapBank takes it)")
@@ -3094,7 +3185,8 @@ class ParticleMH(_Sweep):
     moments=True (with every other keyword BootstrapBank takes) reaches the bank: the filtering means, variances and ESS of the
     LAST sweep — the proposal's, accepted or not — are then read from pmh.bank (filter_mean(), filter_var(), ess()); nothing
     of them is recorded across iterations.  quantiles=(p, ...), covariance=True and smooth_lag=L reach the bank the same way
-    (pmh.bank.filter_quantiles(), pmh.bank.filter_cov(), pmh.bank.smoothed_mean() and smoothed_var())."""
+    (pmh.bank.filter_quantiles(), pmh.bank.filter_cov(), pmh.bank.smoothed_mean() and smoothed_var()), and with smooth_lag=L
+    so does smooth_pairs=True (pmh.bank.smoothed_pairs() and smoothed_cov())."""
 
     def __init__(self, init, step, prior, n_particles: int, n_chains: int, T: int, param_addrs, step_size, obs_addr="y",
                  state_addr="x", resample="systematic", step_extra=None, ess_threshold=None, specialize=True, **bank_kw):

@@ -904,6 +904,49 @@ int gmx_rows_lag_moments(const float* lw_d, const float* carry_d /* may be NULL 
                          double* out_d, int64_t out_ld, int64_t out_lag_stride, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Fixed-lag smoothed pair moments  (additive, ABI still v8.  Reference call site: none of its own — the sufficient statistics
+ * of fixed-lag EM for a state-space model, Olsson, Cappe, Douc and Moulines 2008: the smoothed joint second moments of
+ * consecutive states, for an LGSSM what the RTS smoother returns as P_{s|T} and P_{s,s+1|T}.)
+ *   gmx_rows_lag_pairs   Called for step t AFTER gmx_rows_lag_moments has recorded step t into the rings, with that call's
+ *                   weights, rings, index_stride, t and L.  It reads lw_d, carry_d and the rings and writes out_d only;
+ *                   x_d is not read (it may be null: the slot keeps the nine arguments every gmx_rows_* call opens with),
+ *                   x_ld and x_row_stride are the store's, and rows of hist_x_d are x_row_stride apart as they were recorded.
+ *                   Steps 1 to 3 of gmx_rows_moments' definition give a_i, M and e_i: the same weights bit for bit.  With
+ *                   b_l(i) the walk of gmx_rows_lag_moments (hop 1 through the rows slot t mod (L + 1) of hist_a_d holds),
+ *                   for every row r and lag l in [lag_lo, lag_hi]:
+ *                     1. u_i = x_{t-l}[b_l(i)] and v_i = x_{t-l+1}[b_{l-1}(i)], both from hist_x_d (lag 1's v too);
+ *                     2. in float64, with zu = (1, u), zv = (1, v): Guu_jk = sum_i (e_i zu_j) zu_k, Guv_jk = sum_i (e_i zu_j) zv_k,
+ *                        Gvv_jk = sum_i (e_i zv_j) zv_k, 0 <= j, k <= D; S0 = Guu_00;
+ *                     3. at o = out_d + l * out_lag_stride (signed) + r * out_ld, 2 D + 3 D^2 doubles
+ *                        [mean_s : D][mean_next : D][cov_s : D x D][cross : D x D][cov_next : D x D]:
+ *                        mean_s[j] = Guu_0,j+1 / S0, mean_next[k] = Gvv_0,k+1 / S0,
+ *                        cross[j][k] = Guv_j+1,k+1 / S0 - mean_s[j] mean_next[k] (not symmetric, not clamped),
+ *                        cov_s and cov_next as gmx_rows_covariance forms its matrix from Guu and Gvv (j <= k computed once and
+ *                        stored twice, the diagonal clamped at 0);
+ *                     4. a row without mass (S0 = 0) writes NaN into all 2 D + 3 D^2 outputs of every lag.  It is not an error.
+ *                   lag_lo > lag_hi is the empty range: the call returns 0 and launches nothing.  The summation order is
+ *                   gmx_rows_covariance's: a lag's result depends on n alone, not on the range it was asked in.  The CPU
+ *                   build sums in column order.
+ *                   n <= 1024: ONE launch with gmx_resample_rows' packing (a flush of more than 20 lags: lags 1 .. 20 in one,
+ *                   each later lag in one of its own), the tables of hops 2 .. lag_hi in LDS, the operands gathered from
+ *                   hist_x_d along the walk, three 16 x 16 accumulator tiles of v_mfma_f64_16x16x4_f64 per wave; nothing in
+ *                   the workspace.  n > 1024: per (row, tile of 1024 columns) the walk through hist_a_d in global memory and
+ *                   the tile's matrices relative to its own maximum, then per row their combination under
+ *                   s_b = exp(m_b - M) taken in float64.
+ *                   Limits: those of gmx_rows_lag_moments but 1 <= D <= 15, 1 <= lag_lo, lag_hi <= min(L, t),
+ *                   out_ld >= 2 D + 3 D^2; workspace_d: gmx_rows_lag_pairs_workspace(rows, n, D, L) bytes (16 for
+ *                   n <= 1024; past it 528 L doubles and a float per (row, tile)), 8-byte aligned, not null.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+size_t gmx_rows_lag_pairs_workspace(int64_t rows, int64_t n, int32_t D, int32_t L);
+int gmx_rows_lag_pairs(const float* lw_d, const float* carry_d /* may be NULL */, int64_t rows, int64_t n, int64_t ld,
+                       const float* x_d /* not read, may be NULL */, int32_t D, int64_t x_ld, int64_t x_row_stride,
+                       int64_t index_stride, int64_t t, int32_t L, int32_t lag_lo, int32_t lag_hi,
+                       const float* hist_x_d /* [L + 1, D, hist_x_ld] */, int64_t hist_x_ld,
+                       const int32_t* hist_a_d /* [L + 1, rows, hist_a_ld] */, int64_t hist_a_ld, double* out_d, int64_t out_ld,
+                       int64_t out_lag_stride, void* workspace_d, gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Row-wise weighted quantiles  (additive, ABI still v8.  Reference call site: none of its own — the credible band of each of
  * R filters at a step: the median and the tail quantiles of x_t | y_1..t, from the weights and the state the step has just
  * written, where a mean and a variance would describe a Gaussian.)

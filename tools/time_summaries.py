@@ -9,6 +9,9 @@ time_moments, time_quantiles, time_covariance, time_lag — so they stay compara
                                                                             Gram matrix on the float64 matrix instruction; past it: two)
             smooth_lag  BootstrapBank(..., smooth_lag=8)                    gmx_rows_lag_moments per step (n = 1024: one launch, the
                                                                             ancestor tables in LDS; past it: two, the walk in global memory)
+            smooth_pairs  BootstrapBank(..., smooth_lag=8, smooth_pairs=True)   gmx_rows_lag_pairs after it, from step 8 on (three Gram
+                                                                            matrices gathered along the walk); timed beside
+                                                                            smooth_lag=8 and covariance=True, whose work it does
 
   sweep   R = 256, T = 100, per shape three captured sweeps alternated in one process (two for --summary moments):
             plain       BootstrapBank(...)                   the sweep as it is without a keyword
@@ -21,7 +24,7 @@ time_moments, time_quantiles, time_covariance, time_lag — so they stay compara
             moments                 lgssm:256:1024,lgssm:256:4096     (with the launch's algorithmic bytes, R n 4 (1 + D) read +
                                                                       R 8 (1 + 2 D) written, over the added time)
             quantiles               lgssm:256:256,lgssm:256:1024
-            covariance, smooth_lag  lgssm:256:1024,tracker:256:1024,tracker:256:4096
+            covariance, smooth_lag, smooth_pairs  lgssm:256:1024,tracker:256:1024,tracker:256:4096
 
 Clocks as found; a host clock around work that ends in a device synchronise.  Environment: TS_SHAPES ("model:R:n,..."), TS_T,
 TS_LAG.  Needs the MI355X: there is no CPU path."""
@@ -66,7 +69,11 @@ SUMMARIES = {
                    lambda b, R, n, added: {"mean_cov_last_step": [float(v) for v in b.filter_cov()[T - 1].mean(dim=0).reshape(-1)]}),
     "smooth_lag": ("time_lag", {"smooth_lag": LAG}, WIDE, lambda model: {"model": model, "lag": LAG},
                    lambda b, R, n, added: {"mean_smoothed_first_step": [float(v) for v in b.smoothed_mean().reshape(T, R, -1)[0].mean(dim=0)]}),
+    "smooth_pairs": ("time_lag", {"smooth_lag": LAG, "smooth_pairs": True}, WIDE, lambda model: {"model": model, "lag": LAG},
+                     lambda b, R, n, added: {"mean_cross_first_pair": [float(v) for v in b.smoothed_pairs().cross[0].mean(dim=0).reshape(-1)]}),
 }
+# the keywords a summary is timed beside, in the same alternation (besides plain and moments)
+BESIDE = {"smooth_pairs": {"smooth_lag": {"smooth_lag": LAG}, "covariance": {"covariance": True}}}
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--summary", required=True, choices=sorted(SUMMARIES))
@@ -98,7 +105,7 @@ ys = torch.from_numpy(workloads.lgssm_data(T))
 for model, R, n in shapes:
     init, step = bank_checks._models(model)
     banks = {}
-    for name, kw in {"plain": {}, "moments": {"moments": True}, args.summary: keyword}.items():
+    for name, kw in {"plain": {}, "moments": {"moments": True}, **BESIDE.get(args.summary, {}), args.summary: keyword}.items():
         b = smc.BootstrapBank(init, step, n, R, T, **kw).prepare(split(G.key(7), R), ys)
         b.capture()
         b.launch()
