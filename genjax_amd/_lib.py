@@ -293,6 +293,10 @@ class Backend:
         c.gmx_rows_lag_pairs.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64, c_int64,
                                          c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                          c_void_p, c_int64, c_int64, c_void_p, c_void_p]
+        c.gmx_smooth_back_workspace.argtypes = [c_int64, c_int64, c_int32]
+        c.gmx_smooth_back_workspace.restype = c_size_t
+        c.gmx_smooth_back.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int,
+                                      c_void_p, c_void_p, c_void_p]
         c.gmx_rows_quantiles.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int64, c_int64,
                                          c_void_p, c_int32, c_void_p, c_int64, c_void_p]
         c.gmx_pmmh_propose.argtypes = [POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32,

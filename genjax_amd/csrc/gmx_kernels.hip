@@ -3858,6 +3858,37 @@ extern "C" int gmx_rows_lag_pairs(const float* lw_d, const float* carry_d, int64
 }
 
 // ---------------------------------------------------------------------------
+// backward smoothing (gmx_smooth.h): G (+)= u softmax_rows(A) in float64, the softmax factor formed in registers and fed to
+// the float64 matrix instruction.  Its refusal (gmx_sizes.h), the HIP build's alignment check, then three launches: the rows'
+// maxima and sums, the partial tiles per (strip, run of rows), their sum into G and the count of rows without mass.
+// ---------------------------------------------------------------------------
+#include "gmx_smooth.h"
+
+extern "C" size_t gmx_smooth_back_workspace(int64_t K, int64_t n, int32_t C) { return gmx_smooth_back_bytes_(K, n, C); }
+
+extern "C" int gmx_smooth_back(const float* A_d, int64_t K, int64_t n, int64_t ld, const double* u_d, int32_t C, int64_t u_ld,
+                               double* G_d, int64_t g_ld, int accumulate, int64_t* status_d, void* workspace_d, gmx_stream stream) {
+  const char* who = "gmx_smooth_back";
+  const gmx_refusal no = gmx_smooth_back_refusal_(!A_d || !u_d || !G_d || !status_d || !workspace_d, K, n, ld, C, u_ld, g_ld, u_d, G_d);
+  if (no.fmt) return gmx_fail(no.fmt, who, no.v);
+  if (rows_misaligned_(who, workspace_d, {{A_d, 3}, {status_d, 7}})) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const gmx_smooth_plan p = gmx_smooth_plan_(K, n);
+  const gmx_smooth_ws w = gmx_smooth_back_carve_(workspace_d, K, n, C);
+  if (n <= GMX_PICK_TILE)
+    hipLaunchKernelGGL(k_smooth_rows<1>, dim3((unsigned)((K + 3) / 4)), dim3(GMX_SMOOTH_BLOCK), 0, st, A_d, K, n, ld, w.inv, w.max);
+  else
+    hipLaunchKernelGGL(k_smooth_rows<4>, dim3((unsigned)K), dim3(GMX_SMOOTH_BLOCK), 0, st, A_d, K, n, ld, w.inv, w.max);
+  hipLaunchKernelGGL(k_smooth_contract, dim3((unsigned)p.strips, (unsigned)p.splits), dim3(GMX_SMOOTH_BLOCK), 0, st, A_d, K, n, ld,
+                     u_d, C, u_ld, (const double*)w.inv, (const float*)w.max, p.split_rows, p.np, w.part);
+  hipLaunchKernelGGL(k_smooth_finish, dim3((unsigned)((n + GMX_SMOOTH_BLOCK - 1) / GMX_SMOOTH_BLOCK), (unsigned)C),
+                     dim3(GMX_SMOOTH_BLOCK), 0, st, (const double*)w.part, p.splits, C, n, p.np, G_d, g_ld, accumulate,
+                     (const double*)w.inv, K, status_d);
+  GMX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // row-wise weighted quantiles (gmx_quantiles.h): per row, component and level the state word at which the sorted
 // fixed-point weights cross the level.  Its refusal (gmx_sizes.h), the HIP build's alignment check, ONE launch.
 // ---------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 //   gmx_*_bytes_ / _words_    the bodies of the gmx_*_workspace / _bytes / _words exports: each export is a one-line call
 //   gmx_*_refusal_            argument checks as functions that return the message (a format taking the entry point's
 //                             name, then one integer) or nothing, for gmx_fail, which writes the build's error string:
-//                             the tile-form resamplers, the row-wise draws, moments and quantiles, the particle-MH pair, the
+//                             the tile-form resamplers, the row-wise draws, moments and quantiles, the smoother's contraction, the particle-MH pair, the
 //                             particle-Gibbs three, the sharded / peer family, the sweep history
 //   gmx_resample_dispatch_    the body of gmx_resample: argument checks, the workspace layout and the dispatch over kind
 //                             and size.  It calls exported entry points only, so every build dispatches alike.
@@ -424,6 +424,59 @@ static inline gmx_refusal gmx_rows_lag_pairs_refusal_(bool has_null, int64_t row
   if (gmx_resample_rows_pin_refusal_(rows, n, D, hist_x_ld, x_row_stride).fmt)
     return {"%s: hist_x_ld = %lld does not hold (rows - 1) * x_row_stride + n columns (or is 2^46 or more)", (long long)hist_x_ld};
   if (out_ld < 2 * (int64_t)D + 3 * (int64_t)D * D) return {"%s: out_ld = %lld is smaller than 2 D + 3 D^2", (long long)out_ld};
+  return {nullptr, 0};
+}
+
+// ---- the backward smoother's softmax contraction: gmx_smooth_back (gmx_smooth.h) ----
+#define GMX_SMOOTH_MAX_C 16            /* rows of u: the M side of ONE 16 x 16 accumulator tile */
+#define GMX_SMOOTH_STRIP 64            /* columns of a wave: four accumulator tiles of 16 */
+#define GMX_SMOOTH_CHUNK 64            /* rows of A a workgroup stages u / S and M for at a time: 16 k-steps, 4 a wave */
+#define GMX_SMOOTH_TARGET_WGS 512      /* workgroups the contraction asks for before it stops splitting K (two a CU) */
+#define GMX_SMOOTH_MAX_SPLITS 64
+// How a call is cut: strips of 64 columns (grid x), K in `splits` runs of split_rows rows, a multiple of the chunk (grid y);
+// np: the row pitch of a partial tile, whole strips, so that the contraction stores without a column guard.  A function of
+// (K, n) alone: the summation order, and so the bits of a result, do not depend on the device or on C.
+// max_splits: what `splits` stays below for every K at this n — the workspace is sized by it, so one sized for K serves fewer rows.
+struct gmx_smooth_plan { int64_t strips, np, split_rows, splits, max_splits; };
+static inline gmx_smooth_plan gmx_smooth_plan_(int64_t K, int64_t n) {
+  gmx_smooth_plan p;
+  p.strips = (n + GMX_SMOOTH_STRIP - 1) / GMX_SMOOTH_STRIP;
+  p.np = p.strips * GMX_SMOOTH_STRIP;
+  int64_t want = (GMX_SMOOTH_TARGET_WGS + p.strips - 1) / p.strips;
+  if (want > GMX_SMOOTH_MAX_SPLITS) want = GMX_SMOOTH_MAX_SPLITS;
+  int64_t rows = (K + want - 1) / want;
+  rows = (rows + GMX_SMOOTH_CHUNK - 1) / GMX_SMOOTH_CHUNK * GMX_SMOOTH_CHUNK;
+  p.split_rows = rows;
+  p.splits = (K + rows - 1) / rows;
+  p.max_splits = want;
+  return p;
+}
+// Its workspace: inv f64 [K] (1 / S_k, 0 for a row without mass) | part f64 [max_splits, C, np] | max f32 [K], to 16 bytes
+struct gmx_smooth_ws { double* inv; double* part; float* max; };
+static inline size_t gmx_smooth_back_bytes_(int64_t K, int64_t n, int32_t C) {
+  if (K < 1 || K > 0x7fffffffLL || n < 1 || n > GMX_ROWS_MAX_N || C < 1 || C > GMX_SMOOTH_MAX_C) return 16;
+  const gmx_smooth_plan p = gmx_smooth_plan_(K, n);
+  return (size_t)(((uint64_t)K * 12u + (uint64_t)p.max_splits * (uint64_t)C * (uint64_t)p.np * 8u + 15u) & ~(uint64_t)15u);
+}
+static inline gmx_smooth_ws gmx_smooth_back_carve_(void* workspace, int64_t K, int64_t n, int32_t C) {
+  const gmx_smooth_plan p = gmx_smooth_plan_(K, n);
+  gmx_smooth_ws w;
+  w.inv = (double*)workspace;
+  w.part = w.inv + K;
+  w.max = (float*)(w.part + p.max_splits * C * p.np);
+  return w;
+}
+static inline gmx_refusal gmx_smooth_back_refusal_(bool has_null, int64_t K, int64_t n, int64_t ld, int32_t C, int64_t u_ld,
+                                                   int64_t g_ld, const void* u_d, const void* G_d) {
+  if (has_null) return {"%s: null argument", 0};
+  if (K < 1 || K > 0x7fffffffLL) return {"%s: K = %lld is outside [1, 2^31)", (long long)K};
+  if (n < 1 || n > GMX_ROWS_MAX_N) return {"%s: n = %lld is outside [1, 2^21]", (long long)n};
+  if (C < 1 || C > GMX_SMOOTH_MAX_C)
+    return {"%s: C = %lld is outside [1, 16] (the rows of u are one side of a 16 x 16 MFMA tile)", (long long)C};
+  if (ld < n) return {"%s: ld = %lld is smaller than n", (long long)ld};
+  if (u_ld < K) return {"%s: u_ld = %lld is smaller than K", (long long)u_ld};
+  if (g_ld < n) return {"%s: g_ld = %lld is smaller than n", (long long)g_ld};
+  if (((uintptr_t)u_d | (uintptr_t)G_d) & 7) return {"%s: u_d and G_d must be 8-byte aligned", 0};
   return {nullptr, 0};
 }
 

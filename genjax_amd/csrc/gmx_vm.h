@@ -338,7 +338,7 @@ GMX_HD bool gmx_op_needs_full(uint32_t op) {
 // sweep-history entry points as sequential loops (gmx_history.h) and the row-wise draw and the row-wise resampling as
 // loops over the per-row paths (gmx_backward.h, gmx_resample_rows.h), the row-wise moments, covariance, quantiles and
 // fixed-lag smoothed moments and pair moments as their definitions (gmx_moments.h, gmx_covariance.h, gmx_quantiles.h, gmx_lag.h,
-// gmx_lag_pairs.h), the normal draw's tail over chosen bits
+// gmx_lag_pairs.h), the backward smoother's softmax contraction as its definition (gmx_smooth.h), the normal draw's tail over chosen bits
 // (gmx_draw_tail.h), and the two launches of a particle-MH iteration and the three of a particle-Gibbs iteration as loops
 // over chains (gmx_pmmh.h, gmx_pgibbs.h); hipcc and hiprtc see nothing here.
 #if defined(__cplusplus) && !defined(__HIPCC__) && !defined(__HIPCC_RTC__)
@@ -350,6 +350,7 @@ GMX_HD bool gmx_op_needs_full(uint32_t op) {
 #include "gmx_covariance.h"
 #include "gmx_lag.h"
 #include "gmx_lag_pairs.h"
+#include "gmx_smooth.h"
 #include "gmx_quantiles.h"
 #include "gmx_pmmh.h"
 #include "gmx_pgibbs.h"

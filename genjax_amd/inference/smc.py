@@ -991,7 +991,36 @@ def row_lag_pairs(lw: torch.Tensor, t: int, L: int, lags, rings, *, carry=None, 
     return _pair_blocks(out[:max(hi, 0) + 1, :, :W], D)
 
 
-ROWS_QUANTILES_N_MAX = 1024      # gmx_rows_quantiles sorts a row of one tile
+SMOOTH_BACK_C_MAX = 16           # gmx_smooth_back: the rows of u are one side of a 16 x 16 tile of the float64 matrix instruction
+
+
+def smooth_back(logits: torch.Tensor, u: torch.Tensor, out: torch.Tensor, *, accumulate=False, status=None, workspace=None):
+    """gmx_smooth_back: out (+)= u @ softmax(logits, dim=1) in float64, the softmax factor never stored (three launches).
+    logits float32 [K, n], u float64 [C, K] (C <= 16), out float64 [C, n], each with unit column stride and any row stride;
+    a row's weights are exp(logit - row max) in float32 (row_moments' weights), everything after in float64.  accumulate:
+    add to what out holds (a step fed in slabs of rows).  A row of logits without mass contributes nothing and adds 1 to
+    status (int64 [1], zeroed by the caller; a fresh one by default).  -> status.  workspace: a persistent buffer of
+    gmx_smooth_back_workspace(K, n, C) bytes instead of a fresh one."""
+    be = _lib.get()
+    mats = ((logits, torch.float32, "logits"), (u, torch.float64, "u"), (out, torch.float64, "out"))
+    for a, dt, name in mats:
+        if a.ndim != 2 or a.dtype != dt or (a.shape[1] > 1 and a.stride(1) != 1):
+            raise ValueError(f"smooth_back: {name} is a {str(dt).split('.')[1]} matrix with unit column stride; got "
+                             f"{tuple(a.shape)} {a.dtype}")
+    (K, n), C = (int(v) for v in logits.shape), int(u.shape[0])
+    if tuple(u.shape) != (C, K) or tuple(out.shape) != (C, n):
+        raise ValueError(f"smooth_back: u is [C, K] and out [C, n] for logits [K, n] = {(K, n)}; got {tuple(u.shape)}, {tuple(out.shape)}")
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.int64, device=logits.device)
+    if workspace is None:
+        workspace = _workspace(be.c.gmx_smooth_back_workspace(K, n, C), logits.device)
+    ld, u_ld, g_ld = (int(a.stride(0)) if a.shape[0] > 1 else int(a.shape[1]) for a, _, _ in mats)
+    be.check(be.c.gmx_smooth_back(be.ptr(logits), K, n, ld, be.ptr(u), C, u_ld, be.ptr(out), g_ld, int(bool(accumulate)),
+                                  be.ptr(status), be.ptr(workspace), be.stream()), "gmx_smooth_back")
+    return status
+
+
+ROWS_QUANTILES_N_MAX = 1024     # gmx_rows_quantiles sorts a row of one tile
 ROWS_QUANTILES_Q_MAX = 16        # levels per call (GMX_ROWS_QUANTILES_MAX_Q)
 
 
@@ -1581,6 +1610,8 @@ class _Sweep:
 BACKWARD_ROWS_MAX = 16                 # rows of backward-simulation logits per density launch (and per gmx_pick_rows call)
 BACKWARD_CHUNK_BYTES = 256 << 20       # ... and at most this much of them in memory
 _BACKWARD_CACHE = engine.new_cache()
+MARGINAL_SMOOTH_N_MAX = 16384          # SweepHistory.marginal_smooth: n^2 densities a step (a cost bound, not a kernel limit)
+MarginalSmooth = namedtuple("MarginalSmooth", ["weights", "mean", "var", "cov", "cross"])
 
 
 def _assess_program(model, args, leaves, form, emit, refuse, out, specialize=False, launch=True):
@@ -1657,11 +1688,12 @@ def _transition_choices(sites, obs_addr, y, x_next):
     return con
 
 
-def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
+def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, who="SweepHistory.backward_sample"):
     """out[k, i] = lw[i] + step.assess({sites[d]: x_next[d][k], obs_addr: y}, (x_prev[i], *extra))[0] in float32, for the
     R = out.shape[0] rows in ONE launch: the model's `assess` traced R times, row k's constrained state read from the
     launch-uniform short vectors x_next[d] (as inference/gibbs.py traces K categories), the R sums stored as the rows
-    of `out` ([R, n], rows contiguous).  The program is cached on the model, the leaves' kinds and R."""
+    of `out` ([R, n], rows contiguous).  The program is cached on the model, the leaves' kinds and R.  who: the caller a
+    refusal names."""
     from ..engine import Broadcast, Sym
     R, D = int(out.shape[0]), len(x_next)
 
@@ -1673,7 +1705,7 @@ def _backward_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out):
             tr.prestore(rows[k])            # (stored now: the row's register dies here)
         return rows
     _assess_program(step, (x_prev,) + tuple(extra), [y] + [Broadcast(v) for v in x_next] + [lw], (tuple(sites), obs_addr, R),
-                    emit, _transition_refusal("SweepHistory.backward_sample", sites, obs_addr), out)
+                    emit, _transition_refusal(who, sites, obs_addr), out)
 
 
 def _ancestor_logits(step, sites, obs_addr, x_prev, extra, x_next, y, lw, out, specialize=False, launch=True,
@@ -1701,12 +1733,19 @@ class SweepHistory:
       ancestors    [T, n] int32: row t is the resampling AFTER step t (row T-1 = state()[2])
 
     The reference's SMC carries whole Scan traces through every resampling; here a step is recorded once and a
-    trajectory is ONE backward walk through the ancestor rows (gmx_lineage: one launch, one lane per trajectory)."""
+    trajectory is ONE backward walk through the ancestor rows (gmx_lineage: one launch, one lane per trajectory).
+
+      filter_mean()              E[x_t | y_1..t]
+      lineage() / trajectories() the genealogical paths of the survivors (they coalesce to a few early ancestors)
+      backward_sample(key, m)    m trajectories by forward filtering, backward simulation (FFBS): Monte Carlo noise m^-1/2
+      marginal_smooth()          forward filtering, backward smoothing (FFBSm): every recorded particle's smoothed weight, and
+                                 from them the smoothed mean, covariance and lag-one cross covariance, deterministically — the
+                                 n^2 part on gmx_smooth_back's softmax contraction (the float64 matrix instruction)"""
 
     def __init__(self, xs, lws, ancs, event=(), tuple_state=None, *, step=None, ys=None, step_extra=None, obs_addr=None,
                  state_addr=None):
-        """step / ys / step_extra / obs_addr / state_addr: the sweep's model, for backward_sample() (BootstrapSweep.history()
-        hands them over; every other method works without)"""
+        """step / ys / step_extra / obs_addr / state_addr: the sweep's model, for backward_sample() and marginal_smooth()
+        (BootstrapSweep.history() hands them over; every other method works without)"""
         self._xs, self.log_weights, self.ancestors = xs, lws, ancs
         self._event, self._tuple = tuple(event), tuple_state
         self.T, self.D, self.n = (int(v) for v in xs.shape)
@@ -1754,6 +1793,22 @@ class SweepHistory:
         """the states along those lineages: [m, T] / [m, T, D] / a tuple of [m, T] (views of the kernel's [T, D, m])"""
         return self._state_view(self._walk(start, False, True)[1], 1)
 
+    def _model_sites(self, who, state_sites):
+        """the state's addresses of a method that scores the step model's transition density (`who`), checked"""
+        if self._step is None or self._ys is None or self._obs_addr is None:
+            raise RuntimeError(f"{who}: this SweepHistory was built without the model (step=, ys=, "
+                               "step_extra=, obs_addr=, state_addr=): take it from BootstrapSweep.history()")
+        if state_sites is None:
+            if self.D > 1:
+                raise NotImplementedError(f"{who}: a state of more than one component needs "
+                                          "state_sites= (the address of each component, in order)")
+            state_sites = (self._state_addr,)
+        sites = tuple(state_sites)
+        if len(sites) != self.D:
+            raise ValueError(f"{who}: state_sites names {len(sites)} addresses for a state of "
+                             f"{self.D} components")
+        return sites
+
     def backward_sample(self, key: Key, m: int, state_sites=None, return_paths=False):
         """m trajectories by forward filtering, backward simulation (Godsill, Doucet & West 2004) over the recorded steps:
         the last state is drawn from the final weights, and going back every particle of step t is re-weighted by the
@@ -1778,20 +1833,9 @@ class SweepHistory:
         Returns the trajectories in trajectories()'s layout ([m, T] / [m, T, D] / a tuple of [m, T]); with
         return_paths=True, (paths int32 [T, m], trajectories).  A row without any mass (every candidate's density -inf)
         raises FloatingPointError naming the step."""
-        if self._step is None or self._ys is None or self._obs_addr is None:
-            raise RuntimeError("SweepHistory.backward_sample: this SweepHistory was built without the model (step=, ys=, "
-                               "step_extra=, obs_addr=, state_addr=): take it from BootstrapSweep.history()")
+        sites = self._model_sites("SweepHistory.backward_sample", state_sites)
         if tuple(key.shape) != ():
             raise ValueError("SweepHistory.backward_sample takes ONE key")
-        if state_sites is None:
-            if self.D > 1:
-                raise NotImplementedError("SweepHistory.backward_sample: a state of more than one component needs "
-                                          "state_sites= (the address of each component, in order)")
-            state_sites = (self._state_addr,)
-        sites = tuple(state_sites)
-        if len(sites) != self.D:
-            raise ValueError(f"SweepHistory.backward_sample: state_sites names {len(sites)} addresses for a state of "
-                             f"{self.D} components")
         be = _lib.get()
         dev = self._xs.device
         T_, D, n, m = self.T, self.D, self.n, int(m)
@@ -1840,6 +1884,88 @@ class SweepHistory:
         w = e / e.sum(dim=1, keepdim=True)
         mean = (w[:, None, :] * self._xs.double()).sum(dim=2)
         return mean[:, 0] if (self._tuple is None and not self._event) else mean
+
+    def _step_state(self, t):
+        """step t's particles as the step model takes its state"""
+        x_t = self._state_view(self._xs[t:t + 1], 0)
+        return type(x_t)(v[0] for v in x_t) if self._tuple is not None else x_t[0]
+
+    def marginal_smooth(self, state_sites=None):
+        """The marginal smoother: forward filtering, backward smoothing (Doucet, Godsill & Andrieu 2000) over the recorded
+        steps — the smoothed weight of EVERY recorded particle, deterministically: the Rao-Blackwellised form of
+        backward_sample (the same n^2 transition densities a step, summed instead of sampled).
+
+          w_{T-1|T} = softmax(lw_{T-1})                                                           (float64)
+          t = T-2 .. 0:   A[k, i] = lw_t[i] + step.assess({site_d: x_{t+1}[k][d], obs_addr: y_{t+1}}, (x_t[i], *step_extra(t+1)))[0]
+                          P = softmax over i of A[k, :]     (weights in float32 as row_moments takes them, sums in float64)
+                          w_{t|T}[i] = sum_k w_{t+1|T}[k] P[k, i]
+                          E[x_t x_{t+1}^T | y_1..T] = sum_i x_t[i] (sum_k w_{t+1|T}[k] x_{t+1}[k] P[k, i])^T
+
+        The logits are backward_sample's (one cached site program per BACKWARD_ROWS_MAX rows, written into consecutive
+        rows of a slab of at most BACKWARD_CHUNK_BYTES); per slab ONE gmx_smooth_back call contracts (w, w x_{t+1,1}, ..,
+        w x_{t+1,D}) with the softmax factor on the float64 matrix instruction, P never stored.  The O(n D^2) moment sums
+        are float64 torch expressions.  Nothing passes through the host between steps.
+
+        state_sites as backward_sample takes it; the model may have no latent site besides them and the observation.  At
+        most 15 state components (gmx_smooth_back's 16 rows) and n <= MARGINAL_SMOOTH_N_MAX particles (the cost: n^2
+        densities a step).  -> MarginalSmooth(weights [T, n], mean, var [T] / [T, D], cov [T, D, D], cross [T - 1, D, D]),
+        float64 on the history's device, mean and var laid out as filter_mean(): what an RTS smoother returns as m_{t|T},
+        P_{t|T} and, cross[t] = E[x_t x_{t+1}^T] - m_t m_{t+1}^T, P_{t,t+1|T}.  A step at which next states carrying more
+        than 1e-12 of the smoothed mass have no step-t particle with a positive transition density into them raises
+        FloatingPointError naming the step."""
+        who = "SweepHistory.marginal_smooth"
+        sites = self._model_sites(who, state_sites)
+        T_, D, n = self.T, self.D, self.n
+        if D > SMOOTH_BACK_C_MAX - 1:
+            raise NotImplementedError(f"{who}: a state of D = {D} > {SMOOTH_BACK_C_MAX - 1} components (gmx_smooth_back holds "
+                                      "(w, w x) in the 16 rows of one matrix tile)")
+        if n > MARGINAL_SMOOTH_N_MAX:
+            raise NotImplementedError(f"{who}: n = {n} > {MARGINAL_SMOOTH_N_MAX} particles (a step scores n^2 transition "
+                                      "densities; backward_sample(key, m) scores m n)")
+        be = _lib.get()
+        dev = self._xs.device
+        xs = self._xs.double()
+        weights = torch.empty((T_, n), dtype=torch.float64, device=dev)
+        lw = self.log_weights[T_ - 1].double()
+        e = torch.exp(lw - lw.max())
+        weights[T_ - 1] = e / e.sum()
+        second = torch.empty((max(T_ - 1, 0), D, D), dtype=torch.float64, device=dev)      # E[x_t x_{t+1}^T]
+        status = torch.zeros((T_,), dtype=torch.int64, device=dev)      # word t: the rows of step t without any mass
+        extra = self._step_extra or (lambda t: ())
+        R = max(1, min(BACKWARD_ROWS_MAX, n, 40 // D))
+        rows = max(1, min(n, BACKWARD_CHUNK_BYTES // (4 * n)))
+        slab = torch.empty((rows, n), dtype=torch.float32, device=dev)
+        u = torch.empty((1 + D, n), dtype=torch.float64, device=dev)
+        G = torch.empty((1 + D, n), dtype=torch.float64, device=dev)
+        ws = _workspace(be.c.gmx_smooth_back_workspace(rows, n, 1 + D), dev)
+        for t in range(T_ - 2, -1, -1):
+            u[0] = weights[t + 1]
+            u[1:] = weights[t + 1] * xs[t + 1]
+            x_t = self._step_state(t)
+            for k0 in range(0, n, rows):
+                kc = min(rows, n - k0)
+                for r0 in range(0, kc, R):
+                    rc = min(R, kc - r0)
+                    _backward_logits(self._step, sites, self._obs_addr, x_t, tuple(extra(t + 1)),
+                                     [self._xs[t + 1, d, k0 + r0:k0 + r0 + rc] for d in range(D)], self._ys[t + 1],
+                                     self.log_weights[t], slab[r0:r0 + rc], who=who)
+                smooth_back(slab[:kc], u[:, k0:k0 + kc], G, accumulate=k0 > 0, status=status[t:t + 1], workspace=ws)
+            weights[t] = G[0]
+            second[t] = xs[t] @ G[1:].t()
+        mean = (weights[:, None, :] * xs).sum(dim=2)
+        cov = torch.einsum("tn,tan,tbn->tab", weights, xs, xs) - mean[:, :, None] * mean[:, None, :]
+        cross = second - mean[:-1, :, None] * mean[1:, None, :]
+        mass, dead = weights.sum(dim=1).cpu(), status.cpu()             # the one host read
+        if not bool(mass[T_ - 1] > 0):                                   # (NaN: no finite final weight)
+            raise FloatingPointError(f"{who}: step {T_ - 1}: the final weights carry no mass")
+        for t in range(T_ - 2, -1, -1):
+            if int(dead[t]) and not bool(mass[t + 1] - mass[t] <= 1e-12):
+                raise FloatingPointError(f"{who}: step {t}: {int(dead[t])} of the {n} step-{t + 1} particles have no step-{t} "
+                                         f"particle with a positive transition density into them (rows of -inf logits), and "
+                                         f"they carried {float(mass[t + 1] - mass[t]):.3g} of the smoothed mass")
+        var = torch.diagonal(cov, dim1=1, dim2=2)
+        flat = self._tuple is None and not self._event
+        return MarginalSmooth(weights, mean[:, 0] if flat else mean, var[:, 0] if flat else var, cov, cross)
 
 
 class BootstrapSweep(_Sweep):

@@ -947,6 +947,33 @@ int gmx_rows_lag_pairs(const float* lw_d, const float* carry_d /* may be NULL */
                        int64_t out_lag_stride, void* workspace_d, gmx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Backward smoothing  (additive, ABI still v8.  Reference call site: none of its own — the dense step of forward filtering,
+ * backward smoothing, Doucet, Godsill and Andrieu 2000: the smoothed weights of step t + 1 carried to step t through the
+ * row-normalised backward kernel, with the first moments beside them for the lag-one cross moment.)
+ *   gmx_smooth_back   A_d: float32 logits [K, n], rows ld apart, at any 4-byte boundary; u_d: float64 [C, K], rows u_ld apart;
+ *                   G_d: float64 [C, n], rows g_ld apart.  Nothing is written into A_d or u_d.  For every row k:
+ *                     1. M_k = max_i A[k, i] (a NaN is ignored);
+ *                     2. e[k, i] = exp(A[k, i] - M_k), subtraction and exponential in float32 — gmx_rows_moments' e, the same
+ *                        bits on every build; 0 where the difference is NaN (-inf - -inf, a NaN logit);
+ *                     3. S_k = sum_i (double) e[k, i]; a row with S_k = 0 contributes exactly nothing and adds 1 to *status_d
+ *                        (a word the caller zeroes: calls add to it).  It is not an error;
+ *                     4. in float64, G[c, i] = sum_k u[c, k] e[k, i] / S_k for c < C, i < n, written over G_d (accumulate = 0)
+ *                        or added to what it holds (accumulate = 1: a step fed in slabs of rows).
+ *                   The summation order is fixed by (K, n) alone — the four rows of a matrix instruction, a wave's k-steps in
+ *                   order, the four waves in order, the runs of rows in order, then the old G: the same bits on every run.
+ *                   The CPU build sums rows in order.  Three launches: per row M_k and 1 / S_k into the workspace; per (strip
+ *                   of 64 columns, run of rows) a [C, 64] partial tile on v_mfma_f64_16x16x4_f64, the softmax factor formed in
+ *                   registers and never stored; the partial tiles added into G_d.
+ *                   Limits: 1 <= K < 2^31; 1 <= n <= 2^21; 1 <= C <= 16; ld >= n; u_ld >= K; g_ld >= n; no null pointer;
+ *                   u_d and G_d 8-byte aligned; workspace_d: gmx_smooth_back_workspace(K, n, C) bytes, 8-byte aligned.
+ * A null pointer or an out-of-range size returns non-zero before anything is launched, naming the argument and its value.
+ * ---------------------------------------------------------------------- */
+size_t gmx_smooth_back_workspace(int64_t K, int64_t n, int32_t C);
+int gmx_smooth_back(const float* A_d /* [K, ld] */, int64_t K, int64_t n, int64_t ld, const double* u_d /* [C, u_ld] */, int32_t C,
+                    int64_t u_ld, double* G_d /* [C, g_ld] */, int64_t g_ld, int accumulate, int64_t* status_d, void* workspace_d,
+                    gmx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Row-wise weighted quantiles  (additive, ABI still v8.  Reference call site: none of its own — the credible band of each of
  * R filters at a step: the median and the tail quantiles of x_t | y_1..t, from the weights and the state the step has just
  * written, where a mean and a variance would describe a Gaussian.)
